@@ -12,21 +12,28 @@ The update-to-data ratio is a stated design parameter: 1 learn() o
 Workload (BASELINE.json configs[1]): 4,096 parallel straight_line envs per GPU, HIRL-soft, fp32, synthetic random-init
 episodes (random_reset, Philox), synthetic 20,000-row expert set, seeded-init networks.  Prints ONE JSON line (rank 0).
 
-    python bench.py                       # 1 GPU, defaults finish in about a minute (incl. the bounded CPU baselines)
+    python bench.py                       # 1 GPU: the headline line only (set-up, W warm-up steps, K timed steps)
+    python bench.py --full                # + everything else it measures; finishes in about a minute (incl. the bounded CPU baselines)
+    python bench.py --dump-outputs DIR    # + what the last timed step computed, as DIR/<name>.npy (same arguments: same inputs)
     python bench.py --gpus N ...          # starts N ranks itself (torch.distributed.run as a child process, before this process touches
                                           # a GPU) and relays rank 0's line; fails if fewer than N GPUs are visible
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
-Shape of a run: [settle: untimed steps for --settle-s seconds] -> W warm-up steps -> [--dry-regions (1) untimed region of the same shape,
-declared] -> R = --reps (3) repetitions of { barrier + synchronize -> EXACTLY K steps with nothing but the hot path on the stream ->
-synchronize + barrier (max over ranks) }; `value` / `ms_per_step` are the MEDIAN repetition, all R are listed.
-Everything that needs events or stamped launches (stage times, the act + env launch's own duration for the roofline, the stand-alone env
-kernel, all-reduce times) runs in a SECOND pass after the clock has been read.
+Shape of a run: [settle: untimed steps for --settle-s seconds] -> W warm-up steps -> [--dry-regions untimed regions of the same shape,
+declared] -> R = --reps repetitions of { barrier + synchronize -> EXACTLY K steps with nothing but the hot path on the stream ->
+synchronize + barrier (max over ranks) }; `value` / `ms_per_step` are the MEDIAN repetition, all R are listed.  A plain run
+has no settle phase, no dry region and R = 1: it times exactly K steps; --full makes them 1.5 s, 1 and 3.
+With --full, everything that needs events or stamped launches (stage times, the act + env launch's own duration for the roofline, the
+stand-alone env kernel, all-reduce times) runs in a SECOND pass after the clock has been read, and the other legs follow (the reference-order
+leg, the env-step kernel sweep, the CPU baselines; N > 1: the exchange probe before the timed loop, the replica check after it).
 
 Which loop: the FRONT loop (env step + the first two launches of learn() in one launch, HirlEngine.step_learn) where it
 applies AND every rank has a GPU of its own; the reference's order otherwise (`config.loop`, `config.loop_reason`).  The front launch waits inside the
 launch; if such a wait ever gives up (sticky status word) the run is repeated in the reference's order IN THIS PROCESS and the line says so
 (`config.loop = "reference order (front tripped)"`, `front_status`): a valid line and exit code 0, never a crash and never a number from a tripped loop.
+With --ordered-slots (the default with --dump-outputs) the replay ring fills in row-tile order where the acting launch is per tile and every rank has
+a GPU of its own (`config.ring_slots`): the same arguments give the same results every run.  Its waits are in-launch too; one that gives up
+(`slot_status`) makes the run repeat with atomic slots.
 
 The pieces: tools/bench_inputs.py (synthetic inputs), tools/bench_roofline.py (roofline records and their rule), tools/bench_baselines.py (CPU legs).
 """
@@ -59,8 +66,24 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20000)  # ~2 s of GPU time
     p.add_argument("--warmup", type=int, default=2000)
-    p.add_argument("--settle-s", dest="settle_s", type=float, default=1.5,
-                   help="untimed steps of the same loop for this many seconds BEFORE the warm-up (clocks, caches, allocator); 0 = off")
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline figure: settle phase, dry region and 3 repetitions by default, the instrumented second pass "
+                        "(stage times, roofline records), the reference-order leg, the env-step kernel sweep, the CPU baselines, the exchange probe "
+                        "and the replica check of N > 1, env statistics.  Without it a run sets up, warms up, times EXACTLY --steps steps once and "
+                        "prints the line")
+    p.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the timed path computed in its last step as DIR/<name>.npy (float32): actions, obs, "
+                        "reward, done, success of every env (a fixed seeded sample of %d envs beyond that, their ids in env_rows.npy), the "
+                        "learn() losses, the actor / policy and critic weights.  Same arguments, same inputs; the same outputs (the losses up to the "
+                        "rounding of their sums) where the ring fills in row-tile order (--ordered-slots, on by default here): a GPU per rank and "
+                        "per-tile acting launches, as by default (config.ring_slots)" % (1 << 18))
+    p.add_argument("--ordered-slots", dest="ordered_slots", action=argparse.BooleanOptionalAction, default=None,
+                   help="fill the replay ring in row-tile order (include/hirl4ucav.h HX_LAYOUT_ORDERED_SLOTS): the same arguments draw the same "
+                        "minibatches every run.  Costs ~0.8 us per step at 4,096 envs (in-launch waits of the acting workgroups).  Default: on with "
+                        "--dump-outputs, off otherwise (one atomic per workgroup, as the training driver runs)")
+    p.add_argument("--settle-s", dest="settle_s", type=float, default=None,
+                   help="untimed steps of the same loop for this many seconds BEFORE the warm-up (clocks, caches, allocator); 0 = off.  Default: "
+                        "1.5 with --full (0 with --dump-outputs: a time-bounded phase would make the dumped step depend on the clock), else 0")
     p.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     p.add_argument("--batch", type=int, default=128, help="rows of the minibatch of one learn(); up to 1,024 (beyond 256: the reference's order)")
     p.add_argument("--scenario", default="straight_line", choices=["straight_line", "serpentine", "circular", "mixed"],
@@ -73,9 +96,11 @@ def parse(argv=None):
                         "operands on the bf16 matrix cores at every size (fp32 results up to summation order; f32 takes it from 4,096 rows on); "
                         "bf16: actor AND critic — policy inference and the three 256<->512 products of every network in learn() on bf16 MFMA, fp32 "
                         "accumulation, fp32 master weights / Adam / LayerNorm / dynamics (BASELINE.json configs[4]); bf16_policy: policy inference only")
-    p.add_argument("--reps", type=int, default=3, help="timed repetitions of K steps; value = the median repetition (SURVEY.md 8d)")
-    p.add_argument("--dry-regions", dest="dry_regions", type=int, default=1,
-                   help="untimed barrier-to-barrier regions of K steps between the warm-up and the timed repetitions (declared in the JSON line)")
+    p.add_argument("--reps", type=int, default=None,
+                   help="timed repetitions of K steps; value = the median repetition (SURVEY.md 8d).  Default: 3 with --full, else 1")
+    p.add_argument("--dry-regions", dest="dry_regions", type=int, default=None,
+                   help="untimed barrier-to-barrier regions of K steps between the warm-up and the timed repetitions (declared in the JSON line).  "
+                        "Default: 1 with --full, else 0")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=20.0, help="total budget of the CPU baseline legs")
     p.add_argument("--no-sweep", action="store_true", help="skip the env-step kernel sweep over 4k..4M envs per launch (< 1 s)")
@@ -125,7 +150,16 @@ def parse(argv=None):
     p.add_argument("--inject-front-trip", dest="inject_front_trip", action="store_true",
                    help="tests: the LAST rank sets its front launch's status word after the timed region, as a wait that gave up would — every rank "
                         "must then repeat the run in the reference's order and rank 0 print a valid line")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.settle_s is None:
+        args.settle_s = 1.5 if (args.full and args.dump_outputs is None) else 0.0
+    if args.reps is None:
+        args.reps = 3 if args.full else 1
+    if args.ordered_slots is None:
+        args.ordered_slots = args.dump_outputs is not None
+    if args.dry_regions is None:
+        args.dry_regions = 1 if args.full else 0
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -207,7 +241,7 @@ class Loop:
     else; step_measured() is the same step with events around the stages and, on request, act / env step as two launches with the
     env launch stamped — it is used only AFTER the timed region."""
 
-    def __init__(self, args, rank, world, device, shared_device=False, forced_reason=None):
+    def __init__(self, args, rank, world, device, shared_device=False, forced_reason=None, ordered_slots=True):
         import torch
 
         from hirl4ucav_amd import _lib
@@ -219,7 +253,10 @@ class Loop:
         self.args, self.rank, self.world = args, rank, world
         n = args.envs
         self.max_step = 1900 if args.scenario == "circular" else 1500  # train_all.py:159-183
-        self.replay = DeviceReplay(max(1 << 20, 2 * n), device)
+        # --ordered-slots: ring slots in row-tile order (include/hirl4ucav.h HX_LAYOUT_ORDERED_SLOTS): the same arguments fill the ring, and draw the
+        # minibatches, in the same order every run.  The per-tile acting launches wait in-launch for that; like the front launch's waits, not where ranks
+        # share a GPU.
+        self.replay = DeviceReplay(max(1 << 20, 2 * n), device, ordered_slots=ordered_slots and args.ordered_slots and not shared_device)
         scenario = args.scenario
         if scenario == "mixed":  # contiguous thirds: wavefronts never mix scenarios
             scenario = np.sort((np.arange(n) + rank * n) % 3).astype(np.int32)
@@ -542,15 +579,55 @@ def second_pass(ctx, loop):
     return out
 
 
+DUMP_MAX_ROWS = 1 << 18  # envs per array in --dump-outputs: 20 floats each, 21 MB at most
+
+
+def snapshot_outputs(loop):
+    """--dump-outputs: host copies of what the timed path's LAST step gave its caller — the step's (actions, obs, reward, done, success), the losses
+    of its learn(), the networks that learn() left — taken right after the timed region, before anything else runs on the loop"""
+    import torch
+
+    torch.cuda.synchronize()
+    env, eng = loop.env, loop.eng
+    rows = None
+    if env.n > DUMP_MAX_ROWS:  # a fixed, seeded sample of the envs: the same rows in every run with the same --envs
+        rows = np.sort(np.random.default_rng(0).choice(env.n, DUMP_MAX_ROWS, replace=False))
+
+    def per_env(t):
+        a = t.float().cpu().numpy()
+        return a if rows is None else a[rows]
+
+    out = {"actions": per_env(loop.actions), "obs": per_env(env.obs), "reward": per_env(env.reward), "done": per_env(env.done),
+           "success": per_env(env.success), "losses": np.asarray(eng.losses_host(), np.float32),
+           "actor": (eng.policy if loop.sac else eng.actor).float().cpu().numpy(), "critic": eng.critic.float().cpu().numpy()}
+    if rows is not None:
+        out["env_rows"] = rows.astype(np.float64)
+    return out
+
+
+def dump_outputs(path, outputs):
+    total = sum(a.nbytes for a in outputs.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def measure(ctx, loop):
     m = {"settle_steps": settle(ctx, loop)}
     for _ in range(ctx.args.warmup):
         loop.step()
     m["reps"] = timed_regions(ctx, loop)
+    if ctx.args.dump_outputs is not None and ctx.rank == 0:
+        m["outputs"] = snapshot_outputs(loop)
     if ctx.args.inject_front_trip and loop.front and ctx.rank == ctx.world - 1 and getattr(loop.eng, "_front", None) is not None:
         loop.eng._front[1].fill_(1)  # as a launch-B workgroup that gave up would leave it
-    m.update(second_pass(ctx, loop))
+    if ctx.args.full:
+        m.update(second_pass(ctx, loop))
+    else:  # a plain run: the headline figure only
+        m.update({"m_steps": 0, "exchanging": False, "med": {k: None for k in loop.rec}, "env_kernel_us": [], "fused_us": [], "allreduce": {}})
     m["front_status"] = int(ctx.max_over_ranks(loop.front_status()))  # ONE decision for all ranks
+    m["slot_status"] = int(ctx.max_over_ranks(loop.replay.slot_status()))  # (the same)
     return m
 
 
@@ -687,8 +764,9 @@ def run_rank(args):
     ctx = Ctx(args, rank, world, device, pg, backend, shared_device=world > ngpu)
 
     probe = None
-    if world > 1 and args.agent == "hirl" and (args.exchange == "auto" or (args.exchange == "rccl" and args.exchange_probe and not ctx.shared_device)):
-        # (ranks that share a GPU — the gloo rehearsals — probe only on request: --exchange auto)
+    if world > 1 and args.agent == "hirl" and (args.exchange == "auto" or (args.full and args.exchange == "rccl" and args.exchange_probe and
+                                                                            not ctx.shared_device)):
+        # (ranks that share a GPU — the gloo rehearsals — probe only on request: --exchange auto; a plain run probes only to choose its transport)
         # the probe needs the run's rccl transport: build the loop the run would use with `rccl`, probe, then pick
         chosen = args.exchange
         args.exchange = "rccl"
@@ -715,11 +793,27 @@ def run_rank(args):
         loop = Loop(ref_args, rank, world, device, shared_device=ctx.shared_device, forced_reason=why)
         m = measure(ctx, loop)
 
+    slot_status = m["slot_status"]
+    if slot_status:
+        # a wait of the row-tile-ordered ring slots gave up somewhere (a lower tile could not be placed): slots may have collided, the ring and the
+        # outputs are suspect.  Repeat the run with one atomic per workgroup, the same loop otherwise, in THIS process, and say so in the line.
+        sys.stderr.write(f"bench.py rank {rank}: ordered ring slots tripped (status word {slot_status}); repeating the run with atomic slots\n")
+        loop.close()
+        loop = Loop(loop.args, rank, world, device, shared_device=ctx.shared_device, forced_reason=None if loop.front else loop.loop_reason,
+                    ordered_slots=False)
+        m = measure(ctx, loop)
+
     res = record(ctx, loop, m, tripped, probe)
+    res["config"]["ring_slots"] = ("row-tile order (per-tile acting launches; persistent acting and env-only launches: one atomic per workgroup)"
+                                   if loop.replay.slot_header is not None else
+                                   "one atomic per workgroup" + (f" (row-tile order tripped, status word {slot_status}: run repeated)" if slot_status else ""))
+    res["slot_status"] = int(slot_status)
     if rank == 0:
-        if not args.no_sweep:
+        if args.dump_outputs is not None:
+            dump_outputs(args.dump_outputs, m["outputs"])
+        if args.full and not args.no_sweep:
             res["roofline_env_sweep"] = RL.env_sweep(device)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baselines(args, device)
     loop.close()
     if pg and own_pg:
@@ -757,18 +851,19 @@ def record(ctx, loop, m, tripped, probe):
                                   f"all-reduce of the flat gradients; effective batch = {args.batch} x {world}"},
         "update_steps_per_s": round(args.steps / dt, 1), "update_samples_per_s": round(args.batch * args.steps / dt, 1),
         "timed_region": "R x [K x step() between two barrier + synchronize pairs]; no events, no stamped or split launches inside (those are the "
-                        "second pass); `dry_regions` untimed regions of the same shape run before the first timed one",
-        "stage_us": {"pass": f"second pass, {m['m_steps']} steps after the timed region (events add a few us per step)",
-                     "act+env_step(1 kernel)": None if med["act+env"] is None else round(med["act+env"], 2),
-                     "act(own launch, every 4th step)": None if act_us is None else round(act_us, 2),
-                     "env_step(own launch, every 4th step)": None if med["env"] is None else round(med["env"], 2),
-                     "sample+learn": None if learn_us is None else round(learn_us, 2)},
+                        "second pass, --full); `dry_regions` untimed regions of the same shape run before the first timed one",
     }
+    if args.full:
+        res["stage_us"] = {"pass": f"second pass, {m['m_steps']} steps after the timed region (events add a few us per step)",
+                           "act+env_step(1 kernel)": None if med["act+env"] is None else round(med["act+env"], 2),
+                           "act(own launch, every 4th step)": None if act_us is None else round(act_us, 2),
+                           "env_step(own launch, every 4th step)": None if med["env"] is None else round(med["env"], 2),
+                           "sample+learn": None if learn_us is None else round(learn_us, 2)}
     cfg = res["config"]
     cfg["loop"] = "front" if loop.front else ("reference order (front tripped)" if tripped else "reference order")
     cfg["loop_reason"] = loop.loop_reason
     res["front_status"] = int(tripped)
-    if loop.front and world == 1 and not ctx.pg:
+    if args.full and loop.front and world == 1 and not ctx.pg:
         res["reference_order"] = reference_order_leg(ctx, args)
     if loop.front and args.agent == "hirl" and args.dtype == "f32" and loop.eng.front_x9:
         cfg["acting_product"] = ("fp32 operands, the 256 -> 512 product through the exact three-way bf16 split of both operands (hi | mid | lo), six of "
@@ -782,19 +877,21 @@ def record(ctx, loop, m, tripped, probe):
         cfg["draw"] = ("uniform without replacement over the transitions that are in the ring before AND after this step's insert (drawn from the ring "
                        "as it stood before the step, without the n slots the step may overwrite: HxSample.guard); --no-front draws after the insert, "
                        "like the reference")
-        res["stage_us"]["front launch + rest of learn() (3 of every 4 steps of the second pass; the front launch stamped: + ~25 us of instruments)"] = \
-            None if med["front+back"] is None else round(med["front+back"], 2)
+        if args.full:
+            res["stage_us"]["front launch + rest of learn() (3 of every 4 steps of the second pass; the front launch stamped: + ~25 us of "
+                            "instruments)"] = None if med["front+back"] is None else round(med["front+back"], 2)
 
-    env_roof = RL.env_kernel_roof(args.envs, m["env_kernel_us"])
-    if m["fused_us"]:
-        res["roofline"] = RL.launch_roofline(args, loop, m["fused_us"])
-        res["roofline_env_kernel"] = env_roof
-    else:
-        res["roofline"] = env_roof
-    if learn_us:
-        res["roofline_update"] = RL.update_roof(args, learn_us)
-    if act_us and not loop.uniform:  # (with --actions uniform the 'act' stage is a torch uniform_ fill, not the policy)
-        res["roofline_act"] = RL.act_roof(args, loop, act_us)
+    if args.full:  # the roofline records: from the second pass's stamped launches
+        env_roof = RL.env_kernel_roof(args.envs, m["env_kernel_us"])
+        if m["fused_us"]:
+            res["roofline"] = RL.launch_roofline(args, loop, m["fused_us"])
+            res["roofline_env_kernel"] = env_roof
+        else:
+            res["roofline"] = env_roof
+        if learn_us:
+            res["roofline_update"] = RL.update_roof(args, learn_us)
+        if act_us and not loop.uniform:  # (with --actions uniform the 'act' stage is a torch uniform_ fill, not the policy)
+            res["roofline_act"] = RL.act_roof(args, loop, act_us)
     if ctx.pg:
         ids = [None] * world
         torch.distributed.all_gather_object(ids, (socket.gethostname(), str(getattr(torch.cuda.get_device_properties(device.index), "uuid", device.index))))
@@ -804,7 +901,7 @@ def record(ctx, loop, m, tripped, probe):
                              "rccl_version": ".".join(str(v) for v in torch.cuda.nccl.version()) if ctx.backend == "nccl" else None}
     if probe is not None:
         res["exchange_probe"] = probe
-    if world > 1:  # the replicas must still be bit-identical after every sharded update so far
+    if args.full and world > 1:  # the replicas must still be bit-identical after every sharded update so far
         mine = torch.tensor([loop.eng.replica_checksum()], dtype=torch.int64, device=device)
         every = [torch.zeros_like(mine) for _ in range(world)]
         torch.distributed.all_gather(every, mine)
@@ -815,7 +912,8 @@ def record(ctx, loop, m, tripped, probe):
         if world == 1:
             res["allreduce_note"] = ("world size 1: the collective library short-circuits an in-place all-reduce of one rank (no kernel is launched); "
                                      "the figure is the host-side call on the stream, NOT an exchange time — the N > 1 term stays unmeasured on this box")
-    res["env_stats"] = loop.env.stats_dict()
+    if args.full:
+        res["env_stats"] = loop.env.stats_dict()
     del rank
     return res
 

@@ -27,6 +27,9 @@ class HxStepOpts(ctypes.Structure):
                 ("ev_start", _vp), ("ev_stop", _vp), ("layout", _i32)]
 
 
+LAYOUT_ORDERED_SLOTS = 1 << 16  # HX_LAYOUT_ORDERED_SLOTS: the ring behind HxStepOpts.total carries the slot header (DeviceReplay(ordered_slots=True))
+
+
 def layout(pair, envs_per_block):
     """HX_LAYOUT(pair, envs_per_block) of include/hirl4ucav.h: force the env-step launch shape (0 = library's choice)."""
     return ((1 if pair else 0) << 8) | (int(envs_per_block) // 4)

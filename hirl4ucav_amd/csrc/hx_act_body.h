@@ -490,7 +490,11 @@ __device__ __forceinline__ void act_fused_body(const ActFusedArgs& A, const int 
             const unsigned long long bal = __ballot(store && !env_opp);
             rank = __popcll(bal & ((1ull << (lane & ~1)) - 1ull));  // both lanes of a pair get the env's rank
             nstore = __popcll(bal);
-            if (lane == 0 && nstore > 0) base = atomicAdd((unsigned long long*)A.o.total, (unsigned long long)nstore);
+            const int ntile = (A.rows + ROWS - 1) / ROWS;
+            if ((A.o.layout & HX_LAYOUT_ORDERED_SLOTS) && (long long)ntile * 16 <= A.o.cap)  // (the header holds 3 + cap / 16 words)
+                base = ordered_slots((unsigned long long*)A.o.total, bid, ntile, nstore, lane);
+            else if (lane == 0 && nstore > 0)
+                base = atomicAdd((unsigned long long*)A.o.total, (unsigned long long)nstore);
         }
         __syncthreads();  // actions of all rows in s_act
         STAMP();

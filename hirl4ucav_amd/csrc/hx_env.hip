@@ -67,7 +67,7 @@ void launch_step_shape(const StepArgs& A, hipStream_t st) {
 }
 template <bool INSERT>
 int launch_step(const StepArgs& A, hipStream_t st) {
-    const Layout L = pick_layout(A.n, A.o.layout);
+    const Layout L = pick_layout(A.n, A.o.layout & 0xFFFF);  // (HX_LAYOUT_ORDERED_SLOTS is not a shape)
     if (L.pair) {
         switch (L.epb) {
             case 32: launch_step_shape<true, INSERT, 32>(A, st); return 0;

@@ -519,6 +519,39 @@ __device__ __forceinline__ float dpp_f(float v) {
 __device__ __forceinline__ float swap1(float v) { return dpp_f<0xB1>(v); }  // quad_perm [1,0,3,2]: the other lane of the pair
 __device__ __forceinline__ uint32_t swap1u(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false); }
 
+// HX_LAYOUT_ORDERED_SLOTS: the first ring slot of row tile `tile` of `ntile` in one launch, in row-tile order.  hdr = [total, launch sequence,
+// status, one word per row tile].  Every tile reads total and the sequence, publishes (sequence + 1) << 32 | its row count, and adds up the counts of
+// the tiles below it: those were dispatched before it and publish before they wait.  The last tile advances total and the sequence once it has seen
+// every other tile's word — after every read of them.  Called by all 64 lanes of ONE wave; the result is uniform.  A wait gives up after 4,000,000
+// loads of one word (the bound of the front launch's waits): that happens only if a lower tile cannot be placed (processes that share the device
+// holding its CUs); the tile then counts what it has, its slots may collide with another tile's (still inside the ring), and bit 0 of the status word
+// is set and stays set — utils/buffer.DeviceReplay.slot_status, which bench.py reads after its timed region.
+// Relaxed atomics throughout: a published word carries its count and tag together, nothing else needs ordering, and each tile's store of it takes
+// its data from the load of the sequence word — issued after the load of total, so both have returned before any tile can see the word (and the
+// last tile move total on).  Release / acquire at agent scope would write back and invalidate L2 in every tile: +3.2 us per step at 4,096 envs.
+__device__ __forceinline__ unsigned long long ordered_slots(unsigned long long* hdr, int tile, int ntile, int nstore, int lane) {
+    const unsigned long long t0 = __hip_atomic_load(&hdr[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned tag = (unsigned)__hip_atomic_load(&hdr[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
+    if (lane == 0) __hip_atomic_store(&hdr[3 + tile], ((unsigned long long)tag << 32) | (unsigned)nstore, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    int before = 0;
+    bool late = false;
+    for (int j = lane; j < tile; j += 64) {
+        unsigned long long v;
+        int spins = 0;
+        do {
+            v = __hip_atomic_load(&hdr[3 + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } while ((unsigned)(v >> 32) != tag && !(late = ++spins >= 4000000));
+        before += (int)(unsigned)v;
+    }
+    if (late) atomicOr(&hdr[2], 1ull);
+    for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o);
+    if (tile == ntile - 1 && lane == 0) {
+        __hip_atomic_store(&hdr[0], t0 + (unsigned long long)(before + nstore), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&hdr[1], (unsigned long long)tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return t0 + (unsigned long long)before;
+}
+
 // total % cap without a 64-bit division (the software routine is ~150 instructions on a lane every other lane then waits for):
 // quotient estimate in fp64 (exact for total < 2^52), one correction step either way.  cap < 2^31.
 __device__ __forceinline__ unsigned ring_slot(unsigned long long total, unsigned long long cap, double inv_cap) {

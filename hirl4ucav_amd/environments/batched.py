@@ -60,7 +60,7 @@ class BatchedHarfangEnv:
         o.ring, o.ring_success = (_lib.ptr(r.ring), _lib.ptr(r.success)) if r is not None else (None, None)
         o.cap, o.total = (r.capacity, _lib.ptr(r.total)) if r is not None else (0, None)
         o.stats = _lib.ptr(self.stats)
-        o.layout = self.layout
+        o.layout = self.layout | (_lib.LAYOUT_ORDERED_SLOTS if getattr(r, "slot_header", None) is not None else 0)  # (DeviceReplay(ordered_slots=True))
 
     def reset(self, mask=None):
         """reset() / random_reset() of every env (or of the envs with mask != 0) -> obs [N, 13]."""

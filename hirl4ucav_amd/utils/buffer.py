@@ -10,12 +10,20 @@ from .. import _lib
 
 
 class DeviceReplay:
-    def __init__(self, capacity, device="cuda"):
+    def __init__(self, capacity, device="cuda", ordered_slots=False):
         self.capacity = int(capacity)
         self.device = torch.device(device)
         self.ring = torch.zeros((self.capacity, _lib.ROW_WORDS), dtype=torch.float32, device=self.device)
         self.success = torch.zeros(self.capacity, dtype=torch.int8, device=self.device)
-        self.total = torch.zeros(1, dtype=torch.int64, device=self.device)
+        # ordered_slots (opt-in; bench.py): total, then the launch sequence, a status word and one word per row tile of the per-tile acting launches
+        # (include/hirl4ucav.h HX_LAYOUT_ORDERED_SLOTS) — those launches then fill the ring in row-tile order, the same for the same inputs
+        self.slot_header = torch.zeros(3 + self.capacity // 16, dtype=torch.int64, device=self.device) if ordered_slots else None
+        self.total = self.slot_header[:1] if ordered_slots else torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def slot_status(self):
+        """ordered_slots: nonzero once a launch's wait for a lower row tile gave up (its slots may have collided with another tile's); sticky.
+        0 without ordered slots.  Synchronises."""
+        return 0 if self.slot_header is None else int(self.slot_header[2].item())
 
     def __len__(self):  # buffer.py:53-54 (host sync: for drivers/tests, not the hot loop)
         return min(int(self.total.item()), self.capacity)

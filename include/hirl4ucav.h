@@ -105,6 +105,13 @@ typedef struct HxStepOpts {
                               envs_per_block in {32, 64, 128, 256, 512} (pair) / {64, 128, 256} (solo).  Same results bit for bit. */
 } HxStepOpts;
 #define HX_LAYOUT(pair, envs_per_block) ((((pair) ? 1 : 0) << 8) | ((envs_per_block) / 4))
+/* Opt-in, OR-ed into HxStepOpts.layout: `total` is the first of 3 + cap / 16 words (total, launch sequence, status, one word per row tile) and the
+ * PER-TILE acting launches that step the envs (hx_actor_act_step / hx_sac_act_step up to one round of acting workgroups, the front launch's acting
+ * workgroups) hand out ring slots in row-tile order instead of in the order their workgroups reach the counter: the same inputs fill the ring in
+ * the same order.  Each tile waits in-launch for the lower tiles' counts; a wait that gives up sets bit 0 of the status word (sticky) and its slots
+ * may collide.  The persistent acting kernels and hx_env_step keep one atomic per workgroup.  Without the flag (raw callers with a one-word
+ * `total`) every launch does. */
+#define HX_LAYOUT_ORDERED_SLOTS (1 << 16)
 
 /* HarfangEnv.reset / random_reset (+ Serpentine/Circular variants): HarfangEnv_GYM.py:34-81,171-188,374-406,440-474.
  * mask: NULL = all envs, else only envs with mask[i] != 0.  scenario: per-env ids (NULL = scenario_all for all).

@@ -33,6 +33,86 @@ def test_cpu_baseline_legs_run_without_a_gpu():
     assert sac["kind"] == "port" and sac["value"] > 0 and "SAC" in sac["sample"]
 
 
+def test_plain_run_times_exactly_the_steps_and_full_keeps_the_rest():
+    """A plain run: no settle phase, no dry region, ONE timed region of --steps steps; --full: 1.5 s, 1 and 3 (0 s of settling when dumping
+    outputs: a time-bounded phase would make the dumped step depend on the clock); explicit values always win."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    a = bench.parse(["--steps", "7", "--warmup", "3"])
+    assert (a.full, a.settle_s, a.dry_regions, a.reps, a.steps, a.warmup, a.dump_outputs) == (False, 0.0, 0, 1, 7, 3, None)
+    f = bench.parse(["--full"])
+    assert (f.full, f.settle_s, f.dry_regions, f.reps) == (True, 1.5, 1, 3)
+    assert bench.parse(["--full", "--dump-outputs", "out"]).settle_s == 0.0 and bench.parse(["--dump-outputs", "out"]).dump_outputs == "out"
+    e = bench.parse(["--full", "--settle-s", "0.3", "--dry-regions", "0", "--reps", "5"])
+    assert (e.settle_s, e.dry_regions, e.reps) == (0.3, 0, 5)
+    assert bench.parse(["--reps", "2", "--settle-s", "0.5"]).reps == 2
+    # ring slots in row-tile order (repeatable outputs) where outputs are dumped; one atomic per workgroup otherwise, unless asked
+    assert not a.ordered_slots and bench.parse(["--dump-outputs", "out"]).ordered_slots and bench.parse(["--ordered-slots"]).ordered_slots
+    assert not bench.parse(["--dump-outputs", "out", "--no-ordered-slots"]).ordered_slots
+
+
+def test_dump_outputs_writes_npy_files_within_64_mb(tmp_path):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import pytest
+
+    import bench
+
+    arrays = {"obs": np.arange(26, dtype=np.float32).reshape(2, 13), "losses": np.ones(6, np.float32)}
+    bench.dump_outputs(str(tmp_path / "d"), arrays)
+    assert sorted(os.listdir(tmp_path / "d")) == ["losses.npy", "obs.npy"]
+    np.testing.assert_array_equal(np.load(tmp_path / "d" / "obs.npy"), arrays["obs"])
+    with pytest.raises(AssertionError, match="dump-outputs"):
+        bench.dump_outputs(str(tmp_path / "e"), {"big": np.zeros((64 << 20) // 4 + 1, np.float32)})
+    assert not (tmp_path / "e").exists()
+
+
+def test_snapshot_of_a_large_population_is_a_fixed_seeded_sample(monkeypatch):
+    """Beyond bench.DUMP_MAX_ROWS envs the per-env arrays are the same sorted, seeded sample of rows in every run (their ids in env_rows); the
+    whole dump stays within 64 MB.  A stand-in for the loop, on CPU tensors."""
+    sys.path.insert(0, ROOT)
+    import types
+
+    import numpy as np
+    import torch
+
+    import bench
+
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+    n = bench.DUMP_MAX_ROWS + 1000
+    env = types.SimpleNamespace(n=n, obs=torch.arange(n * 13, dtype=torch.float32).reshape(n, 13), reward=torch.arange(n, dtype=torch.float32),
+                                done=torch.ones(n, dtype=torch.uint8), success=torch.zeros(n, dtype=torch.int8))
+    eng = types.SimpleNamespace(losses_host=lambda: (1.0, 2.0, 3.0, 4.0, 5.0, 6.0), actor=torch.ones(10), critic=torch.ones(20))
+    loop = types.SimpleNamespace(env=env, eng=eng, sac=False, actions=torch.zeros(n, 4))
+    a, b = bench.snapshot_outputs(loop), bench.snapshot_outputs(loop)
+    rows = a["env_rows"]
+    assert rows.dtype == np.float64 and rows.shape == (bench.DUMP_MAX_ROWS,) and (np.diff(rows) > 0).all() and rows[-1] < n
+    np.testing.assert_array_equal(rows, b["env_rows"])
+    np.testing.assert_array_equal(a["reward"], rows.astype(np.float32))
+    np.testing.assert_array_equal(a["obs"][:, 0], rows * 13)
+    assert a["obs"].shape == (bench.DUMP_MAX_ROWS, 13) and a["done"].dtype == np.float32 and (a["done"] == 1).all()
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+
+
+def test_ring_slot_header_is_opt_in():
+    """DeviceReplay(ordered_slots=True) — bench.py's ring — carries the header of include/hirl4ucav.h HX_LAYOUT_ORDERED_SLOTS behind `total`
+    (3 + cap / 16 words: total, launch sequence, status, one word per row tile); every other ring keeps a one-word counter."""
+    sys.path.insert(0, ROOT)
+    import torch
+
+    from hirl4ucav_amd.utils.buffer import DeviceReplay
+
+    plain = DeviceReplay(64, "cpu")
+    assert plain.slot_header is None and plain.total.numel() == 1 and plain.slot_status() == 0
+    r = DeviceReplay(64, "cpu", ordered_slots=True)
+    assert r.slot_header.numel() == 3 + 64 // 16 and r.total.data_ptr() == r.slot_header.data_ptr()
+    r.store_rows(torch.ones(5, 32))
+    assert int(r.slot_header[0]) == 5 and len(r) == 5 and r.slot_status() == 0
+    r.slot_header[2] = 1  # what a launch whose wait gave up leaves
+    assert r.slot_status() == 1
+
+
 def test_workload_label_names_a_baseline_config_only_when_the_arguments_match():
     sys.path.insert(0, ROOT)
     import bench

@@ -6,6 +6,7 @@ import signal
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
@@ -119,12 +120,12 @@ def check(d, n_gpus, steps, warmup, envs=4096, dtype="f32", fused=True, shared_g
 
 
 needs_gpu = pytest.mark.skipif(not torch.cuda.is_available(), reason="needs a GPU")
-FAST = ["--steps", "60", "--warmup", "10", "--no-sweep", "--no-cpu-baseline", "--settle-s", "0.2"]
+FAST = ["--full", "--steps", "60", "--warmup", "10", "--no-sweep", "--no-cpu-baseline", "--settle-s", "0.2"]
 
 
 @needs_gpu
 def test_bench_single_gpu_line():
-    d = run([sys.executable, "bench.py", "--steps", "120", "--warmup", "20", "--cpu-seconds", "6", "--settle-s", "0.3"])
+    d = run([sys.executable, "bench.py", "--full", "--steps", "120", "--warmup", "20", "--cpu-seconds", "6", "--settle-s", "0.3"])
     check(d, 1, 120, 20)
     assert "configs[1]" in d["config"]["workload"]
     c = d["cpu_baseline"]
@@ -139,6 +140,27 @@ def test_bench_single_gpu_line():
     tp = d["roofline"]["traffic_from_profiles"]
     assert d["roofline"]["traffic"] == tp["bytes"] == tp["fetch_bytes"] + tp["write_bytes"] and tp["source"] == "profiles/pmc_env_traffic.json"
     assert d["roofline_env_kernel"]["traffic"] == d["roofline_env_kernel"]["traffic_from_profiles"]["bytes"]
+
+
+@needs_gpu
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """Without --full: set-up, W warm-up steps, EXACTLY K timed steps in one region, the line — none of what --full adds.  --dump-outputs writes what
+    the last timed step gave its caller, float32 (the sample taken beyond 262,144 envs: tests/test_bench_cpu.py)."""
+    d = run([sys.executable, "bench.py", "--steps", "50", "--warmup", "10", "--dump-outputs", str(tmp_path / "a")])
+    assert d["steps"] == 50 and d["warmup"] == 10 and d["settle_steps"] == 0 and d["dry_regions"] == 0 and d["n_gpus"] == 1
+    assert d["repetitions"]["count"] == 1 and d["repetitions"]["ms_per_step"] == [d["ms_per_step"]]
+    assert d["metric"].startswith("env steps/sec") and d["unit"] == "env steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] > 0 and abs(d["value"] - 4096 * 1e3 / d["ms_per_step"]) < 1e-3 * d["value"]
+    assert d["config"]["loop"] == "front" and d["front_status"] == 0 and "configs[1]" in d["config"]["workload"]
+    assert d["config"]["ring_slots"].startswith("row-tile order") and d["slot_status"] == 0  # (--dump-outputs: repeatable outputs)
+    for k in ("stage_us", "roofline", "roofline_update", "roofline_act", "reference_order", "cpu_baseline", "roofline_env_sweep", "env_stats"):
+        assert k not in d, k
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    shapes = {"actions": (4096, 4), "obs": (4096, 13), "reward": (4096,), "done": (4096,), "success": (4096,), "losses": (6,)}
+    assert set(a) == set(shapes) | {"actor", "critic"}
+    for name, arr in a.items():
+        assert arr.dtype == np.float32 and np.isfinite(arr).all() and arr.shape == shapes.get(name, arr.shape), name
+    assert np.abs(a["actions"]).max() <= 1 and a["actor"].ndim == a["critic"].ndim == 1 and a["critic"].size > a["actor"].size > 0
 
 
 @needs_gpu
@@ -232,7 +254,7 @@ def test_two_rank_launch_soak():
     """The two-rank launch form N times in a row (the hang of round 2 showed once in a dozen runs): every run must finish."""
     for k in range(int(os.environ["HX_SOAK"])):
         d = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
-                 str(29400 + (os.getpid() + k) % 500), "bench.py", "--gpus", "2", "--steps", "40", "--warmup", "5", "--reps", "1", "--no-cpu-baseline",
+                 str(29400 + (os.getpid() + k) % 500), "bench.py", "--gpus", "2", "--full", "--steps", "40", "--warmup", "5", "--reps", "1", "--no-cpu-baseline",
                  "--no-sweep", "--settle-s", "0.3", "--measure-steps", "16"], env={"HX_BENCH_BACKEND": "gloo"})
         assert d["replicas_identical"] is True, k
 
@@ -250,10 +272,10 @@ def test_front_loop_under_contention_gives_a_valid_line_either_way():
 # peer-read exchanges with both ranks on ONE GPU: the waiting rank's kernel shares the chip with the peer's launches — with 16 workgroups
 # (OneShotExchange picks that when ranks share a device; 256 spinning workgroups keep the peer's 1024-thread workgroups from being placed
 # for seconds at a time) — a functional check with a long timeout; ranks with a GPU each never wait like that
-PEER = ["--steps", "12", "--warmup", "2", "--no-cpu-baseline", "--no-sweep", "--settle-s", "0", "--exchange-timeout-ms", "120000", "--measure-steps", "16"]
+PEER = ["--full", "--steps", "12", "--warmup", "2", "--no-cpu-baseline", "--no-sweep", "--settle-s", "0", "--exchange-timeout-ms", "120000", "--measure-steps", "16"]
 GLOO = {"HX_BENCH_BACKEND": "gloo"}
 # the FRONT loop on a shared GPU, asked for explicitly: short on purpose — a box on which its waits DID run into their ~1 s bound pays that per launch
-SHORT = ["--steps", "20", "--warmup", "4", "--no-cpu-baseline", "--no-sweep", "--settle-s", "0", "--measure-steps", "16"]
+SHORT = ["--full", "--steps", "20", "--warmup", "4", "--no-cpu-baseline", "--no-sweep", "--settle-s", "0", "--measure-steps", "16"]
 
 
 def check_two_ranks(d, steps, warm, exchange, world=2, sac=False):

@@ -6,6 +6,6 @@ A=$(realpath "$1"); B=$(realpath "$2"); N=${3:-3}; shift 3 || shift $#
 cd "${GRAFT_REPO_ROOT:-$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)}"
 for i in $(seq "$N"); do
   for L in "$A" "$B"; do
-    HX_LIBRARY="$L" python3 bench.py --no-sweep --no-cpu-baseline "$@" 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$(basename "$L")', round(d['ms_per_step']*1e3,2), 'us/step', d.get('update_steps_per_s'))"
+    HX_LIBRARY="$L" python3 bench.py --full --no-sweep --no-cpu-baseline "$@" 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$(basename "$L")', round(d['ms_per_step']*1e3,2), 'us/step', d.get('update_steps_per_s'))"
   done
 done

@@ -10,10 +10,10 @@ cd "$R"
 : > "$O/bench_large_batch.jsonl"
 for cfg in "--batch 128" "--batch 256" "--batch 256 --no-front" "--batch 512" "--batch 1024" "--batch 512 --dtype bf16" "--batch 1024 --dtype bf16"; do
   # shellcheck disable=SC2086
-  python3 bench.py $cfg --no-cpu-baseline --no-sweep --steps 6000 --warmup 500 2>/dev/null | tail -1 >> "$O/bench_large_batch.jsonl"
+  python3 bench.py --full $cfg --no-cpu-baseline --no-sweep --steps 6000 --warmup 500 2>/dev/null | tail -1 >> "$O/bench_large_batch.jsonl"
 done
 for B in 512 1024; do
-  ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_b$B" -- python3 "$R/bench.py" --no-cpu-baseline --no-sweep --steps 2000 --warmup 300 --settle-s 0.5 --batch $B > "$O/bench_batch${B}_line_under_rocprof.json" 2> "$O/bench_batch${B}_rocprof.err" )
+  ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_b$B" -- python3 "$R/bench.py" --full --no-cpu-baseline --no-sweep --steps 2000 --warmup 300 --settle-s 0.5 --batch $B > "$O/bench_batch${B}_line_under_rocprof.json" 2> "$O/bench_batch${B}_rocprof.err" )
   cp "$O"/prof_b$B/*/*kernel_stats.csv "$O/bench_batch${B}_kernel_stats.csv" 2>/dev/null
   rm -rf "$O/prof_b$B"
 done

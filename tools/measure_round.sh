@@ -10,13 +10,13 @@ TAG=${1:-r06}; QUICK=${2:-}
 O="$R/gpurun_out/$TAG"
 mkdir -p "$O"
 cd "$R"
-python3 bench.py > "$O/bench_default_line_with_sweep_and_cpu.json" 2> "$O/bench_default.err"
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$O/bench_driver_form_steps20_warmup5.json" 2>/dev/null
+python3 bench.py --full > "$O/bench_default_line_with_sweep_and_cpu.json" 2> "$O/bench_default.err"
+python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$O/bench_driver_form_steps20_warmup5.json" 2>/dev/null
 : > "$O/bench_other_configs.jsonl"
 while read -r cfg; do
   [ -z "$cfg" ] && continue
   # shellcheck disable=SC2086
-  python3 bench.py $cfg --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 >> "$O/bench_other_configs.jsonl"
+  python3 bench.py --full $cfg --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 >> "$O/bench_other_configs.jsonl"
 done <<'CFGS'
 --no-front
 --dtype bf16
@@ -46,7 +46,7 @@ CFGS
 STEPS=4000
 stats() {  # stats <name> <bench flags...>: per-kernel stats of a $STEPS-step run under rocprofv3
   local name=$1; shift
-  ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_$name" -- python3 "$R/bench.py" --no-cpu-baseline --no-sweep --steps $STEPS --warmup 500 --settle-s 0.5 "$@" > "$O/bench_${name}_line_under_rocprof.json" 2> "$O/bench_${name}_rocprof.err" )
+  ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_$name" -- python3 "$R/bench.py" --full --no-cpu-baseline --no-sweep --steps $STEPS --warmup 500 --settle-s 0.5 "$@" > "$O/bench_${name}_line_under_rocprof.json" 2> "$O/bench_${name}_rocprof.err" )
   cp "$O"/prof_"$name"/*/*kernel_stats.csv "$O/bench_${name}_kernel_stats.csv" 2>/dev/null
   rm -rf "$O/prof_$name"
 }
@@ -68,11 +68,11 @@ if [ -z "$QUICK" ]; then
 fi
 # the sharded rank's launch sequence with its two messages per actor call through RCCL (world size 1): the launcher is a python -m module, so the
 # profiler wraps the RANK (bench.py re-enters itself as the single rank when WORLD_SIZE is set)
-( cd /tmp && export TMPDIR=/tmp && WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_nccl1" -- python3 "$R/bench.py" --gpus 1 --staged --no-cpu-baseline --no-sweep --steps 4000 --warmup 500 --settle-s 0.5 > "$O/bench_staged_nccl_world1_line_under_rocprof.json" 2> "$O/bench_staged_nccl_world1.err" )
+( cd /tmp && export TMPDIR=/tmp && WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_nccl1" -- python3 "$R/bench.py" --full --gpus 1 --staged --no-cpu-baseline --no-sweep --steps 4000 --warmup 500 --settle-s 0.5 > "$O/bench_staged_nccl_world1_line_under_rocprof.json" 2> "$O/bench_staged_nccl_world1.err" )
 cp "$O"/prof_nccl1/*/*kernel_stats.csv "$O/bench_staged_nccl_world1_kernel_stats.csv" 2>/dev/null
 rm -rf "$O/prof_nccl1"
-WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29518 python3 bench.py --gpus 1 --staged --no-cpu-baseline --no-sweep > "$O/bench_staged_nccl_world1.json" 2>/dev/null
+WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29518 python3 bench.py --full --gpus 1 --staged --no-cpu-baseline --no-sweep > "$O/bench_staged_nccl_world1.json" 2>/dev/null
 # the same through torch.distributed.all_reduce (the round-3 path): what taking the host out of the exchange is worth at world size 1
-WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29519 python3 bench.py --gpus 1 --staged --exchange rccl-torch --no-cpu-baseline --no-sweep > "$O/bench_staged_nccl_world1_torch_allreduce.json" 2>/dev/null
+WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29519 python3 bench.py --full --gpus 1 --staged --exchange rccl-torch --no-cpu-baseline --no-sweep > "$O/bench_staged_nccl_world1_torch_allreduce.json" 2>/dev/null
 ls -la "$O"
 tail -c 400 "$O/bench_driver_form_steps20_warmup5.json"

@@ -10,7 +10,7 @@ cd "$R"
 while read -r cfg; do
   [ -z "$cfg" ] && continue
   # shellcheck disable=SC2086
-  timeout 300 python3 bench.py $cfg --reps 1 --warmup 100 --no-cpu-baseline --no-sweep 2>"$O/soak.err" | tail -1 >> "$O/soak_front_roles.jsonl" || { echo "FAILED: $cfg"; tail -5 "$O/soak.err"; }
+  timeout 300 python3 bench.py --full $cfg --reps 1 --warmup 100 --no-cpu-baseline --no-sweep 2>"$O/soak.err" | tail -1 >> "$O/soak_front_roles.jsonl" || { echo "FAILED: $cfg"; tail -5 "$O/soak.err"; }
 done <<'CFGS'
 --dtype bf16 --steps 400000
 --envs 16384 --scenario mixed --dtype bf16 --steps 300000

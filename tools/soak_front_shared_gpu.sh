@@ -13,7 +13,7 @@ run_set() {  # $1 = label, $2.. = bench flags (environment: as exported by the c
   local label=$1; shift
   local pids=()
   for p in $(seq 1 "$P"); do
-    timeout 600 python3 bench.py "$@" --steps "$K" --reps 1 --warmup 100 --no-cpu-baseline --no-sweep > "$O/p$p.out" 2> "$O/p$p.err" &
+    timeout 600 python3 bench.py --full "$@" --steps "$K" --reps 1 --warmup 100 --no-cpu-baseline --no-sweep > "$O/p$p.out" 2> "$O/p$p.err" &
     pids+=($!)
   done
   local ok=1

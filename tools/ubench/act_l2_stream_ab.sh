@@ -32,7 +32,7 @@ TAG=${2:-r06_act_l2_stream_ab}; O="$R/gpurun_out"; mkdir -p "$O"
     for rep in 1 2 3; do
       for L in libhx_mi355.so libhx_hot1.so libhx_hot2.so; do
         # shellcheck disable=SC2086
-        HX_LIBRARY="$R/hirl4ucav_amd/$L" python3 bench.py $cfg --no-cpu-baseline --no-sweep --steps 6000 --warmup 500 2>/dev/null | tail -1 | python3 -c "
+        HX_LIBRARY="$R/hirl4ucav_amd/$L" python3 bench.py --full $cfg --no-cpu-baseline --no-sweep --steps 6000 --warmup 500 2>/dev/null | tail -1 | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 print('$L', '[$cfg]', '|', round(d['ms_per_step'] * 1e3, 2), 'us/step | dominant launch', round(d['roofline']['us_per_launch'], 2), 'us | act alone', d.get('roofline_act', {}).get('us'))"

@@ -13,7 +13,7 @@ TAG=${1:-r06_back_fold_ab}; O="$R/gpurun_out"; mkdir -p "$O"
     for rep in 1 2 3; do
       for fold in 0 1; do
         # shellcheck disable=SC2086
-        HX_BACK_FOLD=$fold python3 bench.py $cfg --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | python3 -c "
+        HX_BACK_FOLD=$fold python3 bench.py --full $cfg --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 print('fold=$fold', '[$cfg]', '|', round(d['ms_per_step'] * 1e3, 2), 'us/step', d['repetitions']['ms_per_step'], '| front_status', d['front_status'], '| sample+learn', d['stage_us']['sample+learn'])"

@@ -1,6 +1,7 @@
 import sys, os
-sys.path.insert(0, "/root/repo")
-os.chdir("/root/repo")
+REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, REPO)
+os.chdir(REPO)
 import torch  # noqa: F401 (CUDA context for the imports below)
 from tests import test_bf16_update_gpu as T
 from hirl4ucav_amd.agents import engine as E

@@ -6,7 +6,7 @@ while read -r cfg; do
   [ -z "$cfg" ] && continue
   for c in 1 0 1 0; do
     # shellcheck disable=SC2086
-    HX_FRONT_C=$c python3 bench.py $cfg --no-cpu-baseline --no-sweep --reps 3 2>/dev/null | python3 -c "
+    HX_FRONT_C=$c python3 bench.py --full $cfg --no-cpu-baseline --no-sweep --reps 3 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('HX_FRONT_C=$c', '$cfg', '|', round(d['value']/1e6,1), 'M', round(d['ms_per_step']*1e3,2), 'us', d['update_steps_per_s'])"
   done

@@ -6,7 +6,7 @@ for P in 1 2 3; do
   echo "== $P process(es), launch C riding (HX_FRONT_C=1), 8,192 envs, 3,000 steps each"
   pids=()
   for p in $(seq 1 $P); do
-    ( timeout 200 env HX_FRONT_C=1 python3 bench.py --envs 8192 --scenario circular --type linear --bc_weight 0.5 --steps 3000 --reps 1 --warmup 100 --no-cpu-baseline --no-sweep > /tmp/cp$p.out 2> /tmp/cp$p.err; echo "exit code $?" >> /tmp/cp$p.err ) &
+    ( timeout 200 env HX_FRONT_C=1 python3 bench.py --full --envs 8192 --scenario circular --type linear --bc_weight 0.5 --steps 3000 --reps 1 --warmup 100 --no-cpu-baseline --no-sweep > /tmp/cp$p.out 2> /tmp/cp$p.err; echo "exit code $?" >> /tmp/cp$p.err ) &
     pids+=($!)
   done
   wait

@@ -11,17 +11,17 @@ print('$1', round(d['ms_per_step'] * 1e3, 2), 'us/step', round(d['value'] / 1e6,
 {
   for rep in 1 2; do
     for w in 176 128 144 160 192; do
-      HX_FRONT_PERSIST_WGS=$w python3 bench.py --envs 16384 --scenario mixed --dtype bf16 --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "16,384 mixed bf16, acting workgroups <= $w"
+      HX_FRONT_PERSIST_WGS=$w python3 bench.py --full --envs 16384 --scenario mixed --dtype bf16 --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "16,384 mixed bf16, acting workgroups <= $w"
     done
   done
   for rep in 1 2; do
     for w in 176 128 256; do
-      HX_FRONT_PERSIST_WGS=$w python3 bench.py --envs 8192 --scenario mixed --dtype bf16 --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "8,192 mixed bf16, acting workgroups <= $w"
+      HX_FRONT_PERSIST_WGS=$w python3 bench.py --full --envs 8192 --scenario mixed --dtype bf16 --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "8,192 mixed bf16, acting workgroups <= $w"
     done
   done
   for rep in 1 2; do
     for o in 0 1 2; do
-      HX_FRONT_ORDER=$o python3 bench.py --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "4,096 fp32, HX_FRONT_ORDER=$o"
+      HX_FRONT_ORDER=$o python3 bench.py --full --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "4,096 fp32, HX_FRONT_ORDER=$o"
     done
   done
 } 2>&1 | tee "$O/ab.txt"

@@ -12,13 +12,13 @@ print('$1', round(d['ms_per_step'] * 1e3, 2), 'us/step', round(d['value'] / 1e6,
 {
   for rep in 1 2 3; do
     for m in 1 0; do
-      HX_FRONT_ROWMAP=$m python3 bench.py --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "rowmap=$m default-run"
-      HX_FRONT_ROWMAP=$m python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "rowmap=$m driver-form"
+      HX_FRONT_ROWMAP=$m python3 bench.py --full --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "rowmap=$m default-run"
+      HX_FRONT_ROWMAP=$m python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "rowmap=$m driver-form"
     done
   done
   for m in 1 0; do
-    HX_FRONT_ROWMAP=$m python3 bench.py --envs 8192 --scenario circular --type linear --bc_weight 0.5 --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "rowmap=$m circ8192"
-    HX_FRONT_ROWMAP=$m python3 bench.py --dtype bf16 --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "rowmap=$m bf16-4096"
+    HX_FRONT_ROWMAP=$m python3 bench.py --full --envs 8192 --scenario circular --type linear --bc_weight 0.5 --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "rowmap=$m circ8192"
+    HX_FRONT_ROWMAP=$m python3 bench.py --full --dtype bf16 --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "rowmap=$m bf16-4096"
   done
 } | tee "$O/ab.txt"
 [ -n "${NO_PMC:-}" ] && exit 0

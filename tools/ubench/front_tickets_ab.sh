@@ -5,10 +5,10 @@ cd $GRAFT_REPO_ROOT
 HX_FRONT_TICKETS=1 python -m pytest tests/test_front_gpu.py -m gpu -x -q 2>&1 | tail -3
 for rep in 1 2 3; do
  for t in 0 1; do
-  HX_FRONT_TICKETS=$t python bench.py --no-cpu-baseline --no-sweep 2>/dev/null | python -c "
+  HX_FRONT_TICKETS=$t python bench.py --full --no-cpu-baseline --no-sweep 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('tickets=$t default', round(d['ms_per_step']*1e3,2), 'us', 'front launch', d['roofline']['us_per_launch'])"
-  HX_FRONT_TICKETS=$t python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-sweep 2>/dev/null | python -c "
+  HX_FRONT_TICKETS=$t python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-sweep 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('tickets=$t driver form', round(d['ms_per_step']*1e3,2), 'us', [round(x*1e3,1) for x in d['repetitions']['ms_per_step']])"
  done

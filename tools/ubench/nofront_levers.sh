@@ -10,10 +10,10 @@ d = json.loads(sys.stdin.read())
 print('$1', round(d['ms_per_step'] * 1e3, 2), 'us/step', round(d['value'] / 1e6, 2), 'M env steps/s', round(d.get('update_steps_per_s', 0)), 'learn()/s')"; }
 {
   for rep in 1 2 3; do
-    python3 bench.py --no-front --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "reference order, default             "
-    HX_FWD_NT64=1 python3 bench.py --no-front --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "reference order, launch B in 64 columns"
-    python3 bench.py --no-front --dtype f32x9 --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "reference order, exact-split acting   "
-    python3 bench.py --no-front --steps 20 --warmup 5 --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "reference order, default, driver form "
-    python3 bench.py --no-front --dtype f32x9 --steps 20 --warmup 5 --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "reference order, exact-split, driver form"
+    python3 bench.py --full --no-front --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "reference order, default             "
+    HX_FWD_NT64=1 python3 bench.py --full --no-front --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "reference order, launch B in 64 columns"
+    python3 bench.py --full --no-front --dtype f32x9 --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "reference order, exact-split acting   "
+    python3 bench.py --full --no-front --steps 20 --warmup 5 --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "reference order, default, driver form "
+    python3 bench.py --full --no-front --dtype f32x9 --steps 20 --warmup 5 --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | line "reference order, exact-split, driver form"
   done
 } 2>&1 | tee "$O/ab.txt"

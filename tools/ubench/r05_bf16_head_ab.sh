@@ -17,7 +17,7 @@ O="$R/gpurun_out/$TAG"; mkdir -p "$O"; cd "$R"
     for rep in 1 2; do
       for L in "$A" "$B"; do
         # shellcheck disable=SC2086
-        HX_LIBRARY="$L" python3 bench.py $cfg --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | python3 -c "
+        HX_LIBRARY="$L" python3 bench.py --full $cfg --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 r = d['roofline']

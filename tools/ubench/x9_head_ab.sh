@@ -38,7 +38,7 @@ for cfg in "--envs 65536 --scenario circular --type linear --bc_weight 0.5" "--a
   for rep in 1 2; do
     for L in $LA $LB; do
       # shellcheck disable=SC2086
-      HX_LIBRARY="$R/$L" python3 bench.py $cfg --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | python3 -c "
+      HX_LIBRARY="$R/$L" python3 bench.py --full $cfg --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 print('$(basename "$L")', '[$cfg]', '|', round(d['value'] / 1e6, 1), 'M env steps/s', round(d['ms_per_step'] * 1e3, 2), 'us/step | dominant launch', round(d['roofline']['us_per_launch'], 2), 'us')"

@@ -55,7 +55,7 @@ PY
     for rep in 1 2; do
       for L in hirl4ucav_amd/libhx_mi355.so hirl4ucav_amd/libhx_x9full.so; do
         # shellcheck disable=SC2086
-        HX_LIBRARY="$R/$L" python3 bench.py $cfg --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | python3 -c "
+        HX_LIBRARY="$R/$L" python3 bench.py --full $cfg --no-cpu-baseline --no-sweep 2>/dev/null | tail -1 | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 print('$(basename "$L")', '[$cfg]', '|', round(d['value'] / 1e6, 1), 'M env steps/s', round(d['ms_per_step'] * 1e3, 2), 'us/step | dominant launch', round(d['roofline']['us_per_launch'], 2), 'us')"
