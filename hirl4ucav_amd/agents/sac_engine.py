@@ -16,7 +16,7 @@ _P = ctypes.POINTER
 
 class HxSacNets(ctypes.Structure):
     _fields_ = [(k, _vp) for k in ("policy", "critic", "target_critic", "grad_policy", "grad_critic", "m_policy", "v_policy", "m_critic",
-                                   "v_critic", "losses", "alpha_state", "ws", "policy_w2_f32i", "policy_w2_x9")]
+                                   "v_critic", "losses", "alpha_state", "ws", "policy_w2_f32i", "policy_w2_x9", "w2_bf16_all", "policy_w2_bf16")]
 
 
 class HxSacBatch(ctypes.Structure):
@@ -32,6 +32,10 @@ _lib.register("hx_sac_act_step_f32i", [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_i
 _lib.register("hx_sac_act_x9", [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _i32, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp])
 _lib.register("hx_sac_act_step_x9", [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _i32, _vp, ctypes.c_uint64, ctypes.c_uint32,
                                       ctypes.c_uint32, _vp, _vp, _vp, _P(_lib.HxStepOpts), _vp])
+_lib.register("hx_sac_act_bf16", [_vp, _vp, _vp, ctypes.c_int64, _vp, _i32, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp])
+_lib.register("hx_sac_act_step_bf16", [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _i32, _vp, ctypes.c_uint64, ctypes.c_uint32,
+                                        ctypes.c_uint32, _vp, _vp, _vp, _P(_lib.HxStepOpts), _vp])
+_lib.register("hx_sac_pack_update_images", [_P(HxSacNets), _vp])
 _lib.register("hx_sac_critic_grads", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _i32, _vp])
 _lib.register("hx_sac_critic_grads_sampled", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _P(E.HxSample), _i32, _vp])
 _lib.register("hx_sac_critic_step", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _P(E.HxSample), _i32, _i32, _vp])
@@ -107,7 +111,7 @@ class SacEngine:
         self.alpha_state[3] = 1.0  # log_alpha = 0 -> alpha = 1  (agent.py:106-107)
         self.nets = HxSacNets(*(t.data_ptr() for t in (self.policy, self.critic, self.target_critic, self.grad_policy, self.grad_critic,
                                                         self.m_policy, self.v_policy, self.m_critic, self.v_critic, self.losses,
-                                                        self.alpha_state, self.ws)), None, None)
+                                                        self.alpha_state, self.ws)), None, None, None, None)
         for i, cls in ((5, HxSacNets), (6, HxSacBatch), (0, _lib.HxStepOpts), (2, E.HxHyper), (4, E.HxSample)):
             _lib.check_struct(i, cls)  # this binding's structs against the loaded library's (hx_abi_sizes)
         # fp32 image of the policy's W2 in the acting kernel's operand order (hx_pack_w2_f32i): kept current by hx_sac_adam(which = 1)
@@ -117,6 +121,8 @@ class SacEngine:
         # (hx_sac_act*_x9: every partial product exact, fp32 accumulation; 34 against 45 us at 16,384 rows, tools/ubench/actp_time.py);
         # None: fp32 MFMA at every size.  The hi | mid | lo images are built at the first such call, the policy's optimizer step keeps them current.
         self.x9_rows, self.w2_x9 = 16384, None
+        # set_act_dtype / set_update_dtype: fp32 by default; the bf16 images (one block for the bf16 update, or the acting image alone) when asked for
+        self.act_dtype, self.update_dtype, self.images, self.w2_bf16 = "f32", "f32", None, None
         self.hyper = E.HxHyper(gamma, tau, lr, lr, 0.0, 0.5, 0.0, 0)
         self.target_entropy, self.interval = float(target_entropy), int(target_update_interval)
         self.learning_steps = 0
@@ -132,15 +138,66 @@ class SacEngine:
             self.target_critic.copy_(self.critic)
         self.refresh_images()
 
+    def set_act_dtype(self, dtype):
+        """"f32": policy inference in fp32 (fp32 MFMA, or the exact bf16 split from x9_rows rows on).  "bf16": the 256 -> 512 product on bf16
+        MFMA from a bf16 image of W2 that every policy step keeps current; layer 1 and the Gaussian head stay fp32 (include/hirl4ucav.h
+        "SAC bf16 path").  The bf16 update goes with the bf16 acting image: set the update back to "f32" first."""
+        if dtype not in ("f32", "bf16"):
+            raise ValueError(dtype)
+        if dtype != "bf16" and self.update_dtype == "bf16":
+            raise ValueError("the SAC bf16 update goes with the bf16 acting image (set_update_dtype('f32') first)")
+        self.act_dtype = dtype
+        self._bind_images()
+        self.refresh_images()
+
+    def set_update_dtype(self, dtype):
+        """"f32": learn() on fp32 MFMA (parity 1e-5 vs the reference).  "bf16": the three products of the 256 <-> 512 layer of the policy,
+        both critics and both target critics on bf16 MFMA with fp32 accumulation; master weights, Adam, the Gaussian heads, the log-alpha step
+        and the losses stay fp32.  Goes with the bf16 acting image (set_act_dtype("bf16") first)."""
+        if dtype not in ("f32", "bf16"):
+            raise ValueError(dtype)
+        if dtype == "bf16" and self.act_dtype != "bf16":
+            raise ValueError("the SAC bf16 update goes with the bf16 acting image (set_act_dtype('bf16') first)")
+        self.update_dtype = dtype
+        self._bind_images()
+        self.refresh_images()
+
+    def _bind_images(self):
+        """which images the kernels see: the bf16 update path holds every image in ONE block (its first image is the acting image; no fp32
+        or exact-split image then), a bf16 policy beside the fp32 update its own acting image, the fp32 policy the fp32 image (and, from
+        x9_rows rows on, the exact-split images: rebuilt by the next large call)"""
+        self.nets.policy_w2_x9, self.w2_x9 = None, None
+        if self.update_dtype == "bf16":
+            if self.images is None:
+                L = _lib.load()
+                L.hx_bf16_images_elems.restype = ctypes.c_int64
+                self.images = torch.zeros(int(L.hx_bf16_images_elems()), dtype=torch.bfloat16, device=self.device)
+            self.w2_bf16 = self.images[:H2 * H1]
+            self.nets.w2_bf16_all, self.nets.policy_w2_bf16, self.nets.policy_w2_f32i = self.images.data_ptr(), None, None
+            return
+        self.nets.w2_bf16_all, self.nets.policy_w2_f32i = None, self.w2_f32i.data_ptr()
+        if self.act_dtype == "bf16":
+            if self.w2_bf16 is None or (self.images is not None and self.w2_bf16.data_ptr() == self.images.data_ptr()):
+                self.w2_bf16 = torch.zeros(H2 * H1, dtype=torch.bfloat16, device=self.device)
+            self.nets.policy_w2_bf16 = self.w2_bf16.data_ptr()
+        else:
+            self.nets.policy_w2_bf16 = None
+
     def refresh_images(self):
-        """Rebuild the acting kernel's image of the policy's W2 (after load_params / a checkpoint restore or any direct write to
-        `self.policy`; the policy's Adam step maintains it otherwise)."""
-        _lib.call("hx_pack_w2_f32i", self.policy.data_ptr(), 13, self.w2_f32i.data_ptr(), _lib.stream_ptr())
+        """Rebuild the kernels' images of W2 from the fp32 networks (after load_params / a checkpoint restore or any direct write to a
+        network; the optimizer and Polyak steps maintain them otherwise): whatever images are live."""
+        st = _lib.stream_ptr()
+        if self.update_dtype == "bf16":
+            _lib.call("hx_sac_pack_update_images", ctypes.byref(self.nets), st)
+            return
+        _lib.call("hx_pack_w2_f32i", self.policy.data_ptr(), 13, self.w2_f32i.data_ptr(), st)
+        if self.act_dtype == "bf16":
+            _lib.call("hx_pack_w2_bf16", self.policy.data_ptr(), 13, self.w2_bf16.data_ptr(), st)
         if self.w2_x9 is not None:
-            _lib.call("hx_pack_w2_x9", self.policy.data_ptr(), 13, self.w2_x9.data_ptr(), _lib.stream_ptr())
+            _lib.call("hx_pack_w2_x9", self.policy.data_ptr(), 13, self.w2_x9.data_ptr(), st)
 
     def _x9_for(self, n):
-        if self.x9_rows is None or n < self.x9_rows:
+        if self.act_dtype != "f32" or self.x9_rows is None or n < self.x9_rows:
             return False
         if self.w2_x9 is None:  # first large call: build the images; nets.policy_w2_x9 makes every later policy step refresh them
             self.w2_x9 = torch.zeros(3 * H2 * H1, dtype=torch.bfloat16, device=self.device)
@@ -179,6 +236,7 @@ class SacEngine:
         self.load_params(strip(f["policy"], "policy."), strip(f["critic"], "Q1.Q."), strip(f["critic"], "Q2.Q."), hard_update_target=False)
         self.target_critic[:Q_SIZE].copy_(pack_mlp(strip(f["critic_target"], "Q1.Q."), Q_BLOCK, Q_SIZE, 17, 1, self.device))
         self.target_critic[Q_SIZE:].copy_(pack_mlp(strip(f["critic_target"], "Q2.Q."), Q_BLOCK, Q_SIZE, 17, 1, self.device))
+        self.refresh_images()  # (the target critics' images follow the loaded targets)
 
     def act(self, obs, eps=None, explore=True, seed=0, row0=0, out=None):
         """explore (agent.py:183-188): sampled tanh-Gaussian action (eps [N, 4] given, else Philox); exploit (:191-196): tanh(mean)."""
@@ -187,6 +245,10 @@ class SacEngine:
             out = torch.empty((n, 4), dtype=torch.float32, device=self.device)
         mode = 0 if not explore else (1 if eps is not None else 2)
         self.act_calls += 1
+        if self.act_dtype == "bf16":
+            _lib.call("hx_sac_act_bf16", self.policy.data_ptr(), self.w2_bf16.data_ptr(), obs.data_ptr(), n, out.data_ptr(), mode, _lib.ptr(eps),
+                      int(seed), int(row0), self.act_calls, _lib.stream_ptr())
+            return out
         if self._x9_for(n):
             _lib.call("hx_sac_act_x9", self.policy.data_ptr(), self.w2_x9.data_ptr(), self.w2_f32i.data_ptr(), obs.data_ptr(), n, out.data_ptr(), mode,
                       _lib.ptr(eps), int(seed), int(row0), self.act_calls, _lib.stream_ptr())
@@ -204,6 +266,11 @@ class SacEngine:
         mode = 0 if not explore else (1 if eps is not None else 2)
         self.act_calls += 1
         env.steps_issued += 1
+        if self.act_dtype == "bf16":
+            _lib.call("hx_sac_act_step_bf16", self.policy.data_ptr(), self.w2_bf16.data_ptr(), env.state.data_ptr(), n, env.pitch, env.obs.data_ptr(),
+                      out.data_ptr(), mode, _lib.ptr(eps), int(seed), int(env.env_id0), self.act_calls, env.reward.data_ptr(), env.done.data_ptr(),
+                      env.success.data_ptr(), ctypes.byref(env._opts), _lib.stream_ptr())
+            return out, env.obs, env.reward, env.done, env.success
         if self._x9_for(n):
             _lib.call("hx_sac_act_step_x9", self.policy.data_ptr(), self.w2_x9.data_ptr(), self.w2_f32i.data_ptr(), env.state.data_ptr(), n, env.pitch,
                       env.obs.data_ptr(), out.data_ptr(), mode, _lib.ptr(eps), int(seed), int(env.env_id0), self.act_calls, env.reward.data_ptr(),
@@ -281,12 +348,18 @@ class SacEngine:
         """One iteration of the vector loop — act_step(env) then sample(env.replay, ..., defer=True) then learn() — in FRONT form (include/hirl4ucav.h
         hx_sac_front): the env step and the first forward launch of learn() are ONE launch, the minibatch pre-drawn by the previous call.  As in
         HirlEngine.step_learn the minibatch is drawn from the ring as it stood BEFORE this env step, without the env.n slots the step may overwrite.
-        More than 8,192 envs (the persistent acting kernel), one GPU, the one-call learn(), Philox draws.  -> (actions, obs, reward, done, success)."""
+        More than 8,192 envs (the persistent acting kernel), one GPU, the one-call learn(), Philox draws.  Acting and update in one format: fp32, or
+        bf16 for both (a bf16 policy beside the fp32 update runs act_step, then the sampled learn()).  -> (actions, obs, reward, done, success)."""
         replay, n, B = env.replay, env.n, self.batch
         if self.world > 1 or replay is None or n <= 8192 or getattr(self, "separate_critic_adam", False) or getattr(self, "staged_policy", False):
             raise _lib.HxError("SacEngine.step_learn: one GPU, the one-call learn(), more than 8,192 envs with a replay ring attached")
         if getattr(self, "_pending", None) is not None:
             raise _lib.HxError("step_learn draws its own minibatch: a sample(defer=True) is still pending")
+        if self.act_dtype != self.update_dtype:  # bf16 acting beside the fp32 update: the front launch has no such mix (the reference's order)
+            res = self.act_step(env, explore=explore, seed=act_seed, out=out)
+            self.sample(replay, expert, n_main=n_main, seed=sample_seed, defer=True)
+            self.learn()
+            return res
         if getattr(self, "_front_tiles", None) is None:
             second = torch.zeros(B * 32 + B, dtype=torch.float32, device=self.device)
             self._front_tiles = [(self.rows, self._idx), (second[:B * 32], second[B * 32:].view(torch.int32))]
@@ -311,8 +384,8 @@ class SacEngine:
         self.learning_steps += 1
         batch = HxSacBatch(cur[0].data_ptr(), B, None, None, int(sample_seed), self.learning_steps)
         nets, hyper, st = ctypes.byref(self.nets), ctypes.byref(self.hyper), _lib.stream_ptr()
-        x9 = self._x9_for(n)
-        _lib.call("hx_sac_front", self.policy.data_ptr(), self.w2_x9.data_ptr() if x9 else None, self.w2_f32i.data_ptr(), env.state.data_ptr(), n, env.pitch,
+        x9, b16 = self._x9_for(n), self.update_dtype == "bf16"  # (bf16: the acting image is nets.w2_bf16_all's first)
+        _lib.call("hx_sac_front", self.policy.data_ptr(), self.w2_x9.data_ptr() if x9 else None, None if b16 else self.w2_f32i.data_ptr(), env.state.data_ptr(), n, env.pitch,
                   env.obs.data_ptr(), out.data_ptr(), 2 if explore else 0, None, int(act_seed), int(env.env_id0), self.act_calls, env.reward.data_ptr(),
                   env.done.data_ptr(), env.success.data_ptr(), ctypes.byref(env._opts), nets, ctypes.byref(batch), st)
         env.steps_issued += 1

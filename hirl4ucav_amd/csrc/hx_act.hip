@@ -75,7 +75,7 @@ static void launch_act(const ActFusedArgs& H, hipStream_t st) {
         return;
     }
     if (GAUSS || H.slope == 0.0f) {
-        if (!GAUSS && H.w2b) launch_act_t<false, true, true>(H, st);  // (no entry point hands a Gaussian policy a plain bf16 image: its bf16-core format is the exact split above)
+        if (H.w2b) launch_act_t<GAUSS, true, true>(H, st);  // bf16 (the Gaussian head: hx_sac_act_bf16, its head in fp32)
         else if (H.w2f) launch_act_t<GAUSS, false, true, true>(H, st);
         else launch_act_t<GAUSS, false, true>(H, st);
     } else {
@@ -263,11 +263,11 @@ int hx_actor_act_step_f32i(const float* actor, const float* w2_f32i, float* stat
 /* SacAgent.explore / exploit (SAC/agent.py:183-196) for `rows` observations.  mode 0: exploit = tanh(mean); 1: sample with the
  * standard-normal draws eps[rows][4]; 2: sample with Philox(seed; row0 + row, call).  ws: unused since the whole policy runs in one kernel (may be NULL). */
 static int sac_act_impl(const float* policy, const float* w2f, const float* obs, int64_t rows, float* actions, int32_t mode, const float* eps,
-                        uint64_t seed, uint32_t row0, uint32_t call, void* stream, const uint16_t* w2x = nullptr) {
+                        uint64_t seed, uint32_t row0, uint32_t call, void* stream, const uint16_t* w2x = nullptr, const uint16_t* w2b = nullptr) {
     HX_REQUIRE(policy && obs && actions && rows > 0 && mode >= 0 && mode <= 2 && (mode != 1 || eps), "hx_sac_act: bad arguments");
     const bool x9 = w2x && rows > kFuseEnvMax && persist_enabled();  // the exact split exists for the Gaussian head in the persistent kernel only
     ActFusedArgs H{policy, kPolicy, const_cast<float*>(obs), (int)rows, 0.0f, actions, mode == 1 ? eps : nullptr, 1, 0.0f, mode, seed, row0, call,
-                   nullptr, 0, nullptr, nullptr, nullptr, HxStepOpts{}, 0.0, x9 ? w2x : nullptr, x9 ? nullptr : w2f, x9 ? 1 : 0};
+                   nullptr, 0, nullptr, nullptr, nullptr, HxStepOpts{}, 0.0, x9 ? w2x : w2b, (x9 || w2b) ? nullptr : w2f, x9 ? 1 : 0};
     launch_act<true>(H, (hipStream_t)stream);
     HX_CHECK_LAUNCH("hx_sac_act");
     return 0;
@@ -286,19 +286,19 @@ int hx_sac_act_f32i(const float* policy, const float* w2_f32i, const float* obs,
 /* SacAgent.explore / exploit + HarfangEnv.step in one launch (train_sac.py:238-241): hx_sac_act, then hx_env_step in the kernel's tail. */
 static int sac_act_step_impl(const float* policy, const float* w2f, float* state, int64_t n, int64_t stride, float* obs_io, float* actions, int32_t mode,
                              const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done, int8_t* success,
-                             const HxStepOpts* opts, void* stream, const uint16_t* w2x = nullptr) {
+                             const HxStepOpts* opts, void* stream, const uint16_t* w2x = nullptr, const uint16_t* w2b = nullptr) {
     HX_REQUIRE(policy && mode >= 0 && mode <= 2 && (mode != 1 || eps), "hx_sac_act_step: bad arguments");
     const HxStepOpts o = opts ? *opts : HxStepOpts{};
     if (int rc = check_step_args(state, n, stride, obs_io, actions, reward, done, success, o, "hx_sac_act_step")) return rc;
     const bool x9 = w2x && n > kFuseEnvMax && persist_enabled();
     ActFusedArgs H{policy, kPolicy, obs_io, (int)n, 0.0f, actions, mode == 1 ? eps : nullptr, 1, 0.0f, mode, seed, row0, call,
-                   state, stride, reward, done, success, o, o.cap > 0 ? 1.0 / (double)o.cap : 0.0, x9 ? w2x : nullptr, x9 ? nullptr : w2f, x9 ? 1 : 0};
+                   state, stride, reward, done, success, o, o.cap > 0 ? 1.0 / (double)o.cap : 0.0, x9 ? w2x : w2b, (x9 || w2b) ? nullptr : w2f, x9 ? 1 : 0};
     if (n > kFuseEnvMax) {
         if (persist_enabled() && launch_act_persist(H, true, (hipStream_t)stream)) {
             HX_CHECK_LAUNCH("hx_sac_act_step");
             return 0;
         }
-        if (int rc = sac_act_impl(policy, w2f, obs_io, n, actions, mode, eps, seed, row0, call, stream, w2x)) return rc;
+        if (int rc = sac_act_impl(policy, w2f, obs_io, n, actions, mode, eps, seed, row0, call, stream, w2x, w2b)) return rc;
         return hx_env_step(state, n, stride, actions, obs_io, reward, done, success, opts, stream);
     }
     launch_act<true>(H, (hipStream_t)stream);
@@ -329,6 +329,21 @@ int hx_sac_act_step_x9(const float* policy, const uint16_t* w2_x9, const float* 
     HX_REQUIRE(w2_x9 && w2_f32i && (reinterpret_cast<uintptr_t>(w2_x9) & 15u) == 0 && (reinterpret_cast<uintptr_t>(w2_f32i) & 15u) == 0,
                "hx_sac_act_step_x9: w2_x9 (hi | mid | lo images) and w2_f32i (the fallback up to 8,192 rows) must be 16-byte aligned images of W2");
     return sac_act_step_impl(policy, w2_f32i, state, n, stride, obs_io, actions, mode, eps, seed, row0, call, reward, done, success, opts, stream, w2_x9);
+}
+
+/* bf16 policy inference of the Gaussian policy (include/hirl4ucav.h "SAC bf16 path"): the 256 -> 512 product from the bf16 image w2_bf16
+ * (hx_pack_w2_bf16(policy, 13, ...) or the first image of HxSacNets.w2_bf16_all); layer 1 and the head stay fp32.  Up to 8,192 rows the per-tile
+ * kernel, beyond that the streaming persistent kernel (MODE 2): the same bits for a row either way. */
+int hx_sac_act_bf16(const float* policy, const uint16_t* w2_bf16, const float* obs, int64_t rows, float* actions, int32_t mode, const float* eps,
+                    uint64_t seed, uint32_t row0, uint32_t call, void* stream) {
+    HX_REQUIRE(w2_bf16 && (reinterpret_cast<uintptr_t>(w2_bf16) & 15u) == 0, "hx_sac_act_bf16: w2_bf16 must be a 16-byte aligned bf16 image of W2");
+    return sac_act_impl(policy, nullptr, obs, rows, actions, mode, eps, seed, row0, call, stream, nullptr, w2_bf16);
+}
+int hx_sac_act_step_bf16(const float* policy, const uint16_t* w2_bf16, float* state, int64_t n, int64_t stride, float* obs_io, float* actions,
+                         int32_t mode, const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done,
+                         int8_t* success, const HxStepOpts* opts, void* stream) {
+    HX_REQUIRE(w2_bf16 && (reinterpret_cast<uintptr_t>(w2_bf16) & 15u) == 0, "hx_sac_act_step_bf16: w2_bf16 must be a 16-byte aligned bf16 image of W2");
+    return sac_act_step_impl(policy, nullptr, state, n, stride, obs_io, actions, mode, eps, seed, row0, call, reward, done, success, opts, stream, nullptr, w2_bf16);
 }
 
 }  // extern "C"

@@ -155,8 +155,12 @@ __device__ __forceinline__ void act_fused_body(const ActFusedArgs& A, const int 
     const int cwi = cw;
     constexpr int kHotSlab = 1;
 #endif
-    uint4 w3q = {0u, 0u, 0u, 0u};  // BF16: this lane's A fragment of the final layer (hx_act.h w3_fragment)
-    if constexpr (BF16) w3q = w3_fragment(net, m, cw, lane);
+    // BH = the deterministic head's bf16 format (LayerNorm 2 and the final layer from the accumulators, the final layer on bf16 MFMA).  The
+    // Gaussian head (SacAgent, bf16 acting) keeps the fp32 z2 tile and the fp32 head of the other formats: exp(log_std) amplifies head error,
+    // and the bf16 update's heads are fp32 too.  Its product and LayerNorm 1 are act_persist_stream_body's MODE 2, so both agree bit for bit.
+    constexpr bool BH = BF16 && !GAUSS;
+    uint4 w3q = {0u, 0u, 0u, 0u};  // BH: this lane's A fragment of the final layer (hx_act.h w3_fragment)
+    if constexpr (BH) w3q = w3_fragment(net, m, cw, lane);
     if constexpr (BF16) {
         // requested only now, behind the prologue's own operands: every workgroup pulls the whole 256 KB image through L2 (64 MB per
         // launch at 4,096 rows, ~6 us of L2 service); issued at kernel entry those requests queue up in front of OTHER workgroups'
@@ -202,7 +206,7 @@ __device__ __forceinline__ void act_fused_body(const ActFusedArgs& A, const int 
     // apart at NRT = 2: the pitch is 8 mod 64 dwords, so the four rows of a wave's 16-byte reads fall on disjoint banks)
     constexpr int kRowWaves = 4 * NRT;
     const int gq = lane >> 4, gc = lane & 15;
-    if constexpr (BF16) {
+    if constexpr (BH) {
         // [r5] 32 lanes per row, two rows per wave (hx_act.h row_stats32): the statistics act_persist_bf16_body computes on all of its 16 waves — same bits
         if (wave < ROWS / 2) {
             const int row = 2 * wave + (lane >> 5), c = lane & 31;
@@ -407,7 +411,7 @@ __device__ __forceinline__ void act_fused_body(const ActFusedArgs& A, const int 
 #undef ACT_MUL
 #undef ACT_LOAD
 #undef ACT_STORE
-        if constexpr (BF16) {
+        if constexpr (BH) {
             // [r5] no z2 tile: bias, then the wave's partial LayerNorm-2 statistics of its 32 columns of rows r / 16 + r (hx_act.h, step 1) -> part
             const v4f bb0 = *reinterpret_cast<const v4f*>(net + m.b2() + cw * 16 + 4 * g), bb1 = *reinterpret_cast<const v4f*>(net + m.b2() + 256 + cw * 16 + 4 * g);
 #pragma unroll
@@ -429,6 +433,15 @@ __device__ __forceinline__ void act_fused_body(const ActFusedArgs& A, const int 
                 const v4f o = mfma16_bf16(w3q, hq, v4f{0.f, 0.f, 0.f, 0.f});  // outputs 0..3 of row r in the g = 0 lanes
                 if (g == 0) *reinterpret_cast<v4f*>(outp + ((size_t)cw * ROWS + t * RT + r) * 4) = o;
             }
+        } else if constexpr (BF16) {
+            // Gaussian head: z2 tile (lane (r, g) holds columns 4 g .. + 3 of row r: the operands are swapped), then the fp32 head below
+            const v4f bb0 = *reinterpret_cast<const v4f*>(net + m.b2() + cw * 16 + 4 * g), bb1 = *reinterpret_cast<const v4f*>(net + m.b2() + 256 + cw * 16 + 4 * g);
+#pragma unroll
+            for (int t = 0; t < NRT; ++t) {
+                *reinterpret_cast<v4f*>(z2s + (t * RT + r) * LDA2 + cw * 16 + 4 * g) = acc[t][0] + bb0;
+                *reinterpret_cast<v4f*>(z2s + (t * RT + r) * LDA2 + 256 + cw * 16 + 4 * g) = acc[t][1] + bb1;
+            }
+            himg.store(hps, net, m, tid);  // (h1 / x / W1 are dead: the product read the bf16 tile)
         } else {
         const float bb0 = net[m.b2() + cw * 16 + r], bb1 = net[m.b2() + 256 + cw * 16 + r];
 #pragma unroll
@@ -443,11 +456,10 @@ __device__ __forceinline__ void act_fused_body(const ActFusedArgs& A, const int 
     }
     __syncthreads();
     STAMP();
-    if (!BF16) env_load();  // (BF16: requested in front of the LayerNorm-2 steps above — the short last step would not hide the round trip)
+    if (!BH) env_load();  // (BH: requested in front of the LayerNorm-2 steps above — the short last step would not hide the round trip)
     // head, 16 lanes per row (hx_act.h): waves 0 .. 4 NRT - 1, four rows each, the same rows as in the LN1 statistics
-    if constexpr (BF16) {
+    if constexpr (BH) {
         // [r5] the last step: waves 0 .. NRT - 1, a lane per (row, component) — the 16 column groups' shares in group order + b3, tanh, noise, clamp
-        static_assert(!(BF16 && GAUSS), "the bf16 acting format is the deterministic head's");
         if (wave < NRT) {
             const int lrow = wave * RT + (lane >> 2), c = lane & 3;
             if (lrow < nrow) {

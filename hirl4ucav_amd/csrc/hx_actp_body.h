@@ -330,18 +330,22 @@ __device__ __forceinline__ void act_persist_bf16_body(const ActFusedArgs& A, con
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// fp32 (MODE 0: the fp32 image, fp32 MFMA) and fp32 through the exact three-way bf16 split (MODE 1: hi | mid | lo images, bf16 MFMA; six partial products, hx_act.h HX_X9_TERMS): W2 does
-// not fit the register file (512 / 768 KB), so each wave STREAMS its column slices from L2 once per pass over 64 rows — four row tiles per B
+// fp32 (MODE 0: the fp32 image, fp32 MFMA), fp32 through the exact three-way bf16 split (MODE 1: hi | mid | lo images, bf16 MFMA; six partial products, hx_act.h HX_X9_TERMS)
+// and plain bf16 (MODE 2, the Gaussian head only: one bf16 image, h1 rounded to bf16 once, one product per k step; the head stays fp32).  W2 does
+// not fit the register file beside the Gaussian head's pass (512 / 768 / 256 KB), so each wave STREAMS its column slices from L2 once per pass over 64 rows — four row tiles per B
 // fragment, a quarter of act_fused_kernel<2>'s L2 traffic per row — and z2 leaves the accumulators in two halves of 32 rows through the
 // LDS that held h1.  Per pass: layer 1 | LayerNorm 1 (16 lanes per row, every wave four rows) | the product | 2 x { z2 half -> LDS, head }.
-// The k order of every accumulator, and with MODE 1 the order of the partial products, are act_fused_kernel's: the same bits.
+// The k order of every accumulator, and with MODE 1 the order of the partial products, are act_fused_kernel's: the same bits (MODE 2: act_fused_kernel's
+// Gaussian bf16 instantiation — the same MFMA shape and operand order, the same LayerNorm-1 statistics).
 // ---------------------------------------------------------------------------------------------------------------
 template <int MODE, bool GAUSS, bool ENV>
 struct ActpsLds {
     static constexpr bool X9 = MODE == 1;
+    static_assert(MODE != 2 || GAUSS, "MODE 2 is the Gaussian head's bf16 format (the deterministic head's is act_persist_bf16_body)");
     static constexpr int NRT = 4, TR = NRT * RT, HR = 32;  // rows per pass; rows per z2 half
     typedef HeadImage<GAUSS ? 8 : 4> Img;
-    static constexpr int kH1 = X9 ? 3 * TR * LDB1 / 2 : TR * LDA1;  // h1: three bf16 tiles (hi | mid | lo) or one fp32 tile; before that the fp32 pre-activations
+    // h1: three bf16 tiles (hi | mid | lo), one bf16 tile or one fp32 tile; before that the fp32 pre-activations
+    static constexpr int kH1 = X9 ? 3 * TR * LDB1 / 2 : MODE == 2 ? TR * LDB1 / 2 : TR * LDA1;
     static constexpr int kPre = TR * LDA1;
     static constexpr int kZ = HR * LDA2;
     static constexpr int kTail = ENV ? hxenv::kEnvBlockLds<true, kEnvPass> : 0;
@@ -353,7 +357,7 @@ struct ActpsLds {
 template <int MODE, bool GAUSS, bool ENV, bool RELU>
 __device__ __forceinline__ void act_persist_stream_body(const ActFusedArgs& A, const int tiles_per_wg, const int bid, const int nwg, ActpsLds<MODE, GAUSS, ENV>& SL) {
     typedef ActpsLds<MODE, GAUSS, ENV> Lds;
-    constexpr bool X9 = MODE == 1;
+    constexpr bool X9 = MODE == 1, B1 = MODE == 2;
     constexpr int NRT = 4, TR = NRT * RT, HR = 32;
     constexpr int OUT = GAUSS ? 8 : 4;
     typedef HeadImage<OUT> Img;
@@ -451,7 +455,7 @@ __device__ __forceinline__ void act_persist_stream_body(const ActFusedArgs& A, c
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[4 * k + e] = ln_act<RELU>(v[4 * k + e], mean, rstd, g[e], be[e], slope);
             }
-            if (X9) __syncthreads();  // the three bf16 tiles lie over the pre-activations: every row has been read
+            if (X9 || B1) __syncthreads();  // the bf16 tile(s) lie over the pre-activations: every row has been read
             // the next pass's observations (xs was last read by layer 1, two barriers ago in either mode)
             if (tid < TR * 13) xs[(tid / 13) * XP + tid % 13] = xv;
             xv = obs_of(p + 2, tid);
@@ -465,6 +469,10 @@ __device__ __forceinline__ void act_persist_stream_body(const ActFusedArgs& A, c
                     *reinterpret_cast<uint2*>(dst) = make_uint2(hi[0] | ((unsigned)hi[1] << 16), hi[2] | ((unsigned)hi[3] << 16));
                     *reinterpret_cast<uint2*>(dst + TR * LDB1) = make_uint2(mid[0] | ((unsigned)mid[1] << 16), mid[2] | ((unsigned)mid[3] << 16));
                     *reinterpret_cast<uint2*>(dst + 2 * TR * LDB1) = make_uint2(lo[0] | ((unsigned)lo[1] << 16), lo[2] | ((unsigned)lo[3] << 16));
+                } else if constexpr (B1) {
+                    typedef __bf16 v4bf __attribute__((ext_vector_type(4)));
+                    const v4bf hb = {(__bf16)v[4 * k], (__bf16)v[4 * k + 1], (__bf16)v[4 * k + 2], (__bf16)v[4 * k + 3]};  // round to nearest even
+                    *reinterpret_cast<uint2*>(h1x + row * LDB1 + 64 * k + 4 * gc) = __builtin_bit_cast(uint2, hb);
                 } else {
                     *reinterpret_cast<v4f*>(h1s + row * LDA1 + 64 * k + 4 * gc) = v4f{v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]};
                 }
@@ -476,7 +484,7 @@ __device__ __forceinline__ void act_persist_stream_body(const ActFusedArgs& A, c
         v4f acc[NRT][2];
 #pragma unroll
         for (int t = 0; t < NRT; ++t) acc[t][0] = acc[t][1] = v4f{0.f, 0.f, 0.f, 0.f};
-        const int cw = X9 ? ((wave + bid) & 15) : wave;  // which 32 columns (x9: rotated with the workgroup, as act_fused_kernel)
+        const int cw = (X9 || B1) ? ((wave + bid) & 15) : wave;  // which 32 columns (bf16 images: rotated with the workgroup, as act_fused_kernel)
         if constexpr (X9) {
             v4f rest[NRT][2];
 #pragma unroll
@@ -524,6 +532,31 @@ __device__ __forceinline__ void act_persist_stream_body(const ActFusedArgs& A, c
             for (int t = 0; t < NRT; ++t)
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct) acc[t][ct] = acc[t][ct] + rest[t][ct];
+        } else if constexpr (B1) {
+            // 8 slabs of 32 k; per slab ONE B fragment per column tile (a contiguous kilobyte of the image), PF slabs ahead; weights as A, rows as B,
+            // slabs in ascending order: act_fused_kernel's BF16 product
+            constexpr int NSL = H1 / 32, PF = 2;
+            const uint16_t* img = A.w2b + (size_t)(cw * 8) * 512 + lane * 8;  // column tile 16 + cw at + 16 * 8 * 512, slab sl at + 512 sl
+            uint4 b0[NSL], b1[NSL];
+#pragma unroll
+            for (int sl = 0; sl < PF; ++sl) {
+                b0[sl] = *reinterpret_cast<const uint4*>(img + sl * 512);
+                b1[sl] = *reinterpret_cast<const uint4*>(img + (size_t)16 * 8 * 512 + sl * 512);
+            }
+#pragma unroll
+            for (int sl = 0; sl < NSL; ++sl) {
+                if (sl + PF < NSL) {
+                    b0[sl + PF] = *reinterpret_cast<const uint4*>(img + (sl + PF) * 512);
+                    b1[sl + PF] = *reinterpret_cast<const uint4*>(img + (size_t)16 * 8 * 512 + (sl + PF) * 512);
+                }
+                __builtin_amdgcn_sched_barrier(0);  // the requests stay ahead of the multiply
+#pragma unroll
+                for (int t = 0; t < NRT; ++t) {
+                    const uint4 aq = *reinterpret_cast<const uint4*>(h1x + (t * RT + lr) * LDB1 + 32 * sl + 8 * lg);
+                    acc[t][0] = mfma16_bf16(b0[sl], aq, acc[t][0]);
+                    acc[t][1] = mfma16_bf16(b1[sl], aq, acc[t][1]);
+                }
+            }
         } else {
             // 16 chunks of 16 k: B fragments (one contiguous kilobyte per load from the fp32 image) PF chunks ahead; the h1 fragments are
             // read per chunk (32 MFMAs = 1,024 matrix-core cycles per wave and chunk, and three more waves on the SIMD, cover the round trip)

@@ -137,11 +137,13 @@ __global__ __launch_bounds__(kWide) void actps_front_kernel(ActFusedArgs H, FwdA
 
 // SAC (explore + env step + insert, then SacAgent.learn): the policy's acting launch beyond 8,192 envs is the streaming persistent kernel on every CU (one
 // 64-row pass each at 16,384 envs); the FIRST forward launch of learn() — policy(s'), policy(s), Q1/Q2(s, a): no dependency inside — rides behind it as further
-// workgroups that start as the acting ones leave: one boundary less and no draw in its workgroups (the tiles were pre-drawn).  MODE as act_persist_stream_kernel.
+// workgroups that start as the acting ones leave: one boundary less and no draw in its workgroups (the tiles were pre-drawn).  MODE as act_persist_stream_kernel;
+// MODE 2 (bf16 acting) goes with the SAC bf16 update path: its forward workgroups read the bf16 images (FwdArgsC::images).
 template <int MODE>
 __global__ __launch_bounds__(kWide) void actps_sac_front_kernel(ActFusedArgs H, FwdArgsC FA, FrontCtl C, int tiles) {
+    constexpr bool BF16 = MODE == 2;
     typedef ActpsLds<MODE, true, true> LdsAct;
-    typedef FwdLds<kNT, false, false> LdsF;
+    typedef FwdLds<kNT, false, BF16> LdsF;
     __shared__ union {
         LdsAct act;
         LdsF f;
@@ -153,7 +155,7 @@ __global__ __launch_bounds__(kWide) void actps_sac_front_kernel(ActFusedArgs H, 
     }
     b -= C.n_act;
     const int k = b / C.per, bx = b - k * C.per;
-    fwd_l2_body<kNT, true, false, false, 0>(FA, NoSample{}, bx, (int)C.order[k], u.f, FrontSync{});
+    fwd_l2_body<kNT, true, false, BF16, 0>(FA, NoSample{}, bx, (int)C.order[k], u.f, FrontSync{});
 }
 
 }  // namespace
@@ -161,11 +163,13 @@ __global__ __launch_bounds__(kWide) void actps_sac_front_kernel(ActFusedArgs H, 
 namespace hxu {
 
 int launch_front_sac(const ActFusedArgs& H, const FwdArgs& FA, hipStream_t st) {
-    HX_REQUIRE(H.state && H.o.ring && H.rows > kFuseEnvMax && (H.w2f || (H.w2b && H.x9)), "hx_sac_front: more than 8,192 envs with a replay ring, the policy's W2 from an image");
+    HX_REQUIRE(H.state && H.o.ring && H.rows > kFuseEnvMax && (H.w2f || H.w2b), "hx_sac_front: more than 8,192 envs with a replay ring, the policy's W2 from an image");
+    const bool x9 = H.w2b && H.x9, b16 = H.w2b && !H.x9;
+    HX_REQUIRE(b16 == (FA.images != nullptr), "hx_sac_front: the bf16 acting image goes with the bf16 update path (HxSacNets.w2_bf16_all), and only with it");
     HX_REQUIRE(!FA.sample && FA.njobs >= 3 && FA.njobs <= 8 && FA.slope == 0.0f, "hx_sac_front: the first forward launch of learn() on finished minibatch tiles");
     FwdArgsC CA{};
     for (int j = 0; j < FA.njobs; ++j) { CA.job[j] = pack_fwd(FA.job[j]); CA.job[j].slope = FA.slope; }
-    CA.slope = FA.slope; CA.zero_nf = FA.zero_nf; CA.zero_f = FA.zero_f; CA.zero_i = FA.zero_i; CA.images = nullptr; CA.rowmap = 1;
+    CA.slope = FA.slope; CA.zero_nf = FA.zero_nf; CA.zero_f = FA.zero_f; CA.zero_i = FA.zero_i; CA.images = FA.images; CA.rowmap = 1;
     const int rows = FA.job[0].rows, tiles = (rows + RT - 1) / RT;
     HX_REQUIRE(tiles * FA.njobs < 128, "hx_sac_front: minibatches of at most 256 rows");
     FrontCtl C{};
@@ -174,11 +178,10 @@ int launch_front_sac(const ActFusedArgs& H, const FwdArgs& FA, hipStream_t st) {
     const int npass = (H.rows + 4 * RT - 1) / (4 * RT), per_wg = (npass + 255) / 256;
     C.n_act = (npass + per_wg - 1) / per_wg;
     const dim3 grid((unsigned)(C.n_act + C.per * FA.njobs));
-    const bool x9 = H.w2b && H.x9;
 #define HX_SACF(MODE_) do { \
         if (H.o.ev_start && H.o.ev_stop) hipExtLaunchKernelGGL((actps_sac_front_kernel<MODE_>), grid, dim3(kWide), 0, st, (hipEvent_t)H.o.ev_start, (hipEvent_t)H.o.ev_stop, 0, H, CA, C, per_wg); \
         else hipLaunchKernelGGL((actps_sac_front_kernel<MODE_>), grid, dim3(kWide), 0, st, H, CA, C, per_wg); } while (0)
-    if (x9) HX_SACF(1); else HX_SACF(0);
+    if (b16) HX_SACF(2); else if (x9) HX_SACF(1); else HX_SACF(0);
 #undef HX_SACF
     HX_CHECK_LAUNCH("hx_sac_front");
     return 0;

@@ -32,23 +32,26 @@ int bwd_blocks(const BwdArgs& a, int rows_per_wg) {  // per job (every job of a 
     return ((a.job[0].rows + rows_per_wg - 1) / rows_per_wg) * kColWgB;
 }
 template <int GRP>
-void launch_bwd_t(const BwdArgs& G, hipStream_t st) {
+int launch_bwd_t(const BwdArgs& G, hipStream_t st) {
     BwdArgsC C{};
     for (int j = 0; j < G.njobs; ++j) C.job[j] = pack_bwd(G.job[j], G);
     C.images = G.images;
     static const int rowmap = getenv("HX_XCD_ROWMAP") ? atoi(getenv("HX_XCD_ROWMAP")) : 3;  // bit 1: bwd_l2
     C.rowmap = (rowmap >> 1) & 1;
     const dim3 grid(bwd_blocks(G, (GRP <= 2 || GRP >= 4) ? RT / 2 : RT) , G.njobs);
-    if constexpr (GRP <= 2) {  // the bf16 update path covers the HIRL / TD3 / BC jobs (GRP 3 = SAC's given head gradients: fp32)
-        static const int dbg_off = getenv("HX_DBG_BF16_OFF") ? atoi(getenv("HX_DBG_BF16_OFF")) : 0;
-        if (G.images && !(dbg_off & 2)) {
+    static const int dbg_off = getenv("HX_DBG_BF16_OFF") ? atoi(getenv("HX_DBG_BF16_OFF")) : 0;
+    if (G.images && !(dbg_off & 2)) {  // the bf16 update path: the HIRL / TD3 / BC jobs (GRP 0 .. 2) and SAC's given head gradients (GRP 3)
+        // SAC's folded prologues (GRP 4, 5) have no bf16 form: hx_sac.hip runs the staged q_select / policy_dout launches on that path
+        HX_REQUIRE(GRP <= 3, "launch_bwd: bwd_l2<%d> has no bf16 instantiation (the SAC bf16 path runs the staged form)", GRP);
+        if constexpr (GRP <= 3) {
             if (G.slope == 0.0f) hipLaunchKernelGGL((bwd_l2_kernel<GRP, true, true>), grid, dim3(kWide), 0, st, C);
             else hipLaunchKernelGGL((bwd_l2_kernel<GRP, false, true>), grid, dim3(kWide), 0, st, C);
-            return;
         }
+        return 0;
     }
     if (G.slope == 0.0f) hipLaunchKernelGGL((bwd_l2_kernel<GRP, true>), grid, dim3(kWide), 0, st, C);
     else hipLaunchKernelGGL((bwd_l2_kernel<GRP, false>), grid, dim3(kWide), 0, st, C);
+    return 0;
 }
 
 }  // namespace
@@ -103,14 +106,14 @@ void launch_fwd(const FwdArgs& F, hipStream_t st) {
 #undef HX_FWD
 }
 
-void launch_bwd(int grp, const BwdArgs& G, hipStream_t st) {
+int launch_bwd(int grp, const BwdArgs& G, hipStream_t st) {
     switch (grp) {
-        case 0: launch_bwd_t<0>(G, st); break;
-        case 1: launch_bwd_t<1>(G, st); break;
-        case 2: launch_bwd_t<2>(G, st); break;
-        case 4: launch_bwd_t<4>(G, st); break;
-        case 5: launch_bwd_t<5>(G, st); break;
-        default: launch_bwd_t<3>(G, st); break;
+        case 0: return launch_bwd_t<0>(G, st);
+        case 1: return launch_bwd_t<1>(G, st);
+        case 2: return launch_bwd_t<2>(G, st);
+        case 4: return launch_bwd_t<4>(G, st);
+        case 5: return launch_bwd_t<5>(G, st);
+        default: return launch_bwd_t<3>(G, st);
     }
 }
 

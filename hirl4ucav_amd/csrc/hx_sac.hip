@@ -34,7 +34,24 @@ struct GaussLaunch {
     int nb0;       // workgroups of g[0]; g[1] follows (rows 0: none)
     int nb_gauss;  // workgroups of g[0] + g[1]; Polyak blocks follow
     float* target; const float* source; int n; float tau;  // soft_update (n = 0: none)
+    // SAC bf16 path: the bf16 images of the targets' W2 follow the step (element e of segment s = W2 of head s: [seg_lo[s], + 512 x 256) of target)
+    uint16_t* img[2]; int seg_lo[2];
 };
+// the bf16 image element(s) of the target weight(s) at flat index i (four consecutive k of one column when `four`)
+__device__ __forceinline__ void polyak_image(const GaussLaunch& L, int i, const float* t, bool four) {
+#pragma unroll
+    for (int sg = 0; sg < 2; ++sg) {
+        if (!L.img[sg] || i < L.seg_lo[sg] || i >= L.seg_lo[sg] + H2 * H1) continue;
+        const uint32_t e = (uint32_t)(i - L.seg_lo[sg]), col = e / H1, k = e % H1;
+        if (four) {
+            typedef __bf16 v4bf __attribute__((ext_vector_type(4)));
+            const v4bf r = {(__bf16)t[0], (__bf16)t[1], (__bf16)t[2], (__bf16)t[3]};
+            *reinterpret_cast<uint2*>(L.img[sg] + w2_image_index(col, k)) = __builtin_bit_cast(uint2, r);
+        } else {
+            L.img[sg][w2_image_index(col, k)] = __builtin_bit_cast(uint16_t, (__bf16)t[0]);
+        }
+    }
+}
 __device__ __forceinline__ void gauss_head_rows(const GaussArgs& A, int block);
 __global__ __launch_bounds__(kThreads) void gauss_head_kernel(GaussLaunch L) {
     const int b = blockIdx.x;
@@ -46,8 +63,14 @@ __global__ __launch_bounds__(kThreads) void gauss_head_kernel(GaussLaunch L) {
             t4.x = polyak_update(t4.x, s4.x, L.tau); t4.y = polyak_update(t4.y, s4.y, L.tau);
             t4.z = polyak_update(t4.z, s4.z, L.tau); t4.w = polyak_update(t4.w, s4.w, L.tau);
             *reinterpret_cast<float4*>(L.target + i) = t4;
+            const float tv[4] = {t4.x, t4.y, t4.z, t4.w};
+            polyak_image(L, i, tv, true);  // (W2 starts at a multiple of 4 floats: the float4 is inside or outside)
         } else {
-            for (int c = 0; i + c < L.n; ++c) L.target[i + c] = polyak_update(L.target[i + c], L.source[i + c], L.tau);
+            for (int c = 0; i + c < L.n; ++c) {
+                const float tv = polyak_update(L.target[i + c], L.source[i + c], L.tau);
+                L.target[i + c] = tv;
+                polyak_image(L, i + c, &tv, false);
+            }
         }
         return;
     }
@@ -197,8 +220,12 @@ static SacAux sac_aux(const HxSacNets* N, int B) {
     float* p = N->ws + (size_t)S_COUNT * kSlotFloats * B;
     return SacAux{p, p + 4 * B, p + 5 * B, p + 9 * B};  // [B][4], [B], [B][4], [B][16]
 }
-static void launch_gauss(const GaussArgs& g0, const GaussArgs* g1, float* target, const float* source, int n, float tau, hipStream_t st) {
+static void launch_gauss(const GaussArgs& g0, const GaussArgs* g1, float* target, const float* source, int n, float tau, hipStream_t st,
+                         uint16_t* images = nullptr) {
     GaussLaunch L{};
+    if (images && n > 0) {  // SAC bf16 path: IM_TC1 / IM_TC2 follow the Polyak step of the target critics
+        for (int h = 0; h < 2; ++h) { L.img[h] = images + (IM_TC1 + h) * kImgElems; L.seg_lo[h] = h * kQs.padded() + kQs.W2(); }
+    }
     L.g[0] = g0;
     L.nb0 = (g0.rows + 3) / 4;
     L.nb_gauss = L.nb0;
@@ -226,15 +253,18 @@ static void sac_launch_1(const HxSacNets* N, const HxSacBatch* Bt, FwdArgs& F) {
     F = FwdArgs{};
     F.njobs = 4; F.slope = 0.0f;
     F.zero_f = N->losses; F.zero_nf = 5;
-    F.job[0] = FwdJob{N->policy, kPolicy, src, 17, 0, Head{}, nullptr, 0.f, s[SS_PN], B, 0};
-    F.job[1] = FwdJob{N->policy, kPolicy, src, 0, 0, Head{}, nullptr, 0.f, s[SS_PC], B, 1};
-    F.job[2] = FwdJob{q1, kQs, src, 0, 0, Head{}, nullptr, 0.f, s[SS_Q1], B, 1};
-    F.job[3] = FwdJob{q2, kQs, src, 0, 0, Head{}, nullptr, 0.f, s[SS_Q2], B, 1};
+    F.job[0] = FwdJob{N->policy, kPolicy, src, 17, 0, Head{}, nullptr, 0.f, s[SS_PN], B, 0, IM_ACTOR};
+    F.job[1] = FwdJob{N->policy, kPolicy, src, 0, 0, Head{}, nullptr, 0.f, s[SS_PC], B, 1, IM_ACTOR};
+    F.job[2] = FwdJob{q1, kQs, src, 0, 0, Head{}, nullptr, 0.f, s[SS_Q1], B, 1, IM_C1};
+    F.job[3] = FwdJob{q2, kQs, src, 0, 0, Head{}, nullptr, 0.f, s[SS_Q2], B, 1, IM_C2};
+    F.images = N->w2_bf16_all;  // (NULL: fp32)
 }
 // skip_first: launch 1 has run already (as workgroups of hx_sac_front's launch)
 static int sac_critic_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, const HxSample* S, int32_t polyak_first, void* stream,
                                  int adam_step = 0, bool one_call = false, bool skip_first = false) {
     HX_REQUIRE(N && Bt && Hy && Bt->rows && Bt->batch > 0 && Bt->batch % 16 == 0, "hx_sac_critic_grads: bad arguments");
+    if (int rc = sac_check_formats(N, "hx_sac_critic_grads")) return rc;
+    uint16_t* const im = N->w2_bf16_all;  // the SAC bf16 path (include/hirl4ucav.h), or NULL
     hipStream_t st = (hipStream_t)stream;
     const int B = Bt->batch;
     SampleDev SD{};
@@ -248,8 +278,11 @@ static int sac_critic_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const
     const SacAux X = sac_aux(N, B);
     const RowSrc src{Bt->rows, nullptr, nullptr, 0, 32};
     const int nq = 2 * kQs.padded();
-    if (polyak_first && !one_call)  // soft_update(critic_target, critic) BEFORE the update, agent.py:278-279
+    if (polyak_first && !one_call) {  // soft_update(critic_target, critic) BEFORE the update, agent.py:278-279
         launch_polyak(N->target_critic, N->critic, nq, Hy->tau, nullptr, nullptr, 0, st);
+        if (im)  // ... and the targets' bf16 images follow it
+            for (int h = 0; h < 2; ++h) launch_pack_bf16(N->target_critic + h * kQs.padded() + kQs.W2(), im + (IM_TC1 + h) * kImgElems, false, st);
+    }
     const float* q1 = N->critic; const float* q2 = N->critic + kQs.padded();
     const float* t1 = N->target_critic; const float* t2 = N->target_critic + kQs.padded();
     if (!skip_first) {   // policy(s'), policy(s), Q1/Q2(s, a)
@@ -262,7 +295,7 @@ static int sac_critic_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const
         const GaussArgs G{N->policy, kPolicy, s[SS_PN].z2, Bt->eps_next, B, Bt->eps_next ? 1 : 2, X.act_n, X.ent_n, nullptr, Bt->seed, 0x40000000u, Bt->call};
         if (one_call) {
             const GaussArgs G2{N->policy, kPolicy, s[SS_PC].z2, Bt->eps_cur, B, Bt->eps_cur ? 1 : 2, X.act_c, nullptr, X.aux_c, Bt->seed, 0x80000000u, Bt->call};
-            launch_gauss(G, &G2, N->target_critic, N->critic, polyak_first ? nq : 0, Hy->tau, st);
+            launch_gauss(G, &G2, N->target_critic, N->critic, polyak_first ? nq : 0, Hy->tau, st, im);
         } else {
             launch_gauss(G, nullptr, nullptr, nullptr, 0, 0.0f, st);
         }
@@ -270,8 +303,9 @@ static int sac_critic_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const
     {   // target Q1/Q2 (s', a')
         FwdArgs F{};
         F.njobs = 2; F.slope = 0.0f;
-        F.job[0] = FwdJob{t1, kQs, src, 17, 3, Head{}, X.act_n, 0.f, s[SS_T1], B, 0};
-        F.job[1] = FwdJob{t2, kQs, src, 17, 3, Head{}, X.act_n, 0.f, s[SS_T2], B, 0};
+        F.job[0] = FwdJob{t1, kQs, src, 17, 3, Head{}, X.act_n, 0.f, s[SS_T1], B, 0, IM_TC1};
+        F.job[1] = FwdJob{t2, kQs, src, 17, 3, Head{}, X.act_n, 0.f, s[SS_T2], B, 0, IM_TC2};
+        F.images = im;
         launch_fwd(F, st);
     }
     {   // y, losses, dq, dh1
@@ -283,12 +317,15 @@ static int sac_critic_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const
             J.net = h ? q2 : q1; J.m = kQs; J.ws = s[SS_Q1 + h]; J.rows = B; J.mode = BM_CRITIC_TD;
             J.t1 = Head{t1, kQs, s[SS_T1]}; J.t2 = Head{t2, kQs, s[SS_T2]}; J.src = src; J.gamma = Hy->gamma;
             J.bonus = X.ent_n; J.bonus_scale = N->alpha_state + 3; J.loss_slot = h;
+            J.img_t = IM_C1_T + h;
         }
-        launch_bwd(0, G, st);
+        G.images = im;
+        if (int rc = launch_bwd(0, G, st)) return rc;
     }
     {
         WgArgs W{};
         W.njobs = 2; W.slope = 0.0f; W.w_kind = 0; W.inv_batch = 1.0f / B; W.soft_count = nullptr; W.wstate = nullptr;
+        W.bf16 = im != nullptr;
         for (int h = 0; h < 2; ++h) {
             WgJob& J = W.job[h];
             J = WgJob{};
@@ -297,6 +334,7 @@ static int sac_critic_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const
             if (adam_step > 0) {  // q1_optim.step() / q2_optim.step() ride in the wgrad launch (one GPU): the thread that produced a gradient steps it
                 J.p = N->critic + h * kQs.padded();
                 J.mom = N->m_critic + h * kQs.padded(); J.var = N->v_critic + h * kQs.padded();
+                if (im) { J.w2b = im + (IM_C1 + h) * kImgElems; J.w2tb = im + (IM_C1_T + h) * kImgElems; }  // the critic's images follow its step
             }
         }
         if (adam_step > 0) {
@@ -338,6 +376,8 @@ int hx_sac_critic_step(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* 
 static int sac_policy_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, void* stream, int adam_step, float target_entropy,
                                  const SampleDev* predraw = nullptr) {
     HX_REQUIRE(N && Bt && Hy && Bt->rows && Bt->batch > 0 && Bt->batch % 16 == 0, "hx_sac_policy_grads: bad arguments");
+    if (int rc = sac_check_formats(N, "hx_sac_policy_grads")) return rc;
+    uint16_t* const im = N->w2_bf16_all;  // the SAC bf16 path, or NULL
     hipStream_t st = (hipStream_t)stream;
     const int B = Bt->batch;
     Slot s[S_COUNT];
@@ -352,14 +392,17 @@ static int sac_policy_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const
     {
         FwdArgs F{};
         F.njobs = 2; F.slope = 0.0f;
-        F.job[0] = FwdJob{q1, kQs, src, 0, 3, Head{}, X.act_c, 0.f, s[SS_Q1P], B, 1};
-        F.job[1] = FwdJob{q2, kQs, src, 0, 3, Head{}, X.act_c, 0.f, s[SS_Q2P], B, 1};
+        F.job[0] = FwdJob{q1, kQs, src, 0, 3, Head{}, X.act_c, 0.f, s[SS_Q1P], B, 1, IM_C1};
+        F.job[1] = FwdJob{q2, kQs, src, 0, 3, Head{}, X.act_c, 0.f, s[SS_Q2P], B, 1, IM_C2};
+        F.images = im;
         launch_fwd(F, st);
     }
     // one call (adam_step > 0): min(Q1, Q2) is selected in the critics' backward prologue and the policy's head gradient is formed in the
     // policy's backward prologue (bwd_l2<4> / <5>) — q_select_kernel and policy_dout_kernel as launches of their own are the staged form
     static const bool fold_env = !(getenv("HX_SAC_FOLD") && getenv("HX_SAC_FOLD")[0] == '0');  // A/B knob
-    const bool fold = adam_step > 0 && fold_env;
+    // The SAC bf16 path keeps the staged form: built in bf16, the folded one call gave policy b2 gradients that differ from the staged sequence's in
+    // the last bit (77 of 512 entries at the first call; dW2 and every other gradient equal), so the fold has no bf16 instantiation (launch_bwd refuses).
+    const bool fold = adam_step > 0 && fold_env && !im;
     if (!fold) {
         QSelArgs Q{q1, q2, kQs, s[SS_Q1P], s[SS_Q2P], B, 1.0f / B, N->losses};
         hipLaunchKernelGGL(q_select_kernel, dim3((unsigned)((B + 3) / 4)), dim3(kThreads), 0, st, Q);
@@ -372,8 +415,10 @@ static int sac_policy_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const
             J = BwdJob{};
             J.net = h ? q2 : q1; J.m = kQs; J.ws = s[SS_Q1P + h]; J.rows = B; J.mode = fold ? BM_SAC_QMIN : BM_GIVEN;
             if (fold) { J.t1 = Head{h ? q1 : q2, kQs, s[SS_Q1P + (1 - h)]}; J.loss_slot = h; }
+            J.img_t = IM_C1_T + h;
         }
-        launch_bwd(fold ? 4 : 3, G, st);
+        G.images = im;
+        if (int rc = launch_bwd(fold ? 4 : 3, G, st)) return rc;
     }
     if (!fold) {
         PDoutArgs P{q1, q2, kQs, s[SS_Q1P], s[SS_Q2P], s[SS_PC], X.aux_c, N->alpha_state, B, 1.0f / B, N->losses};
@@ -389,11 +434,14 @@ static int sac_policy_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const
             J.t1 = Head{q1, kQs, s[SS_Q1P]}; J.t2 = Head{q2, kQs, s[SS_Q2P]};
             J.bonus = X.aux_c; J.bonus_scale = N->alpha_state + 3;
         }
-        launch_bwd(fold ? 5 : 3, G, st);
+        J.img_t = IM_ACTOR_T;
+        G.images = im;
+        if (int rc = launch_bwd(fold ? 5 : 3, G, st)) return rc;
     }
     {
         WgArgs W{};
         W.njobs = 1; W.slope = 0.0f; W.w_kind = 0; W.inv_batch = 1.0f / B;
+        W.bf16 = im != nullptr;
         WgJob& J = W.job[0];
         J = WgJob{};
         J.net = N->policy; J.grad = N->grad_policy; J.m = kPolicy; J.ws[0] = s[SS_PC]; J.rows[0] = B; J.nslots = 1; J.wmode[0] = 0;
@@ -404,6 +452,8 @@ static int sac_policy_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const
             J.p = N->policy; J.mom = N->m_policy; J.var = N->v_policy;
             J.w2f = N->policy_w2_f32i;  // the acting kernels' images of the policy's W2 follow its optimizer step
             if (N->policy_w2_x9) { J.w2b = N->policy_w2_x9; J.w2b_x9 = 1; }
+            if (N->policy_w2_bf16) J.w2b = N->policy_w2_bf16;  // bf16 acting beside an fp32 update
+            if (im) { J.w2b = im + IM_ACTOR * kImgElems; J.w2tb = im + IM_ACTOR_T * kImgElems; }  // the bf16 path: forward (= acting) and transposed images
             W.ad = WgAdam{};
             W.ad.b1 = (float)b1; W.ad.b2 = (float)b2; W.ad.eps = 1e-8f;
             W.ad.step_size = (float)(Hy->lr_actor / bc1);
@@ -437,15 +487,45 @@ int hx_sac_learn(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, co
 int hx_sac_front(const float* policy, const uint16_t* w2_x9, const float* w2_f32i, float* state, int64_t n, int64_t stride, float* obs_io, float* actions, int32_t mode,
                  const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done, int8_t* success, const HxStepOpts* opts,
                  const HxSacNets* N, const HxSacBatch* Bt, void* stream) {
-    HX_REQUIRE(policy && (w2_x9 || w2_f32i) && opts && N && Bt && Bt->rows && Bt->batch > 0 && Bt->batch % 16 == 0 && Bt->batch <= kFusedBatchMax && mode >= 0 && mode <= 2 &&
+    HX_REQUIRE(N && opts && Bt && Bt->rows && Bt->batch > 0 && Bt->batch % 16 == 0 && Bt->batch <= kFusedBatchMax && mode >= 0 && mode <= 2 &&
                (mode != 1 || eps), "hx_sac_front: bad arguments");
+    if (int rc = sac_check_formats(N, "hx_sac_front")) return rc;
+    HX_REQUIRE(N->w2_bf16_all || !N->policy_w2_bf16,
+               "hx_sac_front: bf16 acting beside the fp32 update (policy_w2_bf16 without w2_bf16_all) has no front form: hx_sac_act_step_bf16 + hx_sac_learn");
+    // the acting format follows nets: the bf16 path acts from its first image (the image arguments must be NULL), the fp32 update from w2_x9 / w2_f32i
+    const uint16_t* w2b = N->w2_bf16_all ? sac_act_image(N) : nullptr;
+    HX_REQUIRE(policy && (w2b ? (!w2_x9 && !w2_f32i) : (w2_x9 || w2_f32i)),
+               "hx_sac_front: with nets->w2_bf16_all the acting image is its first one (w2_x9, w2_f32i NULL); else w2_x9 or w2_f32i");
     if (int rc = hxact::check_step_args(state, n, stride, obs_io, actions, reward, done, success, *opts, "hx_sac_front")) return rc;
     hxact::ActFusedArgs H{policy, kPolicy, obs_io, (int)n, 0.0f, actions, mode == 1 ? eps : nullptr, 1, 0.0f, mode, seed, row0, call,
-                          state, stride, reward, done, success, *opts, opts->cap > 0 ? 1.0 / (double)opts->cap : 0.0, w2_x9, w2_x9 ? nullptr : w2_f32i, w2_x9 ? 1 : 0};
+                          state, stride, reward, done, success, *opts, opts->cap > 0 ? 1.0 / (double)opts->cap : 0.0, w2b ? w2b : w2_x9,
+                          (w2b || w2_x9) ? nullptr : w2_f32i, w2_x9 ? 1 : 0};
     FwdArgs F;
     sac_launch_1(N, Bt, F);
     return launch_front_sac(H, F, (hipStream_t)stream);
 }
+/* Rebuild every bf16 image of the SAC bf16 path from the fp32 networks (after parameters were loaded or written directly), and the bf16 acting
+ * image policy_w2_bf16 when it is a buffer of its own. */
+int hx_sac_pack_update_images(const HxSacNets* N, void* stream) {
+    HX_REQUIRE(N && N->policy && (N->w2_bf16_all || N->policy_w2_bf16), "hx_sac_pack_update_images: the policy and w2_bf16_all or policy_w2_bf16");
+    if (int rc = sac_check_formats(N, "hx_sac_pack_update_images")) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (uint16_t* im = N->w2_bf16_all) {
+        HX_REQUIRE(N->critic && N->target_critic, "hx_sac_pack_update_images: null critic");
+        launch_pack_bf16(N->policy + kPolicy.W2(), im + IM_ACTOR * kImgElems, false, st);
+        launch_pack_bf16(N->policy + kPolicy.W2(), im + IM_ACTOR_T * kImgElems, true, st);
+        for (int h = 0; h < 2; ++h) {
+            launch_pack_bf16(N->critic + h * kQs.padded() + kQs.W2(), im + (IM_C1 + h) * kImgElems, false, st);
+            launch_pack_bf16(N->critic + h * kQs.padded() + kQs.W2(), im + (IM_C1_T + h) * kImgElems, true, st);
+            launch_pack_bf16(N->target_critic + h * kQs.padded() + kQs.W2(), im + (IM_TC1 + h) * kImgElems, false, st);
+        }
+    } else {
+        launch_pack_bf16(N->policy + kPolicy.W2(), N->policy_w2_bf16, false, st);
+    }
+    HX_CHECK_LAUNCH("hx_sac_pack_update_images");
+    return 0;
+}
+
 int hx_sac_learn_back(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, int32_t polyak_first, int32_t step, float target_entropy, const HxSample* next,
                       float* next_rows, void* stream) {
     HX_REQUIRE(step >= 1 && N && Bt && Hy, "hx_sac_learn_back: step is 1-based");

@@ -733,11 +733,24 @@ inline int prepare_draw(const HxSample* S, int B, float* rows, float* bc_rows, f
                            S->sigma, S->idx, S->idx_bc, noise, rows, S->bc_table ? bc_rows : nullptr, stream);
 }
 
+// SAC: one acting format at a time.  The bf16 update path (w2_bf16_all) acts from its first image (policy_w2_bf16 NULL or that image) and excludes
+// the fp32 and exact-split images; the bf16 acting image beside an fp32 update (policy_w2_bf16) excludes the exact split.
+inline int sac_check_formats(const HxSacNets* N, const char* who) {
+    const uint16_t* im = N->w2_bf16_all;
+    HX_REQUIRE(!im || (reinterpret_cast<uintptr_t>(im) & 15u) == 0, "%s: w2_bf16_all must be a 16-byte aligned buffer", who);
+    HX_REQUIRE(!N->policy_w2_bf16 || (reinterpret_cast<uintptr_t>(N->policy_w2_bf16) & 15u) == 0, "%s: policy_w2_bf16 must be 16-byte aligned", who);
+    HX_REQUIRE(!im || (!N->policy_w2_x9 && !N->policy_w2_f32i && (!N->policy_w2_bf16 || N->policy_w2_bf16 == im + IM_ACTOR * kImgElems)),
+               "%s: w2_bf16_all excludes policy_w2_x9 and policy_w2_f32i, and policy_w2_bf16 must be NULL or its first image (one acting format at a time)", who);
+    HX_REQUIRE(!N->policy_w2_bf16 || !N->policy_w2_x9, "%s: policy_w2_bf16 excludes policy_w2_x9 (one acting format at a time)", who);
+    return 0;
+}
+// the bf16 acting image of a SAC policy: the update path's first image, else policy_w2_bf16 (NULL: none)
+inline const uint16_t* sac_act_image(const HxSacNets* N) { return N->w2_bf16_all ? N->w2_bf16_all + IM_ACTOR * kImgElems : N->policy_w2_bf16; }
 
 // launchers (defined beside their kernels)
 void launch_fwd(const FwdArgs& F, hipStream_t st);                          // hx_fwdbwd.hip
 void set_fwd_nt(int nt, int skip, int count);                                                  // hx_fwdbwd.hip (hx_debug_set_fwd_nt)
-void launch_bwd(int grp, const BwdArgs& G, hipStream_t st);                 // hx_fwdbwd.hip: grp = bwd_l2_kernel's GRP (0..3)
+int launch_bwd(int grp, const BwdArgs& G, hipStream_t st);                  // hx_fwdbwd.hip: grp = bwd_l2_kernel's GRP (0..5); != 0: refused
 // hx_front.hip: the act + env + insert workgroups of hx_actor_act_step_f32i (32 rows each) and the workgroups of launches A and B as ONE launch
 int launch_front(const float* actor, const float* w2f, const uint16_t* w2x, const uint16_t* w2b, float* state, int64_t n, int64_t stride, float* obs_io, float* actions, int32_t noise_mode,
                  const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, float* reward, uint8_t* done, int8_t* success,

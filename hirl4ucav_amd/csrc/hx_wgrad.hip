@@ -844,6 +844,26 @@ int hx_sac_adam(const HxSacNets* N, const HxHyper* Hy, int32_t which, int32_t st
         A.w2b_x9 = 1;
         A.w2_lo = kPolicy.W2();
     }
+    if (which == 1 && N->policy_w2_bf16 && !N->w2_bf16_all) {  // ... or the bf16 acting image beside an fp32 update
+        A.w2b = N->policy_w2_bf16;
+        A.w2_lo = kPolicy.W2();
+    }
+    if (int rc = sac_check_formats(N, "hx_sac_adam")) return rc;
+    if (uint16_t* im = N->w2_bf16_all) {  // SAC bf16 path: the forward and transposed images of every W2 this step changes follow it
+        if (which == 0) {
+            A.nseg = 2;
+            for (int h = 0; h < 2; ++h) {
+                A.seg_lo[h] = h * kQs.padded() + kQs.W2();
+                A.seg_w2b[h] = im + (IM_C1 + h) * kImgElems;
+                A.seg_w2tb[h] = im + (IM_C1_T + h) * kImgElems;
+            }
+        } else {
+            A.nseg = 1;
+            A.seg_lo[0] = kPolicy.W2();
+            A.seg_w2b[0] = im + IM_ACTOR * kImgElems;  // (also the acting image)
+            A.seg_w2tb[0] = im + IM_ACTOR_T * kImgElems;
+        }
+    }
     if (which == 1) {
         A.alpha_state = N->alpha_state;
         A.target_entropy = target_entropy;

@@ -64,6 +64,27 @@ def expert_pair_indices(done):
     return np.asarray(out, np.int64)
 
 
+def resolve_dtype(sac, requested, snap_driver=None):
+    """The --dtype a run computes in, given the agent, the flag and the driver record of the snapshot it resumes (None: a fresh run).
+    -> (dtype, warning or None, refusal or None, mark).  The run's arithmetic is part of its state: a snapshot taken under one --dtype does not
+    continue under another (the flag changed meaning before: round 2's "bf16" was policy inference only, since round 3 it is the policy AND
+    learn()'s 256 <-> 512 products).  SAC / E-SAC have no exact-split format (f32x9 runs fp32, with a warning), and before they had a bf16 path
+    a SAC run given --dtype bf16 ran and stored "f32": a SAC snapshot without the `dtype_honoured` mark resumes in fp32 with that old warning,
+    so that such a run keeps resuming with its own command line.  `mark`: whether this run's snapshots carry the mark — not while that legacy
+    fallback applies (a snapshot it writes stays unmarked, and the next resume with the same command line takes the same branch)."""
+    dtype, warning = requested, None
+    marked = snap_driver is not None and bool(snap_driver.get("dtype_honoured"))
+    legacy = sac and requested in ("bf16", "bf16_policy") and snap_driver is not None and not marked
+    if sac and (requested == "f32x9" or legacy):
+        dtype = "f32"
+        warning = f"--dtype {requested} has no effect on " + ("the SAC / E-SAC agents (no exact-split format): running fp32" if requested == "f32x9" else
+                                                              "a SAC run resumed from a snapshot that ran fp32: running fp32")
+    snap_dtype = snap_driver.get("dtype") if snap_driver is not None else None
+    if snap_dtype is not None and snap_dtype != dtype:
+        return dtype, warning, f"was run with --dtype {snap_dtype}, --dtype {dtype} given", not legacy
+    return dtype, warning, None, not legacy
+
+
 def checkpoint_tag(arttir, success, episodes, mean_score):
     return "Agent{}_{}_{}_".format(arttir, round(success / episodes * 100), round(mean_score))  # train_all.py:69
 
@@ -295,21 +316,17 @@ def main(config):
             eng.bc_actor.copy_(E.pack(torch.load(config.bc_actor, map_location="cpu"), E.ACTOR_LAYOUT, E.ACTOR_SIZE, device))
         elif hirl and config.type == "soft" and rank == 0:
             print("WARNING: HIRL-soft without --bc_actor: the soft weight is estimated against a randomly initialised bc_actor", flush=True)
-    dtype = getattr(config, "dtype", "f32")
-    # the run's arithmetic is part of its state: a snapshot taken under one --dtype does not continue under another (the same flag changed
-    # meaning once already: round 2's "bf16" was policy inference only, since round 3 it is the policy AND learn()'s 256 <-> 512 products)
-    if sac and dtype != "f32":  # (before the snapshot comparison: a SAC run started with --dtype bf16 stored "f32", and resumes with the same command line)
-        if rank == 0:
-            print(f"WARNING: --dtype {dtype} has no effect on the SAC / E-SAC agents (their kernels are fp32): running fp32", flush=True)
-        dtype = "f32"
-    snap_dtype = snap["driver"].get("dtype") if snap is not None else None
-    if snap_dtype is not None and snap_dtype != dtype:
-        raise SystemExit(f"train_all: --resume {config.resume} was run with --dtype {snap_dtype}, --dtype {dtype} given")
+    dtype, warning, refusal, mark = resolve_dtype(sac, getattr(config, "dtype", "f32"), snap["driver"] if snap is not None else None)
+    dtype_mark = {"dtype_honoured": True} if mark else {}  # (in every snapshot's driver record)
+    if warning and rank == 0:
+        print(f"WARNING: {warning}", flush=True)
+    if refusal:
+        raise SystemExit(f"train_all: --resume {config.resume} {refusal}")
     if world > 1 and os.environ.get("HX_DIST_BACKEND", "nccl") == "nccl" and hasattr(eng, "use_rccl_direct"):
         eng.use_rccl_direct()  # ncclAllReduce enqueued by the library on the engine's stream (hx_rccl_*): no torch.distributed call inside learn()
     if dtype == "f32x9" and not sac:  # fp32, the acting kernel's 256 -> 512 product through the exact three-way bf16 split of both operands (engine.set_act_dtype)
         eng.set_act_dtype("f32x9")
-    elif dtype != "f32" and not sac:  # bf16: actor AND critic (BASELINE.json configs[4]); bf16_policy: policy inference only
+    elif dtype in ("bf16", "bf16_policy"):  # bf16: policy AND critics (BASELINE.json configs[4]; SAC: SacEngine's bf16 path); bf16_policy: policy inference only
         eng.set_act_dtype("bf16")
         if dtype == "bf16":
             eng.set_update_dtype("bf16")
@@ -385,7 +402,7 @@ def main(config):
             torch.distributed.barrier()
         snap_path = os.path.join(log_dir, f"state_rank{rank}.pt")
         CK.save_run(snap_path, eng, env, replay, {"episode": episode0, "expert_num": expert_num, "high_score": high_score, "success_rate": success_rate,
-                                                  "arttir": arttir, "seed": seed, "dtype": dtype})
+                                                  "arttir": arttir, "seed": seed, "dtype": dtype, **dtype_mark})
         if world > 1:
             torch.distributed.barrier()
     episode = episode0
@@ -515,7 +532,7 @@ def main(config):
                 torch.distributed.barrier()  # every shard of a snapshot comes from the same episode ...
             CK.save_run(os.path.join(log_dir, f"state_rank{rank}.pt"), eng, env, replay,
                         {"episode": episode + 1, "expert_num": expert_num, "high_score": high_score, "success_rate": success_rate, "arttir": arttir,
-                         "seed": seed, "dtype": dtype})
+                         "seed": seed, "dtype": dtype, **dtype_mark})
             if world > 1:
                 torch.distributed.barrier()  # ... and nobody runs ahead while a shard is still being written
             snap_path = os.path.join(log_dir, f"state_rank{rank}.pt")
@@ -565,7 +582,8 @@ def parser():
                    help="f32 (default): fp32 everywhere — from 4,096 envs per GPU on, the ACTING kernel forms its fp32 256->512 product as the exact "
                         "three-way bf16 split of both operands on the bf16 matrix cores (engine.x9_rows); f32x9: that format at every size; bf16: policy inference AND the "
                         "256<->512 products of learn() on bf16 MFMA (fp32 accumulate, fp32 master weights / Adam / LayerNorm / dynamics); bf16_policy: "
-                        "policy inference only.  HIRL / TD3 only: the SAC agents run fp32.  Stored in the snapshot: --resume refuses another value")
+                        "policy inference only.  SAC / E-SAC: bf16 and bf16_policy as above (the Gaussian head stays fp32), f32x9 runs fp32 with a warning.  "
+                        "Stored in the snapshot: --resume refuses another value (a SAC snapshot from before SAC had bf16 resumes in fp32)")
     p.add_argument("--synthetic_expert", action="store_true", help="uniform-random stand-in for the expert CSV (throughput runs and tests ONLY)")
     p.add_argument("--load_dir", type=str, default=None, help="--load_model: directory of the checkpoint files (default: this run's model dir)")
     p.add_argument("--load_tag", type=str, default="Agent20_successRate0.64", help="--load_model: checkpoint tag (train_all.py:240 hard-codes this one)")

@@ -76,6 +76,10 @@ def load_agent(config, device):
         eng = SE.SacEngine(batch=128, lr=1e-3, device=device)
         eng.load_params(_xavier_mlp(13, 8), _xavier_mlp(17, 1), _xavier_mlp(17, 1))
         eng.load_models(config.model_dir, config.model_name)
+        if config.dtype == "bf16":  # the policy's 256 -> 512 product on bf16 MFMA, the Gaussian head in fp32 (SacEngine.set_act_dtype)
+            eng.set_act_dtype("bf16")
+        elif config.dtype != "f32":
+            print(f"WARNING: --dtype {config.dtype} has no effect on the SAC agent (no exact-split format): running fp32", flush=True)
         return eng, True
     hirl = config.agent == "HIRL"
     eng = E.HirlEngine(batch=128, slope=0.0 if hirl else 0.01, use_bc=False, device=device)  # HIRL: ReLU; TD3 / BC: LeakyReLU(0.01)
@@ -135,7 +139,7 @@ def parser():
     p.add_argument("--nums", type=int, default=2)
     p.add_argument("--episodes", type=int, default=50)
     p.add_argument("--validation_step", type=int, default=VALIDATION_STEP)
-    p.add_argument("--dtype", type=str, default="f32", choices=["f32", "f32x9", "bf16"], help="policy inference arithmetic (HIRL / TD3 / BC)")
+    p.add_argument("--dtype", type=str, default="f32", choices=["f32", "f32x9", "bf16"], help="policy inference arithmetic (SAC: f32 or bf16)")
     return p
 
 

@@ -72,8 +72,8 @@ const char* hx_last_error(void);
 /* HX_ABI_VERSION of the library that is loaded.  The structs below are part of the ABI: a caller built against another header version must
  * not call in (round 3 widened HxStepOpts.stats from 9 to HX_STAT_WAYS * HX_STAT_PITCH words and appended fields to HxNets / HxHyper without
  * bumping this: a 9-word stats buffer then took atomics up to word 504).  110: round 4 (hx_abi_sizes, hx_rccl_*, hx_allreduce_twostage).
- * 113: round 5.  114: round 6 (hx_rccl_allreduce_bf16). */
-#define HX_ABI_VERSION 114
+ * 113: round 5.  114: round 6 (hx_rccl_allreduce_bf16).  115: the SAC bf16 path (HxSacNets.w2_bf16_all / policy_w2_bf16, hx_sac_*_bf16). */
+#define HX_ABI_VERSION 115
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -429,7 +429,25 @@ typedef struct HxSacNets {
                               current, hx_sac_act*_f32i read it */
     uint16_t* policy_w2_x9; /* NULL, or the hi | mid | lo bf16 images of the policy's W2 (hx_pack_w2_x9(policy, 13, ...), 3 x 512 x 256): the
                                policy's optimizer step keeps them current, hx_sac_act*_x9 read them */
+    uint16_t* w2_bf16_all;  /* NULL: the update computes in fp32.  Else hx_bf16_images_elems() bf16 elements: the SAC bf16 path (below).  Its first
+                               512 x 256 elements are the policy's image in the bf16 acting format (hx_sac_act*_bf16 read it) */
+    uint16_t* policy_w2_bf16; /* NULL, or the bf16 image of the policy's W2 (hx_pack_w2_bf16(policy, 13, ...)) for bf16 acting beside an fp32
+                               update: the policy's optimizer step keeps it current.  With w2_bf16_all set it must be NULL or its first image */
 } HxSacNets;
+
+/* SAC bf16 path (BASELINE.json configs[4] "bf16 actor/critic + fp32 dynamics" for SacAgent).  With HxSacNets.w2_bf16_all set, every hx_sac_*
+ * update call runs the three products of the 256 <-> 512 layer of the policy, both critics and both target critics on v_mfma_f32_16x16x32_bf16:
+ *     z2 = bf16(h1) bf16(W2)^T + b2        dh1 = bf16(dz2) bf16(W2)        dW2 = bf16(dz2)^T bf16(h1)       (fp32 accumulation)
+ * Images: IM_ACTOR / IM_ACTOR_T = the policy's forward / transposed W2, IM_C1, IM_C2 (+ _T) the critics', IM_TC1, IM_TC2 the target critics'.
+ * Master weights, Adam moments, layer 1 (K = 13 / 17), the Gaussian heads (mean, clamped log_std, exp, tanh, entropy), q_select, the policy's head
+ * gradient, the log-alpha step, TD targets and loss sums stay fp32.  Every optimizer step refreshes the forward and transposed images of the network
+ * it steps (the policy's forward image is the acting image); every Polyak step refreshes IM_TC1 / IM_TC2.  After any OTHER write to a network call
+ * hx_sac_pack_update_images.  Acting (hx_sac_act*_bf16): the 256 -> 512 product as above from the policy's image, layer 1 and the head in fp32 — NOT
+ * the deterministic policy's bf16 head (hx_actor_act_bf16): exp(log_std) amplifies head error, and the update's head is fp32 too.
+ * Tolerances (tests/test_sac_bf16_gpu.py): actions against an fp32 evaluation on the same rounded operands: 99 % within 1e-4, all within 2e-3;
+ * against the fp32 policy: |da| <= 2e-2, mean |da| <= 2e-3.  learn() against the rounded-operand oracle: losses rtol 1e-4; parameters after Adam
+ * as tests/test_bf16_update_gpu.py. */
+int hx_sac_pack_update_images(const HxSacNets* nets, void* stream);
 
 typedef struct HxSacBatch {
     const float* rows;     /* [batch][HX_ROW_WORDS] compact minibatch (hx_sample_batch) */
@@ -464,6 +482,13 @@ int hx_sac_act_step_x9(const float* policy, const uint16_t* w2_x9, const float* 
 int hx_sac_act_step(const float* policy, float* state, int64_t n, int64_t stride, float* obs_io, float* actions, int32_t mode,
                     const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done, int8_t* success,
                     const HxStepOpts* opts /* host, may be NULL */, void* stream);
+/* The same with the 256 -> 512 product on bf16 matrix cores from the bf16 image w2_bf16 ("SAC bf16 path" above): the per-tile kernel up to 8,192
+ * rows, the streaming persistent kernel beyond (the same bits for a row). */
+int hx_sac_act_bf16(const float* policy, const uint16_t* w2_bf16, const float* obs, int64_t rows, float* actions, int32_t mode, const float* eps,
+                    uint64_t seed, uint32_t row0, uint32_t call, void* stream);
+int hx_sac_act_step_bf16(const float* policy, const uint16_t* w2_bf16, float* state, int64_t n, int64_t stride, float* obs_io, float* actions,
+                         int32_t mode, const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done,
+                         int8_t* success, const HxStepOpts* opts /* host, may be NULL */, void* stream);
 /* SacAgent.learn (SAC/agent.py:276-327) in the stages a sharded run separates:
  *   hx_sac_critic_grads   [soft_update of the target critics first on every 3rd call :278-279]; target y = r + (1-d) gamma
  *                         (min Q_target(s', a') + alpha H') :202-210; q1_loss, q2_loss :361-374 -> losses[0..1]; grad_critic
@@ -486,7 +511,8 @@ int hx_sac_policy_grads(const HxSacNets* nets, const HxSacBatch* batch, const Hx
  * hx_sac_policy_grads + hx_sac_adam(which = 1); sample may be NULL (minibatch already assembled); step is 1-based. */
 int hx_sac_learn(const HxSacNets* nets, const HxSacBatch* batch, const HxHyper* hyper, const HxSample* sample, int32_t polyak_first, int32_t step,
                  float target_entropy, void* stream);
-/* The SAC front launch (n > 8,192 envs with a replay ring): hx_sac_act_step_x9 (w2_x9 != NULL) / hx_sac_act_step_f32i — explore / exploit + HarfangEnv.step +
+/* The SAC front launch (n > 8,192 envs with a replay ring): hx_sac_act_step_x9 (w2_x9 != NULL) / hx_sac_act_step_f32i / hx_sac_act_step_bf16 (the
+ * acting format is taken from nets: with nets->w2_bf16_all set the bf16 acting image and the bf16 first launch; w2_x9 and w2_f32i must be NULL then) — explore / exploit + HarfangEnv.step +
  * replay insert (train_sac.py:238-241) — AND the first forward launch of the SacAgent.learn call that follows it (policy(s'), policy(s), Q1/Q2(s, a): SAC/agent.py:
  * 198-210, 276-290) as workgroups of ONE launch that start as the acting ones leave, on the minibatch `batch->rows` holds already.  As for hx_hirl_front the
  * minibatch is drawn from the ring as it stood BEFORE this env step without the n slots the step may overwrite (HxSample.guard = n): by the previous

@@ -159,6 +159,43 @@ def main():
         ok("hx_sac_act", sn.policy, obs, n, act, 2, None, 1, 0, 1, None, None)
         ok("hx_sac_act_f32i", sn.policy, w2f, obs, n, act, 2, None, 1, 0, 1, None)
         ok("hx_sac_act_x9", sn.policy, w2x, w2f, obs, n, act, 2, None, 1, 0, 1, None)
+    # the SAC bf16 path: one image block (no fp32 / exact-split image beside it), the acting entry points, the packer; mixed formats are refused
+    imgs = dev(int(L.hx_bf16_images_elems()) * 2)
+    sb16 = S.HxSacNets(*[getattr(sn, f) for f, _ in S.HxSacNets._fields_])
+    sb16.policy_w2_f32i, sb16.policy_w2_x9, sb16.w2_bf16_all, sb16.policy_w2_bf16 = None, None, imgs, None
+    ok("hx_sac_pack_update_images", ctypes.byref(sb16), None)
+    for polyak_first in (0, 1):
+        ok("hx_sac_learn", ctypes.byref(sb16), ctypes.byref(sb), hs, ctypes.byref(ssmp), polyak_first, 3, -4.0, None)
+        ok("hx_sac_critic_grads", ctypes.byref(sb16), ctypes.byref(sb), hs, polyak_first, None)
+    ok("hx_sac_policy_grads", ctypes.byref(sb16), ctypes.byref(sb), hs, None)
+    for which in (0, 1):
+        ok("hx_sac_adam", ctypes.byref(sb16), hs, which, 3, 1.0, -4.0, None)
+    for n in (4096, 16384):
+        state, obs, act = dev(37 * n * 4), dev(n * 13 * 4), dev(n * 16)
+        ok("hx_sac_act_bf16", sn.policy, imgs, obs, n, act, 2, None, 1, 0, 1, None)
+    # act + env step + insert, and the bf16 front launch with its back half (the acting format from nets), at the per-tile and the streaming sizes
+    for n in (4096, 16384):
+        state, obs, act = dev(37 * n * 4), dev(n * 13 * 4), dev(n * 16)
+        rew, done, succ, epi = dev(n * 4), dev(n), dev(n), dev(n * 4)
+        rcap = max(2 * n, 1 << 16)
+        o = _lib.HxStepOpts(1500, 1, 1, 0, 7, epi, dev(rcap * 128), dev(rcap), rcap, dev(8), dev(4096), None, None, 0)
+        ok("hx_sac_act_step_bf16", sn.policy, imgs, state, n, n, obs, act, 2, None, 1, 0, 1, rew, done, succ, ctypes.byref(o), None)
+        if n > 8192:
+            nxt = E.HxSample(o.total, rcap, o.ring, None, 0, None, 0, B, 3, 2, 0.0, dev(B * 4), None, n)
+            ok("hx_sac_front", sn.policy, None, None, state, n, n, obs, act, 2, None, 1, 0, 1, rew, done, succ, ctypes.byref(o), ctypes.byref(sb16),
+               ctypes.byref(sb), None)
+            ok("hx_sac_learn_back", ctypes.byref(sb16), ctypes.byref(sb), hs, 1, 3, -4.0, ctypes.byref(nxt), dev(B * 128), None)
+            # mixed formats: an fp32 image beside the bf16 path; bf16 acting beside the fp32 update (no front form)
+            refused("hx_sac_front", sn.policy, None, w2f, state, n, n, obs, act, 2, None, 1, 0, 1, rew, done, succ, ctypes.byref(o), ctypes.byref(sb16),
+                    ctypes.byref(sb), None)
+            pb16 = S.HxSacNets(*[getattr(sn, f) for f, _ in S.HxSacNets._fields_])
+            pb16.policy_w2_x9, pb16.policy_w2_bf16 = None, dev(512 * 256 * 2)
+            refused("hx_sac_front", sn.policy, None, w2f, state, n, n, obs, act, 2, None, 1, 0, 1, rew, done, succ, ctypes.byref(o), ctypes.byref(pb16),
+                    ctypes.byref(sb), None)
+    mixed = S.HxSacNets(*[getattr(sb16, f) for f, _ in S.HxSacNets._fields_])
+    mixed.policy_w2_x9 = w2x
+    refused("hx_sac_learn", ctypes.byref(mixed), ctypes.byref(sb), hs, None, 0, 3, -4.0, None)
+    refused("hx_sac_pack_update_images", ctypes.byref(mixed), None)
 
     # ---- the exchanges' host-side pointer arrays (world 2, 3, 8) ----
     vp = ctypes.c_void_p
