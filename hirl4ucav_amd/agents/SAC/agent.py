@@ -1,10 +1,13 @@
 """Drop-in counterpart of agents.SAC.agent.SacAgent (reference hirl/agents/SAC/agent.py:58-448) for what train_sac.py uses:
 constructor keywords, .memory.append / len(.memory), .batch_size, .explore / .exploit, .learn(if_expert, expert_num,
-expert_data), .expert_memory, .writer, .model_dir / .plot_dir, .save_models — on the HIP kernels (SacEngine).
+expert_data), .expert_memory, .writer, .model_dir / .plot_dir, .save_models — on the HIP kernels (SacEngine).  With
+imitative=True (agent.py:315-318, 385-403): load_bc_actor, then learn() draws a second batch from .expert_memory for the
+BC-gated policy loss and logs loss/bc and loss/bc_weight.
 
 The networks are the Linear-ReLU stacks of the reference's un-vendored rltorch builder (initialisation: xavier-uniform
 weights, zero biases — that builder is not in /root/reference, so its exact initialiser is not claimed).  The known crashes of
-the reference (the 14-input bc_actor, train_episode's missing env) are not reproduced.
+the reference (the 14-input bc_actor, train_episode's missing env) are not reproduced: the imitative branch's
+bc_actor is the 13-input LayerNorm actor this project's BC agent writes.
 """
 import os
 
@@ -64,8 +67,9 @@ class SacAgent:
                  target_update_interval=3, eval_interval=1000, cuda=True):
         if tuple(observation_space.shape) != (13,) or tuple(action_space.shape) != (4,) or list(hidden_units) != [256, 512]:
             raise NotImplementedError("the HIP kernels are built for train_sac.py's shape: 13 / 4 / hidden [256, 512]")
-        if imitative or per or multi_step != 1 or not entropy_tuning or grad_clip is not None:
-            raise NotImplementedError("only the configuration train_sac.py runs (non-imitative, uniform replay, entropy tuning) is built")
+        if per or multi_step != 1 or not entropy_tuning or grad_clip is not None:
+            raise NotImplementedError("built: uniform replay, multi_step 1, entropy tuning, no gradient clipping (with or without imitative=True); "
+                                      "per, multi_step != 1, entropy_tuning=False and grad_clip are not")
         self.observation_space, self.action_space = observation_space, action_space
         self.device = device
         self.eng = SE.SacEngine(batch=batch_size, lr=lr, gamma=gamma ** multi_step, tau=tau, target_entropy=-float(np.prod(action_space.shape)),
@@ -73,6 +77,7 @@ class SacAgent:
         self.eng.load_params(_xavier_mlp(13, 8), _xavier_mlp(17, 1), _xavier_mlp(17, 1))
         self.memory = DeviceMemory(memory_size)
         self.expert_memory = None
+        self.imitative = bool(imitative)  # the BC gate needs load_bc_actor(...) and an expert_memory before the first learn()
         self.log_dir = log_dir
         self.model_dir, self.summary_dir, self.plot_dir = (os.path.join(log_dir, d) for d in ("model", "summary", "plot"))
         for d in (self.model_dir, self.summary_dir, self.plot_dir):
@@ -111,8 +116,34 @@ class SacAgent:
     def act(self, state):  # agent.py:175-180
         return self.action_space.sample() if self.start_steps > self.steps else self.explore(state)
 
+    def load_bc_actor(self, ajan, model_name=None, slope=0.01):  # agent.py:158-160
+        """The frozen BC actor of the imitative branch: a state_dict (or a flat block), a path to the file the BC agent of this project
+        writes, or the reference's two-argument call load_bc_actor(ajan, model_name) = the file <model_name>/<ajan>Harfang_GYM."""
+        if model_name is not None:
+            joined = os.path.join(str(model_name), str(ajan) + "Harfang_GYM")
+            # (a file written by the reference on Linux is literally named 'dir\\tagName')
+            ajan = joined if os.path.exists(joined) else (str(model_name) + "\\{}".format(ajan) + "Harfang_GYM" if os.path.exists(
+                str(model_name) + "\\{}".format(ajan) + "Harfang_GYM") else joined)
+        if isinstance(ajan, (str, os.PathLike)):
+            if not os.path.isfile(ajan):
+                raise FileNotFoundError(f"bc_actor checkpoint {ajan} not found (train one with --agent BC)")
+            ajan = torch.load(ajan, map_location="cpu")
+        self.eng.set_imitative(ajan, slope=slope)
+
+    def _expert_batch(self):
+        """expert_memory.sample(batch_size) (agent.py:392) -> the engine's second tile"""
+        if not self.eng.imitative:
+            raise RuntimeError("SacAgent(imitative=True).learn needs the frozen BC actor: call load_bc_actor(...) first")
+        if self.expert_memory is None:
+            raise RuntimeError("SacAgent(imitative=True).learn draws a second batch from agent.expert_memory, which is None: "
+                               "set it to a memory holding the expert transitions")
+        s, a, r, ns, d = self.expert_memory.sample(self.batch_size)
+        self.eng.expert_rows.copy_(torch.cat([s, a, ns, r, d], 1).to(device).contiguous().reshape(-1))
+
     def learn(self, if_expert, expert_num=None, expert_data=None):  # agent.py:276-359
         B = self.batch_size
+        if self.imitative:
+            self._expert_batch()
         if if_expert and expert_num:
             # expert rows were drawn by the caller (expert_memory.sample(expert_num), train_sac.py:272-273) and come last
             main = self.memory.ring[torch.as_tensor(self.memory.sample_indices(B - expert_num), device=device)]
@@ -126,6 +157,10 @@ class SacAgent:
             q1, q2, pl, el, ent, alpha = self.eng.losses_host()
             for k, v in (("loss/Q1", q1), ("loss/Q2", q2), ("loss/policy", pl), ("stats/alpha", alpha), ("stats/entropy", ent)):
                 self.writer.add_scalar(k, v, self.eng.learning_steps)
+            if self.imitative:  # agent.py:353-359
+                bc_loss, bc_weight = self.eng.imitative_losses_host()
+                self.writer.add_scalar("loss/bc", bc_loss, self.eng.learning_steps)
+                self.writer.add_scalar("loss/bc_weight", bc_weight, self.eng.learning_steps)
 
     def save_models(self, ajan):  # agent.py:440-444
         self.eng.save_models(self.model_dir, ajan)

@@ -1,4 +1,4 @@
-"""SacEngine — device-resident state of the SAC agent (reference hirl/agents/SAC/agent.py, non-imitative branch) and the
+"""SacEngine — device-resident state of the SAC agent (reference hirl/agents/SAC/agent.py; set_imitative adds its imitative branch) and the
 host-side sequencing of the hx_sac_* stages.  The networks are the plain Linear-ReLU stacks of the reference's (un-vendored)
 rltorch builder; they reuse the flat MLP-block layout of include/hirl4ucav.h with the LayerNorm slots pinned to (1, 0)."""
 import ctypes
@@ -17,6 +17,11 @@ _P = ctypes.POINTER
 class HxSacNets(ctypes.Structure):
     _fields_ = [(k, _vp) for k in ("policy", "critic", "target_critic", "grad_policy", "grad_critic", "m_policy", "v_policy", "m_critic",
                                    "v_critic", "losses", "alpha_state", "ws", "policy_w2_f32i", "policy_w2_x9", "w2_bf16_all", "policy_w2_bf16")]
+
+
+class HxSacImit(ctypes.Structure):
+    """the imitative branch's buffers (include/hirl4ucav.h HxSacImit)"""
+    _fields_ = [("bc_actor", _vp), ("expert_rows", _vp), ("ws", _vp), ("count", _vp), ("bc_slope", _f32)]
 
 
 class HxSacBatch(ctypes.Structure):
@@ -45,6 +50,9 @@ _lib.register("hx_sac_learn_back", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper)
 _lib.register("hx_sac_learn", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _P(E.HxSample), _i32, _i32, ctypes.c_float, _vp])
 _lib.register("hx_sac_policy_grads", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _vp])
 _lib.register("hx_sac_adam", [_P(HxSacNets), _P(E.HxHyper), _i32, _i32, _f32, _f32, _vp])
+_lib.register("hx_sac_policy_grads_imitative", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _P(HxSacImit), _vp])
+_lib.register("hx_sac_learn_imitative", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _P(E.HxSample), _P(HxSacImit), _P(E.HxSample), _i32, _i32,
+                                          ctypes.c_float, _vp])
 
 H1, H2 = E.H1, E.H2
 SEQ_KEYS = ("0.weight", "0.bias", "2.weight", "2.bias", "4.weight", "4.bias")  # nn.Sequential(Linear, ReLU, Linear, ReLU, Linear)
@@ -129,6 +137,36 @@ class SacEngine:
         self.group = group
         self.world = torch.distributed.get_world_size(group) if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 1
         self.act_calls, self.sample_calls = 0, 0
+        self.imitative, self.imit, self.expert_calls = False, None, 0  # set_imitative
+
+    def set_imitative(self, bc_actor, slope=0.01):
+        """SacAgent(imitative=True) (agent.py:315-318, 385-403): from now on learn() gates a BC term on the expert rows with
+        bc_weight = mean(min Q(s, bc_actor(s)) > min Q(s, pi(s))).  bc_actor: the frozen 13-input LayerNorm actor the BC agent writes, as a
+        state_dict or a flat block (engine.ACTOR_LAYOUT); slope: its leaky slope (agents/BC.py: 0.01).  fp32, one GPU."""
+        if self.update_dtype == "bf16" or self.act_dtype == "bf16":
+            raise ValueError("the imitative branch is fp32 only: set_update_dtype('f32') and set_act_dtype('f32') before set_imitative")
+        if self.world > 1:
+            raise _lib.HxError("the imitative branch runs on one GPU (its gate count is not exchanged between ranks): run it with --gpus 1")
+        L = _lib.load()
+        L.hx_sac_imit_sizeof.restype, L.hx_sac_imit_workspace_floats.restype = ctypes.c_int, ctypes.c_int64
+        if L.hx_sac_imit_sizeof() != ctypes.sizeof(HxSacImit):
+            raise _lib.HxError(f"ABI mismatch: HxSacImit is {ctypes.sizeof(HxSacImit)} bytes here, {L.hx_sac_imit_sizeof()} in {_lib.SO_PATH}")
+        if torch.is_tensor(bc_actor):
+            if bc_actor.numel() != E.ACTOR_SIZE:
+                raise ValueError(f"a flat bc_actor block has {E.ACTOR_SIZE} floats (engine.ACTOR_LAYOUT), got {bc_actor.numel()}")
+            block = bc_actor.detach().to(self.device, torch.float32).reshape(-1).clone()
+        else:
+            block = E.pack(bc_actor, E.ACTOR_LAYOUT, E.ACTOR_SIZE, self.device)
+        B = self.batch
+        self.bc_actor = torch.zeros((E.ACTOR_SIZE + 3) & ~3, dtype=torch.float32, device=self.device)
+        self.bc_actor[:E.ACTOR_SIZE].copy_(block)
+        self.imit_ws = torch.zeros(int(L.hx_sac_imit_workspace_floats(B)), dtype=torch.float32, device=self.device)
+        self.expert_rows = torch.zeros(B * 32, dtype=torch.float32, device=self.device)
+        self.bc_count = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._expert_idx = torch.zeros(B, dtype=torch.int32, device=self.device)
+        self.bc_slope = float(slope)
+        self.imit = HxSacImit(self.bc_actor.data_ptr(), self.expert_rows.data_ptr(), self.imit_ws.data_ptr(), self.bc_count.data_ptr(), self.bc_slope)
+        self.imitative, self._pending_expert = True, None
 
     def load_params(self, policy, q1, q2, hard_update_target=True):
         self.policy.copy_(pack_mlp(policy, POLICY_BLOCK, POLICY_SIZE, 13, 8, self.device))
@@ -144,6 +182,8 @@ class SacEngine:
         "SAC bf16 path").  The bf16 update goes with the bf16 acting image: set the update back to "f32" first."""
         if dtype not in ("f32", "bf16"):
             raise ValueError(dtype)
+        if dtype == "bf16" and self.imitative:
+            raise ValueError("the imitative branch is fp32 only: act in 'f32', or build a SacEngine without set_imitative for bf16 acting")
         if dtype != "bf16" and self.update_dtype == "bf16":
             raise ValueError("the SAC bf16 update goes with the bf16 acting image (set_update_dtype('f32') first)")
         self.act_dtype = dtype
@@ -156,6 +196,8 @@ class SacEngine:
         and the losses stay fp32.  Goes with the bf16 acting image (set_act_dtype("bf16") first)."""
         if dtype not in ("f32", "bf16"):
             raise ValueError(dtype)
+        if dtype == "bf16" and self.imitative:
+            raise ValueError("the imitative branch is fp32 only: keep the update in 'f32', or build a SacEngine without set_imitative for the bf16 update")
         if dtype == "bf16" and self.act_dtype != "bf16":
             raise ValueError("the SAC bf16 update goes with the bf16 acting image (set_act_dtype('bf16') first)")
         self.update_dtype = dtype
@@ -304,6 +346,53 @@ class SacEngine:
                   _lib.stream_ptr())
         self._seed = int(seed)  # learn() without injected draws: Normal.rsample's eps comes from Philox(seed; row, learn call) in-kernel
 
+    def assemble_expert(self, ring, idx):
+        """the imitative branch's second batch by given indices: rows idx of the expert table `ring` -> expert_rows"""
+        _lib.call("hx_sample_batch", None, 0, ring.data_ptr(), None, 0, None, 0, self.batch, self.batch, 0, 0, 0, 0.0, idx.data_ptr(), None,
+                  None, self.expert_rows.data_ptr(), None, _lib.stream_ptr())
+        self._pending_expert = None
+
+    def sample_expert(self, expert, seed=0, defer=False):
+        """expert_memory.sample(batch_size) of the imitative branch (agent.py:394) on the device: B rows of the expert memory, drawn with
+        Philox(seed; row, expert call) as hx_sample_batch draws (the key is offset, so that sample() and sample_expert() given the SAME seed draw
+        independent streams).  defer=True: the next learn() draws them inside its call."""
+        if not self.imitative:
+            raise _lib.HxError("sample_expert is the imitative branch's second batch: call set_imitative first")
+        self.expert_calls += 1
+        seed = (int(seed) ^ 0x4558504552540000) & 0xFFFFFFFFFFFFFFFF
+        sample = E.HxSample(expert.total.data_ptr(), expert.capacity, expert.ring.data_ptr(), None, 0, None, 0, self.batch, int(seed),
+                            self.expert_calls, 0.0, self._expert_idx.data_ptr(), None, 0)
+        if defer:
+            self._pending_expert = (sample, expert)
+            return
+        self._pending_expert = None
+        _lib.call("hx_sample_batch", expert.total.data_ptr(), expert.capacity, expert.ring.data_ptr(), None, 0, None, 0, self.batch, self.batch, 1,
+                  int(seed), self.expert_calls, 0.0, self._expert_idx.data_ptr(), None, None, self.expert_rows.data_ptr(), None, _lib.stream_ptr())
+
+    def _learn_imitative(self, batch, pending, polyak_first, st):
+        """the imitative learn(): one call, or (staged_policy) hx_sac_critic_step + hx_sac_policy_grads_imitative + hx_sac_adam(1)"""
+        if self.world > 1:
+            raise _lib.HxError("the imitative branch runs on one GPU (its gate count is not exchanged between ranks): run it with --gpus 1")
+        nets, hyper, imit = ctypes.byref(self.nets), ctypes.byref(self.hyper), ctypes.byref(self.imit)
+        main = ctypes.byref(pending[0]) if pending is not None else None
+        pe, self._pending_expert = self._pending_expert, None
+        if not getattr(self, "staged_policy", False):
+            _lib.call("hx_sac_learn_imitative", nets, ctypes.byref(batch), hyper, main, imit, ctypes.byref(pe[0]) if pe is not None else None,
+                      polyak_first, self.learning_steps, self.target_entropy, st)
+            return
+        if pe is not None:
+            s = pe[0]
+            _lib.call("hx_sample_batch", s.total, s.cap, s.ring, None, 0, None, 0, self.batch, self.batch, 1, s.seed, s.call, 0.0, s.idx, None, None,
+                      self.expert_rows.data_ptr(), None, st)
+        _lib.call("hx_sac_critic_step", nets, ctypes.byref(batch), hyper, main, polyak_first, self.learning_steps, st)
+        _lib.call("hx_sac_policy_grads_imitative", nets, ctypes.byref(batch), hyper, imit, st)
+        _lib.call("hx_sac_adam", nets, hyper, 1, self.learning_steps, 1.0, self.target_entropy, st)
+
+    def imitative_losses_host(self):
+        """(bc_loss, bc_weight) of the last imitative learn()"""
+        v = self.losses.tolist()
+        return v[6], v[7]
+
     def _allreduce(self, t):
         if self.world > 1:
             torch.distributed.all_reduce(t, group=self.group)
@@ -321,6 +410,8 @@ class SacEngine:
         self.learning_steps += 1
         pending, self._pending = getattr(self, "_pending", None), None
         polyak_first = int(self.learning_steps % self.interval == 0)
+        if self.imitative:
+            return self._learn_imitative(batch, pending, polyak_first, st)
         if self.world == 1 and not getattr(self, "separate_critic_adam", False) and not getattr(self, "staged_policy", False):
             # one GPU: the whole learn() in one call, 9 launches (hx_sac_learn: bit-identical to the staged sequence below, 14 launches)
             _lib.call("hx_sac_learn", nets, ctypes.byref(batch), hyper, ctypes.byref(pending[0]) if pending is not None else None,
@@ -355,6 +446,14 @@ class SacEngine:
             raise _lib.HxError("SacEngine.step_learn: one GPU, the one-call learn(), more than 8,192 envs with a replay ring attached")
         if getattr(self, "_pending", None) is not None:
             raise _lib.HxError("step_learn draws its own minibatch: a sample(defer=True) is still pending")
+        if self.imitative:  # no front form: the reference's order; `expert` is the imitative branch's expert memory, the minibatch is not expert-mixed
+            if expert is None:
+                raise _lib.HxError("SacEngine.step_learn: the imitative branch needs the expert memory (expert=...)")
+            res = self.act_step(env, explore=explore, seed=act_seed, out=out)
+            self.sample(replay, None, seed=sample_seed, defer=True)
+            self.sample_expert(expert, seed=sample_seed, defer=True)
+            self.learn()
+            return res
         if self.act_dtype != self.update_dtype:  # bf16 acting beside the fp32 update: the front launch has no such mix (the reference's order)
             res = self.act_step(env, explore=explore, seed=act_seed, out=out)
             self.sample(replay, expert, n_main=n_main, seed=sample_seed, defer=True)

@@ -1,5 +1,5 @@
-// hx_sac.hip — SacAgent.learn (hirl/agents/SAC/agent.py:276-414, the non-imitative branch train_sac.py uses) on the shared fwd_l2 / bwd_l2<3> /
-// wgrad machinery, plus the small per-row kernels around it (gfx950).
+// hx_sac.hip — SacAgent.learn (hirl/agents/SAC/agent.py:276-414: the non-imitative branch train_sac.py uses, and the imitative one — "SAC, imitative
+// branch" below) on the shared fwd_l2 / bwd_l2<3> / wgrad machinery, plus the small per-row kernels around it (gfx950).
 #include <cmath>
 
 #include "hx_act.h"
@@ -199,6 +199,102 @@ __global__ __launch_bounds__(kThreads) void policy_dout_kernel(PDoutArgs A) {
         if (lane == 0) A.losses[4] = s * A.inv_batch;
     }
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// SAC, imitative branch (SAC/agent.py:385-403): the per-row kernels of the BC-gated policy loss.  One wave per row.
+// ---------------------------------------------------------------------------------------------------------------
+// a_bc = bc_actor(s): the frozen LayerNorm actor's tanh head from its z2 rows (leaky slope = a parameter; SAC's own launches run as ReLU,
+// so the bc_actor has a forward launch and this head kernel of its own)
+struct BcHeadArgs {
+    const float* net;
+    Mlp m;
+    const float* z2;
+    float slope;
+    int rows;
+    float* act;  // [rows][4]
+};
+__global__ __launch_bounds__(kThreads) void bc_head_kernel(BcHeadArgs A) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + wave;
+    if (r >= A.rows) return;
+    RowReg<H2> xh, y;
+    float mean_, rstd_, o[4];
+    head_row4<false>(A.z2 + (size_t)r * H2, A.net, A.m, A.slope, xh, y, mean_, rstd_, o);
+    if (lane < 4) A.act[(size_t)r * 4 + lane] = tanhf(lane == 0 ? o[0] : lane == 1 ? o[1] : lane == 2 ? o[2] : o[3]);
+}
+
+// bc_loss = mse(ae, tanh(mean)) * 10000 (agent.py:395-398) for ONE action component: the squared error and the gradient wrt the head's
+// pre-activation mean_j, scale = 2 * 10000 / (4 B).  Contraction off, the products spelled out: whoever evaluates it rounds alike.
+#pragma clang fp contract(off)
+__device__ __forceinline__ void isac_bc_dout(float mean, float ae, float scale, float& d_mean, float& sq) {
+    const float t = tanhf(mean);
+    const float diff = t - ae;
+    sq = diff * diff;
+    d_mean = (scale * diff) * (1.0f - t * t);
+}
+#pragma clang fp contract(fast)
+
+// Per minibatch row: the gate min(Q1, Q2)(s, a_bc) > min(Q1, Q2)(s, a~) (agent.py:390-393; strict >) counted as an INTEGER, so that
+// bc_weight = count / B does not depend on arrival order; per expert row: the BC head gradient of the 8-wide Gaussian head — the four
+// log_std outputs get exactly zero — and the row's squared error (summed in a fixed order by isac_finish_kernel).
+struct IsacRowsArgs {
+    const float* q1net;
+    const float* q2net;
+    Mlp mq;
+    const float* z2_q1p; const float* z2_q2p;  // Q1 / Q2 (s, a~)
+    const float* z2_q1b; const float* z2_q2b;  // Q1 / Q2 (s, a_bc)
+    const float* policy;
+    Mlp mp;
+    Slot pe;                   // policy(s_e): z2 read, dout written
+    const float* expert_rows;  // [rows][32]: the expert action in columns 13..16
+    int rows;
+    float scale;               // 2 * 10000 / (4 B)
+    int* count;
+    float* row_sq;             // [rows]
+};
+__global__ __launch_bounds__(kThreads) void isac_rows_kernel(IsacRowsArgs A) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + wave;
+    if (r >= A.rows) return;
+    RowReg<H2> xh, y;
+    float mean_, rstd_, qa[1], qb[1];
+    head_row<1, true>(A.z2_q1p + (size_t)r * H2, A.q1net, A.mq, 0.0f, xh, y, mean_, rstd_, qa);
+    head_row<1, true>(A.z2_q2p + (size_t)r * H2, A.q2net, A.mq, 0.0f, xh, y, mean_, rstd_, qb);
+    const float q = fminf(qa[0], qb[0]);
+    head_row<1, true>(A.z2_q1b + (size_t)r * H2, A.q1net, A.mq, 0.0f, xh, y, mean_, rstd_, qa);
+    head_row<1, true>(A.z2_q2b + (size_t)r * H2, A.q2net, A.mq, 0.0f, xh, y, mean_, rstd_, qb);
+    const float bc_q = fminf(qa[0], qb[0]);
+    if (lane == 0 && bc_q > q) atomicAdd(A.count, 1);
+    float o[8];
+    head_row<8, true>(A.pe.z2 + (size_t)r * H2, A.policy, A.mp, 0.0f, xh, y, mean_, rstd_, o);
+    const int j = lane & 3;
+    float d_mean, sq;
+    isac_bc_dout(pick8(o, j), A.expert_rows[(size_t)r * 32 + 13 + j], A.scale, d_mean, sq);
+    const float row_sq = sum16(lane < 4 ? sq : 0.0f);  // lanes 0..3 sit in the first 16-lane row
+    if (lane < 4) {
+        A.pe.dout[(size_t)r * OW + lane] = d_mean;
+        A.pe.dout[(size_t)r * OW + 4 + lane] = 0.0f;
+    }
+    if (lane == 0) A.row_sq[r] = row_sq;
+}
+
+// One wave, after every part of the policy loss is complete: bc_loss (fixed-order sum) -> losses[6], bc_weight -> losses[7], and
+// policy_loss = mean(-q - alpha H) (1 - w) + bc_loss w -> losses[2] (agent.py:400-403).  Contraction off: plain products and sums.
+#pragma clang fp contract(off)
+__global__ __launch_bounds__(64) void isac_finish_kernel(const float* row_sq, const int* count, int rows, float inv_batch, float* losses) {
+    const int lane = threadIdx.x;
+    float s = 0.0f;
+    for (int rr = lane; rr < rows; rr += 64) s += row_sq[rr];
+    s = wave_sum(s);
+    if (lane == 0) {
+        const float bc_loss = s * (2500.0f * inv_batch);  // 10000 * mean over B * 4 elements
+        const float w = (float)(*count) * inv_batch;
+        losses[6] = bc_loss;
+        losses[7] = w;
+        losses[2] = losses[2] * (1.0f - w) + bc_loss * w;
+    }
+}
+#pragma clang fp contract(fast)
 
 }  // namespace
 
@@ -480,6 +576,178 @@ int hx_sac_learn(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, co
     HX_REQUIRE(step >= 1, "hx_sac_learn: step is 1-based");
     if (int rc = sac_critic_grads_impl(N, Bt, Hy, S, polyak_first, stream, step, true)) return rc;
     return sac_policy_grads_impl(N, Bt, Hy, stream, step, target_entropy);
+}
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * SAC, imitative branch (SAC/agent.py:315-318, 353-359, 385-403; imitative=True).  The critic half is the code above, unchanged.  The policy half
+ * is sac_policy_grads_impl's sequence with the BC-gated loss around it (new launches marked +):
+ *     [gauss        a~, H = policy.sample(s)                                     staged form only]
+ *   + fwd_l2        bc_actor(s): LayerNorm actor, leaky slope = imit->bc_slope (a launch of its own: the activation is per launch); clears count
+ *   + bc_head       a_bc = tanh(head(bc_actor))
+ *     fwd_l2        Q1 / Q2 (s, a~), saved                                       (the launch of the plain call, same tiling: same bits)
+ *   + fwd_l2        Q1 / Q2 (s, a_bc) values only, policy(s_e) saved on the B expert rows
+ *   + isac_rows     count += min Q(s, a_bc) > min Q(s, a~) per row (integer); the BC head gradient of policy(s_e), log_std outputs exactly 0
+ *   + bwd_l2<3>     policy(s_e) down to dh1
+ *     [q_select] bwd_l2 (critics) [policy_dout] bwd_l2 (policy(s))               as in the plain call (folded prologues in the one call)
+ *   + isac_finish   losses[6] = bc_loss, losses[7] = bc_weight = count / B, losses[2] = policy_loss (1 - w) + bc_loss w
+ *     wgrad         ONE launch over both policy slots: slot 0 = policy(s) scaled (1 - w), slot 1 = policy(s_e) scaled w, w read from the count
+ *                   (+ Adam and the log-alpha step in the one call)
+ * Departures from the reference: bc_actor is the 13-input LayerNorm actor this project's BC agent writes (the reference builds a 14-input one
+ * against a 13-wide observation and crashes); WHICH expert rows are drawn is not claimed (Philox on the device, as hx_sample_batch).
+ * Imitative workspace: slots 0 bc_actor(s), 1 / 2 Q1 / Q2 (s, a_bc), 3 policy(s_e); then a_bc [B][4] and the per-row squared errors [B].
+ * ------------------------------------------------------------------------------------------------------------------ */
+enum { IS_BCA = 0, IS_Q1B, IS_Q2B, IS_PE, IS_COUNT };
+int hx_sac_imit_sizeof(void) { return (int)sizeof(HxSacImit); }
+int64_t hx_sac_imit_workspace_floats(int32_t batch) { return (int64_t)IS_COUNT * (int64_t)kSlotFloats * batch + 8 * (int64_t)batch; }
+
+static int sac_policy_grads_imit_impl(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, const HxSacImit* I, void* stream, int adam_step,
+                                      float target_entropy, const char* who) {
+    HX_REQUIRE(N && Bt && Hy && Bt->rows && Bt->batch > 0 && Bt->batch % 16 == 0, "%s: bad arguments", who);
+    HX_REQUIRE(I && I->bc_actor && I->expert_rows && I->ws && I->count, "%s: imit needs bc_actor, expert_rows, ws and count", who);
+    HX_REQUIRE(I->bc_slope >= 0.0f && I->bc_slope < 1.0f, "%s: imit->bc_slope is the bc_actor's leaky slope, in [0, 1)", who);
+    HX_REQUIRE(!N->w2_bf16_all, "%s: the imitative branch is fp32 only (nets->w2_bf16_all must be NULL)", who);
+    if (int rc = sac_check_formats(N, who)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int B = Bt->batch;
+    Slot s[S_COUNT], si[IS_COUNT];
+    sac_slots(N, B, s);
+    for (int i = 0; i < IS_COUNT; ++i) si[i] = carve_slot(I->ws + (size_t)i * kSlotFloats * B, B);
+    float* const a_bc = I->ws + (size_t)IS_COUNT * kSlotFloats * B;
+    float* const row_sq = a_bc + 4 * (size_t)B;
+    const SacAux X = sac_aux(N, B);
+    const RowSrc src{Bt->rows, nullptr, nullptr, 0, 32};
+    const RowSrc esrc{I->expert_rows, nullptr, nullptr, 0, 32};
+    const float* q1 = N->critic; const float* q2 = N->critic + kQs.padded();
+    const unsigned nb = (unsigned)((B + 3) / 4);
+    if (adam_step == 0) {
+        const GaussArgs G{N->policy, kPolicy, s[SS_PC].z2, Bt->eps_cur, B, Bt->eps_cur ? 1 : 2, X.act_c, nullptr, X.aux_c, Bt->seed, 0x80000000u, Bt->call};
+        launch_gauss(G, nullptr, nullptr, nullptr, 0, 0.0f, st);
+    }
+    {   // bc_actor(s), no gradient
+        FwdArgs F{};
+        F.njobs = 1; F.slope = I->bc_slope;
+        F.zero_i = I->count;
+        F.job[0] = FwdJob{I->bc_actor, kActor, src, 0, 0, Head{}, nullptr, 0.f, si[IS_BCA], B, 0, IM_BC};
+        launch_fwd(F, st);
+        BcHeadArgs H{I->bc_actor, kActor, si[IS_BCA].z2, I->bc_slope, B, a_bc};
+        hipLaunchKernelGGL(bc_head_kernel, dim3(nb), dim3(kThreads), 0, st, H);
+    }
+    {   // Q1 / Q2 (s, a~): the plain call's launch
+        FwdArgs F{};
+        F.njobs = 2; F.slope = 0.0f;
+        F.job[0] = FwdJob{q1, kQs, src, 0, 3, Head{}, X.act_c, 0.f, s[SS_Q1P], B, 1, IM_C1};
+        F.job[1] = FwdJob{q2, kQs, src, 0, 3, Head{}, X.act_c, 0.f, s[SS_Q2P], B, 1, IM_C2};
+        launch_fwd(F, st);
+    }
+    {   // Q1 / Q2 (s, a_bc): values only; policy(s_e), saved for its backward pass
+        FwdArgs F{};
+        F.njobs = 3; F.slope = 0.0f;
+        F.job[0] = FwdJob{q1, kQs, src, 0, 3, Head{}, a_bc, 0.f, si[IS_Q1B], B, 0, IM_C1};
+        F.job[1] = FwdJob{q2, kQs, src, 0, 3, Head{}, a_bc, 0.f, si[IS_Q2B], B, 0, IM_C2};
+        F.job[2] = FwdJob{N->policy, kPolicy, esrc, 0, 0, Head{}, nullptr, 0.f, si[IS_PE], B, 1, IM_ACTOR};
+        launch_fwd(F, st);
+    }
+    {   // the gate's count, the BC head gradient
+        IsacRowsArgs R{q1, q2, kQs, s[SS_Q1P].z2, s[SS_Q2P].z2, si[IS_Q1B].z2, si[IS_Q2B].z2, N->policy, kPolicy, si[IS_PE], I->expert_rows, B,
+                       (2.0f * 10000.0f * 0.25f) / B, I->count, row_sq};
+        hipLaunchKernelGGL(isac_rows_kernel, dim3(nb), dim3(kThreads), 0, st, R);
+    }
+    {   // policy(s_e) backward down to dh1
+        BwdArgs G{};
+        G.njobs = 1; G.slope = 0.0f; G.inv_batch = 1.0f / B; G.losses = N->losses;
+        BwdJob& J = G.job[0];
+        J = BwdJob{};
+        J.net = N->policy; J.m = kPolicy; J.ws = si[IS_PE]; J.rows = B; J.mode = BM_GIVEN; J.img_t = IM_ACTOR_T;
+        if (int rc = launch_bwd(3, G, st)) return rc;
+    }
+    // from here to the weight gradients: sac_policy_grads_impl's launches on the same values (the one call folds q_select / policy_dout)
+    static const bool fold_env = !(getenv("HX_SAC_FOLD") && getenv("HX_SAC_FOLD")[0] == '0');
+    const bool fold = adam_step > 0 && fold_env;
+    if (!fold) {
+        QSelArgs Q{q1, q2, kQs, s[SS_Q1P], s[SS_Q2P], B, 1.0f / B, N->losses};
+        hipLaunchKernelGGL(q_select_kernel, dim3(nb), dim3(kThreads), 0, st, Q);
+    }
+    {
+        BwdArgs G{};
+        G.njobs = 2; G.slope = 0.0f; G.inv_batch = 1.0f / B; G.losses = N->losses;
+        for (int h = 0; h < 2; ++h) {
+            BwdJob& J = G.job[h];
+            J = BwdJob{};
+            J.net = h ? q2 : q1; J.m = kQs; J.ws = s[SS_Q1P + h]; J.rows = B; J.mode = fold ? BM_SAC_QMIN : BM_GIVEN;
+            if (fold) { J.t1 = Head{h ? q1 : q2, kQs, s[SS_Q1P + (1 - h)]}; J.loss_slot = h; }
+            J.img_t = IM_C1_T + h;
+        }
+        if (int rc = launch_bwd(fold ? 4 : 3, G, st)) return rc;
+    }
+    if (!fold) {
+        PDoutArgs P{q1, q2, kQs, s[SS_Q1P], s[SS_Q2P], s[SS_PC], X.aux_c, N->alpha_state, B, 1.0f / B, N->losses};
+        hipLaunchKernelGGL(policy_dout_kernel, dim3(nb), dim3(kThreads), 0, st, P);
+    }
+    {
+        BwdArgs G{};
+        G.njobs = 1; G.slope = 0.0f; G.inv_batch = 1.0f / B; G.losses = N->losses;
+        BwdJob& J = G.job[0];
+        J = BwdJob{};
+        J.net = N->policy; J.m = kPolicy; J.ws = s[SS_PC]; J.rows = B; J.mode = fold ? BM_SAC_POLICY : BM_GIVEN;
+        if (fold) {
+            J.t1 = Head{q1, kQs, s[SS_Q1P]}; J.t2 = Head{q2, kQs, s[SS_Q2P]};
+            J.bonus = X.aux_c; J.bonus_scale = N->alpha_state + 3;
+        }
+        J.img_t = IM_ACTOR_T;
+        if (int rc = launch_bwd(fold ? 5 : 3, G, st)) return rc;
+    }
+    // both parts of the policy loss are complete: combine them (a launch of its own rather than thread 0 of the weight-gradient launch, whose
+    // SAC step already carries the log-alpha state in the fields HIRL's finish_actor uses — and whose register figures stay what they were)
+    hipLaunchKernelGGL(isac_finish_kernel, dim3(1), dim3(64), 0, st, row_sq, I->count, B, 1.0f / B, N->losses);
+    {
+        WgArgs W{};
+        W.njobs = 1; W.slope = 0.0f; W.w_kind = 1; W.warm = 0.0f; W.inv_batch = 1.0f / B; W.soft_count = I->count;
+        WgJob& J = W.job[0];
+        J = WgJob{};
+        J.net = N->policy; J.grad = N->grad_policy; J.m = kPolicy; J.nslots = 2;
+        J.ws[0] = s[SS_PC]; J.rows[0] = B; J.wmode[0] = 1;     // policy(s):   (1 - w)
+        J.ws[1] = si[IS_PE]; J.rows[1] = B; J.wmode[1] = 2;    // policy(s_e): w
+        if (adam_step > 0) {
+            const double b1 = 0.9, b2 = 0.999;
+            const double bc1 = 1.0 - pow(b1, adam_step), bc2 = 1.0 - pow(b2, adam_step);
+            J.p = N->policy; J.mom = N->m_policy; J.var = N->v_policy;
+            J.w2f = N->policy_w2_f32i;
+            if (N->policy_w2_x9) { J.w2b = N->policy_w2_x9; J.w2b_x9 = 1; }
+            if (N->policy_w2_bf16) J.w2b = N->policy_w2_bf16;
+            W.ad = WgAdam{};
+            W.ad.b1 = (float)b1; W.ad.b2 = (float)b2; W.ad.eps = 1e-8f;
+            W.ad.step_size = (float)(Hy->lr_actor / bc1);
+            W.ad.bc2_sqrt = (float)sqrt(bc2);
+            W.ad.losses = N->losses;
+            W.ad.alpha_state = N->alpha_state; W.ad.target_entropy = target_entropy; W.ad.alpha_step_size = (float)(Hy->lr_actor / bc1);
+            launch_wg(W, true, st);
+        } else {
+            launch_wg(W, false, st);
+        }
+    }
+    HX_CHECK_LAUNCH(who);
+    return 0;
+}
+/* Staged form, gradients only: follow with hx_sac_adam(which = 1). */
+int hx_sac_policy_grads_imitative(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, const HxSacImit* I, void* stream) {
+    return sac_policy_grads_imit_impl(N, Bt, Hy, I, stream, 0, 0.0f, "hx_sac_policy_grads_imitative");
+}
+/* One GPU: the whole imitative SacAgent.learn in one call.  Bit-identical to hx_sac_critic_step + hx_sac_policy_grads_imitative +
+ * hx_sac_adam(which = 1).  expert_sample NULL: the expert rows are in imit->expert_rows already; else the B rows are drawn from the expert
+ * memory it describes (total / cap / ring: the expert ring as the main ring, n_main = batch) as hx_sample_batch draws them. */
+int hx_sac_learn_imitative(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, const HxSample* S, const HxSacImit* I, const HxSample* ES,
+                           int32_t polyak_first, int32_t step, float target_entropy, void* stream) {
+    HX_REQUIRE(step >= 1, "hx_sac_learn_imitative: step is 1-based");
+    HX_REQUIRE(N && Bt && I && I->bc_actor && I->expert_rows && I->ws && I->count, "hx_sac_learn_imitative: imit needs bc_actor, expert_rows, ws and count");
+    HX_REQUIRE(!N->w2_bf16_all, "hx_sac_learn_imitative: the imitative branch is fp32 only (nets->w2_bf16_all must be NULL)");
+    if (ES) {
+        HX_REQUIRE(ES->n_main == Bt->batch && !ES->expert_ring && !ES->bc_table && !ES->idx_bc && !ES->guard && ES->idx,
+                   "hx_sac_learn_imitative: expert_sample describes the expert memory as the main ring (n_main = batch, idx; no expert ring, BC table or guard)");
+        if (int rc = hx_sample_batch(ES->total, ES->cap, ES->ring, nullptr, 0, nullptr, 0, Bt->batch, Bt->batch, 1, ES->seed, ES->call, 0.0f, ES->idx,
+                                     nullptr, nullptr, I->expert_rows, nullptr, stream)) return rc;
+    }
+    if (int rc = sac_critic_grads_impl(N, Bt, Hy, S, polyak_first, stream, step, true)) return rc;
+    return sac_policy_grads_imit_impl(N, Bt, Hy, I, stream, step, target_entropy, "hx_sac_learn_imitative");
 }
 
 /* hx_sac_learn in two parts around an env step (include/hirl4ucav.h "SAC front launch"): hx_sac_front = hx_sac_act_step_x9 / _f32i for n > 8,192 envs AND the first

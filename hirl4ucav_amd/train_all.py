@@ -282,6 +282,9 @@ def main(config):
         return train_bc(config, device, seed, max_step)
     hirl = config.agent == "HIRL"
     esac = config.agent == "SAC" and config.type == "ESAC"
+    isac = config.agent == "SAC" and config.type == "ISAC"  # SacAgent(imitative=True): the BC-gated policy loss; the minibatch is NOT expert-mixed
+    if isac and (world > 1 or getattr(config, "dtype", "f32") != "f32" or not config.bc_actor):
+        raise SystemExit("train_all: " + isac_refusal(config, world))
     batch, buffer_size, checkpoint_rate = 128, config.buffer_size, config.checkpoint_rate  # train_all.py:190-208
     warm_up_rate = 20 if config.agent == "SAC" else 10  # train_sac.py:203 / train_all.py:207
 
@@ -301,7 +304,7 @@ def main(config):
         eng.load_params(init_actor_state_dict(), init_critic_state_dict(), init_actor_state_dict() if hirl else None)
     expert_len = bc_len = 0
     expert = bc_table = None
-    if hirl or esac:
+    if hirl or esac or isac:
         es, ea = load_expert(config)
         rows, succ = label_expert(es, ea, device)
         expert = DeviceReplay(rows.shape[0] + 10, device)
@@ -316,6 +319,10 @@ def main(config):
             eng.bc_actor.copy_(E.pack(torch.load(config.bc_actor, map_location="cpu"), E.ACTOR_LAYOUT, E.ACTOR_SIZE, device))
         elif hirl and config.type == "soft" and rank == 0:
             print("WARNING: HIRL-soft without --bc_actor: the soft weight is estimated against a randomly initialised bc_actor", flush=True)
+        if isac:  # agent.load_bc_actor (SAC/agent.py:158-160): a missing file is an error, as for HIRL
+            if not os.path.exists(config.bc_actor):
+                raise FileNotFoundError(f"--bc_actor {config.bc_actor}: no such file")
+            eng.set_imitative(torch.load(config.bc_actor, map_location="cpu"), slope=0.01)
     dtype, warning, refusal, mark = resolve_dtype(sac, getattr(config, "dtype", "f32"), snap["driver"] if snap is not None else None)
     dtype_mark = {"dtype_honoured": True} if mark else {}  # (in every snapshot's driver record)
     if warning and rank == 0:
@@ -431,9 +438,11 @@ def main(config):
                 continue
             if front_sac and step < max_step - 1:  # SAC / E-SAC: explore + env step + the first forward launch of learn() in one launch (SacEngine.step_learn)
                 expert_num = expert_num_after(expert_num, step, warm_up_rate)
-                eng.step_learn(env, expert if esac else None, n_main=batch - expert_num, act_seed=seed + 1, out=actions, sample_seed=seed + 2 + rank)
+                eng.step_learn(env, expert if (esac or isac) else None, n_main=batch - expert_num, act_seed=seed + 1, out=actions, sample_seed=seed + 2 + rank)
                 if ret is not None:
                     ret += env.reward
+                if isac and writer is not None and step % log_rate == 0:  # SAC/agent.py:353-359
+                    log_imitative(writer, eng, step + episode * max_step)
                 continue
             if config.separate_launches:  # chooseAction, then env.step: two launches
                 eng.act(env.obs, seed=seed + 1, row0=env.env_id0, out=actions) if sac else eng.act(env.obs, sigma=0.1, seed=seed + 1, row0=env.env_id0, out=actions)
@@ -450,6 +459,8 @@ def main(config):
             for _ in range(config.updates_per_step):
                 if sac:  # train_sac.py:270-273 (SAC) / :401-403 (E-SAC: expert rows mixed in while expert_num > 0)
                     eng.sample(replay, expert if esac else None, n_main=batch - expert_num, seed=seed + 2 + rank, defer=True)
+                    if isac:  # expert_memory.sample(batch_size), SAC/agent.py:392: the second batch, drawn inside learn() too
+                        eng.sample_expert(expert, seed=seed + 2 + rank, defer=True)
                     eng.learn()
                     continue
                 eng.sample(replay, expert, bc_table, n_main=batch - expert_num, seed=seed + 2 + rank, defer=True)  # drawn inside learn()'s first launch
@@ -459,6 +470,8 @@ def main(config):
                 c_, a_, b_, r__, f_, _w = eng.losses_host()
                 for tag, v in (("Loss/Critic_Loss", c_), ("Loss/Actor_Loss", a_), ("Loss/BC_Loss", b_), ("Loss/RL_Loss", r__), ("Loss/BC_Fire_Loss", f_)):
                     writer.add_scalar(tag, v, step + episode * max_step)
+            if isac and writer is not None and step % log_rate == 0:  # SAC/agent.py:353-359
+                log_imitative(writer, eng, step + episode * max_step)
         if front and not tripped:
             tripped = front_tripped()  # ... and at every episode's end: nothing of a tripped episode reaches a validation, a checkpoint or a snapshot
         if tripped:
@@ -544,11 +557,45 @@ def main(config):
     return log_dir
 
 
+def log_imitative(writer, eng, at):
+    """loss/bc and loss/bc_weight of the imitative SAC branch (SAC/agent.py:353-359)"""
+    bc_loss, bc_weight = eng.imitative_losses_host()
+    writer.add_scalar("loss/bc", bc_loss, at)
+    writer.add_scalar("loss/bc_weight", bc_weight, at)
+
+
+def isac_refusal(config, world=1):
+    """why `--agent SAC --type ISAC` cannot run as asked, or None"""
+    if config.agent != "SAC" or config.type != "ISAC":
+        return None
+    if getattr(config, "dtype", "f32") != "f32":
+        return f"--type ISAC with --dtype {config.dtype}: the imitative branch is fp32 only (its kernels have no bf16 form): drop --dtype"
+    if (config.gpus and config.gpus > 1) or world > 1:
+        return "--type ISAC runs on one GPU (the gate's count is not exchanged between ranks): use --gpus 1"
+    if not config.bc_actor:
+        return "--type ISAC needs --bc_actor FILE: the frozen actor a `--agent BC` run writes"
+    if not config.expert_csv and not getattr(config, "synthetic_expert", False):
+        return "--type ISAC needs an expert table: --expert_csv FILE or --synthetic_expert"
+    return None
+
+
+def parse_args(argv=None):
+    """parser().parse_args with the cross-flag checks that are argparse errors"""
+    p = parser()
+    cfg = p.parse_args(argv)
+    if cfg.type == "ISAC" and cfg.agent != "SAC":
+        p.error("--type ISAC goes with --agent SAC")
+    why = isac_refusal(cfg)
+    if why:
+        p.error(why)
+    return cfg
+
+
 def parser():
     p = argparse.ArgumentParser()  # the reference's flags, train_all.py:489-513
     p.add_argument("--agent", type=str, default="HIRL", choices=["HIRL", "TD3", "BC", "SAC"])  # SAC: the train_sac.py path (D2)
     p.add_argument("--port", type=int, default=None)
-    p.add_argument("--type", type=str, default="soft", choices=["soft", "linear", "fixed", "SAC", "ESAC"])  # SAC / ESAC: train_sac.py:440-458
+    p.add_argument("--type", type=str, default="soft", choices=["soft", "linear", "fixed", "SAC", "ESAC", "ISAC"])  # SAC / ESAC: train_sac.py:440-458; ISAC: SacAgent(imitative=True)
     p.add_argument("--bc_weight", type=float, default=0.5)
     p.add_argument("--model_name", type=str, default="model")
     p.add_argument("--load_model", action="store_true")
@@ -601,7 +648,7 @@ def parser():
 if __name__ == "__main__":
     import sys
 
-    cfg = parser().parse_args()
+    cfg = parse_args()
     if cfg.gpus and cfg.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(cfg.gpus, sys.argv[1:]))
     main(cfg)

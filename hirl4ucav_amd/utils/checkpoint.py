@@ -19,6 +19,8 @@ def engine_state(eng):
     st = {"arena": eng.arena.detach().cpu().clone(), "counters": {k: getattr(eng, k) for k in ENGINE_COUNTERS if hasattr(eng, k)}}
     if hasattr(eng, "acting_format"):
         st["acting_format"] = eng.acting_format()  # the run's arithmetic is part of its state (train_all.py: --dtype; here: what the flag does not say)
+    if getattr(eng, "imitative", False):  # SAC's imitative branch only (a plain SAC snapshot stays as it was): the frozen BC actor and the expert-draw counter
+        st["imitative"] = {"bc_actor": eng.bc_actor.detach().cpu().clone(), "bc_slope": eng.bc_slope, "expert_calls": eng.expert_calls}
     return st
 
 
@@ -32,7 +34,12 @@ def load_engine_state(eng, st):
         # (a snapshot from before round 6 carries no format: round 5's default, or round 4's x9_rows = 16,384 with nine terms — it cannot tell)
         warnings.warn(f"snapshot was written under acting format {was if was is not None else 'unrecorded (a round <= 5 snapshot)'}, this engine "
                       f"acts under {now}: the run continues under other acting arithmetic (fp32 results up to summation order)", stacklevel=2)
+    if ("imitative" in st) != bool(getattr(eng, "imitative", False)):
+        raise ValueError("snapshot and engine disagree about SAC's imitative branch (--type ISAC): resume with the type the run was started with")
     eng.arena.copy_(st["arena"])
+    if "imitative" in st:
+        eng.bc_actor.copy_(st["imitative"]["bc_actor"])
+        eng.expert_calls = st["imitative"]["expert_calls"]
     if hasattr(eng, "needs_reload"):
         eng.needs_reload = False  # host counters and device state agree again from here
     if hasattr(eng, "front_reset"):

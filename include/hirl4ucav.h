@@ -72,8 +72,9 @@ const char* hx_last_error(void);
 /* HX_ABI_VERSION of the library that is loaded.  The structs below are part of the ABI: a caller built against another header version must
  * not call in (round 3 widened HxStepOpts.stats from 9 to HX_STAT_WAYS * HX_STAT_PITCH words and appended fields to HxNets / HxHyper without
  * bumping this: a 9-word stats buffer then took atomics up to word 504).  110: round 4 (hx_abi_sizes, hx_rccl_*, hx_allreduce_twostage).
- * 113: round 5.  114: round 6 (hx_rccl_allreduce_bf16).  115: the SAC bf16 path (HxSacNets.w2_bf16_all / policy_w2_bf16, hx_sac_*_bf16). */
-#define HX_ABI_VERSION 115
+ * 113: round 5.  114: round 6 (hx_rccl_allreduce_bf16).  115: the SAC bf16 path (HxSacNets.w2_bf16_all / policy_w2_bf16, hx_sac_*_bf16).
+ * 116: SAC's imitative branch (HxSacImit, hx_sac_imit_*, hx_sac_policy_grads_imitative, hx_sac_learn_imitative). */
+#define HX_ABI_VERSION 116
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -422,7 +423,7 @@ typedef struct HxSacNets {
     float* policy; float* critic; float* target_critic;
     float* grad_policy; float* grad_critic;
     float* m_policy; float* v_policy; float* m_critic; float* v_critic;
-    float* losses;      /* [8]: q1_loss, q2_loss, policy_loss, entropy_loss, mean entropy, alpha */
+    float* losses;      /* [8]: q1_loss, q2_loss, policy_loss, entropy_loss, mean entropy, alpha, -, -  (imitative calls: [6] bc_loss, [7] bc_weight) */
     float* alpha_state; /* [4]: log_alpha, its Adam m and v, alpha = exp(log_alpha)  (SAC/agent.py:106-108) */
     float* ws;          /* hx_sac_workspace_floats(batch) */
     float* policy_w2_f32i; /* NULL, or the fp32 image of the policy's W2 (hx_pack_w2_f32i(policy, 13, ...)): hx_sac_adam(which = 1) keeps it
@@ -526,6 +527,39 @@ int hx_sac_learn_back(const HxSacNets* nets, const HxSacBatch* batch, const HxHy
                       const HxSample* next, float* next_rows, void* stream);
 int hx_sac_adam(const HxSacNets* nets, const HxHyper* hyper, int32_t which, int32_t step, float grad_scale, float target_entropy,
                 void* stream);
+
+/* SAC, imitative branch (SAC/agent.py:315-318, 353-359, 385-403; SacAgent(imitative=True)).  After the two critic steps, with the UPDATED critics:
+ *     a~, H     = policy.sample(s)                          q    = min(Q1, Q2)(s, a~)
+ *     a_bc      = bc_actor(s)   (frozen, no gradient)       bc_q = min(Q1, Q2)(s, a_bc)
+ *     bc_weight = mean(bc_q > q)                            strict >, over the batch rows; a plain number: no gradient through it
+ *     bc_loss   = mse(a_e, tanh(mean(s_e))) * 10000         on a SECOND batch of B rows from the expert memory; mean = first half of the policy head
+ *     policy_loss = mean(-q - alpha H) (1 - bc_weight) + bc_loss bc_weight
+ * then policy_optim.step() and the log-alpha step exactly as in the plain call.  losses[2] = the COMBINED policy loss, losses[6] = bc_loss,
+ * losses[7] = bc_weight.  The gate is an INTEGER count (imit->count), so the weight does not depend on arrival order; bc_loss is a fixed-order sum.
+ * Launch sequence of the policy half (+ = added to the plain call's): [policy.sample(s)] + bc_actor(s) + its tanh head; Q1 / Q2 (s, a~);
+ * + Q1 / Q2 (s, a_bc) and policy(s_e); + the gate's count and the BC head gradient (zero for the four log_std outputs); + policy(s_e) backward;
+ * the critics' and policy(s)'s backward as in the plain call; + the loss combination; ONE weight-gradient launch over both policy slots,
+ * policy(s) scaled (1 - w) and policy(s_e) scaled w (with Adam and the log-alpha step inside it in the one call).
+ * Departures from the reference: (1) it builds bc_actor with 14 inputs against the 13-wide observation and so crashes as written; here bc_actor
+ * is the 13-input LayerNorm actor (hx_actor_param_count() floats, the flat actor layout) that the BC agent of this project writes, leaky slope
+ * bc_slope (0.01 there); (2) which expert rows are drawn is not claimed: Philox on the device, as hx_sample_batch.  fp32 only: with
+ * nets->w2_bf16_all set both entry points return an error.  One GPU. */
+typedef struct HxSacImit {
+    const float* bc_actor; /* the frozen BC actor's flat block */
+    float* expert_rows;    /* [batch][HX_ROW_WORDS]: the second minibatch, B rows of the expert memory (s_e in columns 0..12, a_e in 13..16) */
+    float* ws;             /* hx_sac_imit_workspace_floats(batch), beside HxSacNets.ws */
+    int32_t* count;        /* one word: rows whose bc_q > q in the last call */
+    float bc_slope;        /* leaky slope of bc_actor */
+} HxSacImit;
+int hx_sac_imit_sizeof(void); /* sizeof(HxSacImit) of the loaded library (hx_abi_sizes has no free word) */
+int64_t hx_sac_imit_workspace_floats(int32_t batch);
+/* Staged form of the imitative policy half: gradients only (grad_policy holds (1 - w) dL_rl + w dL_bc); follow with hx_sac_adam(which = 1). */
+int hx_sac_policy_grads_imitative(const HxSacNets* nets, const HxSacBatch* batch, const HxHyper* hyper, const HxSacImit* imit, void* stream);
+/* One GPU: the whole imitative learn() in one call; its critic half is hx_sac_learn's.  expert_sample NULL: imit->expert_rows holds the expert
+ * rows already; else it describes the expert memory as the main ring of an HxSample (total / cap / ring, n_main = batch, idx) and the rows are
+ * drawn as hx_sample_batch draws them.  Bit-identical to hx_sac_critic_step + hx_sac_policy_grads_imitative + hx_sac_adam(which = 1). */
+int hx_sac_learn_imitative(const HxSacNets* nets, const HxSacBatch* batch, const HxHyper* hyper, const HxSample* sample, const HxSacImit* imit,
+                           const HxSample* expert_sample, int32_t polyak_first, int32_t step, float target_entropy, void* stream);
 
 
 /* ------------------------------------------------------------------------------------------------------------

@@ -192,6 +192,17 @@ def main():
             pb16.policy_w2_x9, pb16.policy_w2_bf16 = None, dev(512 * 256 * 2)
             refused("hx_sac_front", sn.policy, None, w2f, state, n, n, obs, act, 2, None, 1, 0, 1, rew, done, succ, ctypes.byref(o), ctypes.byref(pb16),
                     ctypes.byref(sb), None)
+    # SAC's imitative branch: both entry points, expert rows given and drawn; refused on the bf16 path and without its buffers
+    L.hx_sac_imit_workspace_floats.restype = ctypes.c_int64
+    assert L.hx_sac_imit_sizeof() == ctypes.sizeof(S.HxSacImit)
+    imit = S.HxSacImit(dev(140000 * 4), dev(B * 128), dev(int(L.hx_sac_imit_workspace_floats(B)) * 4), dev(4), 0.01)
+    esmp = E.HxSample(dev(8), 1024, dev(1024 * 128), None, 0, None, 0, B, 3, 2, 0.0, dev(B * 4), None, 0)
+    ok("hx_sac_policy_grads_imitative", ctypes.byref(sn), ctypes.byref(sb), hs, ctypes.byref(imit), None)
+    for es in (None, ctypes.byref(esmp)):
+        ok("hx_sac_learn_imitative", ctypes.byref(sn), ctypes.byref(sb), hs, None, ctypes.byref(imit), es, 1, 3, -4.0, None)
+    refused("hx_sac_policy_grads_imitative", ctypes.byref(sb16), ctypes.byref(sb), hs, ctypes.byref(imit), None)
+    refused("hx_sac_learn_imitative", ctypes.byref(sb16), ctypes.byref(sb), hs, None, ctypes.byref(imit), None, 1, 3, -4.0, None)
+    refused("hx_sac_learn_imitative", ctypes.byref(sn), ctypes.byref(sb), hs, None, ctypes.byref(S.HxSacImit()), None, 1, 3, -4.0, None)
     mixed = S.HxSacNets(*[getattr(sb16, f) for f, _ in S.HxSacNets._fields_])
     mixed.policy_w2_x9 = w2x
     refused("hx_sac_learn", ctypes.byref(mixed), ctypes.byref(sb), hs, None, 0, 3, -4.0, None)
