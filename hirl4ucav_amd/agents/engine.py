@@ -135,6 +135,34 @@ def len_of(replay):
     return 0 if replay is None else int(getattr(replay, "fixed_len", replay.capacity))
 
 
+def carve(sizes, device):
+    """ONE zeroed fp32 arena for everything an engine's update kernels touch, cut into views of `sizes` floats in that order, each on a
+    256-byte boundary: a single contiguous mapping keeps the number of distinct pages / translations a short kernel has to fetch small.
+    -> (arena, views)"""
+    offs, tot = [], 0
+    for n in sizes:
+        offs.append(tot)
+        tot += (n + 63) & ~63
+    arena = torch.zeros(tot, dtype=torch.float32, device=device)
+    return arena, [arena[o:o + n] for o, n in zip(offs, sizes)]
+
+
+def _noise_mode(noise, sigma):
+    """hx_actor_act*'s noise_mode: 0 none, 1 one shared draw noise[4], 2 noise[N, 4] per row, 3 Philox N(0, sigma^2) per row and component"""
+    if noise is not None:
+        return 1 if noise.numel() == 4 else 2
+    return 3 if sigma > 0 else 0
+
+
+def _bc_weight_kind(bc_weight_now):
+    """learn()'s bc_weight_now -> (w_kind, w_given): None = keep the stored device value, 100 = estimate the soft weight now (HIRL.py:299), else given"""
+    if bc_weight_now is None:
+        return 2, 0.0
+    if bc_weight_now == 100:
+        return 1, 0.0
+    return 0, float(bc_weight_now)
+
+
 class HirlEngine:
     def __init__(self, batch=128, lr_actor=1e-3, lr_critic=1e-3, tau=0.005, gamma=0.99, slope=0.0, use_bc=True,
                  device="cuda", group=None, layer_norm=True):
@@ -147,19 +175,12 @@ class HirlEngine:
         assert L.hx_actor_param_count() == ACTOR_SIZE and L.hx_critic_param_count() == CRITIC_SIZE
         L.hx_hirl_workspace_floats.restype = ctypes.c_int64
         self.batch = int(batch)
-        # ONE arena for everything the update kernels touch (5 nets, gradients, Adam moments, workspace, minibatch tiles):
-        # a single contiguous mapping keeps the number of distinct pages / translations a short kernel has to fetch small
+        # ONE arena (carve) for the 5 nets, gradients, Adam moments, workspace and minibatch tiles
         ws_floats = int(L.hx_hirl_workspace_floats(self.batch))
-        sizes = [ACTOR_SIZE] * 3 + [CRITIC_SIZE] * 2 + [CRITIC_SIZE + ACTOR_SIZE] + [ACTOR_SIZE] * 2 + [CRITIC_SIZE] * 2 + \
-                [64, 64, 64, ws_floats, self.batch * 32, self.batch * 32, self.batch, self.batch, 64]
-        offs, tot = [], 0
-        for n in sizes:
-            offs.append(tot)
-            tot += (n + 63) & ~63  # 256-B aligned carve-outs
-        self.arena = torch.zeros(tot, dtype=torch.float32, device=self.device)
-        carve = [self.arena[o:o + n] for o, n in zip(offs, sizes)]
+        self.arena, views = carve([ACTOR_SIZE] * 3 + [CRITIC_SIZE] * 2 + [CRITIC_SIZE + ACTOR_SIZE] + [ACTOR_SIZE] * 2 + [CRITIC_SIZE] * 2 +
+                                  [64, 64, 64, ws_floats, self.batch * 32, self.batch * 32, self.batch, self.batch, 64], self.device)
         (self.actor, self.target_actor, self.bc_actor, self.critic, self.target_critic, self.grad, self.m_actor, self.v_actor,
-         self.m_critic, self.v_critic, self.losses, sc, self.wstate, self.ws, self.rows, self.bc_rows, ix, ixb, self._noise) = carve
+         self.m_critic, self.v_critic, self.losses, sc, self.wstate, self.ws, self.rows, self.bc_rows, ix, ixb, self._noise) = views
         self.grad_critic, self.grad_actor = self.grad[:CRITIC_SIZE], self.grad[CRITIC_SIZE:]
         self.soft_count, self._idx, self._idx_bc = sc.view(torch.int32), ix.view(torch.int32), ixb.view(torch.int32)
         self.losses, self.wstate, self._noise = self.losses[:8], self.wstate[:1], self._noise[:4]
@@ -315,6 +336,14 @@ class HirlEngine:
             self._x9_live = True
         return True
 
+    def _act_format(self, n):
+        """the engine's own actor on n rows -> (suffix of the hx_actor_act* / hx_actor_act_step* entry point, its image pointer), the suffix one of "_bf16", "_x9", "_f32i" """
+        if self.act_dtype == "bf16":
+            return "_bf16", self.w2_bf16.data_ptr()
+        if self._x9_for(n):
+            return "_x9", self.w2_x9.data_ptr()
+        return "_f32i", self.w2_f32i.data_ptr()
+
     refresh_images = refresh_bf16
 
     def acting_format(self):
@@ -357,27 +386,15 @@ class HirlEngine:
         n = obs.shape[0]
         if out is None:
             out = torch.empty((n, 4), dtype=torch.float32, device=self.device)
-        mode = 0
-        if noise is not None:
-            mode = 1 if noise.numel() == 4 else 2
-        elif sigma > 0:
-            mode = 3
+        mode = _noise_mode(noise, sigma) | self._mode_bits
         self.act_calls += 1
-        if self.act_dtype == "bf16" and net is None:
-            _lib.call("hx_actor_act_bf16", self.actor.data_ptr(), self.w2_bf16.data_ptr(), obs.data_ptr(), n, out.data_ptr(), mode | self._mode_bits, _lib.ptr(noise),
-                      float(sigma), int(seed), int(row0), self.act_calls, self.slope, _lib.stream_ptr())
+        if net is None:  # the engine's own actor: W2 from an image (fp32 image: same bits as hx_actor_act, no LDS staging of W2)
+            fmt, image = self._act_format(n)
+            _lib.call("hx_actor_act" + fmt, self.actor.data_ptr(), image, obs.data_ptr(), n, out.data_ptr(), mode, _lib.ptr(noise), float(sigma), int(seed),
+                      int(row0), self.act_calls, self.slope, _lib.stream_ptr())
             return out
-        if net is None and self._x9_for(n):
-            _lib.call("hx_actor_act_x9", self.actor.data_ptr(), self.w2_x9.data_ptr(), obs.data_ptr(), n, out.data_ptr(), mode | self._mode_bits, _lib.ptr(noise),
-                      float(sigma), int(seed), int(row0), self.act_calls, self.slope, _lib.stream_ptr())
-            return out
-        if net is None:  # the engine's own actor: W2 from its fp32 image (same bits as hx_actor_act, no LDS staging of W2)
-            _lib.call("hx_actor_act_f32i", self.actor.data_ptr(), self.w2_f32i.data_ptr(), obs.data_ptr(), n, out.data_ptr(), mode | self._mode_bits, _lib.ptr(noise),
-                      float(sigma), int(seed), int(row0), self.act_calls, self.slope, _lib.stream_ptr())
-            return out
-        _lib.call("hx_actor_act", net.data_ptr(), obs.data_ptr(), n, out.data_ptr(), mode | self._mode_bits,
-                  _lib.ptr(noise), float(sigma), int(seed), int(row0), self.act_calls, self.slope, None,
-                  _lib.stream_ptr())
+        _lib.call("hx_actor_act", net.data_ptr(), obs.data_ptr(), n, out.data_ptr(), mode, _lib.ptr(noise), float(sigma), int(seed), int(row0), self.act_calls,
+                  self.slope, None, _lib.stream_ptr())
         return out
 
     def act_step(self, env, noise=None, sigma=0.0, seed=0, out=None):
@@ -387,26 +404,13 @@ class HirlEngine:
         n = env.n
         if out is None:
             out = torch.empty((n, 4), dtype=torch.float32, device=self.device)
-        mode = 0
-        if noise is not None:
-            mode = 1 if noise.numel() == 4 else 2
-        elif sigma > 0:
-            mode = 3
+        mode = _noise_mode(noise, sigma) | self._mode_bits
         self.act_calls += 1
         env.steps_issued += 1
-        if self.act_dtype == "bf16":
-            _lib.call("hx_actor_act_step_bf16", self.actor.data_ptr(), self.w2_bf16.data_ptr(), env.state.data_ptr(), n, env.pitch, env.obs.data_ptr(),
-                      out.data_ptr(), mode | self._mode_bits, _lib.ptr(noise), float(sigma), int(seed), int(env.env_id0), self.act_calls, self.slope,
-                      env.reward.data_ptr(), env.done.data_ptr(), env.success.data_ptr(), ctypes.byref(env._opts), _lib.stream_ptr())
-            return out, env.obs, env.reward, env.done, env.success
-        if self._x9_for(n):
-            _lib.call("hx_actor_act_step_x9", self.actor.data_ptr(), self.w2_x9.data_ptr(), env.state.data_ptr(), n, env.pitch, env.obs.data_ptr(),
-                      out.data_ptr(), mode | self._mode_bits, _lib.ptr(noise), float(sigma), int(seed), int(env.env_id0), self.act_calls, self.slope,
-                      env.reward.data_ptr(), env.done.data_ptr(), env.success.data_ptr(), ctypes.byref(env._opts), _lib.stream_ptr())
-            return out, env.obs, env.reward, env.done, env.success
-        _lib.call("hx_actor_act_step_f32i", self.actor.data_ptr(), self.w2_f32i.data_ptr(), env.state.data_ptr(), n, env.pitch, env.obs.data_ptr(),
-                  out.data_ptr(), mode | self._mode_bits, _lib.ptr(noise), float(sigma), int(seed), int(env.env_id0), self.act_calls, self.slope,
-                  env.reward.data_ptr(), env.done.data_ptr(), env.success.data_ptr(), ctypes.byref(env._opts), _lib.stream_ptr())
+        fmt, image = self._act_format(n)
+        _lib.call("hx_actor_act_step" + fmt, self.actor.data_ptr(), image, env.state.data_ptr(), n, env.pitch, env.obs.data_ptr(), out.data_ptr(), mode,
+                  _lib.ptr(noise), float(sigma), int(seed), int(env.env_id0), self.act_calls, self.slope, env.reward.data_ptr(), env.done.data_ptr(),
+                  env.success.data_ptr(), ctypes.byref(env._opts), _lib.stream_ptr())
         return out, env.obs, env.reward, env.done, env.success
 
     # ---- learning --------------------------------------------------------------------------------------------
@@ -513,12 +517,7 @@ class HirlEngine:
         batch = HxBatch(self.rows.data_ptr(), self.bc_rows.data_ptr() if self.use_bc else None, B, noise.data_ptr())
         smp = ctypes.byref(pending[0]) if pending is not None else None
         nets, hyper = ctypes.byref(self.nets), ctypes.byref(self.hyper)
-        if bc_weight_now is None:
-            w_kind, w_given = 2, 0.0
-        elif bc_weight_now == 100:
-            w_kind, w_given = 1, 0.0
-        else:
-            w_kind, w_given = 0, float(bc_weight_now)
+        w_kind, w_given = _bc_weight_kind(bc_weight_now)
         actor_phase = self.actor_trainable  # HIRL.py:291
         self.critic_step += 1
         if actor_phase:
@@ -638,23 +637,14 @@ class HirlEngine:
                       cur[1].data_ptr() if bc_table is not None else None, n, _lib.stream_ptr())
         if out is None:
             out = torch.empty((n, 4), dtype=torch.float32, device=self.device)
-        mode = 0
-        if act_noise is not None:
-            mode = 1 if act_noise.numel() == 4 else 2
-        elif act_sigma > 0:
-            mode = 3
+        mode = _noise_mode(act_noise, act_sigma) | self._mode_bits
         self.act_calls += 1
         if self._front_epoch >= 200_000_000:  # the tiles' counters advance by up to 16 per launch: start over long before 32 bits run out (stream-ordered reset)
             flags.zero_()
             self._front_epoch = self._front_c_epoch = 0
         self._front_epoch += 1
         batch, nets, hyper, st = tiles_of(cur), ctypes.byref(self.nets), ctypes.byref(self.hyper), _lib.stream_ptr()
-        if bc_weight_now is None:
-            w_kind, w_given = 2, 0.0
-        elif bc_weight_now == 100:
-            w_kind, w_given = 1, 0.0
-        else:
-            w_kind, w_given = 0, float(bc_weight_now)
+        w_kind, w_given = _bc_weight_kind(bc_weight_now)
         actor_phase = self.actor_trainable  # HIRL.py:291
         self.critic_step += 1
         if actor_phase:
@@ -667,7 +657,7 @@ class HirlEngine:
         if carries_c:
             self._front_c_epoch += 1  # the counters of launch C's producers advance only in launches that carry it
         front = HxFront(flags.data_ptr(), status.data_ptr(), self._front_epoch, self._front_c_epoch if carries_c else 0)
-        _lib.call("hx_hirl_front", env.state.data_ptr(), n, env.pitch, env.obs.data_ptr(), out.data_ptr(), mode | self._mode_bits | (32 if (not bf16 and self._x9_for(n, front=True)) else 0),
+        _lib.call("hx_hirl_front", env.state.data_ptr(), n, env.pitch, env.obs.data_ptr(), out.data_ptr(), mode | (32 if (not bf16 and self._x9_for(n, front=True)) else 0),
                   _lib.ptr(act_noise), float(act_sigma), int(act_seed), int(env.env_id0), self.act_calls, env.reward.data_ptr(), env.done.data_ptr(),
                   env.success.data_ptr(), ctypes.byref(env._opts), nets, ctypes.byref(batch), hyper, int(actor_phase), w_kind, ctypes.byref(front), st)
         self._front_enqueued = True  # from here on a failure leaves the device AHEAD of any rollback (step_learn)

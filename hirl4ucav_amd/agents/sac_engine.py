@@ -94,6 +94,28 @@ def unpack_mlp(flat, block, in_dim, out_dim):
             for key, slot in zip(SEQ_KEYS, ("W1", "b1", "W2", "b2", "W3", "b3"))}
 
 
+def _draw(replay, expert, n_main, seed, call, idx, guard=0):
+    """the draw of a SAC minibatch as a record (HxSample; no BC table, no smoothing noise): n_main rows of `replay`, the rest of the batch from
+    `expert`, Philox(seed; row, call), the indices into `idx`; guard: the newest `guard` slots of the ring are not drawn (a front launch's inserts)"""
+    return E.HxSample(replay.total.data_ptr(), replay.capacity, replay.ring.data_ptr(), expert.ring.data_ptr() if expert is not None else None,
+                      E.len_of(expert), None, 0, int(n_main), int(seed), call, 0.0, idx.data_ptr(), None, guard)
+
+
+def _gather(s, batch, rows, noise=None, draw=1, st=None):
+    """hx_sample_batch (hx_sample_batch_guarded with s.guard) for the record `s`: `batch` rows into the tile `rows`.  draw=0: the indices in s.idx are given."""
+    args = (s.total, s.cap, s.ring, s.expert_ring, s.expert_len, None, 0, batch, s.n_main, draw, s.seed, s.call, 0.0, s.idx, None, _lib.ptr(noise), rows.data_ptr(), None)
+    st = _lib.stream_ptr() if st is None else st
+    if s.guard:
+        _lib.call("hx_sample_batch_guarded", *args, s.guard, st)
+    else:
+        _lib.call("hx_sample_batch", *args, st)
+
+
+def _given(ring, idx, batch):
+    """the record of a caller-chosen minibatch: rows idx of the table `ring`"""
+    return E.HxSample(None, 0, ring.data_ptr(), None, 0, None, 0, batch, 0, 0, 0.0, idx.data_ptr(), None, 0)
+
+
 class SacEngine:
     def __init__(self, batch=128, lr=1e-3, gamma=0.99, tau=0.005, target_entropy=-4.0, target_update_interval=3, device="cuda", group=None):
         self.device = torch.device(device)
@@ -104,14 +126,8 @@ class SacEngine:
         assert L.hx_sac_policy_param_count() == POLICY_SIZE
         self.batch = int(batch)
         ws = int(L.hx_sac_workspace_floats(self.batch))
-        sizes = [POLICY_SIZE, 2 * Q_SIZE, 2 * Q_SIZE, POLICY_SIZE + 2 * Q_SIZE, POLICY_SIZE, POLICY_SIZE, 2 * Q_SIZE, 2 * Q_SIZE, 64, 64, ws,
-                 self.batch * 32, self.batch * 4, self.batch * 4, self.batch, 64]
-        offs, tot = [], 0
-        for n in sizes:
-            offs.append(tot)
-            tot += (n + 63) & ~63
-        self.arena = torch.zeros(tot, dtype=torch.float32, device=self.device)
-        c = [self.arena[o:o + n] for o, n in zip(offs, sizes)]
+        self.arena, c = E.carve([POLICY_SIZE, 2 * Q_SIZE, 2 * Q_SIZE, POLICY_SIZE + 2 * Q_SIZE, POLICY_SIZE, POLICY_SIZE, 2 * Q_SIZE, 2 * Q_SIZE, 64, 64, ws,
+                                 self.batch * 32, self.batch * 4, self.batch * 4, self.batch, 64], self.device)
         (self.policy, self.critic, self.target_critic, self.grad, self.m_policy, self.v_policy, self.m_critic, self.v_critic, losses,
          alpha, self.ws, self.rows, self.eps_next, self.eps_cur, ix, noise) = c
         self.grad_critic, self.grad_policy = self.grad[:2 * Q_SIZE], self.grad[2 * Q_SIZE:]
@@ -138,6 +154,13 @@ class SacEngine:
         self.world = torch.distributed.get_world_size(group) if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 1
         self.act_calls, self.sample_calls = 0, 0
         self.imitative, self.imit, self.expert_calls = False, None, 0  # set_imitative
+        # learn() on one GPU is ONE library call; these two run its staged forms instead (the bit-identity tests, the sharded rank's sequence on one GPU):
+        # staged_policy: the policy half as hx_sac_policy_grads[_imitative] + hx_sac_adam(1); separate_critic_adam: the critic half as
+        # hx_sac_critic_grads + hx_sac_adam(0) — and with it the staged policy half
+        self.staged_policy, self.separate_critic_adam = False, False
+        self._seed = 0  # the seed of the last sample(): learn() without injected draws keys Normal.rsample's Philox eps with it
+        self._pending, self._pending_expert = None, None  # draws sample(defer=True) / sample_expert(defer=True) recorded for the next learn()
+        self._front_tiles, self._front_drawn = None, None  # step_learn: the two sets of minibatch tiles, and what the set in waiting was drawn for
 
     def set_imitative(self, bc_actor, slope=0.01):
         """SacAgent(imitative=True) (agent.py:315-318, 385-403): from now on learn() gates a BC term on the expert rows with
@@ -238,14 +261,18 @@ class SacEngine:
         if self.w2_x9 is not None:
             _lib.call("hx_pack_w2_x9", self.policy.data_ptr(), 13, self.w2_x9.data_ptr(), st)
 
-    def _x9_for(self, n):
-        if self.act_dtype != "f32" or self.x9_rows is None or n < self.x9_rows:
-            return False
+    def _act_format(self, n):
+        """Policy inference for n rows -> (suffix of the hx_sac_act* / hx_sac_act_step* entry point, its image pointers): "_bf16", "_x9" (act_dtype "f32"
+        from x9_rows rows on; with the fp32 image for the library's fallback up to 8,192 rows) or "_f32i"."""
+        if self.act_dtype == "bf16":
+            return "_bf16", (self.w2_bf16.data_ptr(),)
+        if self.x9_rows is None or n < self.x9_rows:
+            return "_f32i", (self.w2_f32i.data_ptr(),)
         if self.w2_x9 is None:  # first large call: build the images; nets.policy_w2_x9 makes every later policy step refresh them
             self.w2_x9 = torch.zeros(3 * H2 * H1, dtype=torch.bfloat16, device=self.device)
             self.nets.policy_w2_x9 = self.w2_x9.data_ptr()
             _lib.call("hx_pack_w2_x9", self.policy.data_ptr(), 13, self.w2_x9.data_ptr(), _lib.stream_ptr())
-        return True
+        return "_x9", (self.w2_x9.data_ptr(), self.w2_f32i.data_ptr())
 
     refresh_bf16 = refresh_images  # (the name utils/checkpoint.py calls after a restore)
 
@@ -287,16 +314,9 @@ class SacEngine:
             out = torch.empty((n, 4), dtype=torch.float32, device=self.device)
         mode = 0 if not explore else (1 if eps is not None else 2)
         self.act_calls += 1
-        if self.act_dtype == "bf16":
-            _lib.call("hx_sac_act_bf16", self.policy.data_ptr(), self.w2_bf16.data_ptr(), obs.data_ptr(), n, out.data_ptr(), mode, _lib.ptr(eps),
-                      int(seed), int(row0), self.act_calls, _lib.stream_ptr())
-            return out
-        if self._x9_for(n):
-            _lib.call("hx_sac_act_x9", self.policy.data_ptr(), self.w2_x9.data_ptr(), self.w2_f32i.data_ptr(), obs.data_ptr(), n, out.data_ptr(), mode,
-                      _lib.ptr(eps), int(seed), int(row0), self.act_calls, _lib.stream_ptr())
-            return out
-        _lib.call("hx_sac_act_f32i", self.policy.data_ptr(), self.w2_f32i.data_ptr(), obs.data_ptr(), n, out.data_ptr(), mode, _lib.ptr(eps),
-                  int(seed), int(row0), self.act_calls, _lib.stream_ptr())
+        fmt, images = self._act_format(n)
+        _lib.call("hx_sac_act" + fmt, self.policy.data_ptr(), *images, obs.data_ptr(), n, out.data_ptr(), mode, _lib.ptr(eps), int(seed), int(row0),
+                  self.act_calls, _lib.stream_ptr())
         return out
 
     def act_step(self, env, eps=None, explore=True, seed=0, out=None):
@@ -308,24 +328,14 @@ class SacEngine:
         mode = 0 if not explore else (1 if eps is not None else 2)
         self.act_calls += 1
         env.steps_issued += 1
-        if self.act_dtype == "bf16":
-            _lib.call("hx_sac_act_step_bf16", self.policy.data_ptr(), self.w2_bf16.data_ptr(), env.state.data_ptr(), n, env.pitch, env.obs.data_ptr(),
-                      out.data_ptr(), mode, _lib.ptr(eps), int(seed), int(env.env_id0), self.act_calls, env.reward.data_ptr(), env.done.data_ptr(),
-                      env.success.data_ptr(), ctypes.byref(env._opts), _lib.stream_ptr())
-            return out, env.obs, env.reward, env.done, env.success
-        if self._x9_for(n):
-            _lib.call("hx_sac_act_step_x9", self.policy.data_ptr(), self.w2_x9.data_ptr(), self.w2_f32i.data_ptr(), env.state.data_ptr(), n, env.pitch,
-                      env.obs.data_ptr(), out.data_ptr(), mode, _lib.ptr(eps), int(seed), int(env.env_id0), self.act_calls, env.reward.data_ptr(),
-                      env.done.data_ptr(), env.success.data_ptr(), ctypes.byref(env._opts), _lib.stream_ptr())
-            return out, env.obs, env.reward, env.done, env.success
-        _lib.call("hx_sac_act_step_f32i", self.policy.data_ptr(), self.w2_f32i.data_ptr(), env.state.data_ptr(), n, env.pitch, env.obs.data_ptr(),
-                  out.data_ptr(), mode, _lib.ptr(eps), int(seed), int(env.env_id0), self.act_calls, env.reward.data_ptr(), env.done.data_ptr(),
-                  env.success.data_ptr(), ctypes.byref(env._opts), _lib.stream_ptr())
+        fmt, images = self._act_format(n)
+        _lib.call("hx_sac_act_step" + fmt, self.policy.data_ptr(), *images, env.state.data_ptr(), n, env.pitch, env.obs.data_ptr(), out.data_ptr(), mode,
+                  _lib.ptr(eps), int(seed), int(env.env_id0), self.act_calls, env.reward.data_ptr(), env.done.data_ptr(), env.success.data_ptr(),
+                  ctypes.byref(env._opts), _lib.stream_ptr())
         return out, env.obs, env.reward, env.done, env.success
 
     def assemble(self, ring, idx):
-        _lib.call("hx_sample_batch", None, 0, ring.data_ptr(), None, 0, None, 0, self.batch, self.batch, 0, 0, 0, 0.0, idx.data_ptr(), None,
-                  None, self.rows.data_ptr(), None, _lib.stream_ptr())
+        _gather(_given(ring, idx, self.batch), self.batch, self.rows, draw=0)
 
     def sample(self, replay, expert=None, n_main=None, seed=0, defer=False):
         """memory.sample(batch_size) on the device (E-SAC: batch - expert_num rows from the memory followed by expert_num rows of
@@ -333,23 +343,15 @@ class SacEngine:
         defer=True: nothing is launched now — the next learn() draws and gathers inside its first launch (hx_sac_critic_grads_sampled)."""
         self.sample_calls += 1
         n_main = self.batch if (n_main is None or expert is None) else int(n_main)
-        self._seed = int(seed)
-        if defer:
-            self._pending = (E.HxSample(replay.total.data_ptr(), replay.capacity, replay.ring.data_ptr(),
-                                        expert.ring.data_ptr() if expert is not None else None, E.len_of(expert), None, 0, n_main, int(seed),
-                                        self.sample_calls, 0.0, self._idx.data_ptr(), None), replay, expert)
-            return
-        self._pending = None
-        _lib.call("hx_sample_batch", replay.total.data_ptr(), replay.capacity, replay.ring.data_ptr(),
-                  expert.ring.data_ptr() if expert is not None else None, E.len_of(expert), None, 0, self.batch, n_main,
-                  1, int(seed), self.sample_calls, 0.0, self._idx.data_ptr(), None, self._noise.data_ptr(), self.rows.data_ptr(), None,
-                  _lib.stream_ptr())
         self._seed = int(seed)  # learn() without injected draws: Normal.rsample's eps comes from Philox(seed; row, learn call) in-kernel
+        draw = _draw(replay, expert, n_main, seed, self.sample_calls, self._idx)
+        self._pending = (draw, replay, expert) if defer else None  # (the tensors are referenced by the record: they must outlive the launch)
+        if not defer:
+            _gather(draw, self.batch, self.rows, self._noise)
 
     def assemble_expert(self, ring, idx):
         """the imitative branch's second batch by given indices: rows idx of the expert table `ring` -> expert_rows"""
-        _lib.call("hx_sample_batch", None, 0, ring.data_ptr(), None, 0, None, 0, self.batch, self.batch, 0, 0, 0, 0.0, idx.data_ptr(), None,
-                  None, self.expert_rows.data_ptr(), None, _lib.stream_ptr())
+        _gather(_given(ring, idx, self.batch), self.batch, self.expert_rows, draw=0)
         self._pending_expert = None
 
     def sample_expert(self, expert, seed=0, defer=False):
@@ -360,33 +362,10 @@ class SacEngine:
             raise _lib.HxError("sample_expert is the imitative branch's second batch: call set_imitative first")
         self.expert_calls += 1
         seed = (int(seed) ^ 0x4558504552540000) & 0xFFFFFFFFFFFFFFFF
-        sample = E.HxSample(expert.total.data_ptr(), expert.capacity, expert.ring.data_ptr(), None, 0, None, 0, self.batch, int(seed),
-                            self.expert_calls, 0.0, self._expert_idx.data_ptr(), None, 0)
-        if defer:
-            self._pending_expert = (sample, expert)
-            return
-        self._pending_expert = None
-        _lib.call("hx_sample_batch", expert.total.data_ptr(), expert.capacity, expert.ring.data_ptr(), None, 0, None, 0, self.batch, self.batch, 1,
-                  int(seed), self.expert_calls, 0.0, self._expert_idx.data_ptr(), None, None, self.expert_rows.data_ptr(), None, _lib.stream_ptr())
-
-    def _learn_imitative(self, batch, pending, polyak_first, st):
-        """the imitative learn(): one call, or (staged_policy) hx_sac_critic_step + hx_sac_policy_grads_imitative + hx_sac_adam(1)"""
-        if self.world > 1:
-            raise _lib.HxError("the imitative branch runs on one GPU (its gate count is not exchanged between ranks): run it with --gpus 1")
-        nets, hyper, imit = ctypes.byref(self.nets), ctypes.byref(self.hyper), ctypes.byref(self.imit)
-        main = ctypes.byref(pending[0]) if pending is not None else None
-        pe, self._pending_expert = self._pending_expert, None
-        if not getattr(self, "staged_policy", False):
-            _lib.call("hx_sac_learn_imitative", nets, ctypes.byref(batch), hyper, main, imit, ctypes.byref(pe[0]) if pe is not None else None,
-                      polyak_first, self.learning_steps, self.target_entropy, st)
-            return
-        if pe is not None:
-            s = pe[0]
-            _lib.call("hx_sample_batch", s.total, s.cap, s.ring, None, 0, None, 0, self.batch, self.batch, 1, s.seed, s.call, 0.0, s.idx, None, None,
-                      self.expert_rows.data_ptr(), None, st)
-        _lib.call("hx_sac_critic_step", nets, ctypes.byref(batch), hyper, main, polyak_first, self.learning_steps, st)
-        _lib.call("hx_sac_policy_grads_imitative", nets, ctypes.byref(batch), hyper, imit, st)
-        _lib.call("hx_sac_adam", nets, hyper, 1, self.learning_steps, 1.0, self.target_entropy, st)
+        draw = _draw(expert, None, self.batch, seed, self.expert_calls, self._expert_idx)
+        self._pending_expert = (draw, expert) if defer else None
+        if not defer:
+            _gather(draw, self.batch, self.expert_rows)
 
     def imitative_losses_host(self):
         """(bc_loss, bc_weight) of the last imitative learn()"""
@@ -398,37 +377,52 @@ class SacEngine:
             torch.distributed.all_reduce(t, group=self.group)
 
     def learn(self, eps_next=None, eps_cur=None):
-        """SacAgent.learn(False) (agent.py:276-327) on the minibatch last assembled.  Enqueues only."""
+        """SacAgent.learn (agent.py:276-327; after set_imitative its imitative branch, one GPU only) on the minibatch last assembled.  Enqueues only.
+        One GPU: one library call.  staged_policy / separate_critic_adam / more than one rank: the critic half, then the policy half, as stages —
+        the imitative branch too: it honours separate_critic_adam (hx_sac_critic_grads + hx_sac_adam(0), then hx_sac_policy_grads_imitative + hx_sac_adam(1))."""
         st = _lib.stream_ptr()
         if eps_next is not None:  # injected draws (parity tests, the façade's torch.randn)
             self.eps_next.copy_(eps_next.reshape(-1))
             self.eps_cur.copy_(eps_cur.reshape(-1))
             batch = HxSacBatch(self.rows.data_ptr(), self.batch, self.eps_next.data_ptr(), self.eps_cur.data_ptr(), 0, 0)
         else:
-            batch = HxSacBatch(self.rows.data_ptr(), self.batch, None, None, getattr(self, "_seed", 0), self.learning_steps + 1)
-        nets, hyper, gs = ctypes.byref(self.nets), ctypes.byref(self.hyper), 1.0 / self.world
+            batch = HxSacBatch(self.rows.data_ptr(), self.batch, None, None, self._seed, self.learning_steps + 1)
+        nets, hyper, gs, bt = ctypes.byref(self.nets), ctypes.byref(self.hyper), 1.0 / self.world, ctypes.byref(batch)
         self.learning_steps += 1
-        pending, self._pending = getattr(self, "_pending", None), None
+        pending, self._pending = self._pending, None
+        smp = ctypes.byref(pending[0]) if pending is not None else None
         polyak_first = int(self.learning_steps % self.interval == 0)
-        if self.imitative:
-            return self._learn_imitative(batch, pending, polyak_first, st)
-        if self.world == 1 and not getattr(self, "separate_critic_adam", False) and not getattr(self, "staged_policy", False):
-            # one GPU: the whole learn() in one call, 9 launches (hx_sac_learn: bit-identical to the staged sequence below, 14 launches)
-            _lib.call("hx_sac_learn", nets, ctypes.byref(batch), hyper, ctypes.byref(pending[0]) if pending is not None else None,
-                      polyak_first, self.learning_steps, self.target_entropy, st)
-            return
-        if self.world == 1 and not getattr(self, "separate_critic_adam", False):
-            # one GPU: the critics' optimizer steps ride in the weight-gradient launch (bit-identical to the two calls below, one launch less)
-            _lib.call("hx_sac_critic_step", nets, ctypes.byref(batch), hyper, ctypes.byref(pending[0]) if pending is not None else None,
-                      polyak_first, self.learning_steps, st)
-        else:
-            if pending is not None:
-                _lib.call("hx_sac_critic_grads_sampled", nets, ctypes.byref(batch), hyper, ctypes.byref(pending[0]), polyak_first, st)
+        if self.imitative and self.world > 1:
+            raise _lib.HxError("the imitative branch runs on one GPU (its gate count is not exchanged between ranks): run it with --gpus 1")
+        imit = ctypes.byref(self.imit) if self.imitative else None
+        pe, self._pending_expert = self._pending_expert, None
+        fused_critic = self.world == 1 and not self.separate_critic_adam
+        if fused_critic and not self.staged_policy:
+            # one GPU: the whole learn() in one call (plain: 9 launches, bit-identical to the staged sequence below, 14 launches)
+            if imit is not None:
+                _lib.call("hx_sac_learn_imitative", nets, bt, hyper, smp, imit, ctypes.byref(pe[0]) if pe is not None else None, polyak_first,
+                          self.learning_steps, self.target_entropy, st)
             else:
-                _lib.call("hx_sac_critic_grads", nets, ctypes.byref(batch), hyper, polyak_first, st)
+                _lib.call("hx_sac_learn", nets, bt, hyper, smp, polyak_first, self.learning_steps, self.target_entropy, st)
+            return
+        if imit is not None and pe is not None:  # the staged form draws the deferred expert rows with a launch of its own
+            _gather(pe[0], self.batch, self.expert_rows, st=st)
+        # the critic half
+        if fused_critic:
+            # one GPU: the critics' optimizer steps ride in the weight-gradient launch (bit-identical to the two calls below, one launch less)
+            _lib.call("hx_sac_critic_step", nets, bt, hyper, smp, polyak_first, self.learning_steps, st)
+        else:
+            if smp is not None:
+                _lib.call("hx_sac_critic_grads_sampled", nets, bt, hyper, smp, polyak_first, st)
+            else:
+                _lib.call("hx_sac_critic_grads", nets, bt, hyper, polyak_first, st)
             self._allreduce(self.grad_critic)
             _lib.call("hx_sac_adam", nets, hyper, 0, self.learning_steps, gs, self.target_entropy, st)
-        _lib.call("hx_sac_policy_grads", nets, ctypes.byref(batch), hyper, st)
+        # the policy half
+        if imit is not None:
+            _lib.call("hx_sac_policy_grads_imitative", nets, bt, hyper, imit, st)
+        else:
+            _lib.call("hx_sac_policy_grads", nets, bt, hyper, st)
         if self.world > 1:  # mean entropy and the policy-loss terms are per-shard means: average them with the gradients
             self._allreduce(self.grad_policy)
             self._allreduce(self.losses)
@@ -442,9 +436,9 @@ class SacEngine:
         More than 8,192 envs (the persistent acting kernel), one GPU, the one-call learn(), Philox draws.  Acting and update in one format: fp32, or
         bf16 for both (a bf16 policy beside the fp32 update runs act_step, then the sampled learn()).  -> (actions, obs, reward, done, success)."""
         replay, n, B = env.replay, env.n, self.batch
-        if self.world > 1 or replay is None or n <= 8192 or getattr(self, "separate_critic_adam", False) or getattr(self, "staged_policy", False):
+        if self.world > 1 or replay is None or n <= 8192 or self.separate_critic_adam or self.staged_policy:
             raise _lib.HxError("SacEngine.step_learn: one GPU, the one-call learn(), more than 8,192 envs with a replay ring attached")
-        if getattr(self, "_pending", None) is not None:
+        if self._pending is not None:
             raise _lib.HxError("step_learn draws its own minibatch: a sample(defer=True) is still pending")
         if self.imitative:  # no front form: the reference's order; `expert` is the imitative branch's expert memory, the minibatch is not expert-mixed
             if expert is None:
@@ -459,36 +453,29 @@ class SacEngine:
             self.sample(replay, expert, n_main=n_main, seed=sample_seed, defer=True)
             self.learn()
             return res
-        if getattr(self, "_front_tiles", None) is None:
+        if self._front_tiles is None:
             second = torch.zeros(B * 32 + B, dtype=torch.float32, device=self.device)
             self._front_tiles = [(self.rows, self._idx), (second[:B * 32], second[B * 32:].view(torch.int32))]
-            self._front_drawn = None
         cur, nxt = self._front_tiles
         n_main = B if (n_main is None or expert is None) else int(n_main)
         self.sample_calls += 1
         self._seed = int(sample_seed)
 
-        def draw(tiles, call):
-            return E.HxSample(replay.total.data_ptr(), replay.capacity, replay.ring.data_ptr(), expert.ring.data_ptr() if expert is not None else None,
-                              E.len_of(expert), None, 0, n_main, int(sample_seed), call, 0.0, tiles[1].data_ptr(), None, n)
-
         want = (env, env.steps_issued, replay, expert, n_main, int(sample_seed), self.sample_calls, n)
         if self._front_drawn != want:  # no tile in waiting for THIS draw: draw now, as a launch of its own
-            _lib.call("hx_sample_batch_guarded", replay.total.data_ptr(), replay.capacity, replay.ring.data_ptr(), expert.ring.data_ptr() if expert is not None else None,
-                      E.len_of(expert), None, 0, B, n_main, 1, int(sample_seed), self.sample_calls, 0.0, cur[1].data_ptr(), None, self._noise.data_ptr(),
-                      cur[0].data_ptr(), None, n, _lib.stream_ptr())
+            _gather(_draw(replay, expert, n_main, sample_seed, self.sample_calls, cur[1], guard=n), B, cur[0], self._noise)
         if out is None:
             out = torch.empty((n, 4), dtype=torch.float32, device=self.device)
         self.act_calls += 1
         self.learning_steps += 1
         batch = HxSacBatch(cur[0].data_ptr(), B, None, None, int(sample_seed), self.learning_steps)
         nets, hyper, st = ctypes.byref(self.nets), ctypes.byref(self.hyper), _lib.stream_ptr()
-        x9, b16 = self._x9_for(n), self.update_dtype == "bf16"  # (bf16: the acting image is nets.w2_bf16_all's first)
-        _lib.call("hx_sac_front", self.policy.data_ptr(), self.w2_x9.data_ptr() if x9 else None, None if b16 else self.w2_f32i.data_ptr(), env.state.data_ptr(), n, env.pitch,
+        fmt, b16 = self._act_format(n)[0], self.update_dtype == "bf16"  # (bf16: the acting image is nets.w2_bf16_all's first)
+        _lib.call("hx_sac_front", self.policy.data_ptr(), self.w2_x9.data_ptr() if fmt == "_x9" else None, None if b16 else self.w2_f32i.data_ptr(), env.state.data_ptr(), n, env.pitch,
                   env.obs.data_ptr(), out.data_ptr(), 2 if explore else 0, None, int(act_seed), int(env.env_id0), self.act_calls, env.reward.data_ptr(),
                   env.done.data_ptr(), env.success.data_ptr(), ctypes.byref(env._opts), nets, ctypes.byref(batch), st)
         env.steps_issued += 1
-        nxt_draw = draw(nxt, self.sample_calls + 1)
+        nxt_draw = _draw(replay, expert, n_main, sample_seed, self.sample_calls + 1, nxt[1], guard=n)
         polyak_first = int(self.learning_steps % self.interval == 0)
         _lib.call("hx_sac_learn_back", nets, ctypes.byref(batch), hyper, polyak_first, self.learning_steps, self.target_entropy, ctypes.byref(nxt_draw),
                   nxt[0].data_ptr(), st)

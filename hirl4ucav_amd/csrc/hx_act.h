@@ -3,6 +3,10 @@
 //   hx_actp.hip   act_persist_kernel: persistent workgroups that keep W2 and loop over their row tiles — beyond 8,192 rows
 // Agent.chooseAction* hirl/agents/HIRL.py:192-212; SacAgent.explore / exploit hirl/agents/SAC/agent.py:183-196.
 #pragma once
+#include <hip/hip_ext.h>
+
+#include <initializer_list>
+
 #include "hx_update.h"
 
 // The "x9" acting format: both operands of the fp32 256 -> 512 product as EXACT three-way bf16 splits (x = hi + mid + lo, 3 x 8 significand bits = 24: nothing
@@ -349,16 +353,84 @@ constexpr int64_t kFuseEnvMax = 8192;
 // Returns false when no persistent instantiation covers the request (the caller falls back to act_fused_kernel).
 bool launch_act_persist(const ActFusedArgs& H, bool gauss, hipStream_t st);
 
-// the buffers and options of an env step that rides in an acting launch (hx_*_act_step*, hx_hirl_front)
-inline int check_step_args(const float* state, int64_t n, int64_t stride, const float* obs_io, const float* actions, const float* reward,
-                           const uint8_t* done, const int8_t* success, const HxStepOpts& o, const char* who) {
-    HX_REQUIRE(state && obs_io && actions && reward && done && success && n > 0 && stride >= n, "%s: bad buffers", who);
+// the buffers and options of an env step that rides in an acting launch (hx_*_act_step*, hx_hirl_front, hx_sac_front): obs is then in/out
+struct ActEnv {
+    float* state;
+    int64_t stride;
+    float* reward;
+    uint8_t* done;
+    int8_t* success;
+    HxStepOpts o;
+};
+inline int check_step_args(const float* obs_io, int64_t n, const float* actions, const ActEnv& E, const char* who) {
+    const HxStepOpts& o = E.o;
+    HX_REQUIRE(E.state && obs_io && actions && E.reward && E.done && E.success && n > 0 && E.stride >= n, "%s: bad buffers", who);
     HX_REQUIRE(n < (int64_t)1 << 31, "%s: at most 2^31 - 1 envs per launch", who);
     HX_REQUIRE(!o.auto_reset || o.episode_ctr, "%s: auto_reset needs episode_ctr", who);
-    HX_REQUIRE(stride < ((int64_t)1 << 25), "%s: stride must be below 2^25 envs", who);
+    HX_REQUIRE(E.stride < ((int64_t)1 << 25), "%s: stride must be below 2^25 envs", who);
     HX_REQUIRE(!o.ring || (o.cap >= 512 && o.cap < ((int64_t)1 << 31) && o.total && (reinterpret_cast<uintptr_t>(o.ring) & 15u) == 0),
                "%s: ring needs 512 <= cap < 2^31, total and 16-byte alignment", who);
     return 0;
+}
+// every image an entry point is handed must be there and 16-byte aligned (the kernels read them 16 bytes at a time); `what`: the entry point's words
+inline int check_images16(const char* who, const char* what, std::initializer_list<const void*> images) {
+    for (const void* p : images) HX_REQUIRE(p && (reinterpret_cast<uintptr_t>(p) & 15u) == 0, "%s: %s", who, what);
+    return 0;
+}
+// the deterministic head's noise_mode argument, with or without its + 16 / + 32 bits
+inline int check_noise_mode(int32_t noise_mode, const float* noise, const char* who) {
+    noise_mode &= 15;
+    HX_REQUIRE(noise_mode >= 0 && noise_mode <= 3 && (noise || (noise_mode != 1 && noise_mode != 2)), "%s: bad noise mode", who);
+    return 0;
+}
+
+// The images of W2 a caller offers; ONE acting format per launch: the bf16 image, else the exact split (hi | mid | lo), else the fp32 image, else W2 itself.
+struct ActImages {
+    const float* w2f;
+    const uint16_t* w2x;
+    const uint16_t* w2b;
+};
+// what the two heads' descriptions share; env: the env step in the launch's tail, or nullptr
+inline ActFusedArgs act_args(const float* net, const Mlp& m, float* obs, int64_t rows, float* actions, uint64_t seed, uint32_t row0, uint32_t call,
+                             const ActImages& im, const ActEnv* env) {
+    ActFusedArgs H{};
+    H.net = net; H.m = m; H.obs = obs; H.rows = (int)rows; H.actions = actions;
+    H.seed = seed; H.row0 = row0; H.call = call;
+    if (env) {
+        H.state = env->state; H.stride = env->stride; H.reward = env->reward; H.done = env->done; H.success = env->success; H.o = env->o;
+        H.inv_cap = env->o.cap > 0 ? 1.0 / (double)env->o.cap : 0.0;
+    }
+    H.w2b = im.w2b ? im.w2b : im.w2x; H.w2f = (im.w2x || im.w2b) ? nullptr : im.w2f; H.x9 = (im.w2x && !im.w2b) ? 1 : 0;
+    return H;
+}
+// the deterministic head (chooseAction*).  noise_mode 0: none, 1: noise[4] shared by all rows, 2: noise[rows][4], 3: N(0, sigma^2) from Philox; + 16: layerNorm = False
+// (the + 32 of hx_hirl_front chose the images and means nothing here)
+inline ActFusedArgs act_args_det(const float* actor, float* obs, int64_t rows, float* actions, int32_t noise_mode, const float* noise, float sigma, uint64_t seed,
+                                 uint32_t row0, uint32_t call, float slope, const ActImages& im, const ActEnv* env = nullptr) {
+    ActFusedArgs H = act_args(actor, Mlp{13, 4, (noise_mode & 16) ? 1 : 0}, obs, rows, actions, seed, row0, call, im, env);
+    noise_mode &= 15;
+    H.slope = slope;
+    H.noise = (noise_mode == 1 || noise_mode == 2) ? noise : nullptr;
+    H.noise_per_row = noise_mode == 2;
+    H.sigma = noise_mode == 3 ? sigma : 0.0f;
+    return H;
+}
+// the Gaussian head (SacAgent.explore / exploit).  mode 0: exploit, 1: sample with eps[rows][4], 2: sample with Philox
+inline ActFusedArgs act_args_gauss(const float* policy, float* obs, int64_t rows, float* actions, int32_t mode, const float* eps, uint64_t seed, uint32_t row0,
+                                   uint32_t call, const ActImages& im, const ActEnv* env = nullptr) {
+    ActFusedArgs H = act_args(policy, kPolicy, obs, rows, actions, seed, row0, call, im, env);
+    H.noise = mode == 1 ? eps : nullptr;
+    H.noise_per_row = 1;
+    H.mode = mode;
+    return H;
+}
+
+// Launch `kernel` on kWide-thread workgroups — stamped with the kernel's own begin / end when the step options carry both events (bench.py's live roofline of
+// the act + env launch, as hx_env_step does for the env kernel), plain otherwise
+template <typename K, typename... Args>
+inline void launch_stamped(K kernel, dim3 grid, hipStream_t st, const HxStepOpts& o, const Args&... args) {
+    if (o.ev_start && o.ev_stop) hipExtLaunchKernelGGL(kernel, grid, dim3(kWide), 0, st, (hipEvent_t)o.ev_start, (hipEvent_t)o.ev_stop, 0, args...);
+    else hipLaunchKernelGGL(kernel, grid, dim3(kWide), 0, st, args...);
 }
 
 }  // namespace hxact
@@ -366,4 +438,7 @@ inline int check_step_args(const float* state, int64_t n, int64_t stride, const 
 namespace hxu {
 // hx_front.hip: the SAC policy's act + env + insert launch (persistent streaming kernel) with the first forward launch of learn() behind it
 int launch_front_sac(const hxact::ActFusedArgs& H, const FwdArgs& FA, hipStream_t st);
+// hx_front.hip: the act + env + insert workgroups of hx_actor_act_step_* (32 rows each, or a persistent role) and the workgroups of launches A and B
+// [and C] of HIRL's learn() as ONE launch
+int launch_front(const hxact::ActFusedArgs& H, const FwdArgs& FA, const FwdArgs& FB, const BwdArgs* GC, const HxFront& front, hipStream_t st);
 }  // namespace hxu

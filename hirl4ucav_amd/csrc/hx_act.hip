@@ -24,15 +24,7 @@ __global__ __launch_bounds__(kWide) void act_fused_kernel(ActFusedArgs A) {
 // The env tail on wave 0 pays while the launch is ONE round of workgroups (256 CUs x 16 or 32 rows: kFuseEnvMax, hx_act.h); beyond that the
 // persistent kernel of hx_actp.hip takes the launch (its env tail runs on all 16 waves, once per workgroup).
 
-// ENV launches carry HxStepOpts: with ev_start / ev_stop set the launch is stamped with the kernel's own begin / end (bench.py's live
-// roofline of the act + env launch, as hx_env_step does for the env kernel)
-template <typename K>
-static void launch_act_k(K kernel, dim3 grid, const ActFusedArgs& H, hipStream_t st) {
-    if (H.state && H.o.ev_start && H.o.ev_stop)
-        hipExtLaunchKernelGGL(kernel, grid, dim3(kWide), 0, st, (hipEvent_t)H.o.ev_start, (hipEvent_t)H.o.ev_stop, 0, H);
-    else
-        hipLaunchKernelGGL(kernel, grid, dim3(kWide), 0, st, H);
-}
+// (ENV launches carry HxStepOpts: launch_stamped, hx_act.h)
 template <bool GAUSS, bool BF16, bool RELU, bool F32I = false, bool X3 = false>
 static void launch_act_t(const ActFusedArgs& H, hipStream_t st) {
     const bool env = H.state != nullptr;
@@ -48,15 +40,15 @@ static void launch_act_t(const ActFusedArgs& H, hipStream_t st) {
     {
         if (H.rows >= (X3 ? nrt2_x9 : BF16 ? nrt2_bf16 : nrt2_f32)) {
             const dim3 grid((unsigned)((H.rows + 2 * RT - 1) / (2 * RT)));
-            if (env) launch_act_k(act_fused_kernel<2, GAUSS, true, BF16, RELU, F32I, X3>, grid, H, st);
-            else launch_act_k(act_fused_kernel<2, GAUSS, false, BF16, RELU, F32I, X3>, grid, H, st);
+            if (env) launch_stamped(act_fused_kernel<2, GAUSS, true, BF16, RELU, F32I, X3>, grid, st, H.o, H);
+            else launch_stamped(act_fused_kernel<2, GAUSS, false, BF16, RELU, F32I, X3>, grid, st, H.o, H);
             return;
         }
     }
     {
         const dim3 grid((unsigned)((H.rows + RT - 1) / RT));
-        if (env) launch_act_k(act_fused_kernel<1, GAUSS, true, BF16, RELU, F32I, X3>, grid, H, st);
-        else launch_act_k(act_fused_kernel<1, GAUSS, false, BF16, RELU, F32I, X3>, grid, H, st);
+        if (env) launch_stamped(act_fused_kernel<1, GAUSS, true, BF16, RELU, F32I, X3>, grid, st, H.o, H);
+        else launch_stamped(act_fused_kernel<1, GAUSS, false, BF16, RELU, F32I, X3>, grid, st, H.o, H);
     }
 }
 // HX_ACT_PERSIST=0 keeps act_fused_kernel at every size (A/B timing, bit-identity tests of the two kernels)
@@ -83,6 +75,23 @@ static void launch_act(const ActFusedArgs& H, hipStream_t st) {
         else if (H.w2f) launch_act_t<false, false, false, true>(H, st);
         else launch_act_t<false, false, false>(H, st);
     }
+}
+
+// H with its env part.  Up to one round of workgroups the env step rides in wave 0 of each; beyond, the persistent kernel takes the launch (env tail on all
+// waves) — and where no persistent instantiation does (no replay ring, HX_ACT_PERSIST=0) two launches: the same rows without the env part, then hx_env_step
+template <bool GAUSS>
+static int launch_act_step(const ActFusedArgs& H, const HxStepOpts* opts, const char* who, const char* who_act, hipStream_t st) {
+    if (H.rows <= kFuseEnvMax) {
+        launch_act<GAUSS>(H, st);
+    } else if (!(persist_enabled() && launch_act_persist(H, GAUSS, st))) {
+        ActFusedArgs A = H;
+        A.state = nullptr; A.stride = 0; A.reward = nullptr; A.done = nullptr; A.success = nullptr; A.o = HxStepOpts{}; A.inv_cap = 0.0;
+        launch_act<GAUSS>(A, st);
+        HX_CHECK_LAUNCH(who_act);
+        return hx_env_step(H.state, H.rows, H.stride, H.actions, H.obs, H.reward, H.done, H.success, opts, st);
+    }
+    HX_CHECK_LAUNCH(who);
+    return 0;
 }
 
 // bf16 image of a [n] fp32 array (round to nearest even): the policy's W2 for the BF16 acting kernels
@@ -137,31 +146,51 @@ int64_t hx_act_workspace_floats(int64_t rows) { (void)rows; return 0; }  // the 
 
 /* chooseAction / chooseActionSmallNoise / chooseActionNoNoise for `rows` observations (HIRL.py:192-212):
  * actions = clamp(actor(obs) + noise, -1, 1).  noise_mode 0: none, 1: noise[4] shared by all rows, 2: noise[rows][4],
- * 3: N(0, sigma^2) per row and component from Philox(seed; row0 + row, call).  ws: unused since the whole policy runs in one kernel (may be NULL). */
-static int actor_act_impl(const float* actor, const uint16_t* w2b, const float* w2f, const float* obs, int64_t rows, float* actions, int32_t noise_mode, const float* noise,
-                 float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, void* stream) {
+ * 3: N(0, sigma^2) per row and component from Philox(seed; row0 + row, call); + 16: layerNorm = False.  ws: unused since the whole policy runs in one kernel (may be NULL). */
+static int actor_act_impl(const float* actor, const ActImages& im, const float* obs, int64_t rows, float* actions, int32_t noise_mode, const float* noise,
+                          float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, void* stream) {
     HX_REQUIRE(actor && obs && actions && rows > 0, "hx_actor_act: bad arguments");
-    const Mlp mA{13, 4, (noise_mode & 16) ? 1 : 0};  // + 16: layerNorm = False
-    const int x9 = (w2b && (noise_mode & 32)) ? 1 : 0;  // + 32 (internal, the *_x9 entry points): w2b is the first of the hi | mid | lo images
-    noise_mode &= 15;
-    HX_REQUIRE(noise_mode >= 0 && noise_mode <= 3 && (noise || (noise_mode != 1 && noise_mode != 2)), "hx_actor_act: bad noise mode");
-    ActFusedArgs H{actor, mA, const_cast<float*>(obs), (int)rows, slope, actions, (noise_mode == 1 || noise_mode == 2) ? noise : nullptr,
-                   noise_mode == 2, noise_mode == 3 ? sigma : 0.0f, 0, seed, row0, call, nullptr, 0, nullptr, nullptr, nullptr, HxStepOpts{}, 0.0, w2b, w2f, x9};
-    launch_act<false>(H, (hipStream_t)stream);
+    if (int rc = check_noise_mode(noise_mode, noise, "hx_actor_act")) return rc;
+    launch_act<false>(act_args_det(actor, const_cast<float*>(obs), rows, actions, noise_mode, noise, sigma, seed, row0, call, slope, im), (hipStream_t)stream);
     HX_CHECK_LAUNCH("hx_actor_act");
     return 0;
+}
+/* chooseAction + HarfangEnv.step for n envs in ONE launch (train_all.py:343-345): actions = clamp(actor(obs_io) + noise, -1, 1) as
+ * hx_actor_act, then hx_env_step with those actions in the tail of the same kernel — obs_io in: current observation, out: next. */
+static int actor_act_step_impl(const float* actor, const ActImages& im, float* state, int64_t n, int64_t stride, float* obs_io, float* actions, int32_t noise_mode,
+                               const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, float* reward,
+                               uint8_t* done, int8_t* success, const HxStepOpts* opts, void* stream) {
+    HX_REQUIRE(actor, "hx_actor_act_step: null actor");
+    if (int rc = check_noise_mode(noise_mode, noise, "hx_actor_act_step")) return rc;
+    const ActEnv E{state, stride, reward, done, success, opts ? *opts : HxStepOpts{}};
+    if (int rc = check_step_args(obs_io, n, actions, E, "hx_actor_act_step")) return rc;
+    return launch_act_step<false>(act_args_det(actor, obs_io, n, actions, noise_mode, noise, sigma, seed, row0, call, slope, im, &E), opts, "hx_actor_act_step",
+                                  "hx_actor_act", (hipStream_t)stream);
 }
 
 int hx_actor_act(const float* actor, const float* obs, int64_t rows, float* actions, int32_t noise_mode, const float* noise,
                  float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, float* ws, void* stream) {
     (void)ws;
-    return actor_act_impl(actor, nullptr, nullptr, obs, rows, actions, noise_mode, noise, sigma, seed, row0, call, slope, stream);
+    return actor_act_impl(actor, ActImages{}, obs, rows, actions, noise_mode, noise, sigma, seed, row0, call, slope, stream);
+}
+int hx_actor_act_step(const float* actor, float* state, int64_t n, int64_t stride, float* obs_io, float* actions, int32_t noise_mode,
+                      const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, float* reward,
+                      uint8_t* done, int8_t* success, const HxStepOpts* opts, void* stream) {
+    return actor_act_step_impl(actor, ActImages{}, state, n, stride, obs_io, actions, noise_mode, noise, sigma, seed, row0, call, slope, reward, done,
+                               success, opts, stream);
 }
 /* The same with the 256 -> 512 layer on bf16 MFMA (BASELINE.json configs[4]): w2_bf16 = hx_pack_w2_bf16 image of full2.weight. */
 int hx_actor_act_bf16(const float* actor, const uint16_t* w2_bf16, const float* obs, int64_t rows, float* actions, int32_t noise_mode,
                       const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, void* stream) {
-    HX_REQUIRE(w2_bf16 && (reinterpret_cast<uintptr_t>(w2_bf16) & 15u) == 0, "hx_actor_act_bf16: w2_bf16 must be a 16-byte aligned bf16 image of W2");
-    return actor_act_impl(actor, w2_bf16, nullptr, obs, rows, actions, noise_mode, noise, sigma, seed, row0, call, slope, stream);
+    if (int rc = check_images16("hx_actor_act_bf16", "w2_bf16 must be a 16-byte aligned bf16 image of W2", {w2_bf16})) return rc;
+    return actor_act_impl(actor, ActImages{nullptr, nullptr, w2_bf16}, obs, rows, actions, noise_mode, noise, sigma, seed, row0, call, slope, stream);
+}
+int hx_actor_act_step_bf16(const float* actor, const uint16_t* w2_bf16, float* state, int64_t n, int64_t stride, float* obs_io, float* actions,
+                           int32_t noise_mode, const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope,
+                           float* reward, uint8_t* done, int8_t* success, const HxStepOpts* opts, void* stream) {
+    if (int rc = check_images16("hx_actor_act_step_bf16", "w2_bf16 must be a 16-byte aligned bf16 image of W2", {w2_bf16})) return rc;
+    return actor_act_step_impl(actor, ActImages{nullptr, nullptr, w2_bf16}, state, n, stride, obs_io, actions, noise_mode, noise, sigma, seed, row0, call, slope,
+                               reward, done, success, opts, stream);
 }
 /* bf16 image (round to nearest even) of an MLP block's W2 [512][256]; in_dim = 13 (actor / policy) or 17 (Q head) locates it. */
 int hx_pack_w2_bf16(const float* net, int32_t in_dim, uint16_t* w2_bf16, void* stream) {
@@ -173,74 +202,36 @@ int hx_pack_w2_bf16(const float* net, int32_t in_dim, uint16_t* w2_bf16, void* s
     return 0;
 }
 
-/* chooseAction + HarfangEnv.step for n envs in ONE launch (train_all.py:343-345): actions = clamp(actor(obs_io) + noise, -1, 1) as
- * hx_actor_act, then hx_env_step with those actions in the tail of the same kernel — obs_io in: current observation, out: next. */
-static int actor_act_step_impl(const float* actor, const uint16_t* w2b, const float* w2f, float* state, int64_t n, int64_t stride, float* obs_io, float* actions, int32_t noise_mode,
-                      const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, float* reward,
-                      uint8_t* done, int8_t* success, const HxStepOpts* opts, void* stream) {
-    HX_REQUIRE(actor, "hx_actor_act_step: null actor");
-    const int32_t mode_in = noise_mode;
-    const Mlp mA{13, 4, (noise_mode & 16) ? 1 : 0};  // + 16: layerNorm = False
-    const int x9 = (w2b && (noise_mode & 32)) ? 1 : 0;  // + 32 (internal): see actor_act_impl
-    noise_mode &= 15;
-    HX_REQUIRE(noise_mode >= 0 && noise_mode <= 3 && (noise || (noise_mode != 1 && noise_mode != 2)), "hx_actor_act_step: bad noise mode");
-    const HxStepOpts o = opts ? *opts : HxStepOpts{};
-    if (int rc = check_step_args(state, n, stride, obs_io, actions, reward, done, success, o, "hx_actor_act_step")) return rc;
-    ActFusedArgs H{actor, mA, obs_io, (int)n, slope, actions, (noise_mode == 1 || noise_mode == 2) ? noise : nullptr,
-                   noise_mode == 2, noise_mode == 3 ? sigma : 0.0f, 0, seed, row0, call, state, stride, reward, done, success, o,
-                   o.cap > 0 ? 1.0 / (double)o.cap : 0.0, w2b, w2f, x9};
-    if (n > kFuseEnvMax) {  // more than one round of 32-row workgroups: the persistent kernel (env tail on all waves), else two launches
-        if (persist_enabled() && launch_act_persist(H, false, (hipStream_t)stream)) {
-            HX_CHECK_LAUNCH("hx_actor_act_step");
-            return 0;
-        }
-        if (int rc = actor_act_impl(actor, w2b, w2f, obs_io, n, actions, mode_in, noise, sigma, seed, row0, call, slope, stream)) return rc;
-        return hx_env_step(state, n, stride, actions, obs_io, reward, done, success, opts, stream);
-    }
-    launch_act<false>(H, (hipStream_t)stream);
-    HX_CHECK_LAUNCH("hx_actor_act_step");
-    return 0;
-}
-
-int hx_actor_act_step(const float* actor, float* state, int64_t n, int64_t stride, float* obs_io, float* actions, int32_t noise_mode,
-                      const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, float* reward,
-                      uint8_t* done, int8_t* success, const HxStepOpts* opts, void* stream) {
-    return actor_act_step_impl(actor, nullptr, nullptr, state, n, stride, obs_io, actions, noise_mode, noise, sigma, seed, row0, call, slope, reward, done,
-                               success, opts, stream);
-}
-int hx_actor_act_step_bf16(const float* actor, const uint16_t* w2_bf16, float* state, int64_t n, int64_t stride, float* obs_io, float* actions,
-                           int32_t noise_mode, const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope,
-                           float* reward, uint8_t* done, int8_t* success, const HxStepOpts* opts, void* stream) {
-    HX_REQUIRE(w2_bf16 && (reinterpret_cast<uintptr_t>(w2_bf16) & 15u) == 0, "hx_actor_act_step_bf16: w2_bf16 must be a 16-byte aligned bf16 image of W2");
-    return actor_act_step_impl(actor, w2_bf16, nullptr, state, n, stride, obs_io, actions, noise_mode, noise, sigma, seed, row0, call, slope, reward, done,
-                               success, opts, stream);
-}
-
 /* The fp32 policy with the 256 -> 512 product through the exact three-way bf16 split of both operands on the bf16 matrix cores (see the header; hx_act.h HX_X9_TERMS). */
 int hx_pack_w2_x9(const float* net, int32_t in_dim, uint16_t* w2_x9, void* stream) {
-    HX_REQUIRE(net && w2_x9 && (in_dim == 13 || in_dim == 17) && (reinterpret_cast<uintptr_t>(w2_x9) & 15u) == 0, "hx_pack_w2_x9: bad arguments");
+    HX_REQUIRE(net && (in_dim == 13 || in_dim == 17), "hx_pack_w2_x9: bad arguments");
+    if (int rc = check_images16("hx_pack_w2_x9", "bad arguments", {w2_x9})) return rc;
     const Mlp m{in_dim, 1, 0};
     const int n = H2 * H1;
     hipLaunchKernelGGL(pack_x9_kernel, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream, net + m.W2(), w2_x9, n);
     HX_CHECK_LAUNCH("hx_pack_w2_x9");
     return 0;
 }
+/* (noise_mode + 32 is hx_hirl_front's way of asking for this format: refused here, with the image check's words) */
 int hx_actor_act_x9(const float* actor, const uint16_t* w2_x9, const float* obs, int64_t rows, float* actions, int32_t noise_mode,
                     const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, void* stream) {
-    HX_REQUIRE(w2_x9 && (reinterpret_cast<uintptr_t>(w2_x9) & 15u) == 0 && (noise_mode & 32) == 0, "hx_actor_act_x9: w2_x9 must be the 16-byte aligned hi | mid | lo images of W2");
-    return actor_act_impl(actor, w2_x9, nullptr, obs, rows, actions, noise_mode | 32, noise, sigma, seed, row0, call, slope, stream);
+    HX_REQUIRE((noise_mode & 32) == 0, "hx_actor_act_x9: w2_x9 must be the 16-byte aligned hi | mid | lo images of W2");
+    if (int rc = check_images16("hx_actor_act_x9", "w2_x9 must be the 16-byte aligned hi | mid | lo images of W2", {w2_x9})) return rc;
+    return actor_act_impl(actor, ActImages{nullptr, w2_x9, nullptr}, obs, rows, actions, noise_mode, noise, sigma, seed, row0, call, slope, stream);
 }
 int hx_actor_act_step_x9(const float* actor, const uint16_t* w2_x9, float* state, int64_t n, int64_t stride, float* obs_io, float* actions,
                          int32_t noise_mode, const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope,
                          float* reward, uint8_t* done, int8_t* success, const HxStepOpts* opts, void* stream) {
-    HX_REQUIRE(w2_x9 && (reinterpret_cast<uintptr_t>(w2_x9) & 15u) == 0 && (noise_mode & 32) == 0, "hx_actor_act_step_x9: w2_x9 must be the 16-byte aligned hi | mid | lo images of W2");
-    return actor_act_step_impl(actor, w2_x9, nullptr, state, n, stride, obs_io, actions, noise_mode | 32, noise, sigma, seed, row0, call, slope, reward, done,
-                               success, opts, stream);
+    HX_REQUIRE((noise_mode & 32) == 0, "hx_actor_act_step_x9: w2_x9 must be the 16-byte aligned hi | mid | lo images of W2");
+    if (int rc = check_images16("hx_actor_act_step_x9", "w2_x9 must be the 16-byte aligned hi | mid | lo images of W2", {w2_x9})) return rc;
+    return actor_act_step_impl(actor, ActImages{nullptr, w2_x9, nullptr}, state, n, stride, obs_io, actions, noise_mode, noise, sigma, seed, row0, call, slope, reward,
+                               done, success, opts, stream);
 }
 
 /* The fp32 policy from the re-ordered fp32 image of W2 (hx_pack_w2_f32i): bit-identical to hx_actor_act / hx_actor_act_step. */
 int hx_pack_w2_f32i(const float* net, int32_t in_dim, float* w2_f32i, void* stream) {
-    HX_REQUIRE(net && w2_f32i && (in_dim == 13 || in_dim == 17) && (reinterpret_cast<uintptr_t>(w2_f32i) & 15u) == 0, "hx_pack_w2_f32i: bad arguments");
+    HX_REQUIRE(net && (in_dim == 13 || in_dim == 17), "hx_pack_w2_f32i: bad arguments");
+    if (int rc = check_images16("hx_pack_w2_f32i", "bad arguments", {w2_f32i})) return rc;
     const Mlp m{in_dim, 1, 0};
     const int n = H2 * H1;
     hipLaunchKernelGGL(pack_f32i_kernel, dim3((n / 4 + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream, net + m.W2(), w2_f32i, n);
@@ -249,86 +240,78 @@ int hx_pack_w2_f32i(const float* net, int32_t in_dim, float* w2_f32i, void* stre
 }
 int hx_actor_act_f32i(const float* actor, const float* w2_f32i, const float* obs, int64_t rows, float* actions, int32_t noise_mode,
                       const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, void* stream) {
-    HX_REQUIRE(w2_f32i && (reinterpret_cast<uintptr_t>(w2_f32i) & 15u) == 0, "hx_actor_act_f32i: w2_f32i must be a 16-byte aligned fp32 image of W2");
-    return actor_act_impl(actor, nullptr, w2_f32i, obs, rows, actions, noise_mode, noise, sigma, seed, row0, call, slope, stream);
+    if (int rc = check_images16("hx_actor_act_f32i", "w2_f32i must be a 16-byte aligned fp32 image of W2", {w2_f32i})) return rc;
+    return actor_act_impl(actor, ActImages{w2_f32i, nullptr, nullptr}, obs, rows, actions, noise_mode, noise, sigma, seed, row0, call, slope, stream);
 }
 int hx_actor_act_step_f32i(const float* actor, const float* w2_f32i, float* state, int64_t n, int64_t stride, float* obs_io, float* actions,
                            int32_t noise_mode, const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope,
                            float* reward, uint8_t* done, int8_t* success, const HxStepOpts* opts, void* stream) {
-    HX_REQUIRE(w2_f32i && (reinterpret_cast<uintptr_t>(w2_f32i) & 15u) == 0, "hx_actor_act_step_f32i: w2_f32i must be a 16-byte aligned fp32 image of W2");
-    return actor_act_step_impl(actor, nullptr, w2_f32i, state, n, stride, obs_io, actions, noise_mode, noise, sigma, seed, row0, call, slope, reward, done,
-                               success, opts, stream);
+    if (int rc = check_images16("hx_actor_act_step_f32i", "w2_f32i must be a 16-byte aligned fp32 image of W2", {w2_f32i})) return rc;
+    return actor_act_step_impl(actor, ActImages{w2_f32i, nullptr, nullptr}, state, n, stride, obs_io, actions, noise_mode, noise, sigma, seed, row0, call, slope,
+                               reward, done, success, opts, stream);
 }
 
+// im.w2x: the exact split exists for the Gaussian head in the persistent kernel only — up to 8,192 rows (or with HX_ACT_PERSIST=0) im.w2f serves
+static ActImages sac_images(ActImages im, int64_t rows) {
+    if (!(rows > kFuseEnvMax && persist_enabled())) im.w2x = nullptr;
+    return im;
+}
 /* SacAgent.explore / exploit (SAC/agent.py:183-196) for `rows` observations.  mode 0: exploit = tanh(mean); 1: sample with the
  * standard-normal draws eps[rows][4]; 2: sample with Philox(seed; row0 + row, call).  ws: unused since the whole policy runs in one kernel (may be NULL). */
-static int sac_act_impl(const float* policy, const float* w2f, const float* obs, int64_t rows, float* actions, int32_t mode, const float* eps,
-                        uint64_t seed, uint32_t row0, uint32_t call, void* stream, const uint16_t* w2x = nullptr, const uint16_t* w2b = nullptr) {
+static int sac_act_impl(const float* policy, const ActImages& im, const float* obs, int64_t rows, float* actions, int32_t mode, const float* eps,
+                        uint64_t seed, uint32_t row0, uint32_t call, void* stream) {
     HX_REQUIRE(policy && obs && actions && rows > 0 && mode >= 0 && mode <= 2 && (mode != 1 || eps), "hx_sac_act: bad arguments");
-    const bool x9 = w2x && rows > kFuseEnvMax && persist_enabled();  // the exact split exists for the Gaussian head in the persistent kernel only
-    ActFusedArgs H{policy, kPolicy, const_cast<float*>(obs), (int)rows, 0.0f, actions, mode == 1 ? eps : nullptr, 1, 0.0f, mode, seed, row0, call,
-                   nullptr, 0, nullptr, nullptr, nullptr, HxStepOpts{}, 0.0, x9 ? w2x : w2b, (x9 || w2b) ? nullptr : w2f, x9 ? 1 : 0};
-    launch_act<true>(H, (hipStream_t)stream);
+    launch_act<true>(act_args_gauss(policy, const_cast<float*>(obs), rows, actions, mode, eps, seed, row0, call, sac_images(im, rows)), (hipStream_t)stream);
     HX_CHECK_LAUNCH("hx_sac_act");
     return 0;
 }
+/* SacAgent.explore / exploit + HarfangEnv.step in one launch (train_sac.py:238-241): hx_sac_act, then hx_env_step in the kernel's tail. */
+static int sac_act_step_impl(const float* policy, const ActImages& im, float* state, int64_t n, int64_t stride, float* obs_io, float* actions, int32_t mode,
+                             const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done, int8_t* success,
+                             const HxStepOpts* opts, void* stream) {
+    HX_REQUIRE(policy && mode >= 0 && mode <= 2 && (mode != 1 || eps), "hx_sac_act_step: bad arguments");
+    const ActEnv E{state, stride, reward, done, success, opts ? *opts : HxStepOpts{}};
+    if (int rc = check_step_args(obs_io, n, actions, E, "hx_sac_act_step")) return rc;
+    return launch_act_step<true>(act_args_gauss(policy, obs_io, n, actions, mode, eps, seed, row0, call, sac_images(im, n), &E), opts, "hx_sac_act_step", "hx_sac_act",
+                                 (hipStream_t)stream);
+}
+
 int hx_sac_act(const float* policy, const float* obs, int64_t rows, float* actions, int32_t mode, const float* eps, uint64_t seed,
                uint32_t row0, uint32_t call, float* ws, void* stream) {
     (void)ws;
-    return sac_act_impl(policy, nullptr, obs, rows, actions, mode, eps, seed, row0, call, stream);
-}
-int hx_sac_act_f32i(const float* policy, const float* w2_f32i, const float* obs, int64_t rows, float* actions, int32_t mode, const float* eps,
-                    uint64_t seed, uint32_t row0, uint32_t call, void* stream) {
-    HX_REQUIRE(w2_f32i && (reinterpret_cast<uintptr_t>(w2_f32i) & 15u) == 0, "hx_sac_act_f32i: w2_f32i must be a 16-byte aligned fp32 image of W2");
-    return sac_act_impl(policy, w2_f32i, obs, rows, actions, mode, eps, seed, row0, call, stream);
-}
-
-/* SacAgent.explore / exploit + HarfangEnv.step in one launch (train_sac.py:238-241): hx_sac_act, then hx_env_step in the kernel's tail. */
-static int sac_act_step_impl(const float* policy, const float* w2f, float* state, int64_t n, int64_t stride, float* obs_io, float* actions, int32_t mode,
-                             const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done, int8_t* success,
-                             const HxStepOpts* opts, void* stream, const uint16_t* w2x = nullptr, const uint16_t* w2b = nullptr) {
-    HX_REQUIRE(policy && mode >= 0 && mode <= 2 && (mode != 1 || eps), "hx_sac_act_step: bad arguments");
-    const HxStepOpts o = opts ? *opts : HxStepOpts{};
-    if (int rc = check_step_args(state, n, stride, obs_io, actions, reward, done, success, o, "hx_sac_act_step")) return rc;
-    const bool x9 = w2x && n > kFuseEnvMax && persist_enabled();
-    ActFusedArgs H{policy, kPolicy, obs_io, (int)n, 0.0f, actions, mode == 1 ? eps : nullptr, 1, 0.0f, mode, seed, row0, call,
-                   state, stride, reward, done, success, o, o.cap > 0 ? 1.0 / (double)o.cap : 0.0, x9 ? w2x : w2b, (x9 || w2b) ? nullptr : w2f, x9 ? 1 : 0};
-    if (n > kFuseEnvMax) {
-        if (persist_enabled() && launch_act_persist(H, true, (hipStream_t)stream)) {
-            HX_CHECK_LAUNCH("hx_sac_act_step");
-            return 0;
-        }
-        if (int rc = sac_act_impl(policy, w2f, obs_io, n, actions, mode, eps, seed, row0, call, stream, w2x, w2b)) return rc;
-        return hx_env_step(state, n, stride, actions, obs_io, reward, done, success, opts, stream);
-    }
-    launch_act<true>(H, (hipStream_t)stream);
-    HX_CHECK_LAUNCH("hx_sac_act_step");
-    return 0;
+    return sac_act_impl(policy, ActImages{}, obs, rows, actions, mode, eps, seed, row0, call, stream);
 }
 int hx_sac_act_step(const float* policy, float* state, int64_t n, int64_t stride, float* obs_io, float* actions, int32_t mode,
                     const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done, int8_t* success,
                     const HxStepOpts* opts, void* stream) {
-    return sac_act_step_impl(policy, nullptr, state, n, stride, obs_io, actions, mode, eps, seed, row0, call, reward, done, success, opts, stream);
+    return sac_act_step_impl(policy, ActImages{}, state, n, stride, obs_io, actions, mode, eps, seed, row0, call, reward, done, success, opts, stream);
+}
+int hx_sac_act_f32i(const float* policy, const float* w2_f32i, const float* obs, int64_t rows, float* actions, int32_t mode, const float* eps,
+                    uint64_t seed, uint32_t row0, uint32_t call, void* stream) {
+    if (int rc = check_images16("hx_sac_act_f32i", "w2_f32i must be a 16-byte aligned fp32 image of W2", {w2_f32i})) return rc;
+    return sac_act_impl(policy, ActImages{w2_f32i, nullptr, nullptr}, obs, rows, actions, mode, eps, seed, row0, call, stream);
 }
 int hx_sac_act_step_f32i(const float* policy, const float* w2_f32i, float* state, int64_t n, int64_t stride, float* obs_io, float* actions,
                          int32_t mode, const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done,
                          int8_t* success, const HxStepOpts* opts, void* stream) {
-    HX_REQUIRE(w2_f32i && (reinterpret_cast<uintptr_t>(w2_f32i) & 15u) == 0, "hx_sac_act_step_f32i: w2_f32i must be a 16-byte aligned fp32 image of W2");
-    return sac_act_step_impl(policy, w2_f32i, state, n, stride, obs_io, actions, mode, eps, seed, row0, call, reward, done, success, opts, stream);
+    if (int rc = check_images16("hx_sac_act_step_f32i", "w2_f32i must be a 16-byte aligned fp32 image of W2", {w2_f32i})) return rc;
+    return sac_act_step_impl(policy, ActImages{w2_f32i, nullptr, nullptr}, state, n, stride, obs_io, actions, mode, eps, seed, row0, call, reward, done, success, opts,
+                             stream);
 }
 
 int hx_sac_act_x9(const float* policy, const uint16_t* w2_x9, const float* w2_f32i, const float* obs, int64_t rows, float* actions, int32_t mode,
                   const float* eps, uint64_t seed, uint32_t row0, uint32_t call, void* stream) {
-    HX_REQUIRE(w2_x9 && w2_f32i && (reinterpret_cast<uintptr_t>(w2_x9) & 15u) == 0 && (reinterpret_cast<uintptr_t>(w2_f32i) & 15u) == 0,
-               "hx_sac_act_x9: w2_x9 (hi | mid | lo images) and w2_f32i (the fallback up to 8,192 rows) must be 16-byte aligned images of W2");
-    return sac_act_impl(policy, w2_f32i, obs, rows, actions, mode, eps, seed, row0, call, stream, w2_x9);
+    if (int rc = check_images16("hx_sac_act_x9", "w2_x9 (hi | mid | lo images) and w2_f32i (the fallback up to 8,192 rows) must be 16-byte aligned images of W2",
+                                {w2_x9, w2_f32i})) return rc;
+    return sac_act_impl(policy, ActImages{w2_f32i, w2_x9, nullptr}, obs, rows, actions, mode, eps, seed, row0, call, stream);
 }
 int hx_sac_act_step_x9(const float* policy, const uint16_t* w2_x9, const float* w2_f32i, float* state, int64_t n, int64_t stride, float* obs_io,
                        float* actions, int32_t mode, const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done,
                        int8_t* success, const HxStepOpts* opts, void* stream) {
-    HX_REQUIRE(w2_x9 && w2_f32i && (reinterpret_cast<uintptr_t>(w2_x9) & 15u) == 0 && (reinterpret_cast<uintptr_t>(w2_f32i) & 15u) == 0,
-               "hx_sac_act_step_x9: w2_x9 (hi | mid | lo images) and w2_f32i (the fallback up to 8,192 rows) must be 16-byte aligned images of W2");
-    return sac_act_step_impl(policy, w2_f32i, state, n, stride, obs_io, actions, mode, eps, seed, row0, call, reward, done, success, opts, stream, w2_x9);
+    if (int rc = check_images16("hx_sac_act_step_x9", "w2_x9 (hi | mid | lo images) and w2_f32i (the fallback up to 8,192 rows) must be 16-byte aligned images of W2",
+                                {w2_x9, w2_f32i})) return rc;
+    return sac_act_step_impl(policy, ActImages{w2_f32i, w2_x9, nullptr}, state, n, stride, obs_io, actions, mode, eps, seed, row0, call, reward, done, success, opts,
+                             stream);
 }
 
 /* bf16 policy inference of the Gaussian policy (include/hirl4ucav.h "SAC bf16 path"): the 256 -> 512 product from the bf16 image w2_bf16
@@ -336,14 +319,15 @@ int hx_sac_act_step_x9(const float* policy, const uint16_t* w2_x9, const float* 
  * kernel, beyond that the streaming persistent kernel (MODE 2): the same bits for a row either way. */
 int hx_sac_act_bf16(const float* policy, const uint16_t* w2_bf16, const float* obs, int64_t rows, float* actions, int32_t mode, const float* eps,
                     uint64_t seed, uint32_t row0, uint32_t call, void* stream) {
-    HX_REQUIRE(w2_bf16 && (reinterpret_cast<uintptr_t>(w2_bf16) & 15u) == 0, "hx_sac_act_bf16: w2_bf16 must be a 16-byte aligned bf16 image of W2");
-    return sac_act_impl(policy, nullptr, obs, rows, actions, mode, eps, seed, row0, call, stream, nullptr, w2_bf16);
+    if (int rc = check_images16("hx_sac_act_bf16", "w2_bf16 must be a 16-byte aligned bf16 image of W2", {w2_bf16})) return rc;
+    return sac_act_impl(policy, ActImages{nullptr, nullptr, w2_bf16}, obs, rows, actions, mode, eps, seed, row0, call, stream);
 }
 int hx_sac_act_step_bf16(const float* policy, const uint16_t* w2_bf16, float* state, int64_t n, int64_t stride, float* obs_io, float* actions,
                          int32_t mode, const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done,
                          int8_t* success, const HxStepOpts* opts, void* stream) {
-    HX_REQUIRE(w2_bf16 && (reinterpret_cast<uintptr_t>(w2_bf16) & 15u) == 0, "hx_sac_act_step_bf16: w2_bf16 must be a 16-byte aligned bf16 image of W2");
-    return sac_act_step_impl(policy, nullptr, state, n, stride, obs_io, actions, mode, eps, seed, row0, call, reward, done, success, opts, stream, nullptr, w2_bf16);
+    if (int rc = check_images16("hx_sac_act_step_bf16", "w2_bf16 must be a 16-byte aligned bf16 image of W2", {w2_bf16})) return rc;
+    return sac_act_step_impl(policy, ActImages{nullptr, nullptr, w2_bf16}, state, n, stride, obs_io, actions, mode, eps, seed, row0, call, reward, done, success, opts,
+                             stream);
 }
 
 }  // extern "C"

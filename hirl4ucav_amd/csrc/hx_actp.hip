@@ -44,14 +44,6 @@ __global__ __launch_bounds__(kWide) void act_persist_stream_kernel(ActFusedArgs 
 }
 
 
-template <typename K>
-static void launch_k(K kernel, dim3 grid, const ActFusedArgs& H, int tiles_per_wg, hipStream_t st) {
-    if (H.state && H.o.ev_start && H.o.ev_stop)
-        hipExtLaunchKernelGGL(kernel, grid, dim3(kWide), 0, st, (hipEvent_t)H.o.ev_start, (hipEvent_t)H.o.ev_stop, 0, H, tiles_per_wg);
-    else
-        hipLaunchKernelGGL(kernel, grid, dim3(kWide), 0, st, H, tiles_per_wg);
-}
-
 // one workgroup per CU: the grid that keeps every weight fetch to ONE per CU (a second resident workgroup would not fit beside 128 VGPRs x
 // 1,024 threads anyway)
 static int persistent_cus() {
@@ -78,11 +70,11 @@ bool launch_act_persist(const ActFusedArgs& H, bool gauss, hipStream_t st) {
         const int per = (ntiles + persistent_cus() - 1) / persistent_cus();
         const dim3 grid((unsigned)((ntiles + per - 1) / per));
         if (env) {
-            if (relu) launch_k(act_persist_bf16_kernel<true, true>, grid, H, per, st);
-            else launch_k(act_persist_bf16_kernel<true, false>, grid, H, per, st);
+            if (relu) launch_stamped(act_persist_bf16_kernel<true, true>, grid, st, H.o, H, per);
+            else launch_stamped(act_persist_bf16_kernel<true, false>, grid, st, H.o, H, per);
         } else {
-            if (relu) launch_k(act_persist_bf16_kernel<false, true>, grid, H, per, st);
-            else launch_k(act_persist_bf16_kernel<false, false>, grid, H, per, st);
+            if (relu) launch_stamped(act_persist_bf16_kernel<false, true>, grid, st, H.o, H, per);
+            else launch_stamped(act_persist_bf16_kernel<false, false>, grid, st, H.o, H, per);
         }
         return true;
     }
@@ -94,7 +86,7 @@ bool launch_act_persist(const ActFusedArgs& H, bool gauss, hipStream_t st) {
         const int per = (ntiles + persistent_cus() - 1) / persistent_cus();
         const dim3 grid((unsigned)((ntiles + per - 1) / per));
 #define HX_STREAM(MODE, G, R) \
-        { if (env) launch_k(act_persist_stream_kernel<MODE, G, true, R>, grid, H, per, st); else launch_k(act_persist_stream_kernel<MODE, G, false, R>, grid, H, per, st); }
+        { if (env) launch_stamped(act_persist_stream_kernel<MODE, G, true, R>, grid, st, H.o, H, per); else launch_stamped(act_persist_stream_kernel<MODE, G, false, R>, grid, st, H.o, H, per); }
         if (b1) HX_STREAM(2, true, true)
         else if (x9 && gauss) HX_STREAM(1, true, true)
         else if (x9) { if (relu) HX_STREAM(1, false, true) else HX_STREAM(1, false, false) }

@@ -178,25 +178,23 @@ int launch_front_sac(const ActFusedArgs& H, const FwdArgs& FA, hipStream_t st) {
     const int npass = (H.rows + 4 * RT - 1) / (4 * RT), per_wg = (npass + 255) / 256;
     C.n_act = (npass + per_wg - 1) / per_wg;
     const dim3 grid((unsigned)(C.n_act + C.per * FA.njobs));
-#define HX_SACF(MODE_) do { \
-        if (H.o.ev_start && H.o.ev_stop) hipExtLaunchKernelGGL((actps_sac_front_kernel<MODE_>), grid, dim3(kWide), 0, st, (hipEvent_t)H.o.ev_start, (hipEvent_t)H.o.ev_stop, 0, H, CA, C, per_wg); \
-        else hipLaunchKernelGGL((actps_sac_front_kernel<MODE_>), grid, dim3(kWide), 0, st, H, CA, C, per_wg); } while (0)
-    if (b16) HX_SACF(2); else if (x9) HX_SACF(1); else HX_SACF(0);
-#undef HX_SACF
+    if (b16) launch_stamped(actps_sac_front_kernel<2>, grid, st, H.o, H, CA, C, per_wg);
+    else if (x9) launch_stamped(actps_sac_front_kernel<1>, grid, st, H.o, H, CA, C, per_wg);
+    else launch_stamped(actps_sac_front_kernel<0>, grid, st, H.o, H, CA, C, per_wg);
     HX_CHECK_LAUNCH("hx_sac_front");
     return 0;
 }
 
-int launch_front(const float* actor, const float* w2f, const uint16_t* w2x, const uint16_t* w2b, float* state, int64_t n, int64_t stride, float* obs_io, float* actions, int32_t noise_mode,
-                 const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, float* reward, uint8_t* done, int8_t* success,
-                 const HxStepOpts& o, const FwdArgs& FA, const FwdArgs& FB, const BwdArgs* GC, const HxFront& front, hipStream_t st) {
-    HX_REQUIRE(actor && (w2f || w2x || w2b) && ((reinterpret_cast<uintptr_t>(w2f) | reinterpret_cast<uintptr_t>(w2x) | reinterpret_cast<uintptr_t>(w2b)) & 15u) == 0,
+// H: the deterministic head's act + env description (act_args_det with its env part), one image of W2 in it.  (hx_hirl_front has run check_step_args on the
+// 64-bit env count already — H.rows is an int — and the noise-mode check, which needs the caller's noise_mode; the env-step buffers are checked again here.)
+int launch_front(const ActFusedArgs& H, const FwdArgs& FA, const FwdArgs& FB, const BwdArgs* GC, const HxFront& front, hipStream_t st) {
+    const bool w2x = H.w2b && H.x9, w2b = H.w2b && !H.x9;  // the acting format: exact split, bf16, else fp32 MFMA from the fp32 image
+    const int64_t n = H.rows;
+    const HxStepOpts& o = H.o;
+    HX_REQUIRE(H.net && (H.w2f || H.w2b) && ((reinterpret_cast<uintptr_t>(H.w2f) | reinterpret_cast<uintptr_t>(H.w2b)) & 15u) == 0,
                "hx_hirl_front: the actor and a 16-byte aligned image of its W2 (HxNets.actor_w2_x9, actor_w2_f32i or actor_w2_bf16)");
     HX_REQUIRE(!w2b == !FA.images && FA.images == FB.images, "hx_hirl_front: the bf16 acting image goes with the bf16 update path (HxNets.w2_bf16_all), and only with it");
-    const Mlp mA{13, 4, (noise_mode & 16) ? 1 : 0};  // + 16: layerNorm = False (as hx_actor_act_step)
-    noise_mode &= 15;
-    HX_REQUIRE(noise_mode >= 0 && noise_mode <= 3 && (noise || (noise_mode != 1 && noise_mode != 2)), "hx_hirl_front: bad noise mode");
-    if (int rc = check_step_args(state, n, stride, obs_io, actions, reward, done, success, o, "hx_hirl_front")) return rc;
+    if (int rc = check_step_args(H.obs, n, H.actions, ActEnv{H.state, H.stride, H.reward, H.done, H.success, o}, "hx_hirl_front")) return rc;
     // bf16: beyond how many envs the acting role is the persistent kernel (tuning knob).  Measured, us per step with the per-tile / the persistent acting role:
     // 4,096 envs 44.0 / 46.8; 8,192 envs 56.2 / 50.7 (there the per-tile role is 256 workgroups — no CU left for the update — the persistent one 128 of two tiles)
     static const int64_t persist_rows = getenv("HX_FRONT_PERSIST_ROWS") ? atoll(getenv("HX_FRONT_PERSIST_ROWS")) : 4096;
@@ -207,9 +205,6 @@ int launch_front(const float* actor, const float* w2f, const uint16_t* w2x, cons
     HX_REQUIRE(!persistent || (w2b && o.ring), "hx_hirl_front: at most 8,192 envs per launch (one round of 32-row acting workgroups); with a replay ring "
                                                "any number in the exact-split format and in bf16 (persistent acting workgroups)");
     HX_REQUIRE(!FA.sample && FA.njobs >= 3 && FB.njobs >= 2, "hx_hirl_front: launch A reads finished minibatch tiles");
-    ActFusedArgs H{actor, mA, obs_io, (int)n, slope, actions, (noise_mode == 1 || noise_mode == 2) ? noise : nullptr,
-                   noise_mode == 2, noise_mode == 3 ? sigma : 0.0f, 0, seed, row0, call, state, stride, reward, done, success, o,
-                   o.cap > 0 ? 1.0 / (double)o.cap : 0.0, w2b ? w2b : w2x, (w2x || w2b) ? nullptr : w2f, w2x ? 1 : 0};
     FwdArgsC CA{}, CB{};
     for (int j = 0; j < FA.njobs; ++j) { CA.job[j] = pack_fwd(FA.job[j]); CA.job[j].slope = FA.slope; }
     for (int j = 0; j < FB.njobs; ++j) { CB.job[j] = pack_fwd(FB.job[j]); CB.job[j].slope = FB.slope; }
@@ -263,23 +258,15 @@ int launch_front(const float* actor, const float* w2f, const uint16_t* w2x, cons
         C.sync.with_c = 1u; C.sync.c_target = front.with_c * cw; C.sync.t_target = front.with_c * 2u * cw;  // (their counters advance only in launches with C)
     }
     const unsigned n_c = GC ? 2u * (unsigned)C.c_per : 0u;
-    const bool relu = slope == 0.0f;
+    const bool relu = H.slope == 0.0f;
     if (stream) {  // up to 16,384 envs one 64-row pass per acting workgroup (the CUs they leave serve the update beside them); beyond, passes over every CU and the
                    // update's workgroups behind them (two boundaries less)
         const int npass = (int)((n + 4 * RT - 1) / (4 * RT)), per_wg = (npass + 255) / 256;
         C.n_act = (npass + per_wg - 1) / per_wg;
         const dim3 sgrid((unsigned)(C.n_act + C.n_fwd) + n_c);
-        if (o.ev_start && o.ev_stop) {
-            if (relu) hipExtLaunchKernelGGL((actps_front_kernel<true>), sgrid, dim3(kWide), 0, st, (hipEvent_t)o.ev_start, (hipEvent_t)o.ev_stop, 0, H, CA, CB, C, per_wg, CG);
-            else hipExtLaunchKernelGGL((actps_front_kernel<false>), sgrid, dim3(kWide), 0, st, (hipEvent_t)o.ev_start, (hipEvent_t)o.ev_stop, 0, H, CA, CB, C, per_wg, CG);
-        } else {
-            if (relu) hipLaunchKernelGGL((actps_front_kernel<true>), sgrid, dim3(kWide), 0, st, H, CA, CB, C, per_wg, CG);
-            else hipLaunchKernelGGL((actps_front_kernel<false>), sgrid, dim3(kWide), 0, st, H, CA, CB, C, per_wg, CG);
-        }
-        HX_CHECK_LAUNCH("hx_hirl_front");
-        return 0;
-    }
-    if (persistent) {
+        if (relu) launch_stamped(actps_front_kernel<true>, sgrid, st, o, H, CA, CB, C, per_wg, CG);
+        else launch_stamped(actps_front_kernel<false>, sgrid, st, o, H, CA, CB, C, per_wg, CG);
+    } else if (persistent) {
         // up to 32,768 envs two thirds of the CUs act (ceil(tiles / 176) row tiles per workgroup) and the rest serve the update beside them; beyond, the acting
         // workgroups take every CU (the update is a small share there) and the update's workgroups start as the first of them leave: two boundaries less
         static const int wide_wgs = getenv("HX_FRONT_PERSIST_WIDE_WGS") ? atoi(getenv("HX_FRONT_PERSIST_WIDE_WGS")) : 256;  // tuning knob
@@ -288,24 +275,15 @@ int launch_front(const float* actor, const float* w2f, const uint16_t* w2x, cons
         const int ntiles = (int)((n + 2 * RT - 1) / (2 * RT)), tiles_per_wg = (ntiles + want - 1) / want;
         C.n_act = (ntiles + tiles_per_wg - 1) / tiles_per_wg;
         const dim3 pgrid((unsigned)(C.n_act + C.n_fwd) + n_c);
-        if (o.ev_start && o.ev_stop) {
-            if (relu) hipExtLaunchKernelGGL((actp_front_kernel<true>), pgrid, dim3(kWide), 0, st, (hipEvent_t)o.ev_start, (hipEvent_t)o.ev_stop, 0, H, CA, CB, C, tiles_per_wg, CG);
-            else hipExtLaunchKernelGGL((actp_front_kernel<false>), pgrid, dim3(kWide), 0, st, (hipEvent_t)o.ev_start, (hipEvent_t)o.ev_stop, 0, H, CA, CB, C, tiles_per_wg, CG);
-        } else {
-            if (relu) hipLaunchKernelGGL((actp_front_kernel<true>), pgrid, dim3(kWide), 0, st, H, CA, CB, C, tiles_per_wg, CG);
-            else hipLaunchKernelGGL((actp_front_kernel<false>), pgrid, dim3(kWide), 0, st, H, CA, CB, C, tiles_per_wg, CG);
-        }
-        HX_CHECK_LAUNCH("hx_hirl_front");
-        return 0;
+        if (relu) launch_stamped(actp_front_kernel<true>, pgrid, st, o, H, CA, CB, C, tiles_per_wg, CG);
+        else launch_stamped(actp_front_kernel<false>, pgrid, st, o, H, CA, CB, C, tiles_per_wg, CG);
+    } else {
+        const dim3 grid((unsigned)(C.n_act + C.n_fwd) + n_c);
+        const auto go = [&](auto kernel) { launch_stamped(kernel, grid, st, o, H, CA, CB, C, CG); };
+        if (w2b) { if (relu) go(act_front_kernel<true, false, true>); else go(act_front_kernel<false, false, true>); }
+        else if (relu) { if (w2x) go(act_front_kernel<true, true, false>); else go(act_front_kernel<true, false, false>); }
+        else { if (w2x) go(act_front_kernel<false, true, false>); else go(act_front_kernel<false, false, false>); }
     }
-    const dim3 grid((unsigned)(C.n_act + C.n_fwd) + n_c);
-#define HX_FRONT(RELU_, X3_, BF16_) do { \
-        if (o.ev_start && o.ev_stop) hipExtLaunchKernelGGL((act_front_kernel<RELU_, X3_, BF16_>), grid, dim3(kWide), 0, st, (hipEvent_t)o.ev_start, (hipEvent_t)o.ev_stop, 0, H, CA, CB, C, CG); \
-        else hipLaunchKernelGGL((act_front_kernel<RELU_, X3_, BF16_>), grid, dim3(kWide), 0, st, H, CA, CB, C, CG); } while (0)
-    if (w2b) { if (relu) HX_FRONT(true, false, true); else HX_FRONT(false, false, true); }
-    else if (relu) { if (w2x) HX_FRONT(true, true, false); else HX_FRONT(true, false, false); }
-    else { if (w2x) HX_FRONT(false, true, false); else HX_FRONT(false, false, false); }
-#undef HX_FRONT
     HX_CHECK_LAUNCH("hx_hirl_front");
     return 0;
 }

@@ -3,7 +3,7 @@
 // delayed actor step (minibatch draw and optimizer steps included); the stage entry points are what a sharded run calls between exchanges.
 #include <cmath>
 
-#include "hx_update.h"
+#include "hx_act.h"
 
 using namespace hxnn;
 using namespace hxu;
@@ -43,14 +43,10 @@ static void make_slots(const HxNets* N, int B, Slot* s) {
  * actor_fwd: 1 = also run the delayed actor step's forward passes that do not depend on the critic update (actor(s),
  * actor(s_bc)), 2 = plus bc_actor(s) for the soft estimate — they ride in launch A instead of a launch of their own.
  */
-// torch.optim.Adam's per-step scalars (defaults: betas (0.9, 0.999), eps 1e-8) for the fused wgrad + Adam launch
+// the fused wgrad + Adam launch's optimizer fields: Adam's per-step scalars (set_adam_scalars) plus HIRL's own
 static WgAdam make_adam(const HxNets* N, const HxHyper* Hy, float lr, int step, bool finish_actor) {
-    const double b1 = 0.9, b2 = 0.999;
-    const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - pow(b2, step);
     WgAdam a{};
-    a.b1 = (float)b1; a.b2 = (float)b2; a.eps = 1e-8f;
-    a.step_size = (float)(lr / bc1);
-    a.bc2_sqrt = (float)sqrt(bc2);
+    set_adam_scalars(a, lr, step);
     a.tau = Hy->tau;
     a.finish_actor = finish_actor ? 1 : 0;
     a.use_bc = Hy->use_bc;
@@ -390,8 +386,12 @@ int hx_hirl_front(float* state, int64_t n, int64_t stride, float* obs_io, float*
     const bool with_c = front_has_c(front->with_c != 0);
     HX_REQUIRE(!with_c || front->with_c != 0, "hx_hirl_front: HX_FRONT_C=1 needs a caller that counts its launches with launch C (HxFront.with_c = 1, 2, ...)");
     if (with_c) make_launch_c(N, Bt, Hy, GC);
-    return launch_front(N->actor, (x9 || bf16) ? nullptr : N->actor_w2_f32i, x9 ? N->actor_w2_x9 : nullptr, bf16 ? N->actor_w2_bf16 : nullptr, state, n, stride, obs_io, actions, noise_mode, noise, sigma, seed,
-                        row0, call, Hy->slope, reward, done, success, *opts, FA, FB, with_c ? &GC : nullptr, *front, (hipStream_t)stream);
+    if (int rc = hxact::check_noise_mode(noise_mode, noise, "hx_hirl_front")) return rc;
+    const hxact::ActEnv E{state, stride, reward, done, success, *opts};
+    if (int rc = hxact::check_step_args(obs_io, n, actions, E, "hx_hirl_front")) return rc;
+    const hxact::ActImages im{(x9 || bf16) ? nullptr : N->actor_w2_f32i, x9 ? N->actor_w2_x9 : nullptr, bf16 ? N->actor_w2_bf16 : nullptr};
+    return launch_front(hxact::act_args_det(N->actor, obs_io, n, actions, noise_mode, noise, sigma, seed, row0, call, Hy->slope, im, &E), FA, FB, with_c ? &GC : nullptr,
+                        *front, (hipStream_t)stream);
 }
 // the predraw of hx_hirl_learn_back / hx_hirl_critic_grads_back as a device-side description (nothing is launched here)
 static int make_predraw(const HxNets* N, const HxBatch* Bt, const HxSample* next, const HxBatch* next_tiles, void* stream, SampleDev* SD) {

@@ -333,6 +333,23 @@ static void launch_gauss(const GaussArgs& g0, const GaussArgs* g1, float* target
 static void sac_slots(const HxSacNets* N, int B, Slot* s) {
     for (int i = 0; i < S_COUNT; ++i) s[i] = carve_slot(N->ws + (size_t)i * kSlotFloats * B, B);
 }
+// what the launches of one learn() share: the workspace slots, the Gaussian heads' row buffers, the minibatch and the two critics
+struct SacCtx {
+    const HxSacNets* N;
+    const HxSacBatch* Bt;
+    int B;
+    hipStream_t st;
+    uint16_t* im;  // the SAC bf16 path's images (include/hirl4ucav.h), or NULL
+    Slot s[S_COUNT];
+    SacAux X;
+    RowSrc src;
+    const float* q1; const float* q2;
+    SacCtx(const HxSacNets* N_, const HxSacBatch* Bt_, void* stream)
+        : N(N_), Bt(Bt_), B(Bt_->batch), st((hipStream_t)stream), im(N_->w2_bf16_all), X(sac_aux(N_, Bt_->batch)), src{Bt_->rows, nullptr, nullptr, 0, 32},
+          q1(N_->critic), q2(N_->critic + kQs.padded()) {
+        sac_slots(N, B, s);
+    }
+};
 
 /* Critic half of SacAgent.learn (SAC/agent.py:278-313): [Polyak of the target critics first when polyak_first], a', H' =
  * policy.sample(s') with eps_next, y = r + (1 - d) gamma (min Q_target(s', a') + alpha H'), q1_loss / q2_loss -> losses[0..1],
@@ -340,57 +357,55 @@ static void sac_slots(const HxSacNets* N, int B, Slot* s) {
 // one_call (hx_sac_learn): the Polyak step rides behind the Gaussian heads' workgroups instead of in a launch of its own, and policy.sample(s)
 // of the policy half is evaluated beside policy.sample(s') — the same arithmetic on the same values, two launches less
 // launch 1 of SacAgent.learn: policy(s'), policy(s), Q1/Q2(s, a)
-static void sac_launch_1(const HxSacNets* N, const HxSacBatch* Bt, FwdArgs& F) {
-    const int B = Bt->batch;
-    Slot s[S_COUNT];
-    sac_slots(N, B, s);
-    const RowSrc src{Bt->rows, nullptr, nullptr, 0, 32};
-    const float* q1 = N->critic; const float* q2 = N->critic + kQs.padded();
+static void sac_launch_1(const SacCtx& C, FwdArgs& F) {
+    const int B = C.B;
     F = FwdArgs{};
     F.njobs = 4; F.slope = 0.0f;
-    F.zero_f = N->losses; F.zero_nf = 5;
-    F.job[0] = FwdJob{N->policy, kPolicy, src, 17, 0, Head{}, nullptr, 0.f, s[SS_PN], B, 0, IM_ACTOR};
-    F.job[1] = FwdJob{N->policy, kPolicy, src, 0, 0, Head{}, nullptr, 0.f, s[SS_PC], B, 1, IM_ACTOR};
-    F.job[2] = FwdJob{q1, kQs, src, 0, 0, Head{}, nullptr, 0.f, s[SS_Q1], B, 1, IM_C1};
-    F.job[3] = FwdJob{q2, kQs, src, 0, 0, Head{}, nullptr, 0.f, s[SS_Q2], B, 1, IM_C2};
-    F.images = N->w2_bf16_all;  // (NULL: fp32)
+    F.zero_f = C.N->losses; F.zero_nf = 5;
+    F.job[0] = FwdJob{C.N->policy, kPolicy, C.src, 17, 0, Head{}, nullptr, 0.f, C.s[SS_PN], B, 0, IM_ACTOR};
+    F.job[1] = FwdJob{C.N->policy, kPolicy, C.src, 0, 0, Head{}, nullptr, 0.f, C.s[SS_PC], B, 1, IM_ACTOR};
+    F.job[2] = FwdJob{C.q1, kQs, C.src, 0, 0, Head{}, nullptr, 0.f, C.s[SS_Q1], B, 1, IM_C1};
+    F.job[3] = FwdJob{C.q2, kQs, C.src, 0, 0, Head{}, nullptr, 0.f, C.s[SS_Q2], B, 1, IM_C2};
+    F.images = C.im;  // (NULL: fp32)
+}
+// a~, H = policy.sample(s) for the policy loss: beside policy.sample(s') in the one call, a launch of its own in the staged form
+static GaussArgs gauss_cur(const SacCtx& C) {
+    return GaussArgs{C.N->policy, kPolicy, C.s[SS_PC].z2, C.Bt->eps_cur, C.B, C.Bt->eps_cur ? 1 : 2, C.X.act_c, nullptr, C.X.aux_c, C.Bt->seed, 0x80000000u, C.Bt->call};
 }
 // skip_first: launch 1 has run already (as workgroups of hx_sac_front's launch)
 static int sac_critic_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, const HxSample* S, int32_t polyak_first, void* stream,
                                  int adam_step = 0, bool one_call = false, bool skip_first = false) {
     HX_REQUIRE(N && Bt && Hy && Bt->rows && Bt->batch > 0 && Bt->batch % 16 == 0, "hx_sac_critic_grads: bad arguments");
     if (int rc = sac_check_formats(N, "hx_sac_critic_grads")) return rc;
-    uint16_t* const im = N->w2_bf16_all;  // the SAC bf16 path (include/hirl4ucav.h), or NULL
-    hipStream_t st = (hipStream_t)stream;
-    const int B = Bt->batch;
+    const SacCtx C(N, Bt, stream);
+    uint16_t* const im = C.im;
+    hipStream_t st = C.st;
+    const int B = C.B;
     SampleDev SD{};
     bool fused = false;
     if (S) {  // memory.sample(batch_size) inside the first forward launch (or, batch > 256, by the sampling launch right here)
         HX_REQUIRE(!S->bc_table && !S->idx_bc, "hx_sac_critic_grads_sampled: SAC has no BC minibatch");
         if (int rc = prepare_draw(S, B, const_cast<float*>(Bt->rows), nullptr, nullptr, stream, &SD, &fused)) return rc;
     }
-    Slot s[S_COUNT];
-    sac_slots(N, B, s);
-    const SacAux X = sac_aux(N, B);
-    const RowSrc src{Bt->rows, nullptr, nullptr, 0, 32};
+    const Slot* s = C.s;
+    const SacAux& X = C.X;
     const int nq = 2 * kQs.padded();
     if (polyak_first && !one_call) {  // soft_update(critic_target, critic) BEFORE the update, agent.py:278-279
         launch_polyak(N->target_critic, N->critic, nq, Hy->tau, nullptr, nullptr, 0, st);
         if (im)  // ... and the targets' bf16 images follow it
             for (int h = 0; h < 2; ++h) launch_pack_bf16(N->target_critic + h * kQs.padded() + kQs.W2(), im + (IM_TC1 + h) * kImgElems, false, st);
     }
-    const float* q1 = N->critic; const float* q2 = N->critic + kQs.padded();
     const float* t1 = N->target_critic; const float* t2 = N->target_critic + kQs.padded();
     if (!skip_first) {   // policy(s'), policy(s), Q1/Q2(s, a)
         FwdArgs F;
-        sac_launch_1(N, Bt, F);
+        sac_launch_1(C, F);
         F.sample = fused ? &SD : nullptr;
         launch_fwd(F, st);
     }
     {   // a', H' = policy.sample(s')
         const GaussArgs G{N->policy, kPolicy, s[SS_PN].z2, Bt->eps_next, B, Bt->eps_next ? 1 : 2, X.act_n, X.ent_n, nullptr, Bt->seed, 0x40000000u, Bt->call};
         if (one_call) {
-            const GaussArgs G2{N->policy, kPolicy, s[SS_PC].z2, Bt->eps_cur, B, Bt->eps_cur ? 1 : 2, X.act_c, nullptr, X.aux_c, Bt->seed, 0x80000000u, Bt->call};
+            const GaussArgs G2 = gauss_cur(C);
             launch_gauss(G, &G2, N->target_critic, N->critic, polyak_first ? nq : 0, Hy->tau, st, im);
         } else {
             launch_gauss(G, nullptr, nullptr, nullptr, 0, 0.0f, st);
@@ -399,8 +414,8 @@ static int sac_critic_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const
     {   // target Q1/Q2 (s', a')
         FwdArgs F{};
         F.njobs = 2; F.slope = 0.0f;
-        F.job[0] = FwdJob{t1, kQs, src, 17, 3, Head{}, X.act_n, 0.f, s[SS_T1], B, 0, IM_TC1};
-        F.job[1] = FwdJob{t2, kQs, src, 17, 3, Head{}, X.act_n, 0.f, s[SS_T2], B, 0, IM_TC2};
+        F.job[0] = FwdJob{t1, kQs, C.src, 17, 3, Head{}, X.act_n, 0.f, s[SS_T1], B, 0, IM_TC1};
+        F.job[1] = FwdJob{t2, kQs, C.src, 17, 3, Head{}, X.act_n, 0.f, s[SS_T2], B, 0, IM_TC2};
         F.images = im;
         launch_fwd(F, st);
     }
@@ -410,8 +425,8 @@ static int sac_critic_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const
         for (int h = 0; h < 2; ++h) {
             BwdJob& J = G.job[h];
             J = BwdJob{};
-            J.net = h ? q2 : q1; J.m = kQs; J.ws = s[SS_Q1 + h]; J.rows = B; J.mode = BM_CRITIC_TD;
-            J.t1 = Head{t1, kQs, s[SS_T1]}; J.t2 = Head{t2, kQs, s[SS_T2]}; J.src = src; J.gamma = Hy->gamma;
+            J.net = h ? C.q2 : C.q1; J.m = kQs; J.ws = s[SS_Q1 + h]; J.rows = B; J.mode = BM_CRITIC_TD;
+            J.t1 = Head{t1, kQs, s[SS_T1]}; J.t2 = Head{t2, kQs, s[SS_T2]}; J.src = C.src; J.gamma = Hy->gamma;
             J.bonus = X.ent_n; J.bonus_scale = N->alpha_state + 3; J.loss_slot = h;
             J.img_t = IM_C1_T + h;
         }
@@ -425,7 +440,7 @@ static int sac_critic_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const
         for (int h = 0; h < 2; ++h) {
             WgJob& J = W.job[h];
             J = WgJob{};
-            J.net = h ? q2 : q1; J.grad = N->grad_critic + h * kQs.padded(); J.m = kQs;
+            J.net = h ? C.q2 : C.q1; J.grad = N->grad_critic + h * kQs.padded(); J.m = kQs;
             J.ws[0] = s[SS_Q1 + h]; J.rows[0] = B; J.nslots = 1; J.wmode[0] = 0;
             if (adam_step > 0) {  // q1_optim.step() / q2_optim.step() ride in the wgrad launch (one GPU): the thread that produced a gradient steps it
                 J.p = N->critic + h * kQs.padded();
@@ -434,17 +449,10 @@ static int sac_critic_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const
             }
         }
         if (adam_step > 0) {
-            const double b1 = 0.9, b2 = 0.999;
-            const double bc1 = 1.0 - pow(b1, adam_step), bc2 = 1.0 - pow(b2, adam_step);
-            W.ad = WgAdam{};
-            W.ad.b1 = (float)b1; W.ad.b2 = (float)b2; W.ad.eps = 1e-8f;
-            W.ad.step_size = (float)(Hy->lr_critic / bc1);
-            W.ad.bc2_sqrt = (float)sqrt(bc2);
+            set_adam_scalars(W.ad, Hy->lr_critic, adam_step);
             W.ad.losses = N->losses;
-            launch_wg(W, true, st);
-        } else {
-            launch_wg(W, false, st);
         }
+        launch_wg(W, adam_step > 0, st);
     }
     HX_CHECK_LAUNCH("hx_sac_critic_grads");
     return 0;
@@ -467,41 +475,35 @@ int hx_sac_critic_step(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* 
     HX_REQUIRE(step >= 1, "hx_sac_critic_step: step is 1-based");
     return sac_critic_grads_impl(N, Bt, Hy, S, polyak_first, stream, step);
 }
-// adam_step > 0 (hx_sac_learn): policy.sample(s) was evaluated in the critic half's launch, and policy_optim.step() + the log-alpha step ride in
-// the policy's weight-gradient launch (the thread that produced a gradient steps it; thread 0 of the launch steps log_alpha)
-static int sac_policy_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, void* stream, int adam_step, float target_entropy,
-                                 const SampleDev* predraw = nullptr) {
-    HX_REQUIRE(N && Bt && Hy && Bt->rows && Bt->batch > 0 && Bt->batch % 16 == 0, "hx_sac_policy_grads: bad arguments");
-    if (int rc = sac_check_formats(N, "hx_sac_policy_grads")) return rc;
-    uint16_t* const im = N->w2_bf16_all;  // the SAC bf16 path, or NULL
-    hipStream_t st = (hipStream_t)stream;
-    const int B = Bt->batch;
-    Slot s[S_COUNT];
-    sac_slots(N, B, s);
-    const SacAux X = sac_aux(N, B);
-    const RowSrc src{Bt->rows, nullptr, nullptr, 0, 32};
-    const float* q1 = N->critic; const float* q2 = N->critic + kQs.padded();
-    if (adam_step == 0) {
-        const GaussArgs G{N->policy, kPolicy, s[SS_PC].z2, Bt->eps_cur, B, Bt->eps_cur ? 1 : 2, X.act_c, nullptr, X.aux_c, Bt->seed, 0x80000000u, Bt->call};
-        launch_gauss(G, nullptr, nullptr, nullptr, 0, 0.0f, st);
-    }
-    {
-        FwdArgs F{};
-        F.njobs = 2; F.slope = 0.0f;
-        F.job[0] = FwdJob{q1, kQs, src, 0, 3, Head{}, X.act_c, 0.f, s[SS_Q1P], B, 1, IM_C1};
-        F.job[1] = FwdJob{q2, kQs, src, 0, 3, Head{}, X.act_c, 0.f, s[SS_Q2P], B, 1, IM_C2};
-        F.images = im;
-        launch_fwd(F, st);
-    }
-    // one call (adam_step > 0): min(Q1, Q2) is selected in the critics' backward prologue and the policy's head gradient is formed in the
-    // policy's backward prologue (bwd_l2<4> / <5>) — q_select_kernel and policy_dout_kernel as launches of their own are the staged form
+
+// ---- the pieces of the policy half: the plain sequence (sac_policy_grads_impl) runs them back to back, the imitative one (sac_policy_grads_imit_impl)
+// ---- with its own launches in between.  The imitative branch is fp32 only: C.im is NULL there.
+// staged form: a~, H = policy.sample(s) as a launch of its own (the one call evaluated it in the critic half's Gaussian launch)
+static void launch_sample_cur(const SacCtx& C) { launch_gauss(gauss_cur(C), nullptr, nullptr, nullptr, 0, 0.0f, C.st); }
+// Q1 / Q2 (s, a~) with the UPDATED critics, saved for their backward pass
+static void launch_q_pi(const SacCtx& C) {
+    FwdArgs F{};
+    F.njobs = 2; F.slope = 0.0f;
+    F.job[0] = FwdJob{C.q1, kQs, C.src, 0, 3, Head{}, C.X.act_c, 0.f, C.s[SS_Q1P], C.B, 1, IM_C1};
+    F.job[1] = FwdJob{C.q2, kQs, C.src, 0, 3, Head{}, C.X.act_c, 0.f, C.s[SS_Q2P], C.B, 1, IM_C2};
+    F.images = C.im;
+    launch_fwd(F, C.st);
+}
+// [q_select] -> both critics backward down to dh1 -> [policy_dout] -> policy(s) backward.
+// one call: min(Q1, Q2) is selected in the critics' backward prologue and the policy's head gradient is formed in the policy's backward
+// prologue (bwd_l2<4> / <5>) — q_select_kernel and policy_dout_kernel as launches of their own are the staged form
+static int launch_policy_tail(const SacCtx& C, bool one_call) {
+    const int B = C.B;
+    const Slot* s = C.s;
+    const HxSacNets* N = C.N;
     static const bool fold_env = !(getenv("HX_SAC_FOLD") && getenv("HX_SAC_FOLD")[0] == '0');  // A/B knob
     // The SAC bf16 path keeps the staged form: built in bf16, the folded one call gave policy b2 gradients that differ from the staged sequence's in
     // the last bit (77 of 512 entries at the first call; dW2 and every other gradient equal), so the fold has no bf16 instantiation (launch_bwd refuses).
-    const bool fold = adam_step > 0 && fold_env && !im;
+    const bool fold = one_call && fold_env && !C.im;
+    const unsigned nb = (unsigned)((B + 3) / 4);
     if (!fold) {
-        QSelArgs Q{q1, q2, kQs, s[SS_Q1P], s[SS_Q2P], B, 1.0f / B, N->losses};
-        hipLaunchKernelGGL(q_select_kernel, dim3((unsigned)((B + 3) / 4)), dim3(kThreads), 0, st, Q);
+        QSelArgs Q{C.q1, C.q2, kQs, s[SS_Q1P], s[SS_Q2P], B, 1.0f / B, N->losses};
+        hipLaunchKernelGGL(q_select_kernel, dim3(nb), dim3(kThreads), 0, C.st, Q);
     }
     {   // both critics backward down to dh1
         BwdArgs G{};
@@ -509,58 +511,64 @@ static int sac_policy_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const
         for (int h = 0; h < 2; ++h) {
             BwdJob& J = G.job[h];
             J = BwdJob{};
-            J.net = h ? q2 : q1; J.m = kQs; J.ws = s[SS_Q1P + h]; J.rows = B; J.mode = fold ? BM_SAC_QMIN : BM_GIVEN;
-            if (fold) { J.t1 = Head{h ? q1 : q2, kQs, s[SS_Q1P + (1 - h)]}; J.loss_slot = h; }
+            J.net = h ? C.q2 : C.q1; J.m = kQs; J.ws = s[SS_Q1P + h]; J.rows = B; J.mode = fold ? BM_SAC_QMIN : BM_GIVEN;
+            if (fold) { J.t1 = Head{h ? C.q1 : C.q2, kQs, s[SS_Q1P + (1 - h)]}; J.loss_slot = h; }
             J.img_t = IM_C1_T + h;
         }
-        G.images = im;
-        if (int rc = launch_bwd(fold ? 4 : 3, G, st)) return rc;
+        G.images = C.im;
+        if (int rc = launch_bwd(fold ? 4 : 3, G, C.st)) return rc;
     }
     if (!fold) {
-        PDoutArgs P{q1, q2, kQs, s[SS_Q1P], s[SS_Q2P], s[SS_PC], X.aux_c, N->alpha_state, B, 1.0f / B, N->losses};
-        hipLaunchKernelGGL(policy_dout_kernel, dim3((unsigned)((B + 3) / 4)), dim3(kThreads), 0, st, P);
+        PDoutArgs P{C.q1, C.q2, kQs, s[SS_Q1P], s[SS_Q2P], s[SS_PC], C.X.aux_c, N->alpha_state, B, 1.0f / B, N->losses};
+        hipLaunchKernelGGL(policy_dout_kernel, dim3(nb), dim3(kThreads), 0, C.st, P);
     }
-    {
-        BwdArgs G{};
-        G.njobs = 1; G.slope = 0.0f; G.inv_batch = 1.0f / B; G.losses = N->losses;
-        BwdJob& J = G.job[0];
-        J = BwdJob{};
-        J.net = N->policy; J.m = kPolicy; J.ws = s[SS_PC]; J.rows = B; J.mode = fold ? BM_SAC_POLICY : BM_GIVEN;
-        if (fold) {
-            J.t1 = Head{q1, kQs, s[SS_Q1P]}; J.t2 = Head{q2, kQs, s[SS_Q2P]};
-            J.bonus = X.aux_c; J.bonus_scale = N->alpha_state + 3;
-        }
-        J.img_t = IM_ACTOR_T;
-        G.images = im;
-        if (int rc = launch_bwd(fold ? 5 : 3, G, st)) return rc;
+    BwdArgs G{};
+    G.njobs = 1; G.slope = 0.0f; G.inv_batch = 1.0f / B; G.losses = N->losses;
+    BwdJob& J = G.job[0];
+    J = BwdJob{};
+    J.net = N->policy; J.m = kPolicy; J.ws = s[SS_PC]; J.rows = B; J.mode = fold ? BM_SAC_POLICY : BM_GIVEN;
+    if (fold) {
+        J.t1 = Head{C.q1, kQs, s[SS_Q1P]}; J.t2 = Head{C.q2, kQs, s[SS_Q2P]};
+        J.bonus = C.X.aux_c; J.bonus_scale = N->alpha_state + 3;
     }
-    {
-        WgArgs W{};
-        W.njobs = 1; W.slope = 0.0f; W.w_kind = 0; W.inv_batch = 1.0f / B;
-        W.bf16 = im != nullptr;
-        WgJob& J = W.job[0];
-        J = WgJob{};
-        J.net = N->policy; J.grad = N->grad_policy; J.m = kPolicy; J.ws[0] = s[SS_PC]; J.rows[0] = B; J.nslots = 1; J.wmode[0] = 0;
-        W.predraw = predraw; W.predraw_batch = B;  // hx_sac_learn_back: one more workgroup assembles the next front launch's minibatch (112 workgroups: CUs to spare)
-        if (adam_step > 0) {
-            const double b1 = 0.9, b2 = 0.999;
-            const double bc1 = 1.0 - pow(b1, adam_step), bc2 = 1.0 - pow(b2, adam_step);
-            J.p = N->policy; J.mom = N->m_policy; J.var = N->v_policy;
-            J.w2f = N->policy_w2_f32i;  // the acting kernels' images of the policy's W2 follow its optimizer step
-            if (N->policy_w2_x9) { J.w2b = N->policy_w2_x9; J.w2b_x9 = 1; }
-            if (N->policy_w2_bf16) J.w2b = N->policy_w2_bf16;  // bf16 acting beside an fp32 update
-            if (im) { J.w2b = im + IM_ACTOR * kImgElems; J.w2tb = im + IM_ACTOR_T * kImgElems; }  // the bf16 path: forward (= acting) and transposed images
-            W.ad = WgAdam{};
-            W.ad.b1 = (float)b1; W.ad.b2 = (float)b2; W.ad.eps = 1e-8f;
-            W.ad.step_size = (float)(Hy->lr_actor / bc1);
-            W.ad.bc2_sqrt = (float)sqrt(bc2);
-            W.ad.losses = N->losses;
-            W.ad.alpha_state = N->alpha_state; W.ad.target_entropy = target_entropy; W.ad.alpha_step_size = (float)(Hy->lr_actor / bc1);
-            launch_wg(W, true, st);
-        } else {
-            launch_wg(W, false, st);
-        }
+    J.img_t = IM_ACTOR_T;
+    G.images = C.im;
+    return launch_bwd(fold ? 5 : 3, G, C.st);
+}
+// The policy's weight-gradient launch: W carries the caller's slots, weights and predraw; slot 0 is policy(s).  adam_step > 0 (the one call):
+// policy_optim.step() + the log-alpha step ride in it (the thread that produced a gradient steps it; thread 0 of the launch steps log_alpha)
+static void launch_policy_wg(WgArgs& W, const SacCtx& C, const HxHyper* Hy, int adam_step, float target_entropy) {
+    const HxSacNets* N = C.N;
+    W.njobs = 1; W.slope = 0.0f; W.inv_batch = 1.0f / C.B;
+    WgJob& J = W.job[0];
+    J.net = N->policy; J.grad = N->grad_policy; J.m = kPolicy; J.ws[0] = C.s[SS_PC]; J.rows[0] = C.B;
+    if (adam_step > 0) {
+        J.p = N->policy; J.mom = N->m_policy; J.var = N->v_policy;
+        J.w2f = N->policy_w2_f32i;  // the acting kernels' images of the policy's W2 follow its optimizer step
+        if (N->policy_w2_x9) { J.w2b = N->policy_w2_x9; J.w2b_x9 = 1; }
+        if (N->policy_w2_bf16) J.w2b = N->policy_w2_bf16;  // bf16 acting beside an fp32 update
+        if (C.im) { J.w2b = C.im + IM_ACTOR * kImgElems; J.w2tb = C.im + IM_ACTOR_T * kImgElems; }  // the bf16 path: forward (= acting) and transposed images
+        set_adam_scalars(W.ad, Hy->lr_actor, adam_step);
+        W.ad.losses = N->losses;
+        W.ad.alpha_state = N->alpha_state; W.ad.target_entropy = target_entropy; W.ad.alpha_step_size = W.ad.step_size;  // (alpha_optim: the policy's learning rate)
     }
+    launch_wg(W, adam_step > 0, C.st);
+}
+
+// adam_step > 0 (hx_sac_learn): policy.sample(s) was evaluated in the critic half's launch, and the optimizer steps ride in the weight-gradient launch
+static int sac_policy_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, void* stream, int adam_step, float target_entropy,
+                                 const SampleDev* predraw = nullptr) {
+    HX_REQUIRE(N && Bt && Hy && Bt->rows && Bt->batch > 0 && Bt->batch % 16 == 0, "hx_sac_policy_grads: bad arguments");
+    if (int rc = sac_check_formats(N, "hx_sac_policy_grads")) return rc;
+    const SacCtx C(N, Bt, stream);
+    if (adam_step == 0) launch_sample_cur(C);
+    launch_q_pi(C);
+    if (int rc = launch_policy_tail(C, adam_step > 0)) return rc;
+    WgArgs W{};
+    W.bf16 = C.im != nullptr;
+    W.job[0].nslots = 1;
+    W.predraw = predraw; W.predraw_batch = C.B;  // hx_sac_learn_back: one more workgroup assembles the next front launch's minibatch (112 workgroups: CUs to spare)
+    launch_policy_wg(W, C, Hy, adam_step, target_entropy);
     HX_CHECK_LAUNCH("hx_sac_policy_grads");
     return 0;
 }
@@ -580,7 +588,7 @@ int hx_sac_learn(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, co
 
 /* ------------------------------------------------------------------------------------------------------------------
  * SAC, imitative branch (SAC/agent.py:315-318, 353-359, 385-403; imitative=True).  The critic half is the code above, unchanged.  The policy half
- * is sac_policy_grads_impl's sequence with the BC-gated loss around it (new launches marked +):
+ * is sac_policy_grads_impl's sequence — the same helpers — with the BC-gated loss around it (new launches marked +):
  *     [gauss        a~, H = policy.sample(s)                                     staged form only]
  *   + fwd_l2        bc_actor(s): LayerNorm actor, leaky slope = imit->bc_slope (a launch of its own: the activation is per launch); clears count
  *   + bc_head       a_bc = tanh(head(bc_actor))
@@ -607,48 +615,36 @@ static int sac_policy_grads_imit_impl(const HxSacNets* N, const HxSacBatch* Bt, 
     HX_REQUIRE(I->bc_slope >= 0.0f && I->bc_slope < 1.0f, "%s: imit->bc_slope is the bc_actor's leaky slope, in [0, 1)", who);
     HX_REQUIRE(!N->w2_bf16_all, "%s: the imitative branch is fp32 only (nets->w2_bf16_all must be NULL)", who);
     if (int rc = sac_check_formats(N, who)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const int B = Bt->batch;
-    Slot s[S_COUNT], si[IS_COUNT];
-    sac_slots(N, B, s);
+    const SacCtx C(N, Bt, stream);
+    hipStream_t st = C.st;
+    const int B = C.B;
+    Slot si[IS_COUNT];
     for (int i = 0; i < IS_COUNT; ++i) si[i] = carve_slot(I->ws + (size_t)i * kSlotFloats * B, B);
     float* const a_bc = I->ws + (size_t)IS_COUNT * kSlotFloats * B;
     float* const row_sq = a_bc + 4 * (size_t)B;
-    const SacAux X = sac_aux(N, B);
-    const RowSrc src{Bt->rows, nullptr, nullptr, 0, 32};
     const RowSrc esrc{I->expert_rows, nullptr, nullptr, 0, 32};
-    const float* q1 = N->critic; const float* q2 = N->critic + kQs.padded();
     const unsigned nb = (unsigned)((B + 3) / 4);
-    if (adam_step == 0) {
-        const GaussArgs G{N->policy, kPolicy, s[SS_PC].z2, Bt->eps_cur, B, Bt->eps_cur ? 1 : 2, X.act_c, nullptr, X.aux_c, Bt->seed, 0x80000000u, Bt->call};
-        launch_gauss(G, nullptr, nullptr, nullptr, 0, 0.0f, st);
-    }
+    if (adam_step == 0) launch_sample_cur(C);
     {   // bc_actor(s), no gradient
         FwdArgs F{};
         F.njobs = 1; F.slope = I->bc_slope;
         F.zero_i = I->count;
-        F.job[0] = FwdJob{I->bc_actor, kActor, src, 0, 0, Head{}, nullptr, 0.f, si[IS_BCA], B, 0, IM_BC};
+        F.job[0] = FwdJob{I->bc_actor, kActor, C.src, 0, 0, Head{}, nullptr, 0.f, si[IS_BCA], B, 0, IM_BC};
         launch_fwd(F, st);
         BcHeadArgs H{I->bc_actor, kActor, si[IS_BCA].z2, I->bc_slope, B, a_bc};
         hipLaunchKernelGGL(bc_head_kernel, dim3(nb), dim3(kThreads), 0, st, H);
     }
-    {   // Q1 / Q2 (s, a~): the plain call's launch
-        FwdArgs F{};
-        F.njobs = 2; F.slope = 0.0f;
-        F.job[0] = FwdJob{q1, kQs, src, 0, 3, Head{}, X.act_c, 0.f, s[SS_Q1P], B, 1, IM_C1};
-        F.job[1] = FwdJob{q2, kQs, src, 0, 3, Head{}, X.act_c, 0.f, s[SS_Q2P], B, 1, IM_C2};
-        launch_fwd(F, st);
-    }
+    launch_q_pi(C);
     {   // Q1 / Q2 (s, a_bc): values only; policy(s_e), saved for its backward pass
         FwdArgs F{};
         F.njobs = 3; F.slope = 0.0f;
-        F.job[0] = FwdJob{q1, kQs, src, 0, 3, Head{}, a_bc, 0.f, si[IS_Q1B], B, 0, IM_C1};
-        F.job[1] = FwdJob{q2, kQs, src, 0, 3, Head{}, a_bc, 0.f, si[IS_Q2B], B, 0, IM_C2};
+        F.job[0] = FwdJob{C.q1, kQs, C.src, 0, 3, Head{}, a_bc, 0.f, si[IS_Q1B], B, 0, IM_C1};
+        F.job[1] = FwdJob{C.q2, kQs, C.src, 0, 3, Head{}, a_bc, 0.f, si[IS_Q2B], B, 0, IM_C2};
         F.job[2] = FwdJob{N->policy, kPolicy, esrc, 0, 0, Head{}, nullptr, 0.f, si[IS_PE], B, 1, IM_ACTOR};
         launch_fwd(F, st);
     }
     {   // the gate's count, the BC head gradient
-        IsacRowsArgs R{q1, q2, kQs, s[SS_Q1P].z2, s[SS_Q2P].z2, si[IS_Q1B].z2, si[IS_Q2B].z2, N->policy, kPolicy, si[IS_PE], I->expert_rows, B,
+        IsacRowsArgs R{C.q1, C.q2, kQs, C.s[SS_Q1P].z2, C.s[SS_Q2P].z2, si[IS_Q1B].z2, si[IS_Q2B].z2, N->policy, kPolicy, si[IS_PE], I->expert_rows, B,
                        (2.0f * 10000.0f * 0.25f) / B, I->count, row_sq};
         hipLaunchKernelGGL(isac_rows_kernel, dim3(nb), dim3(kThreads), 0, st, R);
     }
@@ -660,71 +656,17 @@ static int sac_policy_grads_imit_impl(const HxSacNets* N, const HxSacBatch* Bt, 
         J.net = N->policy; J.m = kPolicy; J.ws = si[IS_PE]; J.rows = B; J.mode = BM_GIVEN; J.img_t = IM_ACTOR_T;
         if (int rc = launch_bwd(3, G, st)) return rc;
     }
-    // from here to the weight gradients: sac_policy_grads_impl's launches on the same values (the one call folds q_select / policy_dout)
-    static const bool fold_env = !(getenv("HX_SAC_FOLD") && getenv("HX_SAC_FOLD")[0] == '0');
-    const bool fold = adam_step > 0 && fold_env;
-    if (!fold) {
-        QSelArgs Q{q1, q2, kQs, s[SS_Q1P], s[SS_Q2P], B, 1.0f / B, N->losses};
-        hipLaunchKernelGGL(q_select_kernel, dim3(nb), dim3(kThreads), 0, st, Q);
-    }
-    {
-        BwdArgs G{};
-        G.njobs = 2; G.slope = 0.0f; G.inv_batch = 1.0f / B; G.losses = N->losses;
-        for (int h = 0; h < 2; ++h) {
-            BwdJob& J = G.job[h];
-            J = BwdJob{};
-            J.net = h ? q2 : q1; J.m = kQs; J.ws = s[SS_Q1P + h]; J.rows = B; J.mode = fold ? BM_SAC_QMIN : BM_GIVEN;
-            if (fold) { J.t1 = Head{h ? q1 : q2, kQs, s[SS_Q1P + (1 - h)]}; J.loss_slot = h; }
-            J.img_t = IM_C1_T + h;
-        }
-        if (int rc = launch_bwd(fold ? 4 : 3, G, st)) return rc;
-    }
-    if (!fold) {
-        PDoutArgs P{q1, q2, kQs, s[SS_Q1P], s[SS_Q2P], s[SS_PC], X.aux_c, N->alpha_state, B, 1.0f / B, N->losses};
-        hipLaunchKernelGGL(policy_dout_kernel, dim3(nb), dim3(kThreads), 0, st, P);
-    }
-    {
-        BwdArgs G{};
-        G.njobs = 1; G.slope = 0.0f; G.inv_batch = 1.0f / B; G.losses = N->losses;
-        BwdJob& J = G.job[0];
-        J = BwdJob{};
-        J.net = N->policy; J.m = kPolicy; J.ws = s[SS_PC]; J.rows = B; J.mode = fold ? BM_SAC_POLICY : BM_GIVEN;
-        if (fold) {
-            J.t1 = Head{q1, kQs, s[SS_Q1P]}; J.t2 = Head{q2, kQs, s[SS_Q2P]};
-            J.bonus = X.aux_c; J.bonus_scale = N->alpha_state + 3;
-        }
-        J.img_t = IM_ACTOR_T;
-        if (int rc = launch_bwd(fold ? 5 : 3, G, st)) return rc;
-    }
+    if (int rc = launch_policy_tail(C, adam_step > 0)) return rc;
     // both parts of the policy loss are complete: combine them (a launch of its own rather than thread 0 of the weight-gradient launch, whose
     // SAC step already carries the log-alpha state in the fields HIRL's finish_actor uses — and whose register figures stay what they were)
     hipLaunchKernelGGL(isac_finish_kernel, dim3(1), dim3(64), 0, st, row_sq, I->count, B, 1.0f / B, N->losses);
-    {
-        WgArgs W{};
-        W.njobs = 1; W.slope = 0.0f; W.w_kind = 1; W.warm = 0.0f; W.inv_batch = 1.0f / B; W.soft_count = I->count;
-        WgJob& J = W.job[0];
-        J = WgJob{};
-        J.net = N->policy; J.grad = N->grad_policy; J.m = kPolicy; J.nslots = 2;
-        J.ws[0] = s[SS_PC]; J.rows[0] = B; J.wmode[0] = 1;     // policy(s):   (1 - w)
-        J.ws[1] = si[IS_PE]; J.rows[1] = B; J.wmode[1] = 2;    // policy(s_e): w
-        if (adam_step > 0) {
-            const double b1 = 0.9, b2 = 0.999;
-            const double bc1 = 1.0 - pow(b1, adam_step), bc2 = 1.0 - pow(b2, adam_step);
-            J.p = N->policy; J.mom = N->m_policy; J.var = N->v_policy;
-            J.w2f = N->policy_w2_f32i;
-            if (N->policy_w2_x9) { J.w2b = N->policy_w2_x9; J.w2b_x9 = 1; }
-            if (N->policy_w2_bf16) J.w2b = N->policy_w2_bf16;
-            W.ad = WgAdam{};
-            W.ad.b1 = (float)b1; W.ad.b2 = (float)b2; W.ad.eps = 1e-8f;
-            W.ad.step_size = (float)(Hy->lr_actor / bc1);
-            W.ad.bc2_sqrt = (float)sqrt(bc2);
-            W.ad.losses = N->losses;
-            W.ad.alpha_state = N->alpha_state; W.ad.target_entropy = target_entropy; W.ad.alpha_step_size = (float)(Hy->lr_actor / bc1);
-            launch_wg(W, true, st);
-        } else {
-            launch_wg(W, false, st);
-        }
-    }
+    WgArgs W{};
+    W.w_kind = 1; W.warm = 0.0f; W.soft_count = I->count;
+    WgJob& J = W.job[0];
+    J.nslots = 2;
+    J.wmode[0] = 1;                                        // policy(s):   (1 - w)
+    J.ws[1] = si[IS_PE]; J.rows[1] = B; J.wmode[1] = 2;    // policy(s_e): w
+    launch_policy_wg(W, C, Hy, adam_step, target_entropy);
     HX_CHECK_LAUNCH(who);
     return 0;
 }
@@ -764,12 +706,11 @@ int hx_sac_front(const float* policy, const uint16_t* w2_x9, const float* w2_f32
     const uint16_t* w2b = N->w2_bf16_all ? sac_act_image(N) : nullptr;
     HX_REQUIRE(policy && (w2b ? (!w2_x9 && !w2_f32i) : (w2_x9 || w2_f32i)),
                "hx_sac_front: with nets->w2_bf16_all the acting image is its first one (w2_x9, w2_f32i NULL); else w2_x9 or w2_f32i");
-    if (int rc = hxact::check_step_args(state, n, stride, obs_io, actions, reward, done, success, *opts, "hx_sac_front")) return rc;
-    hxact::ActFusedArgs H{policy, kPolicy, obs_io, (int)n, 0.0f, actions, mode == 1 ? eps : nullptr, 1, 0.0f, mode, seed, row0, call,
-                          state, stride, reward, done, success, *opts, opts->cap > 0 ? 1.0 / (double)opts->cap : 0.0, w2b ? w2b : w2_x9,
-                          (w2b || w2_x9) ? nullptr : w2_f32i, w2_x9 ? 1 : 0};
+    const hxact::ActEnv E{state, stride, reward, done, success, *opts};
+    if (int rc = hxact::check_step_args(obs_io, n, actions, E, "hx_sac_front")) return rc;
+    const hxact::ActFusedArgs H = hxact::act_args_gauss(policy, obs_io, n, actions, mode, eps, seed, row0, call, hxact::ActImages{w2_f32i, w2_x9, w2b}, &E);
     FwdArgs F;
-    sac_launch_1(N, Bt, F);
+    sac_launch_1(SacCtx(N, Bt, stream), F);
     return launch_front_sac(H, F, (hipStream_t)stream);
 }
 /* Rebuild every bf16 image of the SAC bf16 path from the fp32 networks (after parameters were loaded or written directly), and the bf16 acting

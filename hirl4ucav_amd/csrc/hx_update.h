@@ -34,6 +34,7 @@
 // bytes their prologue asks for (a CU gets ~19 B/clk of lines another XCD has just written), and the workgroup count (a launch is as long
 // as its slowest workgroup plus the drain of its stores).
 #pragma once
+#include <cmath>
 #include <cstdlib>
 #include <type_traits>
 
@@ -698,6 +699,16 @@ struct AdamArgs {
     const float* countf;
     const uint32_t* guard;  // nullptr, or a word that must be 0 for the step to happen (HxNets.xchg_status: a failed exchange)
 };
+// torch.optim.Adam's per-step scalars (defaults: betas (0.9, 0.999), eps 1e-8; step is 1-based) into the fields of that name of a WgAdam (the fused
+// wgrad + Adam launch) or an AdamArgs (adam_kernel).  Formed in double and rounded once: every path that steps a network rounds alike.
+template <typename A>
+inline void set_adam_scalars(A& a, double lr, int step) {
+    const double b1 = 0.9, b2 = 0.999;
+    const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - pow(b2, step);
+    a.b1 = (float)b1; a.b2 = (float)b2; a.eps = 1e-8f;
+    a.step_size = (float)(lr / bc1);
+    a.bc2_sqrt = (float)sqrt(bc2);
+}
 
 constexpr size_t kSlotFloats = XP + H1 + 2 + H1 + H2 + 2 + OW + H2 + H1 + OW + 2 * kColWgB;  // per row
 
@@ -751,10 +762,6 @@ inline const uint16_t* sac_act_image(const HxSacNets* N) { return N->w2_bf16_all
 void launch_fwd(const FwdArgs& F, hipStream_t st);                          // hx_fwdbwd.hip
 void set_fwd_nt(int nt, int skip, int count);                                                  // hx_fwdbwd.hip (hx_debug_set_fwd_nt)
 int launch_bwd(int grp, const BwdArgs& G, hipStream_t st);                  // hx_fwdbwd.hip: grp = bwd_l2_kernel's GRP (0..5); != 0: refused
-// hx_front.hip: the act + env + insert workgroups of hx_actor_act_step_f32i (32 rows each) and the workgroups of launches A and B as ONE launch
-int launch_front(const float* actor, const float* w2f, const uint16_t* w2x, const uint16_t* w2b, float* state, int64_t n, int64_t stride, float* obs_io, float* actions, int32_t noise_mode,
-                 const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, float* reward, uint8_t* done, int8_t* success,
-                 const HxStepOpts& o, const FwdArgs& FA, const FwdArgs& FB, const BwdArgs* GC, const HxFront& front, hipStream_t st);
 void launch_wg(const WgArgs& W, bool adam, hipStream_t st);                 // hx_wgrad.hip: adam = the optimizer step rides in the launch
 void launch_adam(const AdamArgs& A, hipStream_t st);                        // hx_wgrad.hip
 void launch_polyak(float* target, const float* source, int n, float tau, float* target2, const float* source2, int n2, hipStream_t st,

@@ -723,17 +723,13 @@ static int adam_impl(const HxNets* N, const HxHyper* Hy, int32_t which, int32_t 
     const bool polyak = (which & 16) != 0;  // + 16: soft_update of this network's target in the same launch
     which &= 15;
     HX_REQUIRE(N && Hy && step >= 1 && which >= 0 && which <= 2, "hx_adam: bad arguments");
-    const double b1 = 0.9, b2 = 0.999;
-    const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - pow(b2, step);
     AdamArgs A{};
     A.n = which == 0 ? 2 * kQ.padded() : kActor.size();
     A.p = which == 0 ? N->critic : N->actor;
     A.g = which == 0 ? N->grad_critic : N->grad_actor;
     A.m = which == 0 ? N->m_critic : N->m_actor;
     A.v = which == 0 ? N->v_critic : N->v_actor;
-    A.b1 = (float)b1; A.b2 = (float)b2; A.eps = 1e-8f;
-    A.step_size = (float)((which == 0 ? Hy->lr_critic : Hy->lr_actor) / bc1);
-    A.bc2_sqrt = (float)sqrt(bc2);
+    set_adam_scalars(A, which == 0 ? Hy->lr_critic : Hy->lr_actor, step);
     A.gscale = grad_scale;
     A.finish_actor = which == 1;  // which == 2: the actor's Adam step alone (BC pre-training)
     A.w_kind = w_kind; A.w_given = w_given; A.warm = warm; A.inv_batch = 1.0f / (batch > 0 ? batch : 1);
@@ -822,17 +818,13 @@ int hx_polyak(const HxNets* N, const HxHyper* Hy, void* stream) {
  * (SAC/agent.py:318-325).  step: 1-based (all four optimisers step once per learn()).  grad_scale: 1/world after a SUM. */
 int hx_sac_adam(const HxSacNets* N, const HxHyper* Hy, int32_t which, int32_t step, float grad_scale, float target_entropy, void* stream) {
     HX_REQUIRE(N && Hy && step >= 1 && (which == 0 || which == 1), "hx_sac_adam: bad arguments");
-    const double b1 = 0.9, b2 = 0.999;
-    const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - pow(b2, step);
     AdamArgs A{};
     A.n = which == 0 ? 2 * kQs.padded() : kPolicy.padded();
     A.p = which == 0 ? N->critic : N->policy;
     A.g = which == 0 ? N->grad_critic : N->grad_policy;
     A.m = which == 0 ? N->m_critic : N->m_policy;
     A.v = which == 0 ? N->v_critic : N->v_policy;
-    A.b1 = (float)b1; A.b2 = (float)b2; A.eps = 1e-8f;
-    A.step_size = (float)((which == 0 ? Hy->lr_critic : Hy->lr_actor) / bc1);
-    A.bc2_sqrt = (float)sqrt(bc2);
+    set_adam_scalars(A, which == 0 ? Hy->lr_critic : Hy->lr_actor, step);
     A.gscale = grad_scale;
     A.losses = N->losses;
     if (which == 1 && N->policy_w2_f32i) {  // the acting kernel's image of the policy's W2 follows its optimizer step
@@ -867,7 +859,7 @@ int hx_sac_adam(const HxSacNets* N, const HxHyper* Hy, int32_t which, int32_t st
     if (which == 1) {
         A.alpha_state = N->alpha_state;
         A.target_entropy = target_entropy;
-        A.alpha_step_size = (float)(Hy->lr_actor / bc1);
+        A.alpha_step_size = A.step_size;  // alpha_optim runs at the policy's learning rate
     }
     launch_adam(A, (hipStream_t)stream);
     HX_CHECK_LAUNCH("hx_sac_adam");

@@ -113,15 +113,17 @@ def test_isac_learn_matches_restatement_and_reference(SE, golden_dir):
 
 
 def test_isac_one_call_is_bit_identical_to_staged(SE):
-    """hx_sac_learn_imitative against hx_sac_critic_step + hx_sac_policy_grads_imitative + hx_sac_adam(1), and expert rows drawn inside the call
+    """hx_sac_learn_imitative against hx_sac_critic_step + hx_sac_policy_grads_imitative + hx_sac_adam(1), against the same with the critic half as
+    hx_sac_critic_grads + hx_sac_adam(0) (separate_critic_adam), and expert rows drawn inside the call
     (sample_expert(defer=True)) against the same rows injected by index: after 8 calls networks, moments, alpha state and W2 image equal bit
     for bit; so are losses[3..7].  losses[0..2] are sums of float atomics over workgroups in the launches every SAC call shares (logged only,
     order-dependent in the last bit even between two identical runs, as tests/test_sac_gpu.py notes): compared at rtol 1e-6."""
     params = sac_params()
     rep, exp = make_rings()
-    a, b, c = (SE.SacEngine(batch=128) for _ in range(3))
+    a, b, c, d = (SE.SacEngine(batch=128) for _ in range(4))
     b.staged_policy = True
-    for e in (a, b, c):
+    d.separate_critic_adam = True
+    for e in (a, b, c, d):
         e.load_params(params["policy"], params["q1"], params["q2"])
         e.set_imitative(bc_actor_params(), slope=0.01)
     weights = []
@@ -129,18 +131,18 @@ def test_isac_one_call_is_bit_identical_to_staged(SE):
         c.sample(rep, None, seed=11)
         c.sample_expert(exp, seed=11, defer=True)
         c.learn()
-        for e in (a, b):
+        for e in (a, b, d):
             e.sample(rep, None, seed=11)
             e.assemble_expert(exp.ring, c._expert_idx)
             e.learn()
         assert torch.equal(a.expert_rows, c.expert_rows) and torch.equal(a.rows, c.rows), k
         assert len(set(c._expert_idx.cpu().tolist())) == 128 and int(c._expert_idx.max()) < 400  # without replacement, inside the live rows
         weights.append(a.imitative_losses_host()[1])
-        for other in (b, c):
+        for other in (b, c, d):
             assert torch.equal(a.losses[3:8], other.losses[3:8]), (k, a.losses.tolist(), other.losses.tolist())
             np.testing.assert_allclose(a.losses[:3].cpu().numpy(), other.losses[:3].cpu().numpy(), rtol=1e-6)
             assert torch.equal(a.bc_count, other.bc_count)
-    for other in (b, c):
+    for other in (b, c, d):
         for name in STATE:
             assert torch.equal(getattr(a, name), getattr(other, name)), name
     assert any(0 < w < 1 for w in weights), weights  # the mixed case ran

@@ -1,10 +1,10 @@
-"""SacEngine.learn() at B = 128 by device events: plain SAC built from the PARENT commit, plain SAC from this tree, and imitative SAC
-(set_imitative: the BC-gated policy loss) from this tree — alternating, each side a process of its own (two builds of the library cannot
+"""SacEngine.learn() at B = 128 by device events: plain SAC and imitative SAC (set_imitative: the BC-gated policy loss), each built from the PARENT
+commit and from this tree — alternating, each side a process of its own (two builds of the library cannot
 share one), on one box in one call.  Each process: the minibatch (and the expert tile) assembled once, WARMUP calls, then REPS repetitions
 of CALLS back-to-back learn() calls between two events; it reports its median and its own spread.  The driver alternates the sides ROUNDS
 times and reports, per side, the median over the rounds and the run-to-run spread (min .. max of the rounds' medians).
   python tools/ubench/isac_time.py --parent-tree DIR      (DIR: a checkout of the parent commit with its library built)
-  gate 1: imitative learn() <= 2.0 x the parent's plain learn();  gate 2: this tree's plain learn() within the parent's spread.
+  gate 1: imitative learn() <= 2.0 x the parent's plain learn();  gate 2: this tree's plain (and imitative) learn() within the parent's spread.
 profiles/isac_learn_ab.txt is the default run.  Launch counts come from a tracer run of its own, one side at a time:
   rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o <side> -- python tools/ubench/isac_time.py --worker <plain|isac> --trace"""
 import argparse
@@ -73,7 +73,8 @@ def main():
         return worker(a.worker, a.tree, a.trace)
     import numpy as np
 
-    sides = ([("parent_plain", "plain", a.parent_tree)] if a.parent_tree else []) + [("plain", "plain", a.tree), ("isac", "isac", a.tree)]
+    sides = ([("parent_plain", "plain", a.parent_tree), ("parent_isac", "isac", a.parent_tree)] if a.parent_tree else []) + \
+            [("plain", "plain", a.tree), ("isac", "isac", a.tree)]
     got = {name: [] for name, _, _ in sides}
     for _ in range(ROUNDS):
         for name, side, tree in sides:  # a fresh child process per side and round: nothing of one build lives in the other's process
@@ -91,9 +92,10 @@ def main():
     if "parent_plain" in s:
         res["gate1_isac_over_parent_plain"] = s["isac"]["median_us"] / s["parent_plain"]["median_us"]
         res["gate1_ok"] = res["gate1_isac_over_parent_plain"] <= 2.0
-        hi = s["parent_plain"]["spread_us"][1]
-        res["gate2_plain_minus_parent_us"] = s["plain"]["median_us"] - s["parent_plain"]["median_us"]
-        res["gate2_ok"] = s["plain"]["median_us"] <= hi  # no slower than the parent's own slowest round (lo .. hi: its run-to-run spread)
+    for side in ("plain", "isac"):  # gate 2, per side the parent has: no slower than the parent's own slowest round (lo .. hi: its run-to-run spread)
+        if "parent_" + side in s:
+            res[f"gate2_{side}_minus_parent_us"] = s[side]["median_us"] - s["parent_" + side]["median_us"]
+            res[f"gate2_{side}_ok"] = s[side]["median_us"] <= s["parent_" + side]["spread_us"][1]
     print(json.dumps(res), flush=True)
 
 
