@@ -433,11 +433,12 @@ class SacEngine:
         """One iteration of the vector loop — act_step(env) then sample(env.replay, ..., defer=True) then learn() — in FRONT form (include/hirl4ucav.h
         hx_sac_front): the env step and the first forward launch of learn() are ONE launch, the minibatch pre-drawn by the previous call.  As in
         HirlEngine.step_learn the minibatch is drawn from the ring as it stood BEFORE this env step, without the env.n slots the step may overwrite.
-        More than 8,192 envs (the persistent acting kernel), one GPU, the one-call learn(), Philox draws.  Acting and update in one format: fp32, or
-        bf16 for both (a bf16 policy beside the fp32 update runs act_step, then the sampled learn()).  -> (actions, obs, reward, done, success)."""
+        Any number of envs with a replay ring (up to 8,192 the per-tile acting workgroups, beyond the persistent acting kernel), one GPU, the one-call
+        learn(), batch <= 256, Philox draws.  Acting and update in one format: fp32, or bf16 for both (a bf16 policy beside the fp32 update runs act_step,
+        then the sampled learn(); so does the imitative branch).  -> (actions, obs, reward, done, success)."""
         replay, n, B = env.replay, env.n, self.batch
-        if self.world > 1 or replay is None or n <= 8192 or self.separate_critic_adam or self.staged_policy:
-            raise _lib.HxError("SacEngine.step_learn: one GPU, the one-call learn(), more than 8,192 envs with a replay ring attached")
+        if self.world > 1 or replay is None or self.separate_critic_adam or self.staged_policy:
+            raise _lib.HxError("SacEngine.step_learn: one GPU, the one-call learn(), envs with a replay ring attached")
         if self._pending is not None:
             raise _lib.HxError("step_learn draws its own minibatch: a sample(defer=True) is still pending")
         if self.imitative:  # no front form: the reference's order; `expert` is the imitative branch's expert memory, the minibatch is not expert-mixed

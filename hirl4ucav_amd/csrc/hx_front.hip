@@ -158,12 +158,34 @@ __global__ __launch_bounds__(kWide) void actps_sac_front_kernel(ActFusedArgs H, 
     fwd_l2_body<kNT, true, false, BF16, 0>(FA, NoSample{}, bx, (int)C.order[k], u.f, FrontSync{});
 }
 
+// SAC up to 8,192 envs: the acting role is the PER-TILE workgroup of hx_sac_act_step_f32i / _bf16 (act_fused_body with the Gaussian head and the env tail: fp32 MFMA
+// from the fp32 image, or bf16 MFMA from the bf16 image with the bf16 first launch) — one round of 16-row (NRT 1) or 32-row (NRT 2) workgroups, the first forward
+// launch of learn() behind them on the CUs they leave free (or, where they fill the chip, as they leave).  No in-launch wait: the forward jobs depend on nothing.
+constexpr int kSacFrontNrt2F32 = 4097, kSacFrontNrt2Bf16 = 2049;  // defaults of HX_SAC_FRONT_F32_NRT2_ROWS / HX_SAC_FRONT_BF16_NRT2_ROWS (launch_front_sac)
+template <int NRT, bool BF16>
+__global__ __launch_bounds__(kWide) void act_sac_front_kernel(ActFusedArgs H, FwdArgsC FA, FrontCtl C) {
+    typedef ActLds<NRT, true, BF16, !BF16, false> LdsAct;
+    typedef FwdLds<kNT, false, BF16> LdsF;
+    __shared__ union {
+        LdsAct act;
+        LdsF f;
+    } u;
+    int b = (int)blockIdx.x;
+    if (b < C.n_act) {
+        act_fused_body<NRT, true, true, BF16, true, !BF16>(H, b, u.act);
+        return;
+    }
+    b -= C.n_act;
+    const int k = b / C.per, bx = b - k * C.per;
+    fwd_l2_body<kNT, true, false, BF16, 0>(FA, NoSample{}, bx, (int)C.order[k], u.f, FrontSync{});
+}
+
 }  // namespace
 
 namespace hxu {
 
 int launch_front_sac(const ActFusedArgs& H, const FwdArgs& FA, hipStream_t st) {
-    HX_REQUIRE(H.state && H.o.ring && H.rows > kFuseEnvMax && (H.w2f || H.w2b), "hx_sac_front: more than 8,192 envs with a replay ring, the policy's W2 from an image");
+    HX_REQUIRE(H.state && H.o.ring && H.rows >= 1 && (H.w2f || H.w2b), "hx_sac_front: envs with a replay ring, the policy's W2 from an image");
     const bool x9 = H.w2b && H.x9, b16 = H.w2b && !H.x9;
     HX_REQUIRE(b16 == (FA.images != nullptr), "hx_sac_front: the bf16 acting image goes with the bf16 update path (HxSacNets.w2_bf16_all), and only with it");
     HX_REQUIRE(!FA.sample && FA.njobs >= 3 && FA.njobs <= 8 && FA.slope == 0.0f, "hx_sac_front: the first forward launch of learn() on finished minibatch tiles");
@@ -175,6 +197,21 @@ int launch_front_sac(const ActFusedArgs& H, const FwdArgs& FA, hipStream_t st) {
     FrontCtl C{};
     C.per = tiles * (H2 / kNT);
     for (int j = 0; j < FA.njobs; ++j) C.order[j] = (unsigned char)j;
+    if (H.rows <= kFuseEnvMax) {  // one round of per-tile acting workgroups (hx_sac_front has dropped the exact-split image: fp32 acts from the fp32 image here)
+        HX_REQUIRE(!x9, "hx_sac_front: up to 8,192 envs the fp32 policy acts from the fp32 image (w2_f32i)");
+        // 32-row acting workgroups from how many envs on (tuning knob, read once).  16-row workgroups: rows / 16 of them; 32-row ones halve that and leave
+        // CUs to the forward workgroups sooner, but each is longer (DESIGN §4 K5 has the measured rule)
+        static const int nrt2_f32 = getenv("HX_SAC_FRONT_F32_NRT2_ROWS") ? atoi(getenv("HX_SAC_FRONT_F32_NRT2_ROWS")) : kSacFrontNrt2F32;
+        static const int nrt2_bf16 = getenv("HX_SAC_FRONT_BF16_NRT2_ROWS") ? atoi(getenv("HX_SAC_FRONT_BF16_NRT2_ROWS")) : kSacFrontNrt2Bf16;
+        const bool wide = H.rows >= (b16 ? nrt2_bf16 : nrt2_f32);
+        const int tile_rows = wide ? 2 * RT : RT;
+        C.n_act = (H.rows + tile_rows - 1) / tile_rows;
+        const dim3 tgrid((unsigned)(C.n_act + C.per * FA.njobs));
+        if (b16) { if (wide) launch_stamped(act_sac_front_kernel<2, true>, tgrid, st, H.o, H, CA, C); else launch_stamped(act_sac_front_kernel<1, true>, tgrid, st, H.o, H, CA, C); }
+        else { if (wide) launch_stamped(act_sac_front_kernel<2, false>, tgrid, st, H.o, H, CA, C); else launch_stamped(act_sac_front_kernel<1, false>, tgrid, st, H.o, H, CA, C); }
+        HX_CHECK_LAUNCH("hx_sac_front");
+        return 0;
+    }
     const int npass = (H.rows + 4 * RT - 1) / (4 * RT), per_wg = (npass + 255) / 256;
     C.n_act = (npass + per_wg - 1) / per_wg;
     const dim3 grid((unsigned)(C.n_act + C.per * FA.njobs));

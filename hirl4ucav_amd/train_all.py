@@ -373,8 +373,9 @@ def main(config):
     log_rate = 300  # train_all.py:208
     ret = torch.zeros(n, device=device) if config.log_rewards else None
     last_stats = env.stats_dict()
-    # --loop front (default where it applies: HIRL / TD3 in fp32 or bf16 actor + critic, batch <= 256, one update per step): the env
-    # step and the first two launches of learn() as ONE launch (HirlEngine.step_learn) — the minibatch is then drawn from the ring as it stood before
+    # --loop front (default where it applies: HIRL / TD3 in fp32 or bf16 actor + critic, SAC / E-SAC on one GPU at every number of envs — up to 8,192 the
+    # per-tile acting role measured faster than the reference's order in every size class; batch <= 256, one update per step): the env
+    # step and the first two launches of learn() (SAC: its first forward launch) as ONE launch (HirlEngine / SacEngine.step_learn) — the minibatch is then drawn from the ring as it stood before
     # this step's insert.  --loop reference: the reference's order on every step (act -> env step -> insert -> draw -> learn)
     # ... and only with ONE process per GPU: the in-launch waits of the front launch are argued for a chip of its own (include/hirl4ucav.h hx_hirl_front —
     # the waiting workgroups of processes that share a GPU add up; eight front-loop ranks on one GPU tripped in round 5).  HX_FRONT_SHARED_GPU=1 takes it
@@ -382,7 +383,7 @@ def main(config):
     shared_gpu = world > torch.cuda.device_count() and not os.environ.get("HX_FRONT_SHARED_GPU")
     front = (config.loop == "front" and not sac and not config.separate_launches and config.updates_per_step == 1 and batch <= 256
              and getattr(config, "dtype", "f32") in ("f32", "f32x9", "bf16") and not shared_gpu)
-    front_sac = (config.loop == "front" and sac and world == 1 and not config.separate_launches and config.updates_per_step == 1 and batch <= 256 and n > 8192)
+    front_sac = (config.loop == "front" and sac and world == 1 and not config.separate_launches and config.updates_per_step == 1 and batch <= 256)
     if rank == 0:
         which = "front launch (env step + first launches of learn() in one launch; draw before the insert)" if (front or front_sac) else "reference order"
         print(f"vector loop: {which}" + (f" ({world} ranks share a GPU: the front launch is for one process per GPU)" if (shared_gpu and config.loop == "front") else ""),
@@ -615,8 +616,8 @@ def parser():
     p.add_argument("--checkpoint_rate", type=int, default=25, help="episodes between validations (train_all.py:206)")
     p.add_argument("--bc_validate_from", type=int, default=1000, help="BC: first episode with validation (train_all.py:259)")
     p.add_argument("--loop", type=str, default="front", choices=["front", "reference"],
-                   help="front (default where it applies AND every rank has a GPU of its own: HIRL / TD3 in fp32 or bf16 actor + critic, SAC / E-SAC beyond 8,192 envs on "
-                        "one GPU; batch <= 256, one update per step; ranks that share a GPU run the reference's order): env step + the first "
+                   help="front (default where it applies AND every rank has a GPU of its own: HIRL / TD3 in fp32 or bf16 actor + critic, SAC / E-SAC at every number of envs on "
+                        "one GPU (fp32, or bf16 for acting AND update; ISAC and bf16_policy keep the reference's order inside it); batch <= 256, one update per step; ranks that share a GPU run the reference's order): env step + the first "
                         "launches of learn() as one launch; the minibatch is drawn from the ring as it stood before the step's insert, without the slots it may "
                         "overwrite.  reference: act -> env step -> insert -> draw -> learn on every step (the minibatch sees this step's transitions)")
     p.add_argument("--separate_launches", action="store_true",

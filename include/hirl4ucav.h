@@ -73,8 +73,9 @@ const char* hx_last_error(void);
  * not call in (round 3 widened HxStepOpts.stats from 9 to HX_STAT_WAYS * HX_STAT_PITCH words and appended fields to HxNets / HxHyper without
  * bumping this: a 9-word stats buffer then took atomics up to word 504).  110: round 4 (hx_abi_sizes, hx_rccl_*, hx_allreduce_twostage).
  * 113: round 5.  114: round 6 (hx_rccl_allreduce_bf16).  115: the SAC bf16 path (HxSacNets.w2_bf16_all / policy_w2_bf16, hx_sac_*_bf16).
- * 116: SAC's imitative branch (HxSacImit, hx_sac_imit_*, hx_sac_policy_grads_imitative, hx_sac_learn_imitative). */
-#define HX_ABI_VERSION 116
+ * 116: SAC's imitative branch (HxSacImit, hx_sac_imit_*, hx_sac_policy_grads_imitative, hx_sac_learn_imitative).
+ * 117: hx_sac_front takes any number of envs (the per-tile acting role up to 8,192; it refused them before). */
+#define HX_ABI_VERSION 117
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -512,13 +513,21 @@ int hx_sac_policy_grads(const HxSacNets* nets, const HxSacBatch* batch, const Hx
  * hx_sac_policy_grads + hx_sac_adam(which = 1); sample may be NULL (minibatch already assembled); step is 1-based. */
 int hx_sac_learn(const HxSacNets* nets, const HxSacBatch* batch, const HxHyper* hyper, const HxSample* sample, int32_t polyak_first, int32_t step,
                  float target_entropy, void* stream);
-/* The SAC front launch (n > 8,192 envs with a replay ring): hx_sac_act_step_x9 (w2_x9 != NULL) / hx_sac_act_step_f32i / hx_sac_act_step_bf16 (the
- * acting format is taken from nets: with nets->w2_bf16_all set the bf16 acting image and the bf16 first launch; w2_x9 and w2_f32i must be NULL then) — explore / exploit + HarfangEnv.step +
- * replay insert (train_sac.py:238-241) — AND the first forward launch of the SacAgent.learn call that follows it (policy(s'), policy(s), Q1/Q2(s, a): SAC/agent.py:
- * 198-210, 276-290) as workgroups of ONE launch that start as the acting ones leave, on the minibatch `batch->rows` holds already.  As for hx_hirl_front the
+/* The SAC front launch (any n >= 1 envs with a replay ring): hx_sac_act_step_x9 / hx_sac_act_step_f32i / hx_sac_act_step_bf16 — explore / exploit +
+ * HarfangEnv.step + replay insert (train_sac.py:238-241) — AND the first forward launch of the SacAgent.learn call that follows it (policy(s'), policy(s),
+ * Q1/Q2(s, a), E-SAC's extra jobs: SAC/agent.py:198-210, 276-290) as workgroups of ONE launch, on the minibatch `batch->rows` holds already.  No workgroup of it
+ * waits for another.
+ * Which kernel acts: up to 8,192 envs the per-tile workgroups of hx_sac_act_step_f32i / _bf16 (one round of 16- or 32-row workgroups: the tiling is a choice per
+ * size and format, HX_SAC_FRONT_F32_NRT2_ROWS / HX_SAC_FRONT_BF16_NRT2_ROWS, and a row's action does not depend on it), the forward workgroups on the CUs they
+ * leave free; beyond, the streaming persistent kernel on every CU, the forward workgroups starting as the acting ones leave.
+ * Images: the acting format is taken from nets.  With nets->w2_bf16_all set: the bf16 acting image (its first one) and the bf16 first launch; w2_x9 and w2_f32i
+ * must be NULL then.  Else fp32: beyond 8,192 envs from w2_x9 (the exact split) when given, else from w2_f32i; up to 8,192 envs from w2_f32i, which must
+ * then be given — a non-NULL w2_x9 is accepted and ignored there, as in hx_sac_act_step_x9.  bf16 acting beside the fp32 update has no front form.
+ * The draw rule is the same at every size.  As for hx_hirl_front the
  * minibatch is drawn from the ring as it stood BEFORE this env step without the n slots the step may overwrite (HxSample.guard = n): by the previous
  * hx_sac_learn_back (its `next`: one more workgroup of the policy's gradient launch draws and gathers into next_rows) or by hx_sample_batch_guarded.
- * Bit-identical to hx_sac_act_step_* followed by hx_sac_learn with HxSample.total read before the step and HxSample.guard = n.
+ * Bit-identical to hx_sac_act_step_x9 / _f32i / _bf16 for the same n (up to 8,192 envs: hx_sac_act_step_f32i / _bf16) followed by hx_sac_learn with
+ * HxSample.total read before the step and HxSample.guard = n.
  * hx_sac_learn_back = the rest of hx_sac_learn (8 launches). */
 int hx_sac_front(const float* policy, const uint16_t* w2_x9, const float* w2_f32i, float* state, int64_t n, int64_t stride, float* obs_io, float* actions,
                  int32_t mode, const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done, int8_t* success,
