@@ -80,8 +80,8 @@ struct BwdLds {
 
 // GRP 0: BM_CRITIC_TD jobs, 1: BM_CRITIC_PI, 2: BM_ACTOR_PI / BM_ACTOR_BC, 3: BM_GIVEN — the head gradient was written to ws.dout
 // by an earlier kernel, heads up to 8 wide (SAC) (one instantiation per launch keeps the register
-// footprint of each below 128 at 16 waves per workgroup); 4: BM_SAC_QMIN — SAC's min(Q1, Q2)(s, a~) selection in the prologue (role 1: the
-// other critic's head) instead of a launch of its own; 5: BM_SAC_POLICY — the policy's head gradient in the prologue (role 1: dL/da from
+// footprint of each below 128 at 16 waves per workgroup); 4: BM_SAC_QMIN — SAC's min(Q1, Q2)(s, a~) selection in the prologue (role 1: both
+// critics' heads of the row, so that the two jobs compare the same two numbers) instead of a launch of its own; 5: BM_SAC_POLICY — the policy's head gradient in the prologue (role 1: dL/da from
 // both critics' layer-1 backward), 8-wide head.
 // Latency structure (what matters at B = 128, one workgroup per CU): EVERY global load of the workgroup — the W2 fragment
 // of the MFMA phase, the z2 rows, labels, the other nets' rows, all head parameters, the epilogue's z1 — is issued at
@@ -184,8 +184,11 @@ __device__ __forceinline__ void bwd_l2_body(const BwdArgsC& AC, const int bx, co
     if (GRP == 1) {
         if (role1 && J.soft.net) za.load(J.soft.ws.z2 + R * H2);  // same net as J.net: shares the LDS image
     }
-    if (GRP == 4) {  // the other critic on (s, a~): its own LDS image
-        if (role1) za.load(J.t1.ws.z2 + R * H2);
+    if (GRP == 4) {  // the other critic on (s, a~): its own LDS image; the pair's second wave evaluates BOTH heads of the row (below)
+        if (role1) {
+            za.load(J.t1.ws.z2 + R * H2);
+            zb.load(J.ws.z2 + R * H2);
+        }
         pv1.fetch(J.t1.net, J.t1.m, tid);
     }
     float c1v[2] = {0.f, 0.f};
@@ -331,10 +334,28 @@ __device__ __forceinline__ void bwd_l2_body(const BwdArgsC& AC, const int bx, co
                     if (lane == 0) tq[prow] = qs[0];
                 }
             } else if constexpr (GRP == 4) {
-                RowReg<H2> xa, ya;
-                float m1, s1, qo[1];
-                head_regs<1, IMG, RELU>(za, hps + kHpStride, 1, slope, xa, ya, m1, s1, qo, J.t1.m.no_ln);
-                if (lane == 0) tq[prow] = qo[0];
+                // Q1 and Q2 of the row, critic 1 first WHICHEVER job this is, through ONE instruction sequence (a loop that stays a loop): the two
+                // jobs must draw min's weights from the same two numbers.  Two inlined copies of head_regs do not round alike (this wave's and the
+                // row's own wave's differed in the last bit), and with "own head here, other head there" the job of critic 1 compared f(Q1) with
+                // g(Q2) and the job of critic 2 f(Q2) with g(Q1): wherever Q1 and Q2 agreed to the last bits BOTH critics took the weight 1, or
+                // both 0 — on a tie (identical critics) in half of the rows.
+                const bool second = J.loss_slot != 0;  // this job is critic 2's: its own row is zb, the other critic's za
+                float q1v = 0.f, q2v = 0.f;
+#pragma clang loop unroll(disable)
+                for (int c = 0; c < 2; ++c) {
+                    const bool own = (c == 1) == second;
+                    RowReg<H2> zz, xa, ya;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) zz.v[i] = own ? zb.v[i] : za.v[i];
+                    float m1, s1, qc[1];
+                    head_regs<1, IMG, RELU>(zz, hps + (own ? 0 : kHpStride), 1, slope, xa, ya, m1, s1, qc, J.m.no_ln);
+                    if (c == 0) q1v = qc[0];
+                    else q2v = qc[0];
+                }
+                if (lane == 0) {
+                    tq[prow * 4] = second ? q2v : q1v;      // this job's critic
+                    tq[prow * 4 + 1] = second ? q1v : q2v;  // the other one
+                }
             } else if constexpr (GRP == 5) {
                 // dL/da_j = sum over both critics and their 256 hidden units of dz1[k] W1[k][13 + j]; plain stacks: dz1 = dh1 relu'(z1)
                 // (policy_dout_kernel's order: critic 1's four units of the lane, then critic 2's, then the wave sums)
@@ -396,10 +417,11 @@ __device__ __forceinline__ void bwd_l2_body(const BwdArgsC& AC, const int bx, co
             part[0] += diff * diff * A.inv_batch;
         } else if constexpr (GRP == 4) {
             // torch.min(Q1, Q2)'s subgradient: the smaller head takes -1 / B, a tie is shared (q_select_kernel)   SAC/agent.py:380-383
-            const float other = tq[prow];
-            const float w = o[0] < other ? 1.0f : (o[0] == other ? 0.5f : 0.0f);
+            // (both heads as the pair's other wave evaluated them: the same two numbers in the job of either critic)
+            const float mine = tq[prow * 4], other = tq[prow * 4 + 1];
+            const float w = mine < other ? 1.0f : (mine == other ? 0.5f : 0.0f);
             dout[0] = -w * A.inv_batch;
-            if (J.loss_slot == 0) part[2] += -fminf(o[0], other) * A.inv_batch;  // the -min(Q) / B part of the policy loss (logged), once per row
+            if (J.loss_slot == 0) part[2] += -fminf(mine, other) * A.inv_batch;  // the -min(Q) / B part of the policy loss (logged), once per row
         } else if constexpr (GRP == 5) {
             const float ab = bonus_scale * A.inv_batch;  // alpha / B
 #pragma unroll

@@ -100,7 +100,10 @@ void launch_fwd(const FwdArgs& F, hipStream_t st) {
         return;
     }
     if (tiles >= 128) HX_FWD(256);
-    else if (tiles * (H2 / 32) <= 256 && !force64) HX_FWD(32);  // one or two nets at B = 128: 32-column workgroups still fit the chip in one round
+    // one or two nets at B = 128: 32-column workgroups still fit the chip in one round.  Three or four nets keep the 64-column tiling at EVERY batch
+    // size: that is launch A / SAC's first launch, which the sampled form above runs in 64-column workgroups — the K-split of the two tilings differs,
+    // and the deferred draw is bit-identical to the sampling launch only if both forms sum alike (up to 64 rows of four nets the rule took 32 columns)
+    else if (tiles * (H2 / 32) <= 256 && !force64 && F.njobs <= 2) HX_FWD(32);
     else HX_FWD(kNT);
 #undef HX_FWD_T
 #undef HX_FWD

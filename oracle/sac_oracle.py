@@ -1,6 +1,6 @@
 """oracle/sac_oracle.py — CPU ORACLE for the SAC update.  TEST INFRASTRUCTURE ONLY (tests/, smoke(), bench's cpu leg).
 
-Plain fp32 torch-on-CPU restatement of hirl/agents/SAC (non-imitative branch, the one train_sac.py uses):
+Plain torch-on-CPU restatement (fp32 by default; dtype=torch.float64 evaluates the same formulas in double precision) of hirl/agents/SAC (non-imitative branch, the one train_sac.py uses):
 
     policy_forward / sample  <- GaussianPolicy.forward / sample       SAC/model.py:63-82       (U14)
     q_forward                <- TwinnedQNetwork.forward               SAC/model.py:41-45
@@ -66,15 +66,18 @@ def sample(p, s, eps):
     return a, -log_prob.sum(dim=1, keepdim=True), torch.tanh(mean)
 
 
-def to_t(p, grad=False):
-    return {k: torch.tensor(np.asarray(v), dtype=torch.float32, requires_grad=grad) for k, v in p.items()}
+def to_t(p, grad=False, dtype=torch.float32):
+    return {k: torch.tensor(np.asarray(v), dtype=dtype, requires_grad=grad) for k, v in p.items()}
 
 
 class SacOracle:
-    def __init__(self, policy, q1, q2, lr=1e-3, gamma=0.99, tau=0.005, target_entropy=-4.0, target_update_interval=3):
-        self.policy, self.q1, self.q2 = to_t(policy, True), to_t(q1, True), to_t(q2, True)
-        self.q1_t, self.q2_t = to_t(q1), to_t(q2)  # hard_update, agent.py:92
-        self.log_alpha = torch.zeros(1, requires_grad=True)  # agent.py:106
+    def __init__(self, policy, q1, q2, lr=1e-3, gamma=0.99, tau=0.005, target_entropy=-4.0, target_update_interval=3, dtype=torch.float32):
+        """dtype=torch.float64: the same formulas evaluated in double precision (the parameters are the given fp32 values, widened) — the
+        reference for inputs on which fp32 torch itself is not accurate (log_std at the lower clamp: tests/test_oracle_sac.py)"""
+        self.dtype = dtype
+        self.policy, self.q1, self.q2 = to_t(policy, True, dtype), to_t(q1, True, dtype), to_t(q2, True, dtype)
+        self.q1_t, self.q2_t = to_t(q1, dtype=dtype), to_t(q2, dtype=dtype)  # hard_update, agent.py:92
+        self.log_alpha = torch.zeros(1, dtype=dtype, requires_grad=True)  # agent.py:106
         self.alpha = self.log_alpha.exp().detach()
         self.opt_pi, self.opt_q1, self.opt_q2 = Adam(self.policy, lr), Adam(self.q1, lr), Adam(self.q2, lr)
         self.opt_alpha = Adam({"a": self.log_alpha}, lr)
@@ -82,20 +85,23 @@ class SacOracle:
         self.learning_steps = 0
         self.last_grads = {}
 
-    def explore(self, s, eps):  # agent.py:183-188
+    def explore(self, s, eps, dtype=None):  # agent.py:183-188
+        dtype = self.dtype if dtype is None else dtype
         with torch.no_grad():
-            return sample(self.policy, torch.as_tensor(s, dtype=torch.float32).reshape(-1, 13), torch.as_tensor(eps, dtype=torch.float32).reshape(-1, 4))[0].numpy()
+            return sample(self.policy, torch.as_tensor(s, dtype=dtype).reshape(-1, 13), torch.as_tensor(eps, dtype=dtype).reshape(-1, 4))[0].numpy()
 
-    def exploit(self, s):  # agent.py:191-196
+    def exploit(self, s, dtype=None):  # agent.py:191-196
+        dtype = self.dtype if dtype is None else dtype
         with torch.no_grad():
-            return torch.tanh(policy_forward(self.policy, torch.as_tensor(s, dtype=torch.float32).reshape(-1, 13))[0]).numpy()
+            return torch.tanh(policy_forward(self.policy, torch.as_tensor(s, dtype=dtype).reshape(-1, 13))[0]).numpy()
 
-    def learn(self, batch, eps_next, eps_cur):
+    def learn(self, batch, eps_next, eps_cur, dtype=None):
         """batch = (s, a, r[B], s', d[B]); eps_next / eps_cur = the [B, 4] standard-normal draws of the two policy.sample calls.
-        Returns (q1_loss, q2_loss, policy_loss, entropy_loss, mean entropy, alpha after the step)."""
-        s, a, r, ns, d = (torch.as_tensor(x, dtype=torch.float32) for x in batch)
+        Returns (q1_loss, q2_loss, policy_loss, entropy_loss, mean entropy, alpha after the step).  dtype: of the batch and eps tensors (default: the oracle's)."""
+        dtype = self.dtype if dtype is None else dtype
+        s, a, r, ns, d = (torch.as_tensor(x, dtype=dtype) for x in batch)
         r, d = r.reshape(-1, 1), d.reshape(-1, 1)
-        e1, e2 = torch.as_tensor(eps_next, dtype=torch.float32), torch.as_tensor(eps_cur, dtype=torch.float32)
+        e1, e2 = torch.as_tensor(eps_next, dtype=dtype), torch.as_tensor(eps_cur, dtype=dtype)
         self.learning_steps += 1
         if self.learning_steps % self.interval == 0:  # agent.py:278-279 — BEFORE the update
             with torch.no_grad():

@@ -4,10 +4,12 @@ sampling order stay UNPINNED (the vectors inject weights, minibatches and noise)
 import os
 
 import numpy as np
+import pytest
 import torch
 
 from oracle import sac_oracle as S
 from tests import _hirl_data as D
+from tests import _sac_edges as X
 
 torch.set_num_threads(1)
 
@@ -47,3 +49,49 @@ def test_sac_sample_entropy_formula():
     ref = -(n.log_prob(x) - torch.log(1 - torch.tanh(x).pow(2) + 1e-6)).sum(1, keepdim=True)
     np.testing.assert_allclose(h.detach().numpy(), ref.detach().numpy(), rtol=1e-5, atol=1e-5)
     assert torch.all(a.abs() <= 1) and torch.equal(m, torch.tanh(mean))
+
+
+def test_sac_learn_in_float64_matches_reference(golden_dir):
+    """dtype=torch.float64 of the oracle (the reference of tests/test_sac_edges_gpu.py) replays the reference's recorded run within the tolerances
+    of test_sac_learn_matches_reference: the double-precision path is the same update, not a second implementation."""
+    g = np.load(os.path.join(golden_dir, "sac_learn.npz"))
+    params, data = sac_params(), D.make_data(D.DATA_SEED)
+    o = S.SacOracle(params["policy"], params["q1"], params["q2"], dtype=torch.float64)
+    assert o.log_alpha.dtype == torch.float64 and o.opt_pi.m["0.weight"].dtype == torch.float64
+    for k in range(g["out"].shape[0]):
+        rows = data["replay"][g["idx"][k]]
+        out = o.learn((rows[:, 0:13], rows[:, 13:17], rows[:, 30], rows[:, 17:30], rows[:, 31]), g["eps"][k, 0], g["eps"][k, 1])
+        np.testing.assert_allclose(out, g["out"][k], rtol=1e-5, atol=1e-6, err_msg=f"sac call {k}")
+        for j, net in enumerate((o.policy, o.q1, o.q2, o.q1_t, o.q2_t)):
+            assert net["0.weight"].dtype == torch.float64 and o.last_grads["policy"]["0.weight"].dtype == torch.float64
+            s, a, v = D.net_probe(S.flatten(net))
+            np.testing.assert_allclose(v, g["probe_val"][k][j], rtol=1e-5, atol=2e-6, err_msg=f"call {k} net {j}")
+            np.testing.assert_allclose(a, g["probe_abs"][k][j], rtol=1e-6)
+    assert o.learning_steps == 8
+    obs, eps = data["replay"][:5, 0:13], g["eps"][0, 0][:5]
+    o32 = S.SacOracle(params["policy"], params["q1"], params["q2"])
+    for got, ref in ((S.SacOracle(params["policy"], params["q1"], params["q2"], dtype=torch.float64).explore(obs, eps), o32.explore(obs, eps)),
+                     (S.SacOracle(params["policy"], params["q1"], params["q2"], dtype=torch.float64).exploit(obs), o32.exploit(obs))):
+        assert got.dtype == np.float64 and ref.dtype == np.float32
+        np.testing.assert_allclose(got, ref, rtol=1e-5, atol=2e-6)
+
+
+@pytest.mark.parametrize("case,B", X.FAIR_IN_FP32)
+def test_sac_edge_inputs_are_fair_in_float32(case, B):
+    """The edge cases of tests/test_sac_edges_gpu.py hold an fp32 engine to the gradient rule |dg| <= 1e-4 |g| + 2e-5 max|g| against the fp64 oracle.
+    That is fair only where fp32 arithmetic can meet it: on the ragged batches, at the upper clamp with saturated tanh and on the Q1 = Q2 tie the fp32
+    oracle itself must stay inside the rule, entry for entry, three calls from shared states (measured: at most 0.04 x the rule).
+
+    NOTHING is asserted about the fp32 oracle at the LOWER clamp, and nothing may be: there sigma = e^-20 ~ 2e-9, and the reference's formula
+    log_prob = -(x - mean)^2 / (2 sigma^2) - ... with x = mean + sigma eps forms x - mean in fp32, where it is rounding noise (x == mean bit for bit for
+    almost every row) instead of sigma eps.  The fp32 oracle's mean entropy is then off by 1e-2 .. 1e-1, its critic losses by 1 .. 15 at losses of
+    about 450, and essentially every gradient entry misses the rule.  The kernels carry se = sigma eps itself (gauss_head_rows: -(se se) / (2 sigma
+    sigma)), which is exact, so the engine agrees with the fp64 evaluation of the reference's formula.  Do not "repair" a kernel to match fp32 torch
+    at the lower clamp: fp64 is the reference there."""
+    worst, (mean, raw_log_std, x) = X.fp32_against_fp64(case, B)
+    print(f"{case} B={B}: the fp32 oracle uses {worst:.3f} of the gradient rule against fp64")
+    assert worst <= 1.0, (case, B, worst)
+    if case == "upper":  # what the case is built for: the clamp in every row; x_0 small or far in the saturated range, both present
+        assert (raw_log_std[:, 0] > S.LOG_STD_MAX).all()
+        ax = np.abs(x[:, 0])
+        assert ((ax < 3.5) | (ax > 15.0)).all() and (ax < 3.5).any() and (ax > 15.0).any(), ax

@@ -31,17 +31,18 @@ def SE():
     return sac_engine
 
 
-def make_side(SE, n, cap, dtype):
+def make_side(SE, n, cap, dtype, batch=128):
     from hirl4ucav_amd.environments.batched import BatchedHarfangEnv
     from hirl4ucav_amd.utils.buffer import DeviceReplay
     from tests.test_oracle_sac import sac_params
     from tests.test_sac_bf16_gpu import engine
 
     if dtype == "bf16":
+        assert batch == 128
         e = engine(SE, "bf16", "bf16")
     else:
         p = sac_params()
-        e = SE.SacEngine(batch=128)
+        e = SE.SacEngine(batch=batch)
         e.load_params(p["policy"], p["q1"], p["q2"])
     rep = DeviceReplay(cap)
     env = BatchedHarfangEnv(n, scenario=(np.arange(n) % 3).astype(np.int32), seed=5, max_step=6, auto_reset=True, random_reset=True, replay=rep)
@@ -61,21 +62,28 @@ def bits(t):
     return t.view(torch.int16) if t.dtype == torch.bfloat16 else t
 
 
-@pytest.mark.parametrize("n,cap,esac,dtype", [(200, 512, False, "f32"),        # a half-filled last 16-row tile (cap 512: the smallest ring the library takes)
-                                              (256, 640, False, "bf16"),       # the driver tests' size
-                                              (1000, 2400, True, "f32"),       # E-SAC's mixed batch (n_main = 96), ragged tail
-                                              (4096, 10000, False, "f32"),     # one full round of 16-row workgroups
-                                              (4097, 10000, True, "bf16"),     # where the stand-alone bf16 kernel changes its tiling
-                                              (8192, 20000, False, "f32"),     # the last size of the per-tile role
-                                              (8192, 20000, False, "bf16")])
-def test_sac_small_front_launch_equals_act_step_then_guarded_learn(SE, n, cap, esac, dtype):
+@pytest.mark.parametrize("n,cap,esac,dtype,batch", [
+    pytest.param(200, 512, False, "f32", 128, id="200-512-False-f32"),        # a half-filled last 16-row tile (cap 512: the smallest ring the library takes)
+    pytest.param(256, 640, False, "bf16", 128, id="256-640-False-bf16"),      # the driver tests' size
+    pytest.param(1000, 2400, True, "f32", 128, id="1000-2400-True-f32"),      # E-SAC's mixed batch (n_main = 96), ragged tail
+    pytest.param(4096, 10000, False, "f32", 128, id="4096-10000-False-f32"),  # one full round of 16-row workgroups
+    pytest.param(4097, 10000, True, "bf16", 128, id="4097-10000-True-bf16"),  # where the stand-alone bf16 kernel changes its tiling
+    pytest.param(8192, 20000, False, "f32", 128, id="8192-20000-False-f32"),  # the last size of the per-tile role
+    pytest.param(8192, 20000, False, "bf16", 128, id="8192-20000-False-bf16"),
+    pytest.param(200, 512, False, "f32", 48, id="200-512-False-f32-batch48"),    # an odd number of 16-row tiles in the minibatch
+    pytest.param(200, 512, False, "f32", 256, id="200-512-False-f32-batch256")])  # kFusedBatchMax: the largest minibatch the front launch takes
+def test_sac_small_front_launch_equals_act_step_then_guarded_learn(SE, n, cap, esac, dtype, batch):
     """8 steps from shared states with max_step = 6 (episodes reset; the ring fills and wraps): step_learn on side a, the separate launches with the
-    guarded draw on side b.  Every shape leaves the guarded draw at least 128 slots (cap - n once the ring is full, n at the first step); the smallest
-    ring is 512 rows because the library takes none below that (check_step_args)."""
+    guarded draw on side b.  Every shape leaves the guarded draw at least `batch` slots (cap - n once the ring is full; before that the rows of the
+    env steps taken ahead of the first draw: one step, two for 256 rows out of 200 envs); the smallest ring is 512 rows because the library takes none
+    below that (check_step_args)."""
     exp = expert_memory(n) if esac else None
-    (a, env_a, rep_a), (b, env_b, rep_b) = make_side(SE, n, cap, dtype), make_side(SE, n, cap, dtype)
+    (a, env_a, rep_a), (b, env_b, rep_b) = make_side(SE, n, cap, dtype, batch), make_side(SE, n, cap, dtype, batch)
     state = STATE + (("images",) if dtype == "bf16" else ())
-    a.act_step(env_a, seed=3)  # some rows in the ring before the first draw
+    n_main = batch - 32
+    assert cap - n >= batch
+    for _ in range(-(-batch // n)):
+        a.act_step(env_a, seed=3)  # at least `batch` rows in the ring before the first draw
     snap = torch.zeros(1, dtype=torch.int64, device="cuda")
     for k in range(8):
         b.arena.copy_(a.arena)
@@ -88,10 +96,10 @@ def test_sac_small_front_launch_equals_act_step_then_guarded_learn(SE, n, cap, e
             getattr(env_b, name).copy_(getattr(env_a, name))
         rep_b.ring.copy_(rep_a.ring); rep_b.success.copy_(rep_a.success); rep_b.total.copy_(rep_a.total)  # noqa: E702
         tot0 = int(rep_a.total.item())
-        out_a = a.step_learn(env_a, exp, n_main=96, act_seed=3, sample_seed=11)
+        out_a = a.step_learn(env_a, exp, n_main=n_main, act_seed=3, sample_seed=11)
         snap.copy_(rep_b.total)
         out_b = b.act_step(env_b, seed=3)
-        b.sample(rep_b, exp, n_main=96, seed=11, defer=True)
+        b.sample(rep_b, exp, n_main=n_main, seed=11, defer=True)
         b._pending[0].total, b._pending[0].guard = snap.data_ptr(), n
         b.learn()
         for x, y, name in zip(out_a, out_b, ("actions", "obs", "reward", "done", "success")):
@@ -103,7 +111,7 @@ def test_sac_small_front_launch_equals_act_step_then_guarded_learn(SE, n, cap, e
         for name in state:
             assert torch.equal(bits(getattr(a, name)), bits(getattr(b, name))), (k, name)
         i = a._idx.cpu().numpy()
-        m = 96 if esac else 128
+        m = n_main if esac else batch
         assert len(set(i[:m])) == m and np.isin(i[:m], allowed_slots(tot0, cap, n)).all(), (k, tot0)
     assert int(rep_a.total.item()) > cap
 

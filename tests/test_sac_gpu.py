@@ -37,7 +37,7 @@ def sync(o, e, SE):
     a = e.alpha_state.tolist()
     o.log_alpha.data.fill_(a[0])
     o.opt_alpha.m["a"].fill_(a[1]); o.opt_alpha.v["a"].fill_(a[2]); o.opt_alpha.t = e.learning_steps  # noqa: E702
-    o.alpha = torch.tensor([a[3]])
+    o.alpha = torch.tensor([a[3]], dtype=o.log_alpha.dtype)  # (an fp64 oracle, tests/test_sac_edges_gpu.py, keeps its dtype)
     o.learning_steps = e.learning_steps
 
 
@@ -122,10 +122,14 @@ def test_sac_learn_matches_oracle_and_reference(SE, golden_dir):
     assert e.learning_steps == 8
 
 
-@pytest.mark.parametrize("esac", [False, True])
-def test_sac_deferred_draw_is_bit_identical_to_the_sampling_launch(SE, esac):
-    """sample(defer=True) + learn() (hx_sac_critic_grads_sampled: memory.sample inside the first forward launch) against sample() +
-    learn(): the same indices, row tile and — after 8 calls — the same networks, moments and alpha, bit for bit (SAC and E-SAC's expert mix)."""
+# (the ids of the batch-128 cases are the ones these tests had before they took a batch size)
+@pytest.mark.parametrize("esac,batch", [pytest.param(False, 128, id="False"), pytest.param(True, 128, id="True"), pytest.param(False, 48, id="False-batch48"),
+                                        pytest.param(True, 48, id="True-batch48"), pytest.param(False, 272, id="False-batch272"), pytest.param(True, 272, id="True-batch272")])
+def test_sac_deferred_draw_is_bit_identical_to_the_sampling_launch(SE, esac, batch):
+    """sample(defer=True) + learn() (hx_sac_critic_grads_sampled: memory.sample inside the first forward launch; beyond 256 rows a sampling launch
+    that the call issues itself) against sample() + learn(): the same indices, row tile and — after 8 calls — the same networks, moments and alpha,
+    bit for bit (SAC and E-SAC's expert mix; batch 48: an odd number of 16-row tiles, 272: beyond the in-launch draw).  The ring holds a few more rows
+    than the minibatch at the start (150 for the batches up to 128), so that the draw without replacement has a population to draw from."""
     from hirl4ucav_amd.utils.buffer import DeviceReplay
 
     params = sac_params()
@@ -133,10 +137,10 @@ def test_sac_deferred_draw_is_bit_identical_to_the_sampling_launch(SE, esac):
     rep = DeviceReplay(5000)
     rep.ring.copy_(torch.from_numpy(rng.normal(size=(5000, 32)).astype(np.float32)))
     rep.ring[:, 31] = (rep.ring[:, 31] > 1.0).float()
-    rep.total += 150
+    rep.total += max(150, batch + 22)
     exp = DeviceReplay(64)
     exp.store_rows(torch.from_numpy(rng.normal(size=(50, 32)).astype(np.float32)))
-    a, b = (SE.SacEngine(batch=128) for _ in range(2))
+    a, b = (SE.SacEngine(batch=batch) for _ in range(2))
     for e in (a, b):
         e.load_params(params["policy"], params["q1"], params["q2"])
     for k in range(8):
@@ -144,7 +148,7 @@ def test_sac_deferred_draw_is_bit_identical_to_the_sampling_launch(SE, esac):
             rep.total += 100000
         outs = []
         for e, defer in ((a, False), (b, True)):
-            e.sample(rep, exp if esac else None, n_main=100, seed=7, defer=defer)
+            e.sample(rep, exp if esac else None, n_main=batch - 28, seed=7, defer=defer)
             e.learn()
             outs.append((e._idx.clone(), e.rows.clone()))
         assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1]), k
@@ -152,8 +156,9 @@ def test_sac_deferred_draw_is_bit_identical_to_the_sampling_launch(SE, esac):
         assert torch.equal(getattr(a, name), getattr(b, name)), name
 
 
-@pytest.mark.parametrize("defer", [False, True])
-def test_sac_learn_in_one_call_is_bit_identical_to_the_staged_sequence(SE, defer):
+@pytest.mark.parametrize("defer,batch", [pytest.param(False, 128, id="False"), pytest.param(True, 128, id="True"), pytest.param(False, 48, id="False-batch48"),
+                                         pytest.param(True, 48, id="True-batch48"), pytest.param(False, 272, id="False-batch272"), pytest.param(True, 272, id="True-batch272")])
+def test_sac_learn_in_one_call_is_bit_identical_to_the_staged_sequence(SE, defer, batch):
     """hx_sac_learn (one GPU, 9 launches: the soft_update and policy.sample(s) in the launch of policy.sample(s'), the min(Q1, Q2) selection and the
     policy head gradient in the backward prologues, q1 / q2 / policy optimizer
     steps and the log-alpha step inside their weight-gradient launches) against BOTH staged sequences — hx_sac_critic_step +
@@ -167,7 +172,7 @@ def test_sac_learn_in_one_call_is_bit_identical_to_the_staged_sequence(SE, defer
     rep.ring.copy_(torch.from_numpy(rng.normal(size=(4096, 32)).astype(np.float32)))
     rep.ring[:, 31] = (rep.ring[:, 31] > 1.0).float()
     rep.total += 4096
-    a, b, c = (SE.SacEngine(batch=128) for _ in range(3))
+    a, b, c = (SE.SacEngine(batch=batch) for _ in range(3))
     b.staged_policy = True          # hx_sac_critic_step + hx_sac_policy_grads + hx_sac_adam(1)
     c.separate_critic_adam = True   # every stage a call of its own
     for e in (a, b, c):
