@@ -2,7 +2,9 @@
 constructor keywords, .memory.append / len(.memory), .batch_size, .explore / .exploit, .learn(if_expert, expert_num,
 expert_data), .expert_memory, .writer, .model_dir / .plot_dir, .save_models — on the HIP kernels (SacEngine).  With
 imitative=True (agent.py:315-318, 385-403): load_bc_actor, then learn() draws a second batch from .expert_memory for the
-BC-gated policy loss and logs loss/bc and loss/bc_weight.
+BC-gated policy loss and logs loss/bc and loss/bc_weight.  With per=True (agent.py:112-118, 281-284, 329-331): .memory is a prioritized
+device memory — append(..., error), sample(n) -> (batch, indices, weights), update_priority(indices, errors) — and learn() carries the
+weights through the three losses (the store and the draw rule are this project's: rltorch.PrioritizedMemory is un-vendored).
 
 The networks are the Linear-ReLU stacks of the reference's un-vendored rltorch builder (initialisation: xavier-uniform
 weights, zero biases — that builder is not in /root/reference, so its exact initialiser is not claimed).  The known crashes of
@@ -14,7 +16,7 @@ import os
 import numpy as np
 import torch
 
-from ...utils.buffer import DeviceReplay, device
+from ...utils.buffer import PER_EPS, DeviceReplay, PrioritizedReplay, device
 from .. import sac_engine as SE
 
 
@@ -51,6 +53,49 @@ class DeviceMemory(DeviceReplay):
         return rows[:, 0:13], rows[:, 13:17], rows[:, 30:31], rows[:, 17:30], rows[:, 31:32]
 
 
+class PrioritizedDeviceMemory(PrioritizedReplay):
+    """rltorch PrioritizedMemory's append / sample / update_priority / len as SacAgent uses them (SAC/agent.py:115-118, 244-246, 283-284, 331) on the
+    device ring with the priority store of utils.buffer.PrioritizedReplay (multi_step = 1)."""
+
+    def __init__(self, capacity, alpha=0.6, beta=0.4, beta_annealing=0.0001):
+        super().__init__(int(capacity), device, alpha=alpha, beta=beta, beta_annealing=beta_annealing)
+        self._len, self._pos, self._calls = 0, 0, 0
+        self._slot = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def append(self, state, action, reward, next_state, done, error=None, episode_done=None):  # agent.py:244-246
+        row = np.zeros(32, np.float32)
+        row[0:13], row[13:17], row[17:30], row[30], row[31] = state, action, next_state, reward, float(done)
+        self.ring[self._pos] = torch.from_numpy(row).to(self.device)
+        if error is None:  # no TD error given: the row enters at the running maximum
+            self.total += 1
+            self.mark_new(1)
+        else:
+            self._slot.fill_(self._pos)
+            self.set_priorities(self._slot, torch.full((1,), (abs(float(error)) + PER_EPS) ** self.alpha))
+            self.total += 1
+            self.marked_t += 1
+        self._pos = (self._pos + 1) % self.capacity
+        self._len = min(self._len + 1, self.capacity)
+
+    def __len__(self):
+        return self._len
+
+    def sample(self, n):
+        """-> (batch, indices, weights): batch = (s, a, r, s', d) as MultiStepMemory.sample returns it, indices int32 [n], weights [n, 1]"""
+        self._calls += 1
+        idx = torch.zeros(n, dtype=torch.int32, device=self.device)
+        w = torch.zeros(n, dtype=torch.float32, device=self.device)
+        rows = torch.zeros((n, 32), dtype=torch.float32, device=self.device)
+        # rltorch memories draw with numpy's generator (a float64 uniform just below 1 rounds to 1.0f: the sampler takes u in [0, 1])
+        u = torch.as_tensor(np.random.random_sample(n).astype(np.float32)).to(self.device)
+        self.sample_into(n, idx, w, rows, u=u)
+        return (rows[:, 0:13], rows[:, 13:17], rows[:, 30:31], rows[:, 17:30], rows[:, 31:32]), idx, w.reshape(-1, 1)
+
+    def update_priority(self, indices, errors):  # agent.py:331
+        self.update(torch.as_tensor(np.asarray(indices.cpu() if torch.is_tensor(indices) else indices)),
+                    torch.as_tensor(np.asarray(errors.cpu() if torch.is_tensor(errors) else errors, np.float32)))
+
+
 def _xavier_mlp(n_in, n_out):
     sd = {}
     for key, (o, i) in (("0", (256, n_in)), ("2", (512, 256)), ("4", (n_out, 512))):
@@ -67,15 +112,20 @@ class SacAgent:
                  target_update_interval=3, eval_interval=1000, cuda=True):
         if tuple(observation_space.shape) != (13,) or tuple(action_space.shape) != (4,) or list(hidden_units) != [256, 512]:
             raise NotImplementedError("the HIP kernels are built for train_sac.py's shape: 13 / 4 / hidden [256, 512]")
-        if per or multi_step != 1 or not entropy_tuning or grad_clip is not None:
-            raise NotImplementedError("built: uniform replay, multi_step 1, entropy tuning, no gradient clipping (with or without imitative=True); "
-                                      "per, multi_step != 1, entropy_tuning=False and grad_clip are not")
+        if (per and imitative) or multi_step != 1 or not entropy_tuning or grad_clip is not None:
+            raise NotImplementedError("built: uniform replay (with or without imitative=True) or prioritized replay (per=True, without imitative), multi_step 1, "
+                                      "entropy tuning, no gradient clipping; per with imitative=True, multi_step != 1, entropy_tuning=False and grad_clip are not")
         self.observation_space, self.action_space = observation_space, action_space
         self.device = device
         self.eng = SE.SacEngine(batch=batch_size, lr=lr, gamma=gamma ** multi_step, tau=tau, target_entropy=-float(np.prod(action_space.shape)),
                                 target_update_interval=target_update_interval, device=device)
         self.eng.load_params(_xavier_mlp(13, 8), _xavier_mlp(17, 1), _xavier_mlp(17, 1))
-        self.memory = DeviceMemory(memory_size)
+        self.per = bool(per)
+        if self.per:  # agent.py:112-118
+            self.memory = PrioritizedDeviceMemory(memory_size, alpha=alpha, beta=beta, beta_annealing=beta_annealing)
+            self.eng.set_prioritized(self.memory)
+        else:
+            self.memory = DeviceMemory(memory_size)
         self.expert_memory = None
         self.imitative = bool(imitative)  # the BC gate needs load_bc_actor(...) and an expert_memory before the first learn()
         self.log_dir = log_dir
@@ -144,6 +194,14 @@ class SacAgent:
         B = self.batch_size
         if self.imitative:
             self._expert_batch()
+        if self.per:  # agent.py:281-284, 306-331: batch, indices, weights from the memory (expert rows are not mixed in), priorities updated at the end
+            (s, a, r, ns, d), indices, weights = self.memory.sample(B)
+            self.eng.rows.copy_(torch.cat([s, a, ns, r, d], 1).contiguous().reshape(-1))
+            self.eng._idx.copy_(indices)
+            self.eng.per_weights.copy_(weights.reshape(-1))
+            self.eng.learn(torch.randn(B, 4).to(device), torch.randn(B, 4).to(device))  # (ends in memory.update_priority(indices, errors) on the device)
+            self._log()
+            return
         if if_expert and expert_num:
             # expert rows were drawn by the caller (expert_memory.sample(expert_num), train_sac.py:272-273) and come last
             main = self.memory.ring[torch.as_tensor(self.memory.sample_indices(B - expert_num), device=device)]
@@ -153,6 +211,9 @@ class SacAgent:
             rows = self.memory.ring[torch.as_tensor(self.memory.sample_indices(B), device=device)].contiguous()
         self.eng.rows.copy_(rows.reshape(-1))
         self.eng.learn(torch.randn(B, 4).to(device), torch.randn(B, 4).to(device))
+        self._log()
+
+    def _log(self):  # agent.py:333-359
         if self.eng.learning_steps % self.log_interval == 0:
             q1, q2, pl, el, ent, alpha = self.eng.losses_host()
             for k, v in (("loss/Q1", q1), ("loss/Q2", q2), ("loss/policy", pl), ("stats/alpha", alpha), ("stats/entropy", ent)):

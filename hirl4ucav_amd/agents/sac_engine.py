@@ -51,6 +51,7 @@ _lib.register("hx_sac_learn", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _P(
 _lib.register("hx_sac_policy_grads", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _vp])
 _lib.register("hx_sac_adam", [_P(HxSacNets), _P(E.HxHyper), _i32, _i32, _f32, _f32, _vp])
 _lib.register("hx_sac_policy_grads_imitative", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _P(HxSacImit), _vp])
+_lib.register("hx_sac_learn_weighted", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _vp, _vp, _i32, _i32, ctypes.c_float, _vp])
 _lib.register("hx_sac_learn_imitative", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _P(E.HxSample), _P(HxSacImit), _P(E.HxSample), _i32, _i32,
                                           ctypes.c_float, _vp])
 
@@ -161,6 +162,25 @@ class SacEngine:
         self._seed = 0  # the seed of the last sample(): learn() without injected draws keys Normal.rsample's Philox eps with it
         self._pending, self._pending_expert = None, None  # draws sample(defer=True) / sample_expert(defer=True) recorded for the next learn()
         self._front_tiles, self._front_drawn = None, None  # step_learn: the two sets of minibatch tiles, and what the set in waiting was drawn for
+        self.prioritized, self.per_weights, self.per_errors = None, None, None  # set_prioritized
+
+    def set_prioritized(self, replay):
+        """SacAgent(per=True) (agent.py:281-284, 306-331): from now on sample() on `replay` (a utils.buffer.PrioritizedReplay) draws proportionally to
+        the stored priorities and keeps the importance weights, learn() carries them through the three losses (hx_sac_learn_weighted) and hands
+        |Q1(s, a) - y| back as the rows' new priorities (hx_per_update) — all enqueued, no host sync.  fp32, one GPU, not with the imitative branch."""
+        from ..utils.buffer import PrioritizedReplay
+
+        if not isinstance(replay, PrioritizedReplay):
+            raise TypeError("set_prioritized takes a utils.buffer.PrioritizedReplay")
+        if self.update_dtype == "bf16" or self.act_dtype == "bf16":
+            raise ValueError("prioritized replay is fp32 only: set_update_dtype('f32') and set_act_dtype('f32') before set_prioritized")
+        if self.world > 1:
+            raise _lib.HxError("prioritized replay runs on one GPU (priorities and block sums are not exchanged between ranks): run it with --gpus 1")
+        if self.imitative:
+            raise _lib.HxError("prioritized replay does not go with the imitative branch (not built: SacAgent(imitative=True, per=True)): build a SacEngine without set_imitative")
+        self.prioritized = replay
+        self.per_weights = torch.ones(self.batch, dtype=torch.float32, device=self.device)
+        self.per_errors = torch.zeros(self.batch, dtype=torch.float32, device=self.device)
 
     def set_imitative(self, bc_actor, slope=0.01):
         """SacAgent(imitative=True) (agent.py:315-318, 385-403): from now on learn() gates a BC term on the expert rows with
@@ -170,6 +190,8 @@ class SacEngine:
             raise ValueError("the imitative branch is fp32 only: set_update_dtype('f32') and set_act_dtype('f32') before set_imitative")
         if self.world > 1:
             raise _lib.HxError("the imitative branch runs on one GPU (its gate count is not exchanged between ranks): run it with --gpus 1")
+        if self.prioritized is not None:
+            raise _lib.HxError("the imitative branch does not go with prioritized replay (not built: SacAgent(imitative=True, per=True)): build a SacEngine without set_prioritized")
         L = _lib.load()
         L.hx_sac_imit_sizeof.restype, L.hx_sac_imit_workspace_floats.restype = ctypes.c_int, ctypes.c_int64
         if L.hx_sac_imit_sizeof() != ctypes.sizeof(HxSacImit):
@@ -207,6 +229,8 @@ class SacEngine:
             raise ValueError(dtype)
         if dtype == "bf16" and self.imitative:
             raise ValueError("the imitative branch is fp32 only: act in 'f32', or build a SacEngine without set_imitative for bf16 acting")
+        if dtype == "bf16" and self.prioritized is not None:
+            raise ValueError("prioritized replay is fp32 only: act in 'f32', or build a SacEngine without set_prioritized for bf16 acting")
         if dtype != "bf16" and self.update_dtype == "bf16":
             raise ValueError("the SAC bf16 update goes with the bf16 acting image (set_update_dtype('f32') first)")
         self.act_dtype = dtype
@@ -221,6 +245,8 @@ class SacEngine:
             raise ValueError(dtype)
         if dtype == "bf16" and self.imitative:
             raise ValueError("the imitative branch is fp32 only: keep the update in 'f32', or build a SacEngine without set_imitative for the bf16 update")
+        if dtype == "bf16" and self.prioritized is not None:
+            raise ValueError("prioritized replay is fp32 only: keep the update in 'f32', or build a SacEngine without set_prioritized for the bf16 update")
         if dtype == "bf16" and self.act_dtype != "bf16":
             raise ValueError("the SAC bf16 update goes with the bf16 acting image (set_act_dtype('bf16') first)")
         self.update_dtype = dtype
@@ -344,6 +370,13 @@ class SacEngine:
         self.sample_calls += 1
         n_main = self.batch if (n_main is None or expert is None) else int(n_main)
         self._seed = int(seed)  # learn() without injected draws: Normal.rsample's eps comes from Philox(seed; row, learn call) in-kernel
+        if self.prioritized is not None and replay is self.prioritized:  # memory.sample -> batch, indices, weights (agent.py:281-284)
+            if n_main < self.batch:
+                raise _lib.HxError("prioritized replay does not mix expert rows into the minibatch (the reference's learn() drops them when per is on: "
+                                   "agent.py:281-284): sample the prioritized replay alone (n_main = batch)")
+            self._pending = None
+            replay.sample_into(self.batch, self._idx, self.per_weights, self.rows, seed=seed, call=self.sample_calls)
+            return
         draw = _draw(replay, expert, n_main, seed, self.sample_calls, self._idx)
         self._pending = (draw, replay, expert) if defer else None  # (the tensors are referenced by the record: they must outlive the launch)
         if not defer:
@@ -394,6 +427,18 @@ class SacEngine:
         polyak_first = int(self.learning_steps % self.interval == 0)
         if self.imitative and self.world > 1:
             raise _lib.HxError("the imitative branch runs on one GPU (its gate count is not exchanged between ranks): run it with --gpus 1")
+        if self.prioritized is not None:  # the weighted update, then memory.update_priority(indices, errors)  (agent.py:306-331)
+            if self.world > 1 or self.update_dtype == "bf16" or self.imitative:
+                raise _lib.HxError("prioritized replay: one GPU, the fp32 update, no imitative branch")
+            if self.separate_critic_adam or self.staged_policy:
+                raise _lib.HxError("prioritized replay: the weighted update is one library call (hx_sac_learn_weighted) and has no staged entry points: "
+                                   "clear separate_critic_adam and staged_policy")
+            if pending is not None:
+                raise _lib.HxError("prioritized replay: the minibatch comes from sample() on the prioritized replay, but a deferred uniform draw is pending")
+            _lib.call("hx_sac_learn_weighted", nets, bt, hyper, self.per_weights.data_ptr(), self.per_errors.data_ptr(), polyak_first, self.learning_steps,
+                      self.target_entropy, st)
+            _lib.call("hx_per_update", ctypes.byref(self.prioritized.per), self._idx.data_ptr(), self.per_errors.data_ptr(), self.batch, self.prioritized.alpha, st)
+            return
         imit = ctypes.byref(self.imit) if self.imitative else None
         pe, self._pending_expert = self._pending_expert, None
         fused_critic = self.world == 1 and not self.separate_critic_adam
@@ -435,12 +480,26 @@ class SacEngine:
         HirlEngine.step_learn the minibatch is drawn from the ring as it stood BEFORE this env step, without the env.n slots the step may overwrite.
         Any number of envs with a replay ring (up to 8,192 the per-tile acting workgroups, beyond the persistent acting kernel), one GPU, the one-call
         learn(), batch <= 256, Philox draws.  Acting and update in one format: fp32, or bf16 for both (a bf16 policy beside the fp32 update runs act_step,
-        then the sampled learn(); so does the imitative branch).  -> (actions, obs, reward, done, success)."""
+        then the sampled learn(); so does the imitative branch).  After set_prioritized there is no front form either: act_step -> mark_new -> sample ->
+        learn, the reference's order.  -> (actions, obs, reward, done, success)."""
         replay, n, B = env.replay, env.n, self.batch
         if self.world > 1 or replay is None or self.separate_critic_adam or self.staged_policy:
             raise _lib.HxError("SacEngine.step_learn: one GPU, the one-call learn(), envs with a replay ring attached")
         if self._pending is not None:
             raise _lib.HxError("step_learn draws its own minibatch: a sample(defer=True) is still pending")
+        if self.prioritized is not None:
+            # no front form: the front loop draws BEFORE the step's insert, so update() could hit slots the step has overwritten.  The reference's order:
+            # act_step -> mark_new -> sample -> learn (which ends in update)
+            if replay is not self.prioritized:
+                raise _lib.HxError("SacEngine.step_learn: the env's replay ring is not the prioritized replay given to set_prioritized")
+            if expert is not None and n_main is not None and int(n_main) < B:
+                raise _lib.HxError("prioritized replay does not mix expert rows into the minibatch (the reference's learn() drops them when per is on: "
+                                   "agent.py:281-284): run step_learn without expert rows")
+            res = self.act_step(env, explore=explore, seed=act_seed, out=out)
+            replay.mark_new(n)
+            self.sample(replay, None, seed=sample_seed)
+            self.learn()
+            return res
         if self.imitative:  # no front form: the reference's order; `expert` is the imitative branch's expert memory, the minibatch is not expert-mixed
             if expert is None:
                 raise _lib.HxError("SacEngine.step_learn: the imitative branch needs the expert memory (expert=...)")

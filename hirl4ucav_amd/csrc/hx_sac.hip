@@ -126,11 +126,14 @@ struct QSelArgs {
     int rows;
     float inv_batch;
     float* losses;
+    const float* weights;  // WEIGHTED: [rows] importance weights (prioritized replay): inv_batch becomes w_r / B
 };
+template <bool WEIGHTED>
 __global__ __launch_bounds__(kThreads) void q_select_kernel(QSelArgs A) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + wave;
     if (r >= A.rows) return;
+    const float inv_batch = WEIGHTED ? A.weights[r] * A.inv_batch : A.inv_batch;
     RowReg<H2> xh, y;
     float mean_, rstd_, q1[1], q2[1];
     head_row<1, true>(A.s1.z2 + (size_t)r * H2, A.net1, A.m, 0.0f, xh, y, mean_, rstd_, q1);
@@ -139,9 +142,9 @@ __global__ __launch_bounds__(kThreads) void q_select_kernel(QSelArgs A) {
     if (lane == 0) {
         A.s2.st2[r * 2] = mean_; A.s2.st2[r * 2 + 1] = rstd_;
         const float w1 = q1[0] < q2[0] ? 1.0f : (q1[0] == q2[0] ? 0.5f : 0.0f);
-        A.s1.dout[(size_t)r * OW] = -w1 * A.inv_batch;
-        A.s2.dout[(size_t)r * OW] = -(1.0f - w1) * A.inv_batch;
-        atomicAdd(&A.losses[2], -fminf(q1[0], q2[0]) * A.inv_batch);
+        A.s1.dout[(size_t)r * OW] = -w1 * inv_batch;
+        A.s2.dout[(size_t)r * OW] = -(1.0f - w1) * inv_batch;
+        atomicAdd(&A.losses[2], -fminf(q1[0], q2[0]) * inv_batch);
     }
 }
 
@@ -158,11 +161,15 @@ struct PDoutArgs {
     int rows;
     float inv_batch;
     float* losses;
+    const float* weights;  // WEIGHTED: [rows] importance weights (SAC/agent.py:405): inv_batch becomes w_r / B in the gradient and in the logged loss
+    float* wsum;           // WEIGHTED: [2] <- mean(w H), mean(w) in a fixed order: what the weighted log-alpha step consumes (agent.py:408-414)
 };
+template <bool WEIGHTED>
 __global__ __launch_bounds__(kThreads) void policy_dout_kernel(PDoutArgs A) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + wave;
     if (r >= A.rows) return;
+    const float inv_batch = WEIGHTED ? A.weights[r] * A.inv_batch : A.inv_batch;
     float da[4] = {0.f, 0.f, 0.f, 0.f};
     for (int hsel = 0; hsel < 2; ++hsel) {
         const Slot& C = hsel ? A.c2 : A.c1;
@@ -185,10 +192,10 @@ __global__ __launch_bounds__(kThreads) void policy_dout_kernel(PDoutArgs A) {
     if (lane < 4) {
         const float* x = A.aux + (size_t)r * 16;
         float d_mean, d_logstd;
-        sac_policy_dout(lane == 0 ? da[0] : lane == 1 ? da[1] : lane == 2 ? da[2] : da[3], x[lane], x[4 + lane], x[8 + lane], alpha * A.inv_batch, d_mean, d_logstd);
+        sac_policy_dout(lane == 0 ? da[0] : lane == 1 ? da[1] : lane == 2 ? da[2] : da[3], x[lane], x[4 + lane], x[8 + lane], alpha * inv_batch, d_mean, d_logstd);
         A.pol.dout[(size_t)r * OW + lane] = d_mean;
         A.pol.dout[(size_t)r * OW + 4 + lane] = d_logstd;
-        if (lane == 0) atomicAdd(&A.losses[2], -alpha * x[12] * A.inv_batch);  // logged only
+        if (lane == 0) atomicAdd(&A.losses[2], -alpha * x[12] * inv_batch);  // logged only
     }
     // The mean entropy feeds the log-alpha step, so it must not depend on arrival order: the per-row entropies were written by
     // the head kernel before this launch, one wave adds them in a fixed order.
@@ -196,8 +203,81 @@ __global__ __launch_bounds__(kThreads) void policy_dout_kernel(PDoutArgs A) {
         float s = 0.0f;
         for (int rr = lane; rr < A.rows; rr += 64) s += A.aux[(size_t)rr * 16 + 12];
         s = wave_sum(s);
-        if (lane == 0) A.losses[4] = s * A.inv_batch;
+        if (lane == 0) A.losses[4] = s * A.inv_batch;  // (the UNWEIGHTED mean with weights too: stats/entropy, agent.py:351)
+        if (WEIGHTED) {  // the same order, with the weights: at w == 1 mean(w H) has the bits of the mean entropy and mean(w) is exactly 1
+            float sh = 0.0f, sw = 0.0f;
+            for (int rr = lane; rr < A.rows; rr += 64) {
+                sh += A.weights[rr] * A.aux[(size_t)rr * 16 + 12];
+                sw += A.weights[rr];
+            }
+            sh = wave_sum(sh);
+            sw = wave_sum(sw);
+            if (lane == 0) { A.wsum[0] = sh * A.inv_batch; A.wsum[1] = sw / (float)A.rows; }
+        }
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// SAC with importance weights (prioritized replay; SAC/agent.py:361-374, 408-414): the critics' TD head and the log-alpha step as kernels of their
+// own.  One wave per row.
+// ---------------------------------------------------------------------------------------------------------------
+// y = r + (1 - d) gamma (min Q_target(s', a') + alpha H'), errors = |Q1(s, a) - y|, q_h_loss += w (Q_h - y)^2 / B, head gradients 2 w (Q_h - y) / B:
+// what bwd_l2<0>'s prologue (BM_CRITIC_TD) computes, per row and with the weight; the critics' backward then runs with the head gradient given.
+struct TdHeadArgs {
+    const float* q1net; const float* q2net; const float* t1net; const float* t2net;
+    Mlp m;
+    Slot s1, s2;                              // Q1 / Q2 (s, a): z2 read; st2 and dout written
+    const float* z2_t1; const float* z2_t2;   // target Q1 / Q2 (s', a')
+    const float* rows;                        // [rows][32]: reward, done in columns 30, 31
+    const float* ent_next;                    // [rows] H'
+    const float* alpha_state;
+    const float* weights;
+    int nrows;
+    float gamma, inv_batch;
+    float* errors;                            // [rows] out
+    float* losses;
+};
+__global__ __launch_bounds__(kThreads) void td_head_weighted_kernel(TdHeadArgs A) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + wave;
+    if (r >= A.nrows) return;
+    RowReg<H2> xh, y;
+    float mean_, rstd_, t1[1], t2[1], q1[1], q2[1];
+    head_row<1, true>(A.z2_t1 + (size_t)r * H2, A.t1net, A.m, 0.0f, xh, y, mean_, rstd_, t1);
+    head_row<1, true>(A.z2_t2 + (size_t)r * H2, A.t2net, A.m, 0.0f, xh, y, mean_, rstd_, t2);
+    head_row<1, true>(A.s1.z2 + (size_t)r * H2, A.q1net, A.m, 0.0f, xh, y, mean_, rstd_, q1);
+    if (lane == 0) { A.s1.st2[r * 2] = mean_; A.s1.st2[r * 2 + 1] = rstd_; }
+    head_row<1, true>(A.s2.z2 + (size_t)r * H2, A.q2net, A.m, 0.0f, xh, y, mean_, rstd_, q2);
+    if (lane == 0) {
+        A.s2.st2[r * 2] = mean_; A.s2.st2[r * 2 + 1] = rstd_;
+        const float lab0 = A.rows[(size_t)r * 32 + 30], lab1 = A.rows[(size_t)r * 32 + 31];
+        const float qmin = fminf(t1[0], t2[0]);
+        const float target = lab0 + (1.0f - lab1) * (A.gamma * (qmin + A.ent_next[r] * A.alpha_state[3]));  // (bwd_l2<0>'s expression)
+        const float wb = A.weights[r] * A.inv_batch;
+        const float d1 = q1[0] - target, d2 = q2[0] - target;
+        A.errors[r] = fabsf(d1);
+        A.s1.dout[(size_t)r * OW] = 2.0f * d1 * wb;
+        A.s2.dout[(size_t)r * OW] = 2.0f * d2 * wb;
+        atomicAdd(&A.losses[0], d1 * d1 * wb);
+        atomicAdd(&A.losses[1], d2 * d2 * wb);
+    }
+}
+// entropy_loss = -mean(log_alpha (target_entropy - H) w) and alpha_optim.step() (agent.py:322-325, 408-414): what thread 0 of the policy's
+// weight-gradient launch does in the unweighted call, with the gradient mean(w H) - target_entropy mean(w).  One thread.
+struct AlphaStepArgs {
+    float* alpha_state; float* losses; const float* wsum;
+    float target_entropy, b1, b2, eps, step_size, bc2_sqrt;
+};
+__global__ __launch_bounds__(64) void alpha_step_weighted_kernel(AlphaStepArgs A) {
+    if (threadIdx.x != 0) return;
+    const float mean_wh = A.wsum[0], mean_w = A.wsum[1];
+    const float te = A.target_entropy * mean_w;
+    float la = A.alpha_state[0], m = A.alpha_state[1], v = A.alpha_state[2];
+    A.losses[3] = -(la * (te - mean_wh));  // entropy_loss with the log_alpha BEFORE its step
+    adam_update(la, m, v, mean_wh - te, A.b1, A.b2, A.eps, A.step_size, A.bc2_sqrt);
+    A.alpha_state[0] = la; A.alpha_state[1] = m; A.alpha_state[2] = v;
+    A.alpha_state[3] = expf(la);  // self.alpha = self.log_alpha.exp()
+    A.losses[5] = A.alpha_state[3];
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -492,18 +572,20 @@ static void launch_q_pi(const SacCtx& C) {
 // [q_select] -> both critics backward down to dh1 -> [policy_dout] -> policy(s) backward.
 // one call: min(Q1, Q2) is selected in the critics' backward prologue and the policy's head gradient is formed in the policy's backward
 // prologue (bwd_l2<4> / <5>) — q_select_kernel and policy_dout_kernel as launches of their own are the staged form
-static int launch_policy_tail(const SacCtx& C, bool one_call) {
+// weights / wsum (hx_sac_learn_weighted): the staged form with the weighted per-row kernels
+static int launch_policy_tail(const SacCtx& C, bool one_call, const float* weights = nullptr, float* wsum = nullptr) {
     const int B = C.B;
     const Slot* s = C.s;
     const HxSacNets* N = C.N;
     static const bool fold_env = !(getenv("HX_SAC_FOLD") && getenv("HX_SAC_FOLD")[0] == '0');  // A/B knob
     // The SAC bf16 path keeps the staged form: built in bf16, the folded one call gave policy b2 gradients that differ from the staged sequence's in
     // the last bit (77 of 512 entries at the first call; dW2 and every other gradient equal), so the fold has no bf16 instantiation (launch_bwd refuses).
-    const bool fold = one_call && fold_env && !C.im;
+    const bool fold = one_call && fold_env && !C.im && !weights;
     const unsigned nb = (unsigned)((B + 3) / 4);
     if (!fold) {
-        QSelArgs Q{C.q1, C.q2, kQs, s[SS_Q1P], s[SS_Q2P], B, 1.0f / B, N->losses};
-        hipLaunchKernelGGL(q_select_kernel, dim3(nb), dim3(kThreads), 0, C.st, Q);
+        QSelArgs Q{C.q1, C.q2, kQs, s[SS_Q1P], s[SS_Q2P], B, 1.0f / B, N->losses, weights};
+        if (weights) hipLaunchKernelGGL(q_select_kernel<true>, dim3(nb), dim3(kThreads), 0, C.st, Q);
+        else hipLaunchKernelGGL(q_select_kernel<false>, dim3(nb), dim3(kThreads), 0, C.st, Q);
     }
     {   // both critics backward down to dh1
         BwdArgs G{};
@@ -519,8 +601,9 @@ static int launch_policy_tail(const SacCtx& C, bool one_call) {
         if (int rc = launch_bwd(fold ? 4 : 3, G, C.st)) return rc;
     }
     if (!fold) {
-        PDoutArgs P{C.q1, C.q2, kQs, s[SS_Q1P], s[SS_Q2P], s[SS_PC], C.X.aux_c, N->alpha_state, B, 1.0f / B, N->losses};
-        hipLaunchKernelGGL(policy_dout_kernel, dim3(nb), dim3(kThreads), 0, C.st, P);
+        PDoutArgs P{C.q1, C.q2, kQs, s[SS_Q1P], s[SS_Q2P], s[SS_PC], C.X.aux_c, N->alpha_state, B, 1.0f / B, N->losses, weights, wsum};
+        if (weights) hipLaunchKernelGGL(policy_dout_kernel<true>, dim3(nb), dim3(kThreads), 0, C.st, P);
+        else hipLaunchKernelGGL(policy_dout_kernel<false>, dim3(nb), dim3(kThreads), 0, C.st, P);
     }
     BwdArgs G{};
     G.njobs = 1; G.slope = 0.0f; G.inv_batch = 1.0f / B; G.losses = N->losses;
@@ -537,7 +620,8 @@ static int launch_policy_tail(const SacCtx& C, bool one_call) {
 }
 // The policy's weight-gradient launch: W carries the caller's slots, weights and predraw; slot 0 is policy(s).  adam_step > 0 (the one call):
 // policy_optim.step() + the log-alpha step ride in it (the thread that produced a gradient steps it; thread 0 of the launch steps log_alpha)
-static void launch_policy_wg(WgArgs& W, const SacCtx& C, const HxHyper* Hy, int adam_step, float target_entropy) {
+// alpha_step = false (hx_sac_learn_weighted): the log-alpha step is a launch of its own behind this one
+static void launch_policy_wg(WgArgs& W, const SacCtx& C, const HxHyper* Hy, int adam_step, float target_entropy, bool alpha_step = true) {
     const HxSacNets* N = C.N;
     W.njobs = 1; W.slope = 0.0f; W.inv_batch = 1.0f / C.B;
     WgJob& J = W.job[0];
@@ -550,7 +634,7 @@ static void launch_policy_wg(WgArgs& W, const SacCtx& C, const HxHyper* Hy, int 
         if (C.im) { J.w2b = C.im + IM_ACTOR * kImgElems; J.w2tb = C.im + IM_ACTOR_T * kImgElems; }  // the bf16 path: forward (= acting) and transposed images
         set_adam_scalars(W.ad, Hy->lr_actor, adam_step);
         W.ad.losses = N->losses;
-        W.ad.alpha_state = N->alpha_state; W.ad.target_entropy = target_entropy; W.ad.alpha_step_size = W.ad.step_size;  // (alpha_optim: the policy's learning rate)
+        if (alpha_step) { W.ad.alpha_state = N->alpha_state; W.ad.target_entropy = target_entropy; W.ad.alpha_step_size = W.ad.step_size; }  // (alpha_optim: the policy's learning rate)
     }
     launch_wg(W, adam_step > 0, C.st);
 }
@@ -584,6 +668,96 @@ int hx_sac_learn(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, co
     HX_REQUIRE(step >= 1, "hx_sac_learn: step is 1-based");
     if (int rc = sac_critic_grads_impl(N, Bt, Hy, S, polyak_first, stream, step, true)) return rc;
     return sac_policy_grads_impl(N, Bt, Hy, stream, step, target_entropy);
+}
+
+/* SacAgent.learn with per-row importance weights (prioritized replay: SAC/agent.py:306-331, 361-374, 405, 408-414).  One GPU, fp32.  hx_sac_learn's
+ * staged helpers with the weighted per-row kernels in between (+), 13 launches (the one call: 9):
+ *     fwd_l2      policy(s'), policy(s), Q1 / Q2 (s, a); clears the loss sums
+ *     gauss       a', H' = policy.sample(s') and a~, H = policy.sample(s)  [+ the Polyak step of the targets behind them]
+ *     fwd_l2      target Q1 / Q2 (s', a')
+ *   + td_head     y, errors_out = |Q1 - y|, q_h_loss += w (Q_h - y)^2 / B, head gradients 2 w (Q_h - y) / B
+ *     bwd_l2<3>   both critics, head gradient given (instead of BM_CRITIC_TD's own TD head)
+ *     wgrad       critics + q1_optim / q2_optim steps
+ *     fwd_l2      Q1 / Q2 (s, a~) with the updated critics
+ *   + q_select<weighted>, bwd_l2<3> (critics), + policy_dout<weighted> (also mean(w H), mean(w)), bwd_l2<3> (policy)
+ *     wgrad       policy + policy_optim step (WITHOUT the log-alpha step)
+ *   + alpha_step  entropy_loss and alpha_optim.step() from mean(w H) - target_entropy mean(w) */
+int hx_sac_learn_weighted(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, const float* weights, float* errors_out, int32_t polyak_first,
+                          int32_t step, float target_entropy, void* stream) {
+    HX_REQUIRE(step >= 1, "hx_sac_learn_weighted: step is 1-based");
+    HX_REQUIRE(N && Bt && Hy && Bt->rows && Bt->batch > 0 && Bt->batch % 16 == 0 && weights && errors_out, "hx_sac_learn_weighted: bad arguments (nets, batch, hyper, weights, errors_out)");
+    HX_REQUIRE(!N->w2_bf16_all, "hx_sac_learn_weighted: the weighted update is fp32 only (nets->w2_bf16_all must be NULL)");
+    if (int rc = sac_check_formats(N, "hx_sac_learn_weighted")) return rc;
+    const SacCtx C(N, Bt, stream);
+    hipStream_t st = C.st;
+    const int B = C.B;
+    const Slot* s = C.s;
+    const SacAux& X = C.X;
+    const int nq = 2 * kQs.padded();
+    const float* t1 = N->target_critic; const float* t2 = N->target_critic + kQs.padded();
+    float* const wsum = X.aux_c + 16 * (size_t)B;  // two of the workspace's spare words behind the Gaussian heads' row buffers
+    const unsigned nb = (unsigned)((B + 3) / 4);
+    {   // policy(s'), policy(s), Q1/Q2(s, a)
+        FwdArgs F;
+        sac_launch_1(C, F);
+        launch_fwd(F, st);
+    }
+    {   // both Gaussian heads, the Polyak step of the targets behind them (agent.py:278-279: before the update)
+        const GaussArgs G{N->policy, kPolicy, s[SS_PN].z2, Bt->eps_next, B, Bt->eps_next ? 1 : 2, X.act_n, X.ent_n, nullptr, Bt->seed, 0x40000000u, Bt->call};
+        const GaussArgs G2 = gauss_cur(C);
+        launch_gauss(G, &G2, N->target_critic, N->critic, polyak_first ? nq : 0, Hy->tau, st, nullptr);
+    }
+    {   // target Q1/Q2 (s', a')
+        FwdArgs F{};
+        F.njobs = 2; F.slope = 0.0f;
+        F.job[0] = FwdJob{t1, kQs, C.src, 17, 3, Head{}, X.act_n, 0.f, s[SS_T1], B, 0, IM_TC1};
+        F.job[1] = FwdJob{t2, kQs, C.src, 17, 3, Head{}, X.act_n, 0.f, s[SS_T2], B, 0, IM_TC2};
+        launch_fwd(F, st);
+    }
+    {
+        TdHeadArgs T{C.q1, C.q2, t1, t2, kQs, s[SS_Q1], s[SS_Q2], s[SS_T1].z2, s[SS_T2].z2, Bt->rows, X.ent_n, N->alpha_state, weights, B, Hy->gamma, 1.0f / B,
+                     errors_out, N->losses};
+        hipLaunchKernelGGL(td_head_weighted_kernel, dim3(nb), dim3(kThreads), 0, st, T);
+    }
+    {   // both critics backward from the given head gradient
+        BwdArgs G{};
+        G.njobs = 2; G.slope = 0.0f; G.inv_batch = 1.0f / B; G.losses = N->losses;
+        for (int h = 0; h < 2; ++h) {
+            BwdJob& J = G.job[h];
+            J = BwdJob{};
+            J.net = h ? C.q2 : C.q1; J.m = kQs; J.ws = s[SS_Q1 + h]; J.rows = B; J.mode = BM_GIVEN; J.img_t = IM_C1_T + h;
+        }
+        if (int rc = launch_bwd(3, G, st)) return rc;
+    }
+    {   // grad_critic and q1_optim.step() / q2_optim.step() in one launch (sac_critic_grads_impl's)
+        WgArgs W{};
+        W.njobs = 2; W.slope = 0.0f; W.w_kind = 0; W.inv_batch = 1.0f / B; W.soft_count = nullptr; W.wstate = nullptr;
+        for (int h = 0; h < 2; ++h) {
+            WgJob& J = W.job[h];
+            J = WgJob{};
+            J.net = h ? C.q2 : C.q1; J.grad = N->grad_critic + h * kQs.padded(); J.m = kQs;
+            J.ws[0] = s[SS_Q1 + h]; J.rows[0] = B; J.nslots = 1; J.wmode[0] = 0;
+            J.p = N->critic + h * kQs.padded();
+            J.mom = N->m_critic + h * kQs.padded(); J.var = N->v_critic + h * kQs.padded();
+        }
+        set_adam_scalars(W.ad, Hy->lr_critic, step);
+        W.ad.losses = N->losses;
+        launch_wg(W, true, st);
+    }
+    launch_q_pi(C);
+    if (int rc = launch_policy_tail(C, false, weights, wsum)) return rc;
+    {
+        WgArgs W{};
+        W.job[0].nslots = 1;
+        launch_policy_wg(W, C, Hy, step, target_entropy, /*alpha_step=*/false);
+    }
+    {
+        AlphaStepArgs A{N->alpha_state, N->losses, wsum, target_entropy, 0.f, 0.f, 0.f, 0.f, 0.f};
+        set_adam_scalars(A, Hy->lr_actor, step);  // (alpha_optim: the policy's learning rate)
+        hipLaunchKernelGGL(alpha_step_weighted_kernel, dim3(1), dim3(64), 0, st, A);
+    }
+    HX_CHECK_LAUNCH("hx_sac_learn_weighted");
+    return 0;
 }
 
 /* ------------------------------------------------------------------------------------------------------------------

@@ -285,10 +285,18 @@ def main(config):
     isac = config.agent == "SAC" and config.type == "ISAC"  # SacAgent(imitative=True): the BC-gated policy loss; the minibatch is NOT expert-mixed
     if isac and (world > 1 or getattr(config, "dtype", "f32") != "f32" or not config.bc_actor):
         raise SystemExit("train_all: " + isac_refusal(config, world))
+    per = bool(getattr(config, "per", False))  # SacAgent(per=True): prioritized replay, the importance weights through the three losses
+    if per and per_refusal(config, world):
+        raise SystemExit("train_all: " + per_refusal(config, world))
     batch, buffer_size, checkpoint_rate = 128, config.buffer_size, config.checkpoint_rate  # train_all.py:190-208
     warm_up_rate = 20 if config.agent == "SAC" else 10  # train_sac.py:203 / train_all.py:207
 
-    replay = DeviceReplay(buffer_size, device)
+    if per:  # SAC/agent.py:112-118 (alpha 0.6, beta 0.4, beta_annealing 0.0001 are the reference's defaults)
+        from .utils.buffer import PrioritizedReplay
+
+        replay = PrioritizedReplay(buffer_size, device, alpha=config.per_alpha, beta=config.per_beta, beta_annealing=config.per_beta_annealing)
+    else:
+        replay = DeviceReplay(buffer_size, device)
     env = BatchedHarfangEnv(n, scenario=env_type, device=device, seed=seed, max_step=max_step, auto_reset=True,
                             random_reset=config.random, env_id0=rank * n, replay=replay)
     sac = config.agent == "SAC"
@@ -299,6 +307,8 @@ def main(config):
 
         eng = SE.SacEngine(batch=batch, lr=1e-3, device=device)
         eng.load_params(_xavier_mlp(13, 8), _xavier_mlp(17, 1), _xavier_mlp(17, 1))
+        if per:
+            eng.set_prioritized(replay)
     else:
         eng = E.HirlEngine(batch=batch, slope=0.0 if hirl else 0.01, use_bc=hirl, device=device)
         eng.load_params(init_actor_state_dict(), init_critic_state_dict(), init_actor_state_dict() if hirl else None)
@@ -367,6 +377,8 @@ def main(config):
         env.reset()
         for _ in range(math.ceil(20 * max_step / (n * world))):
             env.step(torch.rand((n, 4), device=device) * 2 - 1)
+        if per:
+            replay.mark_new()  # the exploration rows enter at the starting maximum priority
     expert_num, high_score, success_rate, arttir = run["expert_num"], run["high_score"], run["success_rate"], run["arttir"]
     actions = torch.zeros((n, 4), device=device)
     t0, episode0 = time.time(), run["episode"]
@@ -383,9 +395,11 @@ def main(config):
     shared_gpu = world > torch.cuda.device_count() and not os.environ.get("HX_FRONT_SHARED_GPU")
     front = (config.loop == "front" and not sac and not config.separate_launches and config.updates_per_step == 1 and batch <= 256
              and getattr(config, "dtype", "f32") in ("f32", "f32x9", "bf16") and not shared_gpu)
-    front_sac = (config.loop == "front" and sac and world == 1 and not config.separate_launches and config.updates_per_step == 1 and batch <= 256)
+    front_sac = (config.loop == "front" and sac and world == 1 and not config.separate_launches and config.updates_per_step == 1 and batch <= 256 and not per)
     if rank == 0:
         which = "front launch (env step + first launches of learn() in one launch; draw before the insert)" if (front or front_sac) else "reference order"
+        if per:  # the front loop draws before the step's insert: update_priority could then hit slots the step has overwritten
+            which += " (--per: the front launch draws before the step's insert, so the priorities of the drawn rows could be written into overwritten slots)"
         print(f"vector loop: {which}" + (f" ({world} ranks share a GPU: the front launch is for one process per GPU)" if (shared_gpu and config.loop == "front") else ""),
               flush=True)
     # The front launch's in-launch waits (launch B for launch A's rows, launch C for both) assume that the workgroups of ONE launch start in index order —
@@ -452,6 +466,8 @@ def main(config):
                 eng.act_step(env, seed=seed + 1, out=actions)              # replay ring depends on the workgroup schedule)
             else:
                 eng.act_step(env, sigma=0.1, seed=seed + 1, out=actions)
+            if per:
+                replay.mark_new(n)  # this step's rows enter at the running maximum priority (one launch, no host sync)
             if ret is not None:
                 ret += env.reward
             if step == max_step - 1:
@@ -473,6 +489,9 @@ def main(config):
                     writer.add_scalar(tag, v, step + episode * max_step)
             if isac and writer is not None and step % log_rate == 0:  # SAC/agent.py:353-359
                 log_imitative(writer, eng, step + episode * max_step)
+            if per and writer is not None and step % log_rate == 0:
+                writer.add_scalar("stats/per_beta", replay.beta, step + episode * max_step)
+                writer.add_scalar("stats/per_max_priority", replay.pmax, step + episode * max_step)
         if front and not tripped:
             tripped = front_tripped()  # ... and at every episode's end: nothing of a tripped episode reaches a validation, a checkpoint or a snapshot
         if tripped:
@@ -580,10 +599,32 @@ def isac_refusal(config, world=1):
     return None
 
 
+def per_refusal(config, world=1):
+    """why `--per` cannot run as asked, or None"""
+    if not getattr(config, "per", False):
+        return None
+    if config.agent != "SAC":
+        return f"--per goes with --agent SAC --type SAC (prioritized replay is SacAgent's: SAC/agent.py:112-118), not --agent {config.agent}"
+    if config.type == "ESAC":
+        return "--per with --type ESAC: the reference's learn() drops the expert rows when per is on (SAC/agent.py:281-284): use --type SAC"
+    if config.type == "ISAC":
+        return "--per with --type ISAC: prioritized replay with the imitative branch is not built: use --type SAC"
+    if config.type != "SAC":
+        return f"--per goes with --agent SAC --type SAC, not --type {config.type}"
+    if getattr(config, "dtype", "f32") != "f32":
+        return f"--per with --dtype {config.dtype}: the weighted update is fp32 only (its kernels have no bf16 form): drop --dtype"
+    if (config.gpus and config.gpus > 1) or world > 1:
+        return "--per runs on one GPU (priorities and block sums are not exchanged between ranks): use --gpus 1"
+    return None
+
+
 def parse_args(argv=None):
     """parser().parse_args with the cross-flag checks that are argparse errors"""
     p = parser()
     cfg = p.parse_args(argv)
+    why = per_refusal(cfg)
+    if why:
+        p.error(why)
     if cfg.type == "ISAC" and cfg.agent != "SAC":
         p.error("--type ISAC goes with --agent SAC")
     why = isac_refusal(cfg)
@@ -636,6 +677,11 @@ def parser():
     p.add_argument("--load_dir", type=str, default=None, help="--load_model: directory of the checkpoint files (default: this run's model dir)")
     p.add_argument("--load_tag", type=str, default="Agent20_successRate0.64", help="--load_model: checkpoint tag (train_all.py:240 hard-codes this one)")
     p.add_argument("--log_rewards", action="store_true", help="also log Training/Episode Reward (one more small launch per vector step)")
+    p.add_argument("--per", action="store_true", help="SAC: prioritized replay (SacAgent(per=True)): proportional draws with importance weights, priorities from "
+                                                      "|Q1 - y|; fp32, one GPU, --type SAC; the vector loop runs in the reference's order")
+    p.add_argument("--per_alpha", type=float, default=0.6, help="--per: priority exponent (SAC/agent.py:62)")
+    p.add_argument("--per_beta", type=float, default=0.4, help="--per: importance-weight exponent at the start (SAC/agent.py:62)")
+    p.add_argument("--per_beta_annealing", type=float, default=0.0001, help="--per: beta <- min(1, beta + this) per sample call (SAC/agent.py:63)")
     p.add_argument("--max_step", type=int, default=None, help="steps per episode (default: the scenario's, train_all.py:159-183: 1500 / 1500 / 1900); short rehearsal runs")
     p.add_argument("--status_check_every", type=int, default=256,
                    help="front loop: vector steps between reads of the front launch's status word (one host sync each; 0: only at every episode's end)")

@@ -4,6 +4,8 @@ Rows are 32 fp32 words = one 128-B line: s[13] a[4] s'[13] r done (Transition, b
 in a parallel int8 array because sample() never returns it, buffer.py:47-48).  `total` counts transitions ever
 stored; position = total % capacity (buffer.py:36), len = min(total, capacity).
 """
+import ctypes
+
 import torch
 
 from .. import _lib
@@ -42,6 +44,93 @@ class DeviceReplay:
             self.success[idx] = success.to(self.device, torch.int8)
         self.total += k
         self.fixed_len = min(start + k, self.capacity)  # host-known live length (tables filled once: expert ring)
+
+
+
+class HxPer(ctypes.Structure):
+    """the prioritized store's buffers (include/hirl4ucav.h HxPer)"""
+    _fields_ = [("prio", ctypes.c_void_p), ("bsum", ctypes.c_void_p), ("pmax", ctypes.c_void_p), ("marked", ctypes.c_void_p), ("ticket", ctypes.c_void_p),
+                ("total", ctypes.c_void_p), ("cap", ctypes.c_int64)]
+
+
+_vp, _i32 = ctypes.c_void_p, ctypes.c_int32
+_lib.register("hx_per_mark_new", [ctypes.POINTER(HxPer), ctypes.c_int64, _vp])
+_lib.register("hx_per_set", [ctypes.POINTER(HxPer), _vp, _vp, _i32, _vp])
+_lib.register("hx_per_update", [ctypes.POINTER(HxPer), _vp, _vp, _i32, ctypes.c_float, _vp])
+_lib.register("hx_per_resum", [ctypes.POINTER(HxPer), _vp])
+_lib.register("hx_per_sample", [ctypes.POINTER(HxPer), _vp, _i32, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_float, _vp, _vp, _vp, _vp])
+
+PER_BLOCK, PER_EPS, PER_MAX_CAPACITY = 1024, 1e-4, 1 << 24
+
+
+class PrioritizedReplay(DeviceReplay):
+    """The ring with a priority per slot (SacAgent(per=True), SAC/agent.py:112-118; the memory class itself is rltorch's and un-vendored, so the
+    store and the draw are this project's definition: include/hirl4ucav.h "Prioritized replay").  prio[slot] = (|delta| + 1e-4)^alpha, 0 = not live;
+    bsum = one fixed-order sum per 1,024 slots; pmax = running maximum (new rows enter at it: mark_new); beta <- min(1, beta + beta_annealing)
+    per sample call, on the host.  Everything enqueues on the current stream; nothing synchronises."""
+
+    def __init__(self, capacity, device="cuda", ordered_slots=False, alpha=0.6, beta=0.4, beta_annealing=0.0001):
+        if int(capacity) > PER_MAX_CAPACITY:
+            raise ValueError(f"prioritized replay holds at most 2^24 slots (capacity {int(capacity)}): the sampler scans 16,384 block sums")
+        super().__init__(capacity, device, ordered_slots)
+        L = _lib.load()
+        if L.hx_per_sizeof() != ctypes.sizeof(HxPer):
+            raise _lib.HxError(f"ABI mismatch: HxPer is {ctypes.sizeof(HxPer)} bytes here, {L.hx_per_sizeof()} in {_lib.SO_PATH}")
+        self.alpha, self.beta, self.beta_annealing = float(alpha), float(beta), float(beta_annealing)
+        self.nblocks = (self.capacity + PER_BLOCK - 1) // PER_BLOCK
+        self._prio = torch.zeros(self.nblocks * PER_BLOCK, dtype=torch.float32, device=self.device)  # (the padding behind capacity stays 0)
+        self.prio = self._prio[:self.capacity]
+        self.bsum = torch.zeros(self.nblocks, dtype=torch.float32, device=self.device)
+        self._header = torch.zeros(4, dtype=torch.int64, device=self.device)  # word 0: pmax (a float), 1: marked, 2: the launches' ticket
+        self.pmax_t = self._header[:1].view(torch.float32)[:1]
+        self.pmax_t.fill_(1.0)
+        self.marked_t = self._header[1:2]
+        self.per = HxPer(self._prio.data_ptr(), self.bsum.data_ptr(), self._header.data_ptr(), self._header[1:].data_ptr(), self._header[2:].data_ptr(),
+                         self.total.data_ptr(), self.capacity)
+
+    @property
+    def pmax(self):  # host sync (drivers / tests)
+        return float(self.pmax_t.item())
+
+    @property
+    def marked(self):  # host sync
+        return int(self.marked_t.item())
+
+    def mark_new(self, max_new=None):
+        """every slot stored since the last call enters at pmax.  max_new: an upper bound on their number (the envs stepped); default: the whole ring"""
+        _lib.call("hx_per_mark_new", ctypes.byref(self.per), int(max_new) if max_new else self.capacity, _lib.stream_ptr())
+
+    def set_priorities(self, slots, p):
+        """prio[slots] <- p (already raised to alpha)"""
+        slots = torch.as_tensor(slots, device=self.device).to(torch.int32).contiguous().reshape(-1)
+        p = torch.as_tensor(p, device=self.device).to(torch.float32).contiguous().reshape(-1)
+        if slots.numel() != p.numel() or slots.numel() == 0:
+            raise ValueError("set_priorities: as many priorities as slots, at least one")
+        _lib.call("hx_per_set", ctypes.byref(self.per), slots.data_ptr(), p.data_ptr(), slots.numel(), _lib.stream_ptr())
+
+    def update(self, idx, errors):
+        """memory.update_priority(indices, errors) (SAC/agent.py:329-331): prio[idx] <- (|errors| + 1e-4)^alpha, the maximum where a slot repeats"""
+        idx = torch.as_tensor(idx, device=self.device).to(torch.int32).contiguous().reshape(-1)
+        errors = torch.as_tensor(errors, device=self.device).to(torch.float32).contiguous().reshape(-1)
+        if idx.numel() != errors.numel() or idx.numel() == 0:
+            raise ValueError("update: as many errors as indices, at least one")
+        _lib.call("hx_per_update", ctypes.byref(self.per), idx.data_ptr(), errors.data_ptr(), idx.numel(), self.alpha, _lib.stream_ptr())
+
+    def resum(self):
+        _lib.call("hx_per_resum", ctypes.byref(self.per), _lib.stream_ptr())
+
+    def next_beta(self):
+        """the beta of this sample call; advances the annealing (host)"""
+        b = self.beta
+        self.beta = min(1.0, self.beta + self.beta_annealing)
+        return b
+
+    def sample_into(self, batch, idx, weights, rows, u=None, seed=0, call=0, beta=None):
+        """hx_per_sample: `batch` proportional draws with replacement -> idx (int32), weights, the rows' tile.  u: injected uniforms [batch], else Philox"""
+        beta = self.next_beta() if beta is None else float(beta)
+        _lib.call("hx_per_sample", ctypes.byref(self.per), self.ring.data_ptr(), int(batch), _lib.ptr(u), int(seed), int(call), beta, idx.data_ptr(),
+                  weights.data_ptr(), rows.data_ptr(), _lib.stream_ptr())
+        return beta
 
 
 # ---- reference-API façade -------------------------------------------------------------------------------------------

@@ -21,6 +21,8 @@ def engine_state(eng):
         st["acting_format"] = eng.acting_format()  # the run's arithmetic is part of its state (train_all.py: --dtype; here: what the flag does not say)
     if getattr(eng, "imitative", False):  # SAC's imitative branch only (a plain SAC snapshot stays as it was): the frozen BC actor and the expert-draw counter
         st["imitative"] = {"bc_actor": eng.bc_actor.detach().cpu().clone(), "bc_slope": eng.bc_slope, "expert_calls": eng.expert_calls}
+    if getattr(eng, "prioritized", None) is not None:  # (a plain snapshot carries no such key)
+        st["prioritized"] = True
     return st
 
 
@@ -34,6 +36,8 @@ def load_engine_state(eng, st):
         # (a snapshot from before round 6 carries no format: round 5's default, or round 4's x9_rows = 16,384 with nine terms — it cannot tell)
         warnings.warn(f"snapshot was written under acting format {was if was is not None else 'unrecorded (a round <= 5 snapshot)'}, this engine "
                       f"acts under {now}: the run continues under other acting arithmetic (fp32 results up to summation order)", stacklevel=2)
+    if bool(st.get("prioritized", False)) != (getattr(eng, "prioritized", None) is not None):
+        raise ValueError("snapshot and engine disagree about prioritized replay (--per): resume with the flag the run was started with")
     if ("imitative" in st) != bool(getattr(eng, "imitative", False)):
         raise ValueError("snapshot and engine disagree about SAC's imitative branch (--type ISAC): resume with the type the run was started with")
     eng.arena.copy_(st["arena"])
@@ -52,17 +56,30 @@ def load_engine_state(eng, st):
 
 def replay_state(replay):
     n = min(int(replay.total.item()), replay.capacity)
-    return {"capacity": replay.capacity, "total": int(replay.total.item()), "ring": replay.ring[:n].cpu().clone(),
-            "success": replay.success[:n].cpu().clone()}
+    st = {"capacity": replay.capacity, "total": int(replay.total.item()), "ring": replay.ring[:n].cpu().clone(),
+          "success": replay.success[:n].cpu().clone()}
+    if hasattr(replay, "prio"):  # a prioritized replay only (a plain snapshot stays as it was): the block sums are recomputed on load
+        st["per"] = {"prio": replay.prio[:n].cpu().clone(), "pmax": replay.pmax_t.cpu().clone(), "marked": replay.marked, "beta": replay.beta,
+                     "alpha": replay.alpha, "beta_annealing": replay.beta_annealing}
+    return st
 
 
 def load_replay_state(replay, st):
     if st["capacity"] != replay.capacity:
         raise ValueError(f"snapshot replay capacity {st['capacity']} != {replay.capacity}")
+    if ("per" in st) != hasattr(replay, "prio"):
+        raise ValueError("snapshot and replay disagree about prioritized replay (--per): resume with the flag the run was started with")
     n = st["ring"].shape[0]
     replay.ring[:n].copy_(st["ring"])
     replay.success[:n].copy_(st["success"])
     replay.total.fill_(st["total"])
+    if "per" in st:
+        replay.prio.zero_()
+        replay.prio[:n].copy_(st["per"]["prio"])
+        replay.pmax_t.copy_(st["per"]["pmax"])
+        replay.marked_t.fill_(st["per"]["marked"])
+        replay.beta = st["per"]["beta"]
+        replay.resum()
 
 
 def env_state(env):

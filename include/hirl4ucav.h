@@ -74,8 +74,9 @@ const char* hx_last_error(void);
  * bumping this: a 9-word stats buffer then took atomics up to word 504).  110: round 4 (hx_abi_sizes, hx_rccl_*, hx_allreduce_twostage).
  * 113: round 5.  114: round 6 (hx_rccl_allreduce_bf16).  115: the SAC bf16 path (HxSacNets.w2_bf16_all / policy_w2_bf16, hx_sac_*_bf16).
  * 116: SAC's imitative branch (HxSacImit, hx_sac_imit_*, hx_sac_policy_grads_imitative, hx_sac_learn_imitative).
- * 117: hx_sac_front takes any number of envs (the per-tile acting role up to 8,192; it refused them before). */
-#define HX_ABI_VERSION 117
+ * 117: hx_sac_front takes any number of envs (the per-tile acting role up to 8,192; it refused them before).
+ * 118: prioritized replay for SAC (HxPer, hx_per_*, hx_sac_learn_weighted). */
+#define HX_ABI_VERSION 118
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -569,6 +570,72 @@ int hx_sac_policy_grads_imitative(const HxSacNets* nets, const HxSacBatch* batch
  * drawn as hx_sample_batch draws them.  Bit-identical to hx_sac_critic_step + hx_sac_policy_grads_imitative + hx_sac_adam(which = 1). */
 int hx_sac_learn_imitative(const HxSacNets* nets, const HxSacBatch* batch, const HxHyper* hyper, const HxSample* sample, const HxSacImit* imit,
                            const HxSample* expert_sample, int32_t polyak_first, int32_t step, float target_entropy, void* stream);
+
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Prioritized replay (SacAgent(per=True): SAC/agent.py:112-118, 281-284, 306-331).  The reference takes `batch, indices, weights` from
+ * rltorch.PrioritizedMemory, carries the per-row weights through its three losses and hands |Q1(s, a) - y| back as the new priorities.  The
+ * memory class is un-vendored, so the store and the draw are THIS project's definition (the loss arithmetic is the reference's: below):
+ *     stored priority  p_i = (|delta_i| + 1e-4)^alpha; 0 = the slot is not live
+ *     draw             row r: target u_r S with S = sum of all priorities -> the slot whose interval of the running sum holds it: independent,
+ *                      proportional to p, WITH replacement; never a slot of priority 0, never one beyond the live length
+ *     weight           w_r = (n p_r / S)^-beta / max_r(.), n = min(*total, cap): the largest weight of a batch is exactly 1
+ *     new rows         enter at the running maximum priority pmax (hx_per_mark_new), not at a TD error of their own
+ * State beside a replay ring of `cap` <= 2^24 slots, all device memory owned by the caller:
+ *     prio   [hx_per_prio_floats(cap)] = cap rounded up to a multiple of 1,024, 16-byte aligned; the padding stays 0
+ *     bsum   [ceil(cap / 1024)] one sum per block of 1,024 consecutive slots, always formed in one fixed order (never by float atomics):
+ *            the same bits for the same prio
+ *     pmax   one float: the running maximum of stored priorities (start it at 1); marked: the `total` up to which slots have been given a
+ *            priority (start 0); ticket: one zeroed word the launches use among themselves
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct HxPer {
+    float* prio; float* bsum; float* pmax;
+    uint64_t* marked; uint32_t* ticket;
+    const uint64_t* total; /* the ring's counter (HxStepOpts.total) */
+    int64_t cap;
+} HxPer;
+int hx_per_sizeof(void); /* sizeof(HxPer) of the loaded library (hx_abi_sizes has no free word) */
+int64_t hx_per_prio_floats(int64_t cap);
+/* Every slot in [marked, *total) mod cap <- pmax, the touched blocks re-summed, marked <- *total; more than cap new rows: the whole ring.  One
+ * launch; max_new = the caller's upper bound on the rows stored since the last call (the envs stepped) sizes its grid — if more arrived, the
+ * first max_new are marked and `marked` advances by as much.  Works with the unordered slot allocation: the slots a step claims are the
+ * contiguous range of `total`. */
+int hx_per_mark_new(const HxPer* per, int64_t max_new, void* stream);
+/* prio[slots[i]] <- p[i] (already raised to alpha; several values for one slot: the largest), blocks re-summed, pmax raised.  A pair with a
+ * slot outside [0, cap) or a negative / non-finite value is skipped.  (memory.append(..., error), resume, tests) */
+int hx_per_set(const HxPer* per, const int32_t* slots, const float* p, int32_t n, void* stream);
+/* memory.update_priority(indices, errors) (SAC/agent.py:329-331): prio[idx[r]] <- (|errors[r]| + 1e-4)^alpha (powf); a slot drawn several times
+ * keeps the MAXIMUM (unsigned atomicMax on the bits of a non-negative float: order-independent); blocks re-summed, pmax raised.  A non-finite
+ * error leaves its slot as it was. */
+int hx_per_update(const HxPer* per, const int32_t* idx, const float* errors, int32_t n, float alpha, void* stream);
+/* every block sum again from prio (after prio was written directly: a restored snapshot) */
+int hx_per_resum(const HxPer* per, void* stream);
+/* memory.sample(batch_size) -> batch, indices, weights (SAC/agent.py:281-284).  One workgroup, as hx_sample_batch.  u[batch] in [0, 1] injected (u = 1, which a
+ * float64 uniform below 1 can round to, is a target AT S and resolves like one that rounded to it), or NULL: Philox4x32-10(seed; row, call, a stream
+ * word of its own).  The block by an inclusive scan of bsum in LDS, the slot by one wave's scan of the
+ * block's 1,024 priorities; a target that rounds to S or lands on empty slots resolves to the nearest LOWER slot that holds priority.  Writes
+ * idx[batch], weights[batch] (powf) and the rows into the compact tile rows[batch][HX_ROW_WORDS].  batch <= 1024.  The promise "never a slot of
+ * priority 0, never one beyond the live length" needs SOME slot to hold priority: sampling while S = 0 (nothing marked or set yet) is the caller's
+ * error, which the device cannot refuse — every row is then slot 0 with weight 1.  Beyond 2^23 slots the scan holds the block sums in pairs (8,192
+ * entries of LDS); tests/test_per_gpu.py runs that form at 2^23 + 2,048 slots. */
+int hx_per_sample(const HxPer* per, const float* ring, int32_t batch, const float* u, uint64_t seed, uint32_t call, float beta, int32_t* idx,
+                  float* weights, float* rows, void* stream);
+/* SacAgent.learn with per-row importance weights (SAC/agent.py:306-331, 361-374, 405, 408-414), one GPU, fp32 (with nets->w2_bf16_all set: an
+ * error), on the minibatch in batch->rows:
+ *     q_h_loss     = mean((Q_h(s, a) - y)^2 w)            -> losses[0..1]        errors_out[r] = |Q1(s, a) - y|_r
+ *     policy_loss  = mean((-min Q(s, a~) - alpha H) w)    -> losses[2]           losses[4] = mean H, UNWEIGHTED (agent.py:351)
+ *     entropy_loss = -mean(log_alpha (target_entropy - H) w) -> losses[3]; the log-alpha step takes its gradient mean(w H) - target_entropy mean(w)
+ * Built from hx_sac_learn's STAGED helpers with per-row kernels of its own in between (+) — 13 launches against the one call's 9: forward (policy(s'),
+ * policy(s), Q1/Q2(s, a)); Gaussian heads [+ Polyak]; target critics forward; + the weighted TD head (y, errors, both critics' head gradients);
+ * critics backward (head gradient given); critics weight gradient + Adam; Q1/Q2(s, a~) forward; + weighted min(Q1, Q2) selection; critics backward;
+ * + weighted policy head gradient; policy backward; policy weight gradient + Adam (without the log-alpha step); + the log-alpha step.  With weights == 1 the call is NOT
+ * bit-identical to hx_sac_learn: its TD head is a per-row kernel (head_row from global memory) where the one call's is a backward prologue (head_regs
+ * from an LDS image) — one formula, two instruction sequences that do not round alike.  Measured after 3 calls at B = 128: up to 1.5e-8 in parameters
+ * (about 5,000 policy and 7,000 critic entries differ), one ulp in the alpha state; tests/test_per_gpu.py holds every network, Adam moment, the alpha
+ * state and the acting image to bars of their own (parameters: tests/test_sac_gpu.py's bar).  The policy half and the log-alpha step are the staged
+ * arithmetic on the same numbers (at w == 1, mean(w) is exactly 1 and mean(w H) has the mean entropy's bits).  step is 1-based. */
+int hx_sac_learn_weighted(const HxSacNets* nets, const HxSacBatch* batch, const HxHyper* hyper, const float* weights, float* errors_out,
+                          int32_t polyak_first, int32_t step, float target_entropy, void* stream);
 
 
 /* ------------------------------------------------------------------------------------------------------------
