@@ -112,14 +112,20 @@ class SacAgent:
                  target_update_interval=3, eval_interval=1000, cuda=True):
         if tuple(observation_space.shape) != (13,) or tuple(action_space.shape) != (4,) or list(hidden_units) != [256, 512]:
             raise NotImplementedError("the HIP kernels are built for train_sac.py's shape: 13 / 4 / hidden [256, 512]")
-        if (per and imitative) or multi_step != 1 or not entropy_tuning or grad_clip is not None:
-            raise NotImplementedError("built: uniform replay (with or without imitative=True) or prioritized replay (per=True, without imitative), multi_step 1, "
-                                      "entropy tuning, no gradient clipping; per with imitative=True, multi_step != 1, entropy_tuning=False and grad_clip are not")
+        if (per and imitative) or multi_step != 1 or (imitative and (not entropy_tuning or grad_clip is not None)):
+            raise NotImplementedError("built: uniform replay (with or without imitative=True) or prioritized replay (per=True, without imitative), multi_step 1; "
+                                      "without imitative also entropy_tuning=False (a fixed ent_coef) and grad_clip; per with imitative=True, multi_step != 1, and "
+                                      "entropy_tuning=False or grad_clip with imitative=True (SacEngine.set_grad_clip / set_entropy_tuning take them) are not")
         self.observation_space, self.action_space = observation_space, action_space
         self.device = device
         self.eng = SE.SacEngine(batch=batch_size, lr=lr, gamma=gamma ** multi_step, tau=tau, target_entropy=-float(np.prod(action_space.shape)),
                                 target_update_interval=target_update_interval, device=device)
         self.eng.load_params(_xavier_mlp(13, 8), _xavier_mlp(17, 1), _xavier_mlp(17, 1))
+        if grad_clip is not None:  # update_params(optim, network, loss, grad_clip), agent.py:310-320
+            self.eng.set_grad_clip(grad_clip)
+        if not entropy_tuning:  # agent.py:108-110: a constant alpha, no log-alpha optimiser
+            self.eng.set_entropy_tuning(False, ent_coef)
+        self.grad_clip = grad_clip
         self.per = bool(per)
         if self.per:  # agent.py:112-118
             self.memory = PrioritizedDeviceMemory(memory_size, alpha=alpha, beta=beta, beta_annealing=beta_annealing)

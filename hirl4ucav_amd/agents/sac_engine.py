@@ -52,6 +52,9 @@ _lib.register("hx_sac_policy_grads", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHype
 _lib.register("hx_sac_adam", [_P(HxSacNets), _P(E.HxHyper), _i32, _i32, _f32, _f32, _vp])
 _lib.register("hx_sac_policy_grads_imitative", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _P(HxSacImit), _vp])
 _lib.register("hx_sac_learn_weighted", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _vp, _vp, _i32, _i32, ctypes.c_float, _vp])
+_lib.register("hx_sac_grad_norm", [_P(HxSacNets), _i32, _vp, _vp])
+_lib.register("hx_sac_adam_clipped", [_P(HxSacNets), _P(E.HxHyper), _i32, _i32, _f32, _f32, _f32, _vp, _vp])
+_lib.register("hx_sac_learn_weighted_clipped", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _vp, _vp, _i32, _i32, ctypes.c_float, _f32, _vp, _vp])
 _lib.register("hx_sac_learn_imitative", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _P(E.HxSample), _P(HxSacImit), _P(E.HxSample), _i32, _i32,
                                           ctypes.c_float, _vp])
 
@@ -163,6 +166,51 @@ class SacEngine:
         self._pending, self._pending_expert = None, None  # draws sample(defer=True) / sample_expert(defer=True) recorded for the next learn()
         self._front_tiles, self._front_drawn = None, None  # step_learn: the two sets of minibatch tiles, and what the set in waiting was drawn for
         self.prioritized, self.per_weights, self.per_errors = None, None, None  # set_prioritized
+        self.grad_clip, self.clip_ws = None, None  # set_grad_clip
+        self.entropy_tuning, self.ent_coef = True, None  # set_entropy_tuning
+
+    def set_grad_clip(self, max_norm):
+        """SacAgent(grad_clip=max_norm) (SAC/utils.py:15-21, agent.py:310-320): from now on learn() scales each network's gradient — Q1, Q2 and the policy,
+        one norm each — to a global L2 norm of at most max_norm before its Adam step: gradients -> hx_sac_grad_norm -> hx_sac_adam_clipped per half
+        (the staged sequence plus one norm launch per half; the one call's optimizer steps ride in the weight-gradient launches and cannot wait for a norm).  The log-alpha step is never clipped.
+        None: back to the unclipped update.  One GPU."""
+        if max_norm is None:
+            self.grad_clip = None
+            return
+        max_norm = float(max_norm)
+        if not max_norm > 0.0:
+            raise ValueError(f"grad_clip is a positive maximum norm, got {max_norm}")
+        if self.world > 1:
+            raise _lib.HxError("gradient clipping runs on one GPU (the norm is taken over this rank's gradient, before any exchange): run it with --gpus 1")
+        if self.clip_ws is None:
+            L = _lib.load()
+            L.hx_sac_clip_floats.restype = ctypes.c_int64
+            self.clip_ws = torch.zeros(int(L.hx_sac_clip_floats()), dtype=torch.float32, device=self.device)
+        self.grad_clip = max_norm
+
+    def set_entropy_tuning(self, on, ent_coef=0.2):
+        """SacAgent(entropy_tuning=False, ent_coef=x) (agent.py:108-110, 322-327): alpha = ent_coef for good — alpha_state[3] holds it, the log-alpha state is
+        not touched and no log-alpha step runs in any form of learn() (the calls get target_entropy = NaN, HX_SAC_FIXED_ALPHA); losses[3] (entropy_loss) stays 0, losses[5] == ent_coef.  on=True: entropy tuning
+        resumes from the log-alpha state as it stands (alpha = exp(log_alpha))."""
+        self.entropy_tuning = bool(on)
+        if on:
+            self.ent_coef = None
+            self.alpha_state[3] = torch.exp(self.alpha_state[0])
+        else:
+            self.ent_coef = float(ent_coef)
+            self.alpha_state[3] = self.ent_coef
+        self.losses[5] = self.alpha_state[3]
+
+    def _target_entropy(self):
+        """what the hx_sac_* calls take as target_entropy: NaN (HX_SAC_FIXED_ALPHA) under a fixed entropy coefficient — no log-alpha step anywhere"""
+        return self.target_entropy if self.entropy_tuning else float("nan")
+
+    def grad_norms_host(self):
+        """((norm_q1, norm_q2, norm_policy), (coef_q1, coef_q2, coef_policy)) of the last clipped learn(): the norms BEFORE clipping"""
+        if self.clip_ws is None:
+            raise _lib.HxError("grad_norms_host: no clip was ever set (set_grad_clip)")
+        v = self.clip_ws[:6].tolist()
+        return tuple(v[:3]), tuple(v[3:])
 
     def set_prioritized(self, replay):
         """SacAgent(per=True) (agent.py:281-284, 306-331): from now on sample() on `replay` (a utils.buffer.PrioritizedReplay) draws proportionally to
@@ -421,6 +469,7 @@ class SacEngine:
         else:
             batch = HxSacBatch(self.rows.data_ptr(), self.batch, None, None, self._seed, self.learning_steps + 1)
         nets, hyper, gs, bt = ctypes.byref(self.nets), ctypes.byref(self.hyper), 1.0 / self.world, ctypes.byref(batch)
+        te = self._target_entropy()
         self.learning_steps += 1
         pending, self._pending = self._pending, None
         smp = ctypes.byref(pending[0]) if pending is not None else None
@@ -435,20 +484,28 @@ class SacEngine:
                                    "clear separate_critic_adam and staged_policy")
             if pending is not None:
                 raise _lib.HxError("prioritized replay: the minibatch comes from sample() on the prioritized replay, but a deferred uniform draw is pending")
-            _lib.call("hx_sac_learn_weighted", nets, bt, hyper, self.per_weights.data_ptr(), self.per_errors.data_ptr(), polyak_first, self.learning_steps,
-                      self.target_entropy, st)
+            if self.grad_clip is not None:
+                _lib.call("hx_sac_learn_weighted_clipped", nets, bt, hyper, self.per_weights.data_ptr(), self.per_errors.data_ptr(), polyak_first,
+                          self.learning_steps, te, self.grad_clip, self.clip_ws.data_ptr(), st)
+            else:
+                _lib.call("hx_sac_learn_weighted", nets, bt, hyper, self.per_weights.data_ptr(), self.per_errors.data_ptr(), polyak_first, self.learning_steps,
+                          te, st)
             _lib.call("hx_per_update", ctypes.byref(self.prioritized.per), self._idx.data_ptr(), self.per_errors.data_ptr(), self.batch, self.prioritized.alpha, st)
             return
         imit = ctypes.byref(self.imit) if self.imitative else None
         pe, self._pending_expert = self._pending_expert, None
-        fused_critic = self.world == 1 and not self.separate_critic_adam
-        if fused_critic and not self.staged_policy:
+        clip = self.grad_clip
+        if clip is not None and self.world > 1:
+            raise _lib.HxError("gradient clipping runs on one GPU (the norm is taken over this rank's gradient, before any exchange): run it with --gpus 1")
+        cw = self.clip_ws.data_ptr() if clip is not None else None
+        fused_critic = self.world == 1 and not self.separate_critic_adam and clip is None
+        if fused_critic and not self.staged_policy and clip is None:
             # one GPU: the whole learn() in one call (plain: 9 launches, bit-identical to the staged sequence below, 14 launches)
             if imit is not None:
                 _lib.call("hx_sac_learn_imitative", nets, bt, hyper, smp, imit, ctypes.byref(pe[0]) if pe is not None else None, polyak_first,
-                          self.learning_steps, self.target_entropy, st)
+                          self.learning_steps, te, st)
             else:
-                _lib.call("hx_sac_learn", nets, bt, hyper, smp, polyak_first, self.learning_steps, self.target_entropy, st)
+                _lib.call("hx_sac_learn", nets, bt, hyper, smp, polyak_first, self.learning_steps, te, st)
             return
         if imit is not None and pe is not None:  # the staged form draws the deferred expert rows with a launch of its own
             _gather(pe[0], self.batch, self.expert_rows, st=st)
@@ -462,7 +519,11 @@ class SacEngine:
             else:
                 _lib.call("hx_sac_critic_grads", nets, bt, hyper, polyak_first, st)
             self._allreduce(self.grad_critic)
-            _lib.call("hx_sac_adam", nets, hyper, 0, self.learning_steps, gs, self.target_entropy, st)
+            if clip is not None:  # a global norm needs every gradient written before any parameter steps: gradients -> norm -> clipped step
+                _lib.call("hx_sac_grad_norm", nets, 0, cw, st)
+                _lib.call("hx_sac_adam_clipped", nets, hyper, 0, self.learning_steps, gs, te, clip, cw, st)
+            else:
+                _lib.call("hx_sac_adam", nets, hyper, 0, self.learning_steps, gs, te, st)
         # the policy half
         if imit is not None:
             _lib.call("hx_sac_policy_grads_imitative", nets, bt, hyper, imit, st)
@@ -472,7 +533,11 @@ class SacEngine:
             self._allreduce(self.grad_policy)
             self._allreduce(self.losses)
             self.losses.mul_(gs)
-        _lib.call("hx_sac_adam", nets, hyper, 1, self.learning_steps, gs, self.target_entropy, st)
+        if clip is not None:  # (the imitative branch: on the combined (1 - w) dL + w dL_bc in grad_policy)
+            _lib.call("hx_sac_grad_norm", nets, 1, cw, st)
+            _lib.call("hx_sac_adam_clipped", nets, hyper, 1, self.learning_steps, gs, te, clip, cw, st)
+        else:
+            _lib.call("hx_sac_adam", nets, hyper, 1, self.learning_steps, gs, te, st)
 
     def step_learn(self, env, expert=None, n_main=None, explore=True, act_seed=0, out=None, sample_seed=0):
         """One iteration of the vector loop — act_step(env) then sample(env.replay, ..., defer=True) then learn() — in FRONT form (include/hirl4ucav.h
@@ -508,6 +573,11 @@ class SacEngine:
             self.sample_expert(expert, seed=sample_seed, defer=True)
             self.learn()
             return res
+        if self.grad_clip is not None:  # no front form: the clipped update is the staged sequence, whose first launch is its own (the reference's order)
+            res = self.act_step(env, explore=explore, seed=act_seed, out=out)
+            self.sample(replay, expert, n_main=n_main, seed=sample_seed, defer=True)
+            self.learn()
+            return res
         if self.act_dtype != self.update_dtype:  # bf16 acting beside the fp32 update: the front launch has no such mix (the reference's order)
             res = self.act_step(env, explore=explore, seed=act_seed, out=out)
             self.sample(replay, expert, n_main=n_main, seed=sample_seed, defer=True)
@@ -537,7 +607,7 @@ class SacEngine:
         env.steps_issued += 1
         nxt_draw = _draw(replay, expert, n_main, sample_seed, self.sample_calls + 1, nxt[1], guard=n)
         polyak_first = int(self.learning_steps % self.interval == 0)
-        _lib.call("hx_sac_learn_back", nets, ctypes.byref(batch), hyper, polyak_first, self.learning_steps, self.target_entropy, ctypes.byref(nxt_draw),
+        _lib.call("hx_sac_learn_back", nets, ctypes.byref(batch), hyper, polyak_first, self.learning_steps, self._target_entropy(), ctypes.byref(nxt_draw),
                   nxt[0].data_ptr(), st)
         self._front_drawn = (env, env.steps_issued, replay, expert, n_main, int(sample_seed), self.sample_calls + 1, n)
         self._front_tiles = [nxt, cur]

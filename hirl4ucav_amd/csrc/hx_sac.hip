@@ -634,7 +634,7 @@ static void launch_policy_wg(WgArgs& W, const SacCtx& C, const HxHyper* Hy, int 
         if (C.im) { J.w2b = C.im + IM_ACTOR * kImgElems; J.w2tb = C.im + IM_ACTOR_T * kImgElems; }  // the bf16 path: forward (= acting) and transposed images
         set_adam_scalars(W.ad, Hy->lr_actor, adam_step);
         W.ad.losses = N->losses;
-        if (alpha_step) { W.ad.alpha_state = N->alpha_state; W.ad.target_entropy = target_entropy; W.ad.alpha_step_size = W.ad.step_size; }  // (alpha_optim: the policy's learning rate)
+        if (alpha_step && !std::isnan(target_entropy)) { W.ad.alpha_state = N->alpha_state; W.ad.target_entropy = target_entropy; W.ad.alpha_step_size = W.ad.step_size; }  // (alpha_optim: the policy's learning rate)
     }
     launch_wg(W, adam_step > 0, C.st);
 }
@@ -682,8 +682,9 @@ int hx_sac_learn(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, co
  *   + q_select<weighted>, bwd_l2<3> (critics), + policy_dout<weighted> (also mean(w H), mean(w)), bwd_l2<3> (policy)
  *     wgrad       policy + policy_optim step (WITHOUT the log-alpha step)
  *   + alpha_step  entropy_loss and alpha_optim.step() from mean(w H) - target_entropy mean(w) */
-int hx_sac_learn_weighted(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, const float* weights, float* errors_out, int32_t polyak_first,
-                          int32_t step, float target_entropy, void* stream) {
+// clip_ws != NULL (hx_sac_learn_weighted_clipped): both weight-gradient launches run without Adam, each followed by the norm and the clipped step
+static int sac_learn_weighted_impl(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, const float* weights, float* errors_out, int32_t polyak_first,
+                                   int32_t step, float target_entropy, float max_norm, float* clip_ws, void* stream) {
     HX_REQUIRE(step >= 1, "hx_sac_learn_weighted: step is 1-based");
     HX_REQUIRE(N && Bt && Hy && Bt->rows && Bt->batch > 0 && Bt->batch % 16 == 0 && weights && errors_out, "hx_sac_learn_weighted: bad arguments (nets, batch, hyper, weights, errors_out)");
     HX_REQUIRE(!N->w2_bf16_all, "hx_sac_learn_weighted: the weighted update is fp32 only (nets->w2_bf16_all must be NULL)");
@@ -737,27 +738,48 @@ int hx_sac_learn_weighted(const HxSacNets* N, const HxSacBatch* Bt, const HxHype
             J = WgJob{};
             J.net = h ? C.q2 : C.q1; J.grad = N->grad_critic + h * kQs.padded(); J.m = kQs;
             J.ws[0] = s[SS_Q1 + h]; J.rows[0] = B; J.nslots = 1; J.wmode[0] = 0;
-            J.p = N->critic + h * kQs.padded();
-            J.mom = N->m_critic + h * kQs.padded(); J.var = N->v_critic + h * kQs.padded();
+            if (!clip_ws) {
+                J.p = N->critic + h * kQs.padded();
+                J.mom = N->m_critic + h * kQs.padded(); J.var = N->v_critic + h * kQs.padded();
+            }
         }
-        set_adam_scalars(W.ad, Hy->lr_critic, step);
-        W.ad.losses = N->losses;
-        launch_wg(W, true, st);
+        if (!clip_ws) {
+            set_adam_scalars(W.ad, Hy->lr_critic, step);
+            W.ad.losses = N->losses;
+        }
+        launch_wg(W, !clip_ws, st);
+        if (clip_ws) {
+            if (int rc = sac_grad_norm(N, 0, clip_ws, st, "hx_sac_learn_weighted_clipped")) return rc;
+            if (int rc = sac_clipped_step(N, Hy, 0, step, 1.0f, target_entropy, max_norm, clip_ws, false, st, "hx_sac_learn_weighted_clipped")) return rc;
+        }
     }
     launch_q_pi(C);
     if (int rc = launch_policy_tail(C, false, weights, wsum)) return rc;
     {
         WgArgs W{};
         W.job[0].nslots = 1;
-        launch_policy_wg(W, C, Hy, step, target_entropy, /*alpha_step=*/false);
+        launch_policy_wg(W, C, Hy, clip_ws ? 0 : step, target_entropy, /*alpha_step=*/false);
+        if (clip_ws) {
+            if (int rc = sac_grad_norm(N, 1, clip_ws, st, "hx_sac_learn_weighted_clipped")) return rc;
+            if (int rc = sac_clipped_step(N, Hy, 1, step, 1.0f, target_entropy, max_norm, clip_ws, false, st, "hx_sac_learn_weighted_clipped")) return rc;
+        }
     }
-    {
+    if (!std::isnan(target_entropy)) {  // (NaN = HX_SAC_FIXED_ALPHA: no log-alpha optimiser)
         AlphaStepArgs A{N->alpha_state, N->losses, wsum, target_entropy, 0.f, 0.f, 0.f, 0.f, 0.f};
         set_adam_scalars(A, Hy->lr_actor, step);  // (alpha_optim: the policy's learning rate)
         hipLaunchKernelGGL(alpha_step_weighted_kernel, dim3(1), dim3(64), 0, st, A);
     }
     HX_CHECK_LAUNCH("hx_sac_learn_weighted");
     return 0;
+}
+int hx_sac_learn_weighted(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, const float* weights, float* errors_out, int32_t polyak_first,
+                          int32_t step, float target_entropy, void* stream) {
+    return sac_learn_weighted_impl(N, Bt, Hy, weights, errors_out, polyak_first, step, target_entropy, 0.0f, nullptr, stream);
+}
+int hx_sac_learn_weighted_clipped(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, const float* weights, float* errors_out, int32_t polyak_first,
+                                  int32_t step, float target_entropy, float max_norm, float* clip_ws, void* stream) {
+    HX_REQUIRE(clip_ws && max_norm > 0.0f, "hx_sac_learn_weighted_clipped: clip_ws (hx_sac_clip_floats() floats) and a positive max_norm");
+    return sac_learn_weighted_impl(N, Bt, Hy, weights, errors_out, polyak_first, step, target_entropy, max_norm, clip_ws, stream);
 }
 
 /* ------------------------------------------------------------------------------------------------------------------

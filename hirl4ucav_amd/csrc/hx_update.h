@@ -758,6 +758,55 @@ inline int sac_check_formats(const HxSacNets* N, const char* who) {
 // the bf16 acting image of a SAC policy: the update path's first image, else policy_w2_bf16 (NULL: none)
 inline const uint16_t* sac_act_image(const HxSacNets* N) { return N->w2_bf16_all ? N->w2_bf16_all + IM_ACTOR * kImgElems : N->policy_w2_bf16; }
 
+// the AdamArgs of a SAC optimizer step (which 0: q1_optim + q2_optim over the flat critic, 1: policy_optim) with every live image of the W2 it changes;
+// alpha_step: the log-alpha step rides in the launch (never with target_entropy NaN = HX_SAC_FIXED_ALPHA).  hx_sac_adam and the clipped step (hx_clip.hip) fill alike.
+inline int sac_adam_fill(AdamArgs& A, const HxSacNets* N, const HxHyper* Hy, int which, int step, float grad_scale, float target_entropy, bool alpha_step,
+                         const char* who) {
+    A.n = which == 0 ? 2 * kQs.padded() : kPolicy.padded();
+    A.p = which == 0 ? N->critic : N->policy;
+    A.g = which == 0 ? N->grad_critic : N->grad_policy;
+    A.m = which == 0 ? N->m_critic : N->m_policy;
+    A.v = which == 0 ? N->v_critic : N->v_policy;
+    set_adam_scalars(A, which == 0 ? Hy->lr_critic : Hy->lr_actor, step);
+    A.gscale = grad_scale;
+    A.losses = N->losses;
+    if (which == 1 && N->policy_w2_f32i) {  // the acting kernel's image of the policy's W2 follows its optimizer step
+        A.w2f = N->policy_w2_f32i;
+        A.w2_lo = kPolicy.W2();
+    }
+    if (which == 1 && N->policy_w2_x9) {  // ... and the hi | mid | lo images of the large-population format
+        A.w2b = N->policy_w2_x9;
+        A.w2b_x9 = 1;
+        A.w2_lo = kPolicy.W2();
+    }
+    if (which == 1 && N->policy_w2_bf16 && !N->w2_bf16_all) {  // ... or the bf16 acting image beside an fp32 update
+        A.w2b = N->policy_w2_bf16;
+        A.w2_lo = kPolicy.W2();
+    }
+    if (int rc = sac_check_formats(N, who)) return rc;
+    if (uint16_t* im = N->w2_bf16_all) {  // SAC bf16 path: the forward and transposed images of every W2 this step changes follow it
+        if (which == 0) {
+            A.nseg = 2;
+            for (int h = 0; h < 2; ++h) {
+                A.seg_lo[h] = h * kQs.padded() + kQs.W2();
+                A.seg_w2b[h] = im + (IM_C1 + h) * kImgElems;
+                A.seg_w2tb[h] = im + (IM_C1_T + h) * kImgElems;
+            }
+        } else {
+            A.nseg = 1;
+            A.seg_lo[0] = kPolicy.W2();
+            A.seg_w2b[0] = im + IM_ACTOR * kImgElems;  // (also the acting image)
+            A.seg_w2tb[0] = im + IM_ACTOR_T * kImgElems;
+        }
+    }
+    if (which == 1 && alpha_step && !std::isnan(target_entropy)) {  // (NaN: fixed alpha, no log-alpha optimiser anywhere)
+        A.alpha_state = N->alpha_state;
+        A.target_entropy = target_entropy;
+        A.alpha_step_size = A.step_size;  // alpha_optim runs at the policy's learning rate
+    }
+    return 0;
+}
+
 // launchers (defined beside their kernels)
 void launch_fwd(const FwdArgs& F, hipStream_t st);                          // hx_fwdbwd.hip
 void set_fwd_nt(int nt, int skip, int count);                                                  // hx_fwdbwd.hip (hx_debug_set_fwd_nt)
@@ -768,5 +817,9 @@ void launch_polyak(float* target, const float* source, int n, float tau, float* 
                    const uint32_t* guard = nullptr);  // guard: a word that must be 0 for the step to happen (a failed exchange)
 // bf16 image of the W2 [512][256] at `w2`: forward order (w2_image_index) or transposed (w2t_image_index)             hx_act.hip
 void launch_pack_bf16(const float* w2, uint16_t* image, bool transposed, hipStream_t st);
+// hx_clip.hip: per-segment sums of squares of grad_critic (which 0) / grad_policy (which 1) into clip_ws, then the optimizer step on g * coef[segment]
+int sac_grad_norm(const HxSacNets* N, int which, float* clip_ws, hipStream_t st, const char* who);
+int sac_clipped_step(const HxSacNets* N, const HxHyper* Hy, int which, int step, float grad_scale, float target_entropy, float max_norm, float* clip_ws,
+                     bool alpha_step, hipStream_t st, const char* who);
 
 }  // namespace hxu

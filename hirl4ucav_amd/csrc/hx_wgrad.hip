@@ -819,48 +819,7 @@ int hx_polyak(const HxNets* N, const HxHyper* Hy, void* stream) {
 int hx_sac_adam(const HxSacNets* N, const HxHyper* Hy, int32_t which, int32_t step, float grad_scale, float target_entropy, void* stream) {
     HX_REQUIRE(N && Hy && step >= 1 && (which == 0 || which == 1), "hx_sac_adam: bad arguments");
     AdamArgs A{};
-    A.n = which == 0 ? 2 * kQs.padded() : kPolicy.padded();
-    A.p = which == 0 ? N->critic : N->policy;
-    A.g = which == 0 ? N->grad_critic : N->grad_policy;
-    A.m = which == 0 ? N->m_critic : N->m_policy;
-    A.v = which == 0 ? N->v_critic : N->v_policy;
-    set_adam_scalars(A, which == 0 ? Hy->lr_critic : Hy->lr_actor, step);
-    A.gscale = grad_scale;
-    A.losses = N->losses;
-    if (which == 1 && N->policy_w2_f32i) {  // the acting kernel's image of the policy's W2 follows its optimizer step
-        A.w2f = N->policy_w2_f32i;
-        A.w2_lo = kPolicy.W2();
-    }
-    if (which == 1 && N->policy_w2_x9) {  // ... and the hi | mid | lo images of the large-population format
-        A.w2b = N->policy_w2_x9;
-        A.w2b_x9 = 1;
-        A.w2_lo = kPolicy.W2();
-    }
-    if (which == 1 && N->policy_w2_bf16 && !N->w2_bf16_all) {  // ... or the bf16 acting image beside an fp32 update
-        A.w2b = N->policy_w2_bf16;
-        A.w2_lo = kPolicy.W2();
-    }
-    if (int rc = sac_check_formats(N, "hx_sac_adam")) return rc;
-    if (uint16_t* im = N->w2_bf16_all) {  // SAC bf16 path: the forward and transposed images of every W2 this step changes follow it
-        if (which == 0) {
-            A.nseg = 2;
-            for (int h = 0; h < 2; ++h) {
-                A.seg_lo[h] = h * kQs.padded() + kQs.W2();
-                A.seg_w2b[h] = im + (IM_C1 + h) * kImgElems;
-                A.seg_w2tb[h] = im + (IM_C1_T + h) * kImgElems;
-            }
-        } else {
-            A.nseg = 1;
-            A.seg_lo[0] = kPolicy.W2();
-            A.seg_w2b[0] = im + IM_ACTOR * kImgElems;  // (also the acting image)
-            A.seg_w2tb[0] = im + IM_ACTOR_T * kImgElems;
-        }
-    }
-    if (which == 1) {
-        A.alpha_state = N->alpha_state;
-        A.target_entropy = target_entropy;
-        A.alpha_step_size = A.step_size;  // alpha_optim runs at the policy's learning rate
-    }
+    if (int rc = sac_adam_fill(A, N, Hy, which, step, grad_scale, target_entropy, /*alpha_step=*/true, "hx_sac_adam")) return rc;
     launch_adam(A, (hipStream_t)stream);
     HX_CHECK_LAUNCH("hx_sac_adam");
     return 0;

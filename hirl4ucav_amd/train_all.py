@@ -288,6 +288,9 @@ def main(config):
     per = bool(getattr(config, "per", False))  # SacAgent(per=True): prioritized replay, the importance weights through the three losses
     if per and per_refusal(config, world):
         raise SystemExit("train_all: " + per_refusal(config, world))
+    grad_clip, fixed_alpha = getattr(config, "grad_clip", None), getattr(config, "fixed_alpha", None)  # SacAgent(grad_clip=c) / (entropy_tuning=False, ent_coef=x)
+    if clip_refusal(config, world):
+        raise SystemExit("train_all: " + clip_refusal(config, world))
     batch, buffer_size, checkpoint_rate = 128, config.buffer_size, config.checkpoint_rate  # train_all.py:190-208
     warm_up_rate = 20 if config.agent == "SAC" else 10  # train_sac.py:203 / train_all.py:207
 
@@ -309,6 +312,10 @@ def main(config):
         eng.load_params(_xavier_mlp(13, 8), _xavier_mlp(17, 1), _xavier_mlp(17, 1))
         if per:
             eng.set_prioritized(replay)
+        if grad_clip is not None:  # update_params(..., grad_clip), SAC/agent.py:310-320
+            eng.set_grad_clip(grad_clip)
+        if fixed_alpha is not None:  # SAC/agent.py:108-110
+            eng.set_entropy_tuning(False, fixed_alpha)
     else:
         eng = E.HirlEngine(batch=batch, slope=0.0 if hirl else 0.01, use_bc=hirl, device=device)
         eng.load_params(init_actor_state_dict(), init_critic_state_dict(), init_actor_state_dict() if hirl else None)
@@ -395,11 +402,13 @@ def main(config):
     shared_gpu = world > torch.cuda.device_count() and not os.environ.get("HX_FRONT_SHARED_GPU")
     front = (config.loop == "front" and not sac and not config.separate_launches and config.updates_per_step == 1 and batch <= 256
              and getattr(config, "dtype", "f32") in ("f32", "f32x9", "bf16") and not shared_gpu)
-    front_sac = (config.loop == "front" and sac and world == 1 and not config.separate_launches and config.updates_per_step == 1 and batch <= 256 and not per)
+    front_sac = (config.loop == "front" and sac and world == 1 and not config.separate_launches and config.updates_per_step == 1 and batch <= 256 and not per and grad_clip is None)
     if rank == 0:
         which = "front launch (env step + first launches of learn() in one launch; draw before the insert)" if (front or front_sac) else "reference order"
         if per:  # the front loop draws before the step's insert: update_priority could then hit slots the step has overwritten
             which += " (--per: the front launch draws before the step's insert, so the priorities of the drawn rows could be written into overwritten slots)"
+        if sac and grad_clip is not None and not per:  # the clipped update is the staged sequence (gradients -> norm -> clipped step): its first launch is its own
+            which += " (--grad_clip: the clipped update runs as stages, which have no front form)"
         print(f"vector loop: {which}" + (f" ({world} ranks share a GPU: the front launch is for one process per GPU)" if (shared_gpu and config.loop == "front") else ""),
               flush=True)
     # The front launch's in-launch waits (launch B for launch A's rows, launch C for both) assume that the workgroups of ONE launch start in index order —
@@ -489,6 +498,9 @@ def main(config):
                     writer.add_scalar(tag, v, step + episode * max_step)
             if isac and writer is not None and step % log_rate == 0:  # SAC/agent.py:353-359
                 log_imitative(writer, eng, step + episode * max_step)
+            if sac and grad_clip is not None and writer is not None and step % log_rate == 0:
+                for tag, v in zip(("q1", "q2", "policy"), eng.grad_norms_host()[0]):
+                    writer.add_scalar("stats/grad_norm_" + tag, v, step + episode * max_step)
             if per and writer is not None and step % log_rate == 0:
                 writer.add_scalar("stats/per_beta", replay.beta, step + episode * max_step)
                 writer.add_scalar("stats/per_max_priority", replay.pmax, step + episode * max_step)
@@ -618,11 +630,29 @@ def per_refusal(config, world=1):
     return None
 
 
+def clip_refusal(config, world=1):
+    """why `--grad_clip` / `--fixed_alpha` cannot run as asked, or None"""
+    clip, fixed = getattr(config, "grad_clip", None), getattr(config, "fixed_alpha", None)
+    if clip is None and fixed is None:
+        return None
+    flag = "--grad_clip" if clip is not None else "--fixed_alpha"
+    if config.agent != "SAC":
+        return (f"{flag} goes with --agent SAC (gradient clipping and the fixed entropy coefficient are SacAgent's: SAC/agent.py:108-110, 310-320), "
+                f"not --agent {config.agent}")
+    if clip is not None and not (clip > 0 and math.isfinite(clip)):
+        return f"--grad_clip {clip}: the maximum gradient norm is a positive number"
+    if fixed is not None and not (fixed >= 0 and math.isfinite(fixed)):
+        return f"--fixed_alpha {fixed}: the entropy coefficient is a number >= 0"
+    if clip is not None and ((config.gpus and config.gpus > 1) or world > 1):
+        return "--grad_clip runs on one GPU (the norm is taken over one rank's gradient, before any exchange): use --gpus 1"
+    return None
+
+
 def parse_args(argv=None):
     """parser().parse_args with the cross-flag checks that are argparse errors"""
     p = parser()
     cfg = p.parse_args(argv)
-    why = per_refusal(cfg)
+    why = per_refusal(cfg) or clip_refusal(cfg)
     if why:
         p.error(why)
     if cfg.type == "ISAC" and cfg.agent != "SAC":
@@ -682,6 +712,12 @@ def parser():
     p.add_argument("--per_alpha", type=float, default=0.6, help="--per: priority exponent (SAC/agent.py:62)")
     p.add_argument("--per_beta", type=float, default=0.4, help="--per: importance-weight exponent at the start (SAC/agent.py:62)")
     p.add_argument("--per_beta_annealing", type=float, default=0.0001, help="--per: beta <- min(1, beta + this) per sample call (SAC/agent.py:63)")
+    p.add_argument("--grad_clip", type=float, default=None, help="SAC: clip each network's gradient (Q1, Q2, policy) to this global L2 norm before its Adam step "
+                                                                 "(SacAgent(grad_clip=C), SAC/utils.py:15-21); one GPU; the vector loop runs in the reference's "
+                                                                 "order.  Stored in the snapshot: --resume refuses another value")
+    p.add_argument("--fixed_alpha", type=float, default=None, help="SAC: a constant entropy coefficient alpha = X and no log-alpha optimiser "
+                                                                   "(SacAgent(entropy_tuning=False, ent_coef=X), SAC/agent.py:108-110).  Stored in the snapshot: "
+                                                                   "--resume refuses another value")
     p.add_argument("--max_step", type=int, default=None, help="steps per episode (default: the scenario's, train_all.py:159-183: 1500 / 1500 / 1900); short rehearsal runs")
     p.add_argument("--status_check_every", type=int, default=256,
                    help="front loop: vector steps between reads of the front launch's status word (one host sync each; 0: only at every episode's end)")

@@ -23,6 +23,10 @@ def engine_state(eng):
         st["imitative"] = {"bc_actor": eng.bc_actor.detach().cpu().clone(), "bc_slope": eng.bc_slope, "expert_calls": eng.expert_calls}
     if getattr(eng, "prioritized", None) is not None:  # (a plain snapshot carries no such key)
         st["prioritized"] = True
+    if getattr(eng, "grad_clip", None) is not None:  # (a snapshot of an unclipped run with entropy tuning carries neither key)
+        st["grad_clip"] = float(eng.grad_clip)
+    if not getattr(eng, "entropy_tuning", True):
+        st["fixed_alpha"] = float(eng.ent_coef)
     return st
 
 
@@ -38,6 +42,13 @@ def load_engine_state(eng, st):
                       f"acts under {now}: the run continues under other acting arithmetic (fp32 results up to summation order)", stacklevel=2)
     if bool(st.get("prioritized", False)) != (getattr(eng, "prioritized", None) is not None):
         raise ValueError("snapshot and engine disagree about prioritized replay (--per): resume with the flag the run was started with")
+    if st.get("grad_clip") != getattr(eng, "grad_clip", None):
+        raise ValueError(f"snapshot was written under --grad_clip {st.get('grad_clip')}, this engine clips at {getattr(eng, 'grad_clip', None)}: "
+                         "resume with the flag the run was started with")
+    now_fixed = None if getattr(eng, "entropy_tuning", True) else float(eng.ent_coef)
+    if st.get("fixed_alpha") != now_fixed:
+        raise ValueError(f"snapshot was written under --fixed_alpha {st.get('fixed_alpha')}, this engine runs under {now_fixed} (None: entropy tuning): "
+                         "resume with the flag the run was started with")
     if ("imitative" in st) != bool(getattr(eng, "imitative", False)):
         raise ValueError("snapshot and engine disagree about SAC's imitative branch (--type ISAC): resume with the type the run was started with")
     eng.arena.copy_(st["arena"])

@@ -75,8 +75,10 @@ const char* hx_last_error(void);
  * 113: round 5.  114: round 6 (hx_rccl_allreduce_bf16).  115: the SAC bf16 path (HxSacNets.w2_bf16_all / policy_w2_bf16, hx_sac_*_bf16).
  * 116: SAC's imitative branch (HxSacImit, hx_sac_imit_*, hx_sac_policy_grads_imitative, hx_sac_learn_imitative).
  * 117: hx_sac_front takes any number of envs (the per-tile acting role up to 8,192; it refused them before).
- * 118: prioritized replay for SAC (HxPer, hx_per_*, hx_sac_learn_weighted). */
-#define HX_ABI_VERSION 118
+ * 118: prioritized replay for SAC (HxPer, hx_per_*, hx_sac_learn_weighted).
+ * 119: gradient-norm clipping and the fixed entropy coefficient for SAC (HX_SAC_FIXED_ALPHA, hx_sac_grad_norm, hx_sac_adam_clipped,
+ * hx_sac_learn_weighted_clipped). */
+#define HX_ABI_VERSION 119
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -537,6 +539,36 @@ int hx_sac_learn_back(const HxSacNets* nets, const HxSacBatch* batch, const HxHy
                       const HxSample* next, float* next_rows, void* stream);
 int hx_sac_adam(const HxSacNets* nets, const HxHyper* hyper, int32_t which, int32_t step, float grad_scale, float target_entropy,
                 void* stream);
+/* SacAgent(entropy_tuning=False, ent_coef=x) (SAC/agent.py:108-110, 322-327): a constant alpha and no log-alpha optimiser — the reference then has no
+ * target entropy at all, and neither has this ABI: every hx_sac_* call that takes target_entropy runs WITHOUT its log-alpha step when it is NaN
+ * (hx_sac_learn, hx_sac_learn_back, hx_sac_learn_imitative, hx_sac_learn_weighted[_clipped], hx_sac_adam, hx_sac_adam_clipped; the fused weight-gradient
+ * launch, adam_kernel and the weighted call's own log-alpha launch alike).  The caller stores ent_coef in alpha_state[3] and in losses[5] once:
+ * alpha_state[0..3] and losses[5] are never written, losses[3] (entropy_loss) stays 0.  No launch structure changes. */
+#define HX_SAC_FIXED_ALPHA (__builtin_nanf(""))
+
+/* Gradient-norm clipping (update_params(optim, network, loss, grad_clip): SAC/utils.py:15-21, SAC/agent.py:310-320): each network's gradient is scaled
+ * to a global L2 norm of at most max_norm before its Adam step, as torch.nn.utils.clip_grad_norm_ does: coef = min(1, max_norm / (norm + 1e-6)).
+ * Three segments, each with its own norm: Q1 and Q2 (the two halves of grad_critic: q1_optim, q2_optim) and the policy (grad_policy).  A norm is over
+ * the reference's parameter words only — W1, b1, W2, b2, W3, b3 of the block; the LayerNorm slots and the padding contribute nothing, whatever they hold.
+ * ONE whole-network clip per optimizer (the reference's loop over network.modules() clips the same parameters again per sub-module: after the first
+ * clip those passes scale by a factor within about 1e-6 / max_norm of 1 — DESIGN.md 5).  The log-alpha step is never clipped.
+ *   hx_sac_grad_norm     one launch: workgroup c of a segment writes the sum of squares of its fixed 4,096-word chunk — a fixed order, no atomics, no
+ *                        workgroup waits for another — into clip_ws (hx_sac_clip_floats() floats, 16-byte aligned)
+ *   hx_sac_adam_clipped  hx_sac_adam's step on g * grad_scale * coef[segment]: every workgroup re-adds its segments' partial sums in the same fixed order
+ *                        and forms the coefficient itself; coef == 1 multiplies exactly, so a max_norm that never binds gives hx_sac_adam's bits.
+ *                        Keeps every live image of W2 current and (which = 1, entropy tuning on) steps log-alpha, as hx_sac_adam does.
+ * clip_ws[0..2] = the norms before clipping (of g * grad_scale) of Q1, Q2 and the policy, clip_ws[3..5] = their coefficients, as of the last clipped step
+ * of each; the words behind hold the partial sums.  The same gradients give the same bits on every run.
+ * Sequence: hx_sac_critic_grads[_sampled], hx_sac_grad_norm(0), hx_sac_adam_clipped(0), hx_sac_policy_grads[_imitative], hx_sac_grad_norm(1),
+ * hx_sac_adam_clipped(1) — the imitative branch is clipped on the combined (1 - w) dL + w dL_bc it leaves in grad_policy. */
+int64_t hx_sac_clip_floats(void);
+/* shape6[0..5] (host) <- the summation shape of one segment's sum of squares: float4 per thread, words per chunk, the most partials one wave re-adds,
+ * the chunks of a Q segment, of the policy segment, and the depth of the whole sum in roundings (the squares included): the sum is within
+ * depth * 2^-24 (relative) of the exact one — every term is non-negative */
+int hx_sac_clip_shape(int32_t* shape6);
+int hx_sac_grad_norm(const HxSacNets* nets, int32_t which, float* clip_ws, void* stream);
+int hx_sac_adam_clipped(const HxSacNets* nets, const HxHyper* hyper, int32_t which, int32_t step, float grad_scale, float target_entropy,
+                        float max_norm, float* clip_ws, void* stream);
 
 /* SAC, imitative branch (SAC/agent.py:315-318, 353-359, 385-403; SacAgent(imitative=True)).  After the two critic steps, with the UPDATED critics:
  *     a~, H     = policy.sample(s)                          q    = min(Q1, Q2)(s, a~)
@@ -636,6 +668,10 @@ int hx_per_sample(const HxPer* per, const float* ring, int32_t batch, const floa
  * arithmetic on the same numbers (at w == 1, mean(w) is exactly 1 and mean(w H) has the mean entropy's bits).  step is 1-based. */
 int hx_sac_learn_weighted(const HxSacNets* nets, const HxSacBatch* batch, const HxHyper* hyper, const float* weights, float* errors_out,
                           int32_t polyak_first, int32_t step, float target_entropy, void* stream);
+/* The same under gradient-norm clipping ("Gradient-norm clipping" above): its two weight-gradient launches run without Adam, each followed by
+ * hx_sac_grad_norm and the clipped step (4 launches more); the log-alpha step stays the launch of its own, unclipped. */
+int hx_sac_learn_weighted_clipped(const HxSacNets* nets, const HxSacBatch* batch, const HxHyper* hyper, const float* weights, float* errors_out,
+                                  int32_t polyak_first, int32_t step, float target_entropy, float max_norm, float* clip_ws, void* stream);
 
 
 /* ------------------------------------------------------------------------------------------------------------
