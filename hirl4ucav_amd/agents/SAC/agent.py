@@ -172,6 +172,43 @@ class SacAgent:
     def act(self, state):  # agent.py:175-180
         return self.action_space.sample() if self.start_steps > self.steps else self.explore(state)
 
+    @staticmethod
+    def _mlp(sd, x):
+        h = torch.relu(x @ sd["0.weight"].T + sd["0.bias"])
+        h = torch.relu(h @ sd["2.weight"].T + sd["2.bias"])
+        return h @ sd["4.weight"].T + sd["4.bias"]
+
+    @staticmethod
+    def _rows(*cols):
+        return [torch.as_tensor(c, dtype=torch.float32).to(device).reshape(-1, w) for c, w in zip(cols, (13, 4, 1, 13, 1))]
+
+    def calc_current_q(self, states, actions, rewards, next_states, dones):  # agent.py:198-200
+        """-> Q1(s, a), Q2(s, a) as [n, 1] tensors.  A plain forward over the engine's fp32 networks: the reference's train_episode calls it for ONE
+        transition per env step (agent.py:234-246) and hands |Q1 - y| to memory.append(..., error); the vector loop's scoring pass is score_new."""
+        s, a, _, _, _ = self._rows(states, actions, rewards, next_states, dones)
+        sd = self.eng.state_dicts()
+        with torch.no_grad():
+            sa = torch.cat([s, a], 1)
+            return self._mlp(sd["q1"], sa), self._mlp(sd["q2"], sa)
+
+    def calc_target_q(self, states, actions, rewards, next_states, dones, eps=None):  # agent.py:202-210
+        """-> y = r + (1 - d) gamma (min Q_target(s', a') + alpha H') as an [n, 1] tensor, a', H' = policy.sample(s') (SAC/model.py:62-82) with one
+        torch.randn draw per row and component (eps [n, 4] injects them)"""
+        _, _, r, ns, d = self._rows(states, actions, rewards, next_states, dones)
+        sd = self.eng.state_dicts()
+        with torch.no_grad():
+            eps = torch.randn(ns.shape[0], 4).to(device) if eps is None else torch.as_tensor(eps, dtype=torch.float32).to(device).reshape(-1, 4)
+            mean, log_std = torch.chunk(self._mlp(sd["policy"], ns), 2, dim=-1)
+            log_std = torch.clamp(log_std, -20.0, 2.0)
+            std = log_std.exp()
+            x = mean + std * eps
+            na = torch.tanh(x)
+            log_prob = (-((x - mean) ** 2) / (2 * std ** 2) - log_std - 0.5 * float(np.log(2 * np.pi))) - torch.log(1 - na.pow(2) + 1e-6)
+            nh = -log_prob.sum(1, keepdim=True)
+            nsa = torch.cat([ns, na], 1)
+            next_q = torch.min(self._mlp(sd["q1_target"], nsa), self._mlp(sd["q2_target"], nsa)) + self.alpha * nh
+            return r + (1.0 - d) * self.gamma_n * next_q
+
     def load_bc_actor(self, ajan, model_name=None, slope=0.01):  # agent.py:158-160
         """The frozen BC actor of the imitative branch: a state_dict (or a flat block), a path to the file the BC agent of this project
         writes, or the reference's two-argument call load_bc_actor(ajan, model_name) = the file <model_name>/<ajan>Harfang_GYM."""

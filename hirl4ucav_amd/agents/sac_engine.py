@@ -166,6 +166,7 @@ class SacEngine:
         self._pending, self._pending_expert = None, None  # draws sample(defer=True) / sample_expert(defer=True) recorded for the next learn()
         self._front_tiles, self._front_drawn = None, None  # step_learn: the two sets of minibatch tiles, and what the set in waiting was drawn for
         self.prioritized, self.per_weights, self.per_errors = None, None, None  # set_prioritized
+        self.per_new_rows = "max"  # set_prioritized(new_rows=...): how step_learn gives a step's rows their first priority
         self.grad_clip, self.clip_ws = None, None  # set_grad_clip
         self.entropy_tuning, self.ent_coef = True, None  # set_entropy_tuning
 
@@ -212,12 +213,16 @@ class SacEngine:
         v = self.clip_ws[:6].tolist()
         return tuple(v[:3]), tuple(v[3:])
 
-    def set_prioritized(self, replay):
+    def set_prioritized(self, replay, new_rows="max"):
         """SacAgent(per=True) (agent.py:281-284, 306-331): from now on sample() on `replay` (a utils.buffer.PrioritizedReplay) draws proportionally to
         the stored priorities and keeps the importance weights, learn() carries them through the three losses (hx_sac_learn_weighted) and hands
-        |Q1(s, a) - y| back as the rows' new priorities (hx_per_update) — all enqueued, no host sync.  fp32, one GPU, not with the imitative branch."""
+        |Q1(s, a) - y| back as the rows' new priorities (hx_per_update) — all enqueued, no host sync.  fp32, one GPU, not with the imitative branch.
+        new_rows: how the loop gives a step's rows their first priority — "max": at the running maximum (replay.mark_new, the default), "td": at a TD
+        error of their own as the reference's train_episode computes it (score_new, agent.py:234-246)."""
         from ..utils.buffer import PrioritizedReplay
 
+        if new_rows not in ("max", "td"):
+            raise ValueError(f"set_prioritized: new_rows is 'max' or 'td', got {new_rows!r}")
         if not isinstance(replay, PrioritizedReplay):
             raise TypeError("set_prioritized takes a utils.buffer.PrioritizedReplay")
         if self.update_dtype == "bf16" or self.act_dtype == "bf16":
@@ -226,9 +231,25 @@ class SacEngine:
             raise _lib.HxError("prioritized replay runs on one GPU (priorities and block sums are not exchanged between ranks): run it with --gpus 1")
         if self.imitative:
             raise _lib.HxError("prioritized replay does not go with the imitative branch (not built: SacAgent(imitative=True, per=True)): build a SacEngine without set_imitative")
-        self.prioritized = replay
+        self.prioritized, self.per_new_rows = replay, new_rows
         self.per_weights = torch.ones(self.batch, dtype=torch.float32, device=self.device)
         self.per_errors = torch.zeros(self.batch, dtype=torch.float32, device=self.device)
+
+    def score_new(self, replay, max_new, eps=None, seed=0):
+        """the rows stored in `replay` since its last mark_new / score_new enter at |Q1(s, a) - y| of their own, computed with the networks as they
+        stand (hx_per_score_new; the reference's train_episode, agent.py:234-246).  Under the conditions of learn() with prioritized replay: one GPU,
+        fp32 update and acting, no imitative branch.  Enqueues only."""
+        from ..utils.buffer import PrioritizedReplay
+
+        if not isinstance(replay, PrioritizedReplay):
+            raise TypeError("score_new takes a utils.buffer.PrioritizedReplay")
+        if self.world > 1:
+            raise _lib.HxError("score_new runs on one GPU (priorities and block sums are not exchanged between ranks): run it with --gpus 1")
+        if self.update_dtype == "bf16" or self.act_dtype == "bf16":
+            raise _lib.HxError("score_new is fp32 only (its forward launches have no bf16 form here): set_update_dtype('f32') and set_act_dtype('f32')")
+        if self.imitative:
+            raise _lib.HxError("score_new does not go with the imitative branch (not built: SacAgent(imitative=True, per=True))")
+        replay.score_new(self, max_new, eps=eps, seed=seed)
 
     def set_imitative(self, bc_actor, slope=0.01):
         """SacAgent(imitative=True) (agent.py:315-318, 385-403): from now on learn() gates a BC term on the expert rows with
@@ -561,7 +582,10 @@ class SacEngine:
                 raise _lib.HxError("prioritized replay does not mix expert rows into the minibatch (the reference's learn() drops them when per is on: "
                                    "agent.py:281-284): run step_learn without expert rows")
             res = self.act_step(env, explore=explore, seed=act_seed, out=out)
-            replay.mark_new(n)
+            if self.per_new_rows == "td":
+                self.score_new(replay, n, seed=sample_seed)
+            else:
+                replay.mark_new(n)
             self.sample(replay, None, seed=sample_seed)
             self.learn()
             return res

@@ -950,3 +950,11 @@ int hx_sac_learn_back(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* H
 }
 
 }  // extern "C"
+
+namespace hxu {
+// (host code only: the device code of this file is what it was)
+void launch_sac_gauss_rows(const float* policy, const float* z2, const float* eps, int rows, float* act, float* ent, uint64_t seed, uint32_t row0,
+                           uint32_t call, hipStream_t st) {
+    launch_gauss(GaussArgs{policy, kPolicy, z2, eps, rows, eps ? 1 : 2, act, ent, nullptr, seed, row0, call}, nullptr, nullptr, nullptr, 0, 0.0f, st);
+}
+}  // namespace hxu

@@ -7,6 +7,7 @@
 //   hx_act.hip      act_fused_kernel + the W2 image packers  hx_actor_act*, hx_sac_act*, hx_pack_w2_*
 //   hx_sampler.hip  sample_kernel                            hx_sample_batch
 //   hx_sac.hip      gauss_head / q_select / policy_dout      hx_sac_critic_*, hx_sac_policy_grads
+//   hx_score.hip    per_new_index / td_score / per_score_commit  hx_per_score_new (host code only besides: it drives fwd_l2 and gauss_head)
 //   hx_hirl.hip     host sequencing of Agent.learn           hx_hirl_*, hx_bc_train_actor
 //
 // What the kernels replace (reference file:line):
@@ -817,6 +818,10 @@ void launch_polyak(float* target, const float* source, int n, float tau, float* 
                    const uint32_t* guard = nullptr);  // guard: a word that must be 0 for the step to happen (a failed exchange)
 // bf16 image of the W2 [512][256] at `w2`: forward order (w2_image_index) or transposed (w2t_image_index)             hx_act.hip
 void launch_pack_bf16(const float* w2, uint16_t* image, bool transposed, hipStream_t st);
+// hx_sac.hip: a', H' = policy.sample(rows) from the policy's z2 rows as a launch of its own (gauss_head_kernel): eps [rows][4] given, or nullptr ->
+// Philox4x32-10(seed; row0 + row, call).  What hx_score.hip runs between its two forward launches.
+void launch_sac_gauss_rows(const float* policy, const float* z2, const float* eps, int rows, float* act, float* ent, uint64_t seed, uint32_t row0,
+                           uint32_t call, hipStream_t st);
 // hx_clip.hip: per-segment sums of squares of grad_critic (which 0) / grad_policy (which 1) into clip_ws, then the optimizer step on g * coef[segment]
 int sac_grad_norm(const HxSacNets* N, int which, float* clip_ws, hipStream_t st, const char* who);
 int sac_clipped_step(const HxSacNets* N, const HxHyper* Hy, int which, int step, float grad_scale, float target_entropy, float max_norm, float* clip_ws,

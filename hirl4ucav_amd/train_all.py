@@ -288,6 +288,9 @@ def main(config):
     per = bool(getattr(config, "per", False))  # SacAgent(per=True): prioritized replay, the importance weights through the three losses
     if per and per_refusal(config, world):
         raise SystemExit("train_all: " + per_refusal(config, world))
+    per_new = getattr(config, "per_new", "max")  # how a step's rows get their first priority: at pmax, or at a TD error of their own (agent.py:234-246)
+    if not per and per_refusal(config, world):  # (--per_new td without --per)
+        raise SystemExit("train_all: " + per_refusal(config, world))
     grad_clip, fixed_alpha = getattr(config, "grad_clip", None), getattr(config, "fixed_alpha", None)  # SacAgent(grad_clip=c) / (entropy_tuning=False, ent_coef=x)
     if clip_refusal(config, world):
         raise SystemExit("train_all: " + clip_refusal(config, world))
@@ -295,9 +298,10 @@ def main(config):
     warm_up_rate = 20 if config.agent == "SAC" else 10  # train_sac.py:203 / train_all.py:207
 
     if per:  # SAC/agent.py:112-118 (alpha 0.6, beta 0.4, beta_annealing 0.0001 are the reference's defaults)
-        from .utils.buffer import PrioritizedReplay
+        from .utils.buffer import PrioritizedReplay, score_chunk_for
 
         replay = PrioritizedReplay(buffer_size, device, alpha=config.per_alpha, beta=config.per_beta, beta_annealing=config.per_beta_annealing)
+        replay.score_chunk = score_chunk_for(n)  # --per_new td: rows per chunk of the scoring pass, by the envs per step (measured: DESIGN.md section 8)
     else:
         replay = DeviceReplay(buffer_size, device)
     env = BatchedHarfangEnv(n, scenario=env_type, device=device, seed=seed, max_step=max_step, auto_reset=True,
@@ -311,7 +315,7 @@ def main(config):
         eng = SE.SacEngine(batch=batch, lr=1e-3, device=device)
         eng.load_params(_xavier_mlp(13, 8), _xavier_mlp(17, 1), _xavier_mlp(17, 1))
         if per:
-            eng.set_prioritized(replay)
+            eng.set_prioritized(replay, new_rows=per_new)
         if grad_clip is not None:  # update_params(..., grad_clip), SAC/agent.py:310-320
             eng.set_grad_clip(grad_clip)
         if fixed_alpha is not None:  # SAC/agent.py:108-110
@@ -384,7 +388,9 @@ def main(config):
         env.reset()
         for _ in range(math.ceil(20 * max_step / (n * world))):
             env.step(torch.rand((n, 4), device=device) * 2 - 1)
-        if per:
+        if per and per_new == "td":  # the exploration rows are appended with an error of their own too (SAC/agent.py:176-177, 234-246: the start_steps rows are scored as well)
+            eng.score_new(replay, math.ceil(20 * max_step / (n * world)) * n, seed=seed + 3 + rank)
+        elif per:
             replay.mark_new()  # the exploration rows enter at the starting maximum priority
     expert_num, high_score, success_rate, arttir = run["expert_num"], run["high_score"], run["success_rate"], run["arttir"]
     actions = torch.zeros((n, 4), device=device)
@@ -475,7 +481,14 @@ def main(config):
                 eng.act_step(env, seed=seed + 1, out=actions)              # replay ring depends on the workgroup schedule)
             else:
                 eng.act_step(env, sigma=0.1, seed=seed + 1, out=actions)
-            if per:
+            if per and per_new == "td":
+                log_new = writer is not None and step % log_rate == 0
+                marked0 = replay.marked if log_new else 0  # (a host read, at the logging step only)
+                eng.score_new(replay, n, seed=seed + 3 + rank)  # this step's rows enter at |Q1(s, a) - y| of their own (no host sync)
+                if log_new:  # the mean over the rows this call covered (a step stores at most n)
+                    k = min(max(replay.marked - marked0, 1), n)
+                    writer.add_scalar("stats/per_mean_new_error", float(replay.errors[:k].mean()), step + episode * max_step)
+            elif per:
                 replay.mark_new(n)  # this step's rows enter at the running maximum priority (one launch, no host sync)
             if ret is not None:
                 ret += env.reward
@@ -612,8 +625,10 @@ def isac_refusal(config, world=1):
 
 
 def per_refusal(config, world=1):
-    """why `--per` cannot run as asked, or None"""
+    """why `--per` / `--per_new` cannot run as asked, or None"""
     if not getattr(config, "per", False):
+        if getattr(config, "per_new", "max") != "max":
+            return f"--per_new {config.per_new} goes with --per (it says how the rows of prioritized replay get their first priority): add --per"
         return None
     if config.agent != "SAC":
         return f"--per goes with --agent SAC --type SAC (prioritized replay is SacAgent's: SAC/agent.py:112-118), not --agent {config.agent}"
@@ -709,6 +724,10 @@ def parser():
     p.add_argument("--log_rewards", action="store_true", help="also log Training/Episode Reward (one more small launch per vector step)")
     p.add_argument("--per", action="store_true", help="SAC: prioritized replay (SacAgent(per=True)): proportional draws with importance weights, priorities from "
                                                       "|Q1 - y|; fp32, one GPU, --type SAC; the vector loop runs in the reference's order")
+    p.add_argument("--per_new", choices=("max", "td"), default="max",
+                   help="--per: the priority a newly stored row enters at.  max (default): the running maximum priority; td: a TD error of its own, "
+                        "|Q1(s, a) - y| with the networks as they stand, as the reference's train_episode computes it for every append "
+                        "(SAC/agent.py:234-246): one scoring pass over the step's rows per vector step (fp32, one GPU)")
     p.add_argument("--per_alpha", type=float, default=0.6, help="--per: priority exponent (SAC/agent.py:62)")
     p.add_argument("--per_beta", type=float, default=0.4, help="--per: importance-weight exponent at the start (SAC/agent.py:62)")
     p.add_argument("--per_beta_annealing", type=float, default=0.0001, help="--per: beta <- min(1, beta + this) per sample call (SAC/agent.py:63)")

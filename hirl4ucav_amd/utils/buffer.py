@@ -58,9 +58,21 @@ _lib.register("hx_per_mark_new", [ctypes.POINTER(HxPer), ctypes.c_int64, _vp])
 _lib.register("hx_per_set", [ctypes.POINTER(HxPer), _vp, _vp, _i32, _vp])
 _lib.register("hx_per_update", [ctypes.POINTER(HxPer), _vp, _vp, _i32, ctypes.c_float, _vp])
 _lib.register("hx_per_resum", [ctypes.POINTER(HxPer), _vp])
+_lib.register("hx_per_score_new", [ctypes.POINTER(HxPer), _vp, _vp, _vp, ctypes.c_int64, _i32, ctypes.c_float, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp])
 _lib.register("hx_per_sample", [ctypes.POINTER(HxPer), _vp, _i32, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_float, _vp, _vp, _vp, _vp])
 
 PER_BLOCK, PER_EPS, PER_MAX_CAPACITY = 1024, 1e-4, 1 << 24
+# rows per chunk of score_new's forward launches (include/hirl4ucav.h "Priorities at insert"); from 1,024 rows on a chunk has 128 row tiles per net:
+# the forward kernel's wide tiling.  A row's score depends on this value (the launch shape fixes the order of the forward kernel's sums), not on how
+# many rows came with it.  Measured (profiles/per_score_new.json): a padded chunk costs what a full one does — 1,024 rows score in
+# 39 / 58 / 99 us at chunks of 1,024 / 2,048 / 4,096 —, and larger chunks are cheaper per row — 16,384 rows in 681 / 530 / 436 us.
+PER_SCORE_CHUNK = 2048
+PER_SCORE_CHUNKS = (1024, 2048, 4096)
+
+
+def score_chunk_for(max_new):
+    """the chunk a loop that scores up to max_new rows per call should use: the smallest of 1,024 / 2,048 / 4,096 that holds them, else 4,096"""
+    return next((c for c in PER_SCORE_CHUNKS if int(max_new) <= c), PER_SCORE_CHUNKS[-1])
 
 
 class PrioritizedReplay(DeviceReplay):
@@ -87,6 +99,8 @@ class PrioritizedReplay(DeviceReplay):
         self.marked_t = self._header[1:2]
         self.per = HxPer(self._prio.data_ptr(), self.bsum.data_ptr(), self._header.data_ptr(), self._header[1:].data_ptr(), self._header[2:].data_ptr(),
                          self.total.data_ptr(), self.capacity)
+        # score_new: the chunk workspace and the errors of the last call (allocated at the first call, kept), the Philox call word
+        self.score_chunk, self.score_calls, self._score_ws, self.errors = PER_SCORE_CHUNK, 0, None, None
 
     @property
     def pmax(self):  # host sync (drivers / tests)
@@ -99,6 +113,32 @@ class PrioritizedReplay(DeviceReplay):
     def mark_new(self, max_new=None):
         """every slot stored since the last call enters at pmax.  max_new: an upper bound on their number (the envs stepped); default: the whole ring"""
         _lib.call("hx_per_mark_new", ctypes.byref(self.per), int(max_new) if max_new else self.capacity, _lib.stream_ptr())
+
+    def score_new(self, engine, max_new, eps=None, seed=0):
+        """every slot stored since the last call enters at a TD error of its own, |Q1(s, a) - y| with `engine`'s networks as they stand (the
+        reference's train_episode, SAC/agent.py:234-246) -> prio = (error + 1e-4)^alpha; a non-finite error enters at pmax.  max_new: an upper bound on
+        their number (the envs stepped).  eps [max_new, 4]: the draws of policy.sample(s'), else Philox(seed; row, score_calls).  The errors of the
+        rows covered are left in self.errors[:rows].  Enqueues only."""
+        max_new = int(max_new)
+        if max_new <= 0:
+            raise ValueError("score_new: max_new is an upper bound on the rows stored since the last call (> 0)")
+        if self._score_ws is None or self._score_ws_chunk != self.score_chunk:
+            L = _lib.load()
+            L.hx_per_score_workspace_floats.restype = ctypes.c_int64
+            words = int(L.hx_per_score_workspace_floats(int(self.score_chunk)))
+            if words <= 0:
+                raise ValueError(f"score_new: score_chunk is a positive multiple of 16, got {self.score_chunk}")
+            self._score_ws, self._score_ws_chunk = torch.zeros(words, dtype=torch.float32, device=self.device), self.score_chunk
+        if self.errors is None or self.errors.numel() < max_new:
+            self.errors = torch.zeros(max_new, dtype=torch.float32, device=self.device)
+        if eps is not None:
+            eps = torch.as_tensor(eps, device=self.device).to(torch.float32).contiguous()
+            if eps.numel() != max_new * 4:
+                raise ValueError(f"score_new: eps is [max_new, 4] = {max_new * 4} draws, got {eps.numel()}")
+        self.score_calls += 1
+        _lib.call("hx_per_score_new", ctypes.byref(self.per), self.ring.data_ptr(), ctypes.byref(engine.nets), ctypes.byref(engine.hyper), max_new,
+                  int(self.score_chunk), self.alpha, _lib.ptr(eps), int(seed), self.score_calls, self._score_ws.data_ptr(), self.errors.data_ptr(),
+                  _lib.stream_ptr())
 
     def set_priorities(self, slots, p):
         """prio[slots] <- p (already raised to alpha)"""

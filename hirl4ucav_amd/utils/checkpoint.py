@@ -23,6 +23,8 @@ def engine_state(eng):
         st["imitative"] = {"bc_actor": eng.bc_actor.detach().cpu().clone(), "bc_slope": eng.bc_slope, "expert_calls": eng.expert_calls}
     if getattr(eng, "prioritized", None) is not None:  # (a plain snapshot carries no such key)
         st["prioritized"] = True
+        if getattr(eng, "per_new_rows", "max") != "max":  # (a snapshot of a run whose new rows enter at pmax stays as it was)
+            st["per_new_rows"] = eng.per_new_rows
     if getattr(eng, "grad_clip", None) is not None:  # (a snapshot of an unclipped run with entropy tuning carries neither key)
         st["grad_clip"] = float(eng.grad_clip)
     if not getattr(eng, "entropy_tuning", True):
@@ -42,6 +44,9 @@ def load_engine_state(eng, st):
                       f"acts under {now}: the run continues under other acting arithmetic (fp32 results up to summation order)", stacklevel=2)
     if bool(st.get("prioritized", False)) != (getattr(eng, "prioritized", None) is not None):
         raise ValueError("snapshot and engine disagree about prioritized replay (--per): resume with the flag the run was started with")
+    if st.get("per_new_rows", "max") != getattr(eng, "per_new_rows", "max"):
+        raise ValueError(f"snapshot was written under --per_new {st.get('per_new_rows', 'max')}, this engine runs under --per_new "
+                         f"{getattr(eng, 'per_new_rows', 'max')}: resume with the flag the run was started with")
     if st.get("grad_clip") != getattr(eng, "grad_clip", None):
         raise ValueError(f"snapshot was written under --grad_clip {st.get('grad_clip')}, this engine clips at {getattr(eng, 'grad_clip', None)}: "
                          "resume with the flag the run was started with")
@@ -72,6 +77,8 @@ def replay_state(replay):
     if hasattr(replay, "prio"):  # a prioritized replay only (a plain snapshot stays as it was): the block sums are recomputed on load
         st["per"] = {"prio": replay.prio[:n].cpu().clone(), "pmax": replay.pmax_t.cpu().clone(), "marked": replay.marked, "beta": replay.beta,
                      "alpha": replay.alpha, "beta_annealing": replay.beta_annealing}
+        if replay.score_calls:  # (score_new was never called: the snapshot stays as it was)
+            st["per"]["score_calls"], st["per"]["score_chunk"] = replay.score_calls, replay.score_chunk  # (a row's score depends on the chunk)
     return st
 
 
@@ -90,6 +97,8 @@ def load_replay_state(replay, st):
         replay.pmax_t.copy_(st["per"]["pmax"])
         replay.marked_t.fill_(st["per"]["marked"])
         replay.beta = st["per"]["beta"]
+        replay.score_calls = st["per"].get("score_calls", 0)
+        replay.score_chunk = st["per"].get("score_chunk", replay.score_chunk)
         replay.resum()
 
 

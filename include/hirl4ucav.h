@@ -77,8 +77,9 @@ const char* hx_last_error(void);
  * 117: hx_sac_front takes any number of envs (the per-tile acting role up to 8,192; it refused them before).
  * 118: prioritized replay for SAC (HxPer, hx_per_*, hx_sac_learn_weighted).
  * 119: gradient-norm clipping and the fixed entropy coefficient for SAC (HX_SAC_FIXED_ALPHA, hx_sac_grad_norm, hx_sac_adam_clipped,
- * hx_sac_learn_weighted_clipped). */
-#define HX_ABI_VERSION 119
+ * hx_sac_learn_weighted_clipped).
+ * 120: priorities at insert for SAC's prioritized replay (hx_per_score_workspace_floats, hx_per_score_new). */
+#define HX_ABI_VERSION 120
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -612,7 +613,8 @@ int hx_sac_learn_imitative(const HxSacNets* nets, const HxSacBatch* batch, const
  *     draw             row r: target u_r S with S = sum of all priorities -> the slot whose interval of the running sum holds it: independent,
  *                      proportional to p, WITH replacement; never a slot of priority 0, never one beyond the live length
  *     weight           w_r = (n p_r / S)^-beta / max_r(.), n = min(*total, cap): the largest weight of a batch is exactly 1
- *     new rows         enter at the running maximum priority pmax (hx_per_mark_new), not at a TD error of their own
+ *     new rows         enter at the running maximum priority pmax (hx_per_mark_new: the default), or at a TD error of their own as the reference's
+ *                      train_episode computes it for every append (hx_per_score_new: "priorities at insert" below)
  * State beside a replay ring of `cap` <= 2^24 slots, all device memory owned by the caller:
  *     prio   [hx_per_prio_floats(cap)] = cap rounded up to a multiple of 1,024, 16-byte aligned; the padding stays 0
  *     bsum   [ceil(cap / 1024)] one sum per block of 1,024 consecutive slots, always formed in one fixed order (never by float atomics):
@@ -668,6 +670,31 @@ int hx_per_sample(const HxPer* per, const float* ring, int32_t batch, const floa
  * arithmetic on the same numbers (at w == 1, mean(w) is exactly 1 and mean(w H) has the mean entropy's bits).  step is 1-based. */
 int hx_sac_learn_weighted(const HxSacNets* nets, const HxSacBatch* batch, const HxHyper* hyper, const float* weights, float* errors_out,
                           int32_t polyak_first, int32_t step, float target_entropy, void* stream);
+/* Priorities at insert (SAC/agent.py:198-210, 234-246: train_episode scores every transition it appends).  Every row (s, a, r, s', d) in
+ * [marked, *total) mod cap — max_new as in hx_per_mark_new: the caller's bound; the first max_new are covered and `marked` advances by as much — is
+ * scored with the networks AS THEY ARE when the launches run (d = the masked done the ring holds):
+ *     a', H' = policy.sample(s')        one standard-normal draw per row and component
+ *     y      = r + (1 - d) gamma (min(Q1_target, Q2_target)(s', a') + alpha H')        alpha = alpha_state[3], gamma = hyper->gamma
+ *     error  = |Q1(s, a) - y|           prio[slot] = (error + 1e-4)^per_alpha (powf, as hx_per_update stores it)
+ * A row whose error is not finite enters at pmax AS IT WAS WHEN THE CALL STARTED (where hx_per_mark_new would place it): a live slot always holds a
+ * priority.  The touched blocks are re-summed in hx_per_*'s fixed order (no float atomics: the same errors give the same bsum bits), pmax is raised to
+ * the largest priority stored, marked advances.  More than cap new rows: the last cap of them — all the ring still holds — are scored, which gives
+ * every slot a priority, and marked <- *total; row i of the call is then the row in slot (*total + i) mod cap.
+ * Only enqueues: *total and *marked are read on the device.  The range is worked through in chunks of exactly chunk_rows rows (a positive multiple of
+ * 16), ceil(min(max_new, cap) / chunk_rows) of them, six launches each: the chunk's slots and its rows gathered into a tile; the forward launch of
+ * policy(s') and Q1(s, a); the Gaussian head; the forward launch of target Q1 / Q2 (s', a'); the per-row TD error; the store.  Every chunk's forward
+ * launches have the same shape — the last chunk is padded with a live row whose results are dropped, never shortened — because the forward kernel
+ * picks its column tiling, and with it the order of its sums, from the launch shape: a row's score depends on the row, the networks, its draw and
+ * chunk_rows, never on how many rows were stored with it or where in the range it falls.
+ * eps [max_new][4]: the draws, row i of the call at eps[4 i ..]; NULL: Philox4x32-10(key = seed; counter = (0xC0000000 + i, call), the Gaussian
+ * head's stream word) — learn() draws at rows 0x40000000 + r and 0x80000000 + r, the acting calls at env ids counted from 0: no collision for the
+ * same (seed, call).  errors_out [max_new] or NULL: error of row i, written for i < the rows covered only.  ws: hx_per_score_workspace_floats(chunk_rows)
+ * floats, 16-byte aligned, the caller's between calls.  fp32 only (nets->w2_bf16_all set: an error); one GPU.  Not built: bf16, scoring inside the front
+ * launch, sharded ranks, the imitative / E-SAC branches, scoring with the acting kernels' formats. */
+int64_t hx_per_score_workspace_floats(int32_t chunk_rows); /* 0 unless chunk_rows is a positive multiple of 16 */
+int hx_per_score_new(const HxPer* per, const float* ring, const HxSacNets* nets, const HxHyper* hyper, int64_t max_new, int32_t chunk_rows,
+                     float per_alpha, const float* eps /* NULL or [max_new][4] */, uint64_t seed, uint32_t call, float* ws,
+                     float* errors_out /* NULL or [max_new] */, void* stream);
 /* The same under gradient-norm clipping ("Gradient-norm clipping" above): its two weight-gradient launches run without Adam, each followed by
  * hx_sac_grad_norm and the clipped step (4 launches more); the log-alpha step stays the launch of its own, unclipped. */
 int hx_sac_learn_weighted_clipped(const HxSacNets* nets, const HxSacBatch* batch, const HxHyper* hyper, const float* weights, float* errors_out,

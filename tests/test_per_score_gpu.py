@@ -1,0 +1,445 @@
+"""GPU tests of priorities at insert for SAC's prioritized replay (hx_per_score_new through PrioritizedReplay.score_new, SacEngine.score_new,
+SacAgent.calc_current_q / calc_target_q and train_all --per_new td).
+
+The error arithmetic is the reference's (SAC/agent.py:198-210, 238-241), held to the project's two existing bars for exactly this quantity: rtol 5e-5 /
+atol 2e-5 against the reference's recorded run, rtol 2e-5 / atol 5e-6 against the fp32 checker tests/_per_score.score.  The store rule is this
+project's own, stated by tests/_per_score.ScoreModel.  Smallest shapes that can still go wrong: rings of 1,024 and 2,048 slots (one and two blocks),
+chunks of 16, 32 and 128 rows with ragged last chunks, and once the chunk train_all uses."""
+import ctypes
+import json
+import os
+import types
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+from tests import _hirl_data as D  # noqa: E402
+from tests import _per_check as P  # noqa: E402
+from tests import _per_score as PS  # noqa: E402
+from tests.test_oracle_sac import sac_params  # noqa: E402
+
+CAP = 2048
+CHECK = dict(rtol=2e-5, atol=5e-6)    # HIP against the fp32 checker (tests/test_per_gpu.py's bar for errors)
+GOLDEN = dict(rtol=5e-5, atol=2e-5)   # ... against the reference's recorded run
+
+
+@pytest.fixture(scope="module")
+def SE():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from hirl4ucav_amd.agents import sac_engine
+
+    return sac_engine
+
+
+@pytest.fixture(scope="module")
+def world(SE):
+    """the generator's parameters in an engine (untouched networks: alpha = 1, targets = critics) and its replay table"""
+    params, data = sac_params(), D.make_data(D.DATA_SEED)
+    e = SE.SacEngine(batch=16)
+    e.load_params(params["policy"], params["q1"], params["q2"])
+    return types.SimpleNamespace(e=e, params=params, rows=data["replay"], targets={"q1": params["q1"], "q2": params["q2"]})
+
+
+def expected(W, rows, eps):
+    return PS.score(W.params, W.targets, 1.0, rows, eps)
+
+
+def assert_errors(W, got, rows, eps):
+    """against the fp64 checker at the project's bar plus what a saturated tanh costs any fp32 evaluation (tests/_per_score.assert_errors)"""
+    PS.assert_errors(got, W.params, W.targets, 1.0, rows, eps)
+
+
+def new_replay(cap=CAP, chunk=32):
+    from hirl4ucav_amd.utils.buffer import PrioritizedReplay
+
+    rep = PrioritizedReplay(cap)
+    rep.score_chunk = chunk
+    return rep
+
+
+def state(rep):
+    return {k: getattr(rep, k).clone() for k in ("_prio", "bsum", "_header")}
+
+
+def check_store(rep, m):
+    """the device's store against the model: priorities at the project's HIP-vs-model bar, the block sums bit for bit in the fixed order — from the
+    device's own prio, and equal to what hx_per_resum forms from it —, pmax, marked"""
+    pr = rep.prio.cpu().numpy()
+    np.testing.assert_allclose(pr, m.prio, rtol=2e-5, atol=0)
+    assert (rep._prio[rep.capacity:] == 0).all()
+    bs = rep.bsum.cpu().numpy()
+    np.testing.assert_array_equal(bs.view(np.uint32), PS.bsum_bits(pr, rep.capacity).view(np.uint32))
+    rep.resum()
+    np.testing.assert_array_equal(bs.view(np.uint32), rep.bsum.cpu().numpy().view(np.uint32))
+    np.testing.assert_allclose(rep.pmax, m.pmax, rtol=2e-5)
+    assert rep.marked == m.marked
+
+
+def ulps(a, b):
+    return np.abs(np.asarray(a, np.float32).view(np.int32).astype(np.int64) - np.asarray(b, np.float32).view(np.int32).astype(np.int64))
+
+
+def test_parity_with_the_reference(SE, world, golden_dir):
+    g = np.load(os.path.join(golden_dir, "sac_per_learn.npz"))
+    assert D.checksum(world.params) == str(g["param_checksum"])
+    rows, eps = world.rows[g["idx"][0]], g["eps"][0, 0]
+    rep = new_replay(chunk=128)
+    rep.store_rows(torch.from_numpy(rows))
+    world.e.score_new(rep, 128, eps=torch.from_numpy(eps).cuda())
+    err = rep.errors[:128].cpu().numpy()
+    ref = expected(world, rows, eps)
+    print(f"errors: vs golden {np.max(np.abs(err - g['errors'][0])):.2e}, vs checker {np.max(np.abs(err - ref)):.2e}")
+    np.testing.assert_allclose(err, g["errors"][0], **GOLDEN)
+    np.testing.assert_allclose(err, ref, **CHECK)
+    pr = rep.prio.cpu().numpy()
+    want = ((err + np.float32(1e-4)).astype(np.float64) ** float(np.float32(0.6))).astype(np.float32)  # powf(err + 1e-4f, 0.6f), correctly rounded
+    assert ulps(pr[:128], want).max() <= 2, ulps(pr[:128], want).max()
+    assert (pr[128:] == 0).all()
+    m = PS.ScoreModel(CAP)
+    m.score_new(128, err)
+    assert rep.pmax == np.float32(max(1.0, pr.max())) and rep.pmax > 1.0  # (errors above 1 exist in this batch: pmax is raised)
+    m.pmax = float(rep.pmax)
+    check_store(rep, m)
+    assert rep.marked == 128 == int(rep.total.item()) and rep.score_calls == 1
+
+
+@pytest.mark.parametrize("chunk", [32, 1024, 2048, 4096])
+def test_a_rows_score_does_not_depend_on_its_company(SE, world, chunk):
+    """the same 16 rows alone (max_new = 16: one padded chunk) and as the LAST 16 rows of a call over 64 / chunk + 16 rows, with the same draws:
+    bit-identical errors.  1,024 / 2,048 / 4,096: the values train_all uses (utils.buffer.score_chunk_for), 2,048 the replay's default."""
+    from hirl4ucav_amd.utils.buffer import PER_SCORE_CHUNK, PER_SCORE_CHUNKS, score_chunk_for
+
+    assert PER_SCORE_CHUNK == 2048 and PER_SCORE_CHUNKS == (1024, 2048, 4096)
+    assert [score_chunk_for(k) for k in (64, 1024, 1025, 2048, 4096, 16384)] == [1024, 1024, 2048, 2048, 4096, 4096]
+    n = 64 if chunk == 32 else chunk + 16
+    rng = np.random.default_rng(chunk)
+    rows = np.resize(world.rows, (n, 32)).copy()
+    eps = rng.normal(size=(n, 4)).astype(np.float32)
+    alone = new_replay(8192, chunk)
+    alone.store_rows(torch.from_numpy(rows[n - 16:]))
+    world.e.score_new(alone, 16, eps=torch.from_numpy(eps[n - 16:]).cuda())
+    full = new_replay(8192, chunk)
+    full.store_rows(torch.from_numpy(rows))
+    world.e.score_new(full, n, eps=torch.from_numpy(eps).cuda())
+    a, b = alone.errors[:16].cpu().numpy(), full.errors[:n].cpu().numpy()
+    np.testing.assert_array_equal(a.view(np.uint32), b[n - 16:].view(np.uint32))
+    np.testing.assert_array_equal(alone.prio[:16].cpu().numpy().view(np.uint32), full.prio[n - 16:n].cpu().numpy().view(np.uint32))
+    assert_errors(world, b, rows, eps)
+    assert alone.marked == 16 and full.marked == n
+
+
+def test_range_edges(SE, world):
+    e = world.e
+    rng = np.random.default_rng(5)
+    rep = new_replay(CAP, 32)
+    m = PS.ScoreModel(CAP)
+    rep.store_rows(torch.from_numpy(world.rows[:1000]))
+    rep.mark_new()
+    m.mark_new(1000)
+    # nothing new: nothing changes
+    rep.errors = torch.full((64,), -7.0, device="cuda")
+    before = state(rep)
+    e.score_new(rep, 64, eps=torch.zeros((64, 4), device="cuda"))
+    assert all(torch.equal(before[k], getattr(rep, k)) for k in before) and (rep.errors == -7.0).all()
+    # 17 rows under a bound of 64: two chunks of 32, the first one ragged, the second one all padding; slots 1000..1016 stay inside block 0
+    rows, eps = world.rows[1000:1017], rng.normal(size=(64, 4)).astype(np.float32)
+    rep.store_rows(torch.from_numpy(rows))
+    before = state(rep)
+    e.score_new(rep, 64, eps=torch.from_numpy(eps).cuda())
+    err = rep.errors.cpu().numpy()
+    assert (err[17:] == -7.0).all(), "the padding rows leave no trace in errors_out"
+    assert_errors(world, err[:17], rows, eps[:17])
+    m.score_new(1017, err[:17])
+    check_store(rep, m)
+    untouched = np.r_[0:1000, 1017:CAP]
+    assert torch.equal(before["_prio"][untouched], rep._prio[untouched]) and before["bsum"][1] == rep.bsum[1]
+    # 40 rows across the block boundary at 1,024, in chunks of 16 (the last one ragged)
+    rep.score_chunk = 16
+    rows, eps = world.rows[1017:1057], rng.normal(size=(40, 4)).astype(np.float32)
+    rep.store_rows(torch.from_numpy(rows))
+    e.score_new(rep, 40, eps=torch.from_numpy(eps).cuda())
+    err = rep.errors[:40].cpu().numpy()
+    assert_errors(world, err, rows, eps)
+    np.testing.assert_array_equal(m.score_new(1057, err), np.arange(1017, 1057))
+    check_store(rep, m)
+    # a bound smaller than the rows stored: the rest is scored by the next call
+    rows, eps = world.rows[1057:1105], rng.normal(size=(32, 4)).astype(np.float32)
+    rep.store_rows(torch.from_numpy(rows))
+    e.score_new(rep, 32, eps=torch.from_numpy(eps).cuda())
+    err = rep.errors[:32].cpu().numpy()
+    assert_errors(world, err, rows[:32], eps)
+    m.score_new(1105, err, max_new=32)
+    check_store(rep, m)
+    assert rep.marked == 1057 + 32 and (rep.prio[1089:1105] == 0).all()
+    e.score_new(rep, 32, eps=torch.from_numpy(eps).cuda())
+    err = rep.errors[:32].cpu().numpy()
+    assert_errors(world, err[:16], rows[32:], eps[:16])
+    m.score_new(1105, err, max_new=32)
+    check_store(rep, m)
+    assert rep.marked == 1105 == int(rep.total.item())
+    # a range that wraps the ring's end (and with it the boundary between the last block and block 0)
+    rep.store_rows(torch.from_numpy(np.resize(world.rows, (2040 - 1105, 32))))
+    rep.mark_new()
+    m.mark_new(2040)
+    rows, eps = world.rows[300:340], rng.normal(size=(40, 4)).astype(np.float32)
+    rep.store_rows(torch.from_numpy(rows))
+    e.score_new(rep, 40, eps=torch.from_numpy(eps).cuda())
+    err = rep.errors[:40].cpu().numpy()
+    assert_errors(world, err, rows, eps)
+    np.testing.assert_array_equal(m.score_new(2080, err), np.r_[2040:2048, 0:32])
+    check_store(rep, m)
+
+
+def test_a_non_finite_error_enters_at_pmax(SE, world):
+    rep = new_replay(CAP, 16)
+    rep.store_rows(torch.from_numpy(world.rows[:8]))
+    rep.mark_new()
+    rep.set_priorities([0], [2.5])
+    assert rep.pmax == 2.5
+    rows = world.rows[100:116].copy()
+    rows[3, 30] = 1000.0    # an error whose priority exceeds pmax, in front of ...
+    rows[5, 30] = np.nan    # ... the row that cannot be scored: it enters at pmax as it was when the call started
+    rows[9, 30] = np.inf
+    eps = np.random.default_rng(9).normal(size=(16, 4)).astype(np.float32)
+    rep.store_rows(torch.from_numpy(rows))
+    world.e.score_new(rep, 16, eps=torch.from_numpy(eps).cuda())
+    err, pr = rep.errors[:16].cpu().numpy(), rep.prio[8:24].cpu().numpy()
+    assert np.isnan(err[5]) and np.isinf(err[9]) and pr[5] == 2.5 and pr[9] == 2.5
+    ok = np.r_[0:5, 6:9, 10:16]
+    assert_errors(world, err[ok], rows[ok], eps[ok])
+    m = PS.ScoreModel(CAP)
+    m.mark_new(8)
+    m.set([0], [2.5])
+    m.score_new(24, err)
+    check_store(rep, m)
+    assert rep.pmax > 60.0 and rep.pmax == np.float32(pr[3])
+
+
+def test_more_rows_than_the_ring_holds(SE, world):
+    """1,040 rows into 1,024 slots between two calls: the last 1,024 are scored — row i of the call is the row in slot (total + i) mod cap —, every slot
+    holds a priority, marked = total"""
+    rep = new_replay(1024, 256)
+    rep.store_rows(torch.from_numpy(world.rows[:1024]))
+    rep.store_rows(torch.from_numpy(world.rows[1024:1040]))
+    eps = np.random.default_rng(11).normal(size=(1040, 4)).astype(np.float32)
+    world.e.score_new(rep, 1040, eps=torch.from_numpy(eps).cuda())
+    err = rep.errors[:1024].cpu().numpy()
+    assert_errors(world, err, world.rows[16:1040], eps[:1024])
+    m = PS.ScoreModel(1024)
+    slots = m.score_new(1040, err)
+    assert slots[0] == 16 and slots[-1] == 15
+    m.pmax = float(rep.pmax)
+    check_store(rep, m)
+    assert rep.marked == 1040 and (rep.prio > 0).all()
+
+
+def test_philox_key(SE, world):
+    """(seed, call) keys the draws; the scorer draws at rows 0xC0000000 + i — not where learn()'s policy.sample(s') draws for the same (seed, call)"""
+    rows = world.rows[:48]
+
+    def run(seed, call, eps=None):
+        rep = new_replay(CAP, 32)
+        rep.store_rows(torch.from_numpy(rows))
+        rep.score_calls = call - 1
+        world.e.score_new(rep, 48, seed=seed, eps=None if eps is None else torch.from_numpy(eps).cuda())
+        assert rep.score_calls == call
+        return rep.errors[:48].cpu().numpy()
+
+    a, b, c, d = run(7, 3), run(7, 3), run(7, 4), run(8, 3)
+    np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32))
+    assert (a != c).mean() > 0.9 and (a != d).mean() > 0.9
+    own = run(7, 3, PS.philox_normals(7, PS.SCORE_ROW0, 3, 48))
+    learns = run(7, 3, PS.philox_normals(7, PS.LEARN_NEXT_ROW0, 3, 48))
+    np.testing.assert_allclose(a, own, rtol=1e-3, atol=1e-3)  # (the host's float64 Box-Muller against the device's logf / sinf / cosf)
+    assert np.abs(a - learns).max() > 0.05 and (np.abs(a - learns) > 1e-2).mean() > 0.5
+
+
+def test_score_new_through_a_real_env(SE):
+    """64 envs, act_step -> score_new -> sample -> learn (step_learn under new_rows="td"), a 2,048-slot ring that wraps"""
+    from hirl4ucav_amd.environments.batched import BatchedHarfangEnv
+    from hirl4ucav_amd.utils.buffer import PrioritizedReplay
+
+    params = sac_params()
+    rep = PrioritizedReplay(CAP, ordered_slots=True)
+    rep.score_chunk = 64
+    env = BatchedHarfangEnv(64, scenario="serpentine", seed=2, auto_reset=True, random_reset=True, replay=rep)
+    env.reset()
+    e = SE.SacEngine(batch=16)
+    e.load_params(params["policy"], params["q1"], params["q2"])
+    e.set_prioritized(rep, new_rows="td")
+    def invariants():
+        total = int(rep.total.item())
+        live = min(total, CAP)
+        pr = rep.prio.cpu().numpy()
+        assert np.isfinite(pr).all() and (pr[:live] > 0).all() and (pr[live:] == 0).all() and rep.marked == total
+        np.testing.assert_array_equal(rep.bsum.cpu().numpy().view(np.uint32), PS.bsum_bits(pr, CAP).view(np.uint32))
+        return total, pr
+
+    for step in range(40):
+        e.step_learn(env, act_seed=5, sample_seed=6)
+        if step == 0:
+            invariants()
+    total, pr = invariants()
+    assert total > CAP and rep.score_calls == 40 and e.learning_steps == 40 and torch.isfinite(e.losses).all()
+    pm = np.float32(rep.pmax)
+    assert (pr < pm).sum() > CAP // 2 and len(np.unique(pr)) > CAP // 2, "the rows hold priorities of their own, below the running maximum"
+    # the draw on these priorities: targets in the middle of chosen slots' intervals of the running sum resolve to exactly those slots
+    m = P.PerModel(CAP)
+    m.prio[:] = pr
+    cum = np.cumsum(m.prio)
+    chosen = np.random.default_rng(1).choice(np.argsort(pr)[CAP // 2:], 16, replace=False)  # (wide intervals: far from the fp32 scan's rounding)
+    u = ((cum[chosen] - 0.5 * m.prio[chosen]) / cum[-1]).astype(np.float32)
+    idx, w, tile = torch.zeros(16, dtype=torch.int32, device="cuda"), torch.zeros(16, device="cuda"), torch.zeros((16, 32), device="cuda")
+    rep.sample_into(16, idx, w, tile, u=torch.from_numpy(u).cuda(), beta=0.4)
+    np.testing.assert_array_equal(idx.cpu().numpy(), chosen)
+    np.testing.assert_array_equal(m.draw(u.astype(np.float64)), chosen)
+
+
+def test_refusals(SE, world):
+    from hirl4ucav_amd import _lib
+    from hirl4ucav_amd.utils.buffer import DeviceReplay
+    from tests.test_isac_gpu import bc_actor_params
+
+    rep = new_replay()
+    rep.store_rows(torch.from_numpy(world.rows[:32]))
+
+    def engine():
+        e = SE.SacEngine(batch=16)
+        e.load_params(world.params["policy"], world.params["q1"], world.params["q2"])
+        return e
+
+    e = engine()
+    e.set_act_dtype("bf16")
+    with pytest.raises(_lib.HxError, match="fp32 only"):
+        e.score_new(rep, 32)
+    e = engine()
+    e.set_imitative(bc_actor_params())
+    with pytest.raises(_lib.HxError, match="imitative"):
+        e.score_new(rep, 32)
+    e = engine()
+    e.world = 2
+    with pytest.raises(_lib.HxError, match="one GPU"):
+        e.score_new(rep, 32)
+    e = engine()
+    with pytest.raises(TypeError):
+        e.score_new(DeviceReplay(64), 32)
+    with pytest.raises(ValueError, match="'max' or 'td'"):
+        e.set_prioritized(rep, new_rows="mean")
+    with pytest.raises(ValueError, match="max_new"):
+        e.score_new(rep, 0)
+    # the library's own
+    L = _lib.load()
+    L.hx_per_score_workspace_floats.restype = ctypes.c_int64
+    assert L.hx_per_score_workspace_floats(24) == 0 and L.hx_per_score_workspace_floats(0) == 0 and L.hx_per_score_workspace_floats(32) > 0
+    ws = torch.zeros(int(L.hx_per_score_workspace_floats(32)), device="cuda")
+
+    def call(per=rep.per, ring=rep.ring.data_ptr(), nets=e.nets, hyper=e.hyper, max_new=32, chunk=32, alpha=0.6, wsp=ws.data_ptr()):
+        _lib.call("hx_per_score_new", ctypes.byref(per), ring, ctypes.byref(nets) if nets is not None else None, ctypes.byref(hyper) if hyper is not None else None,
+                  max_new, chunk, alpha, None, 0, 1, wsp, None, _lib.stream_ptr())
+
+    before = state(rep)
+    for kw, why in ((dict(chunk=24), "multiple of 16"), (dict(chunk=0), "multiple of 16"), (dict(max_new=0), "max_new"), (dict(wsp=None), "ws"),
+                    (dict(ring=None), "ring"), (dict(nets=None), "nets"), (dict(hyper=None), "hyper"), (dict(alpha=1.5), "per_alpha"),
+                    (dict(alpha=-0.1), "per_alpha")):
+        with pytest.raises(_lib.HxError, match=why):
+            call(**kw)
+    e.nets.w2_bf16_all = rep._prio.data_ptr()  # (any non-NULL pointer: the check precedes every launch)
+    with pytest.raises(_lib.HxError, match="fp32 only"):
+        call()
+    e.nets.w2_bf16_all = None
+    assert all(torch.equal(before[k], getattr(rep, k)) for k in before), "a refused call launches nothing"
+
+
+def test_snapshot_carries_the_mode_and_the_call_word(SE, world, tmp_path):
+    from hirl4ucav_amd.utils import checkpoint as CK
+
+    def build(mode):
+        rep = new_replay(CAP, 32)
+        e = SE.SacEngine(batch=16)
+        e.load_params(world.params["policy"], world.params["q1"], world.params["q2"])
+        e.set_prioritized(rep, new_rows=mode)
+        return e, rep
+
+    def steps(e, rep, lo, hi):
+        for k in range(lo, hi):
+            rep.store_rows(torch.from_numpy(world.rows[40 * k:40 * k + 40]))
+            e.score_new(rep, 40, seed=3)
+        return rep.errors[:40].clone()
+
+    e, rep = build("td")
+    steps(e, rep, 0, 2)
+    st_e, st_r = CK.engine_state(e), CK.replay_state(rep)
+    assert st_e["per_new_rows"] == "td" and st_r["per"]["score_calls"] == 2 and st_r["per"]["score_chunk"] == 32
+    last = steps(e, rep, 2, 4)
+    e2, rep2 = build("td")
+    CK.load_engine_state(e2, st_e)
+    CK.load_replay_state(rep2, st_r)
+    assert rep2.score_calls == 2 and rep2.marked == 80
+    assert torch.equal(last, steps(e2, rep2, 2, 4)), "the resumed run draws what the uninterrupted one drew"
+    for name in ("_prio", "bsum", "_header"):
+        assert torch.equal(getattr(rep, name), getattr(rep2, name)), name
+    e3, _ = build("max")
+    with pytest.raises(ValueError, match="--per_new"):
+        CK.load_engine_state(e3, st_e)
+    with pytest.raises(ValueError, match="--per_new"):
+        CK.load_engine_state(e2, CK.engine_state(e3))
+    assert "per_new_rows" not in CK.engine_state(e3) and "score_calls" not in CK.replay_state(new_replay())["per"]
+
+
+def test_facade_target_and_current_q(SE, tmp_path):
+    """SacAgent.calc_current_q / calc_target_q at one row against the checker; the reference's train_episode body (agent.py:234-246) then appends with
+    that error"""
+    from hirl4ucav_amd.agents.SAC.agent import SacAgent
+
+    box = lambda n: types.SimpleNamespace(shape=(n,), sample=lambda: np.zeros(n, np.float32))  # noqa: E731
+    torch.manual_seed(0)  # (the agent's initial networks come from torch's generator)
+    ag = SacAgent(box(13), box(4), str(tmp_path / "log"), batch_size=16, lr=1e-3, hidden_units=[256, 512], memory_size=CAP, per=True, start_steps=0)
+    sd = {k: {kk: vv.cpu().numpy() for kk, vv in v.items()} for k, v in ag.eng.state_dicts().items()}
+    rng = np.random.default_rng(3)
+    state, action, reward, next_state, done = rng.uniform(-1, 1, 13), rng.uniform(-1, 1, 4), -2.5, rng.uniform(-1, 1, 13), False
+    batch = (state, action, reward, next_state, float(done))
+    torch.manual_seed(4)
+    eps = torch.randn(1, 4)
+    torch.manual_seed(4)
+    with torch.no_grad():
+        q1, q2 = ag.calc_current_q(*batch)
+    y = ag.calc_target_q(*batch)  # (draws torch.randn(1, 4), as Normal.rsample would)
+    assert q1.shape == (1, 1) and q2.shape == (1, 1) and y.shape == (1, 1)
+    error = torch.abs(q1 - y).item()
+    row = np.zeros((1, 32), np.float32)
+    row[0, 0:13], row[0, 13:17], row[0, 17:30], row[0, 30], row[0, 31] = state, action, next_state, reward, 0.0
+    nets, targets = {"policy": sd["policy"], "q1": sd["q1"], "q2": sd["q2"]}, {"q1": sd["q1_target"], "q2": sd["q2_target"]}
+    PS.assert_errors([error], nets, targets, 1.0, row, eps.numpy(), gamma=ag.gamma_n, what="calc_current_q / calc_target_q")
+    ag.memory.append(state, action, reward, next_state, done, error, episode_done=done)
+    np.testing.assert_allclose(float(ag.memory.prio[0].item()), (error + 1e-4) ** 0.6, rtol=2e-5)
+    # the same row through the scoring pass, with the same draw
+    ag.memory.marked_t.zero_()
+    ag.memory.score_chunk = 16
+    ag.eng.score_new(ag.memory, 1, eps=eps.cuda())
+    PS.assert_errors([float(ag.memory.errors[0].item())], nets, targets, 1.0, row, eps.numpy(), gamma=ag.gamma_n, what="score_new at one row")
+    assert ag.memory.marked == 1
+
+
+def test_train_all_per_new_td_and_resume(SE, tmp_path, monkeypatch, capsys):
+    """--per --per_new td at 64 envs for two episodes: trains, logs stats/per_mean_new_error, --resume continues and refuses the other mode"""
+    from hirl4ucav_amd import train_all as T
+    from hirl4ucav_amd.utils.scalars import JsonlWriter
+
+    monkeypatch.setattr(T, "make_writer", JsonlWriter)
+    common = ["--agent", "SAC", "--type", "SAC", "--per", "--env", "serpentine", "--random", "--seed", "3", "--num_envs", "64", "--buffer_size", "4096",
+              "--max_step", "24", "--checkpoint_rate", "1000", "--snapshot_every", "1"]
+    run = T.main(T.parse_args(common + ["--per_new", "td", "--episodes", "2", "--result_dir", str(tmp_path / "a")]))
+    out = capsys.readouterr().out
+    assert "vector loop: reference order (--per" in out and "Episode 2:" in out
+    sc = [json.loads(ln) for ln in open(os.path.join(run, "summary", "scalars.jsonl"))]
+    new = [s["value"] for s in sc if s["tag"] == "stats/per_mean_new_error"]
+    assert len(new) == 2 and all(np.isfinite(new)) and all(v > 0 for v in new), new
+    T.main(T.parse_args(common + ["--per_new", "td", "--episodes", "3", "--resume", run, "--result_dir", str(tmp_path / "b")]))
+    assert "Episode 3:" in capsys.readouterr().out
+    for other in (["--per_new", "max"], []):
+        with pytest.raises(ValueError, match="--per_new"):
+            T.main(T.parse_args(common + other + ["--episodes", "3", "--resume", run, "--result_dir", str(tmp_path / "c")]))
