@@ -581,32 +581,15 @@ class SacEngine:
             if expert is not None and n_main is not None and int(n_main) < B:
                 raise _lib.HxError("prioritized replay does not mix expert rows into the minibatch (the reference's learn() drops them when per is on: "
                                    "agent.py:281-284): run step_learn without expert rows")
-            res = self.act_step(env, explore=explore, seed=act_seed, out=out)
-            if self.per_new_rows == "td":
-                self.score_new(replay, n, seed=sample_seed)
-            else:
-                replay.mark_new(n)
-            self.sample(replay, None, seed=sample_seed)
-            self.learn()
-            return res
+            return self._step_then_learn(env, explore, act_seed, out, sample_seed, new_rows=self.per_new_rows)
         if self.imitative:  # no front form: the reference's order; `expert` is the imitative branch's expert memory, the minibatch is not expert-mixed
             if expert is None:
                 raise _lib.HxError("SacEngine.step_learn: the imitative branch needs the expert memory (expert=...)")
-            res = self.act_step(env, explore=explore, seed=act_seed, out=out)
-            self.sample(replay, None, seed=sample_seed, defer=True)
-            self.sample_expert(expert, seed=sample_seed, defer=True)
-            self.learn()
-            return res
-        if self.grad_clip is not None:  # no front form: the clipped update is the staged sequence, whose first launch is its own (the reference's order)
-            res = self.act_step(env, explore=explore, seed=act_seed, out=out)
-            self.sample(replay, expert, n_main=n_main, seed=sample_seed, defer=True)
-            self.learn()
-            return res
-        if self.act_dtype != self.update_dtype:  # bf16 acting beside the fp32 update: the front launch has no such mix (the reference's order)
-            res = self.act_step(env, explore=explore, seed=act_seed, out=out)
-            self.sample(replay, expert, n_main=n_main, seed=sample_seed, defer=True)
-            self.learn()
-            return res
+            return self._step_then_learn(env, explore, act_seed, out, sample_seed, defer=True, imit_expert=expert)
+        # no front form either: the clipped update is the staged sequence, whose first launch is its own; bf16 acting beside the fp32 update is a mix the
+        # front launch does not have
+        if self.grad_clip is not None or self.act_dtype != self.update_dtype:
+            return self._step_then_learn(env, explore, act_seed, out, sample_seed, expert=expert, n_main=n_main, defer=True)
         if self._front_tiles is None:
             second = torch.zeros(B * 32 + B, dtype=torch.float32, device=self.device)
             self._front_tiles = [(self.rows, self._idx), (second[:B * 32], second[B * 32:].view(torch.int32))]
@@ -637,6 +620,21 @@ class SacEngine:
         self._front_tiles = [nxt, cur]
         self.rows, self._idx = cur
         return out, env.obs, env.reward, env.done, env.success
+
+    def _step_then_learn(self, env, explore, act_seed, out, sample_seed, expert=None, n_main=None, defer=False, new_rows=None, imit_expert=None):
+        """step_learn without a front form, the reference's order: act_step, [the step's rows get their first priority: new_rows "max" | "td"],
+        sample(env.replay, expert, n_main), [sample_expert(imit_expert)], learn()"""
+        replay = env.replay
+        res = self.act_step(env, explore=explore, seed=act_seed, out=out)
+        if new_rows == "td":
+            self.score_new(replay, env.n, seed=sample_seed)
+        elif new_rows == "max":
+            replay.mark_new(env.n)
+        self.sample(replay, expert, n_main=n_main, seed=sample_seed, defer=defer)
+        if imit_expert is not None:
+            self.sample_expert(imit_expert, seed=sample_seed, defer=defer)
+        self.learn()
+        return res
 
     def losses_host(self):
         """(q1_loss, q2_loss, policy_loss, entropy_loss, mean entropy, alpha)"""

@@ -410,8 +410,7 @@ __device__ __forceinline__ void bwd_l2_body(const BwdArgsC& AC, const int bx, co
         } else if constexpr (GRP == 0) {
             const float qmin = tq[prow];  // min(Q1', Q2') of this row, from the pair's other wave
             // HIRL.py:270-274; with `bonus` SAC's r + (1 - d) gamma (min Q' + alpha H')  SAC/agent.py:202-210
-            const float target = J.bonus ? lab0 + (1.0f - lab1) * (J.gamma * (qmin + bonus * bonus_scale))
-                                         : lab0 + (J.gamma * qmin) * (1.0f - lab1);
+            const float target = J.bonus ? sac_td_target(lab0, lab1, J.gamma, qmin, bonus, bonus_scale) : lab0 + (J.gamma * qmin) * (1.0f - lab1);
             const float diff = o[0] - target;
             dout[0] = 2.0f * diff * A.inv_batch;  // d mse / dq
             part[0] += diff * diff * A.inv_batch;

@@ -1,7 +1,7 @@
 // hx_clip.hip — gradient-norm clipping for SAC (gfx950): update_params(optim, network, loss, grad_clip) = clip_grad_norm_ before optimizer.step()
 // (SAC/utils.py:15-21, SAC/agent.py:310-320).
 //   grad_sumsq    per-segment sums of squares of a flat gradient buffer, one partial per fixed 4,096-word chunk (no atomics, a fixed order)
-//   adam_clip     adam_kernel's step for SAC on g * gscale * coef[segment]; every workgroup re-adds its segments' partials and forms coef itself
+//   adam_clip     the optimizer step (adam_step4) on g * gscale * coef[segment]; every workgroup re-adds its segments' partials and forms coef itself
 // On one GPU the unclipped update steps every parameter inside the launch that produces its gradient (wgrad_kernel<ADAM>); a global norm is a grid-wide
 // dependency between "all gradients written" and "any parameter stepped", so the clipped update runs wgrad (no Adam), grad_sumsq, adam_clip.
 #include <cmath>
@@ -66,9 +66,9 @@ struct ClipArgs {
     float max_norm;
 };
 
-// adam_kernel's step for the SAC networks (no BC mix, no exchange guard, no target: SAC steps none of them here) with the gradient scaled by its
-// segment's clip coefficient.  Same adam_update on (g * gscale) * coef: coef == 1.0f multiplies exactly, so a max_norm that never binds leaves
-// adam_kernel's bits in parameters, moments and every image.
+// adam_step4 for the SAC networks (no BC mix, no exchange guard; A.target is NULL: SAC steps no target here) with the gradient scaled by its
+// segment's clip coefficient: (g * gscale) * coef, and coef == 1.0f multiplies exactly, so a max_norm that never binds leaves adam_kernel's bits in
+// parameters, moments and every image.
 __global__ __launch_bounds__(kThreads) void adam_clip_kernel(AdamArgs A, ClipArgs K) {
     __shared__ float coef_s[2];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -82,61 +82,13 @@ __global__ __launch_bounds__(kThreads) void adam_clip_kernel(AdamArgs A, ClipArg
         }
     }
     __syncthreads();
-    if (A.alpha_state && blockIdx.x == 0 && tid == 0) {  // the log-alpha step: never clipped (update_params(self.alpha_optim, None, entropy_loss))
-        const float mean_h = A.losses[4];
-        float la = A.alpha_state[0], m = A.alpha_state[1], v = A.alpha_state[2];
-        A.losses[3] = -(la * (A.target_entropy - mean_h));  // entropy_loss with the log_alpha BEFORE its step
-        adam_update(la, m, v, mean_h - A.target_entropy, A.b1, A.b2, A.eps, A.alpha_step_size, A.bc2_sqrt);
-        A.alpha_state[0] = la; A.alpha_state[1] = m; A.alpha_state[2] = v;
-        A.alpha_state[3] = expf(la);  // self.alpha = self.log_alpha.exp()
-        A.losses[5] = A.alpha_state[3];
-    }
+    if (A.alpha_state && blockIdx.x == 0 && tid == 0)  // the log-alpha step: never clipped (update_params(self.alpha_optim, None, entropy_loss))
+        sac_alpha_step(A.alpha_state, A.losses, A.losses[4], A.target_entropy, A.b1, A.b2, A.eps, A.alpha_step_size, A.bc2_sqrt);
     const int i = (blockIdx.x * kThreads + tid) * 4;
     if (i + 4 > A.n) return;  // (A.n is a multiple of 4: the blocks are padded)
     const float coef = coef_s[K.nseg > 1 && i >= K.seg_len ? 1 : 0];  // (segments start at multiples of 4 words: a float4 lies in one)
-    float4 p4 = *reinterpret_cast<const float4*>(A.p + i), g4 = *reinterpret_cast<const float4*>(A.g + i);
-    float4 m4 = *reinterpret_cast<const float4*>(A.m + i), v4 = *reinterpret_cast<const float4*>(A.v + i);
-    adam_update(p4.x, m4.x, v4.x, (g4.x * A.gscale) * coef, A.b1, A.b2, A.eps, A.step_size, A.bc2_sqrt);
-    adam_update(p4.y, m4.y, v4.y, (g4.y * A.gscale) * coef, A.b1, A.b2, A.eps, A.step_size, A.bc2_sqrt);
-    adam_update(p4.z, m4.z, v4.z, (g4.z * A.gscale) * coef, A.b1, A.b2, A.eps, A.step_size, A.bc2_sqrt);
-    adam_update(p4.w, m4.w, v4.w, (g4.w * A.gscale) * coef, A.b1, A.b2, A.eps, A.step_size, A.bc2_sqrt);
-    *reinterpret_cast<float4*>(A.p + i) = p4;
-    *reinterpret_cast<float4*>(A.m + i) = m4;
-    *reinterpret_cast<float4*>(A.v + i) = v4;
-    typedef __bf16 v4bf __attribute__((ext_vector_type(4)));
-    if (A.w2b && i >= A.w2_lo && i < A.w2_lo + H2 * H1) {  // W2 starts at a multiple of 4 floats: the float4 is inside or outside
-        const v4bf r = {(__bf16)p4.x, (__bf16)p4.y, (__bf16)p4.z, (__bf16)p4.w};
-        const uint32_t e = (uint32_t)(i - A.w2_lo);  // four consecutive k of one column: adjacent in the image too
-        const uint32_t ix = w2_image_index(e / H1, e % H1);
-        *reinterpret_cast<uint2*>(A.w2b + ix) = __builtin_bit_cast(uint2, r);
-        if (A.w2b_x9) {  // the other two parts of the exact split (split3_bf16)
-            const float pv[4] = {p4.x, p4.y, p4.z, p4.w};
-            uint16_t md[4], lw[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { uint16_t h; split3_bf16(pv[q], h, md[q], lw[q]); }
-            *reinterpret_cast<uint2*>(A.w2b + kImgElems + ix) = make_uint2((uint32_t)md[0] | ((uint32_t)md[1] << 16), (uint32_t)md[2] | ((uint32_t)md[3] << 16));
-            *reinterpret_cast<uint2*>(A.w2b + 2 * kImgElems + ix) = make_uint2((uint32_t)lw[0] | ((uint32_t)lw[1] << 16), (uint32_t)lw[2] | ((uint32_t)lw[3] << 16));
-        }
-    }
-    if (A.w2f && i >= A.w2_lo && i < A.w2_lo + H2 * H1) {
-        const uint32_t e = (uint32_t)(i - A.w2_lo);
-        *reinterpret_cast<float4*>(A.w2f + w2f_image_index(e / H1, e % H1)) = p4;
-    }
-    // bf16 update path: the forward and transposed images of every W2 this step changes follow it
-    for (int sg = 0; sg < A.nseg; ++sg) {
-        if (i < A.seg_lo[sg] || i >= A.seg_lo[sg] + H2 * H1) continue;
-        const uint32_t e = (uint32_t)(i - A.seg_lo[sg]), col = e / H1, k = e % H1;  // four consecutive k of one column
-        const v4bf r = {(__bf16)p4.x, (__bf16)p4.y, (__bf16)p4.z, (__bf16)p4.w};
-        if (A.seg_w2b[sg]) *reinterpret_cast<uint2*>(A.seg_w2b[sg] + w2_image_index(col, k)) = __builtin_bit_cast(uint2, r);
-        if (A.seg_w2tb[sg]) {
-            const uint2 q = __builtin_bit_cast(uint2, r);
-            uint16_t* tb = A.seg_w2tb[sg];
-            tb[w2t_image_index(k, col)] = (uint16_t)(q.x & 0xFFFFu);
-            tb[w2t_image_index(k + 1, col)] = (uint16_t)(q.x >> 16);
-            tb[w2t_image_index(k + 2, col)] = (uint16_t)(q.y & 0xFFFFu);
-            tb[w2t_image_index(k + 3, col)] = (uint16_t)(q.y >> 16);
-        }
-    }
+    const float4 g4 = *reinterpret_cast<const float4*>(A.g + i);
+    adam_step4(A, i, make_float4((g4.x * A.gscale) * coef, (g4.y * A.gscale) * coef, (g4.z * A.gscale) * coef, (g4.w * A.gscale) * coef));
 }
 
 inline int clip_chunks(const Mlp& m) { return (m.padded() + kClipChunk - 1) / kClipChunk; }

@@ -3,35 +3,14 @@
 // un-vendored rltorch, so the draw rule here is this project's own — include/hirl4ucav.h "Prioritized replay").
 #include <cmath>
 
-#include "hx_update.h"
+#include "hx_per_dev.h"
 
 using namespace hxnn;
 using namespace hxu;
 
 namespace {
 
-constexpr int kPerBlock = 1024;     // slots per block sum
-constexpr int kPerThreads = 256;    // workgroup of the store kernels: one float4 of the block per thread
 constexpr int kScanMax = 8192;      // entries of the block-sum scan the sampler holds in LDS (cap <= 2^24: at most two blocks per entry)
-
-struct PerDev {
-    float* prio; float* bsum; float* pmax;
-    unsigned long long* marked; unsigned* ticket;
-    const unsigned long long* total;
-    long long cap;
-    int nblocks;
-};
-
-// bsum[b] <- the sum of block b in a FIXED order ((x + y) + (z + w) per thread, the DPP tree per wave, ((w0 + w1) + (w2 + w3)) over the four waves):
-// the same bits for the same priorities, whoever re-sums.  All kPerThreads threads of the workgroup call it; `part` = 4 floats of LDS.
-__device__ __forceinline__ void resum_block(const PerDev& P, int b, float* part) {
-    const int tid = threadIdx.x;
-    const float4 v = reinterpret_cast<const float4*>(P.prio + (size_t)b * kPerBlock)[tid];  // (the padding behind cap holds zeros)
-    const float s = wave_sum((v.x + v.y) + (v.z + v.w));
-    if ((tid & 63) == 0) part[tid >> 6] = s;
-    __syncthreads();
-    if (tid == 0) P.bsum[b] = (part[0] + part[1]) + (part[2] + part[3]);
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // mark_new: every slot in [marked, *total) mod cap <- pmax; workgroup g owns block (first touched block + g) mod nblocks — it writes, then re-sums,
@@ -76,8 +55,8 @@ __global__ __launch_bounds__(kPerThreads) void per_mark_kernel(PerDev P, long lo
 // whose value is not finite (or negative) is skipped: the slot keeps the priority it had.
 // ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool per_value(const float* val, int i, int mode, float alpha, float& p) {
-    const float x = val[i];
-    p = mode ? powf(fabsf(x) + 1e-4f, alpha) : x;
+    if (mode) return per_priority(fabsf(val[i]), alpha, p);
+    p = val[i];
     return p >= 0.0f && p <= 3.0e38f;  // (false for NaN)
 }
 __global__ __launch_bounds__(kPerThreads) void per_write_kernel(PerDev P, const int* __restrict__ slots, const float* __restrict__ val, int n, int mode, float alpha) {
@@ -305,15 +284,6 @@ __global__ __launch_bounds__(1024) void per_sample_kernel(PerSampleArgs A) {
         const int r = e >> 3, c = e & 7;
         reinterpret_cast<float4*>(A.rows)[e] = reinterpret_cast<const float4*>(A.ring + (size_t)fin[r] * 32)[c];
     }
-}
-
-int per_dev(const HxPer* p, const char* who, PerDev* out) {
-    HX_REQUIRE(p && p->prio && p->bsum && p->pmax && p->marked && p->ticket && p->total && p->cap > 0, "%s: per needs prio, bsum, pmax, marked, ticket, total and cap > 0", who);
-    HX_REQUIRE(p->cap <= ((int64_t)1 << 24), "%s: prioritized replay holds at most 2^24 slots (cap = %lld): 16,384 block sums is what the sampler scans", who, (long long)p->cap);
-    HX_REQUIRE((reinterpret_cast<uintptr_t>(p->prio) & 15u) == 0, "%s: prio must be 16-byte aligned", who);
-    *out = PerDev{p->prio, p->bsum, p->pmax, (unsigned long long*)p->marked, p->ticket, (const unsigned long long*)p->total, (long long)p->cap,
-                  (int)((p->cap + kPerBlock - 1) / kPerBlock)};
-    return 0;
 }
 
 }  // namespace

@@ -44,9 +44,7 @@ __device__ __forceinline__ void polyak_image(const GaussLaunch& L, int i, const 
         if (!L.img[sg] || i < L.seg_lo[sg] || i >= L.seg_lo[sg] + H2 * H1) continue;
         const uint32_t e = (uint32_t)(i - L.seg_lo[sg]), col = e / H1, k = e % H1;
         if (four) {
-            typedef __bf16 v4bf __attribute__((ext_vector_type(4)));
-            const v4bf r = {(__bf16)t[0], (__bf16)t[1], (__bf16)t[2], (__bf16)t[3]};
-            *reinterpret_cast<uint2*>(L.img[sg] + w2_image_index(col, k)) = __builtin_bit_cast(uint2, r);
+            *reinterpret_cast<uint2*>(L.img[sg] + w2_image_index(col, k)) = pack4_bf16(t[0], t[1], t[2], t[3]);
         } else {
             L.img[sg][w2_image_index(col, k)] = __builtin_bit_cast(uint16_t, (__bf16)t[0]);
         }
@@ -241,20 +239,13 @@ __global__ __launch_bounds__(kThreads) void td_head_weighted_kernel(TdHeadArgs A
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + wave;
     if (r >= A.nrows) return;
-    RowReg<H2> xh, y;
-    float mean_, rstd_, t1[1], t2[1], q1[1], q2[1];
-    head_row<1, true>(A.z2_t1 + (size_t)r * H2, A.t1net, A.m, 0.0f, xh, y, mean_, rstd_, t1);
-    head_row<1, true>(A.z2_t2 + (size_t)r * H2, A.t2net, A.m, 0.0f, xh, y, mean_, rstd_, t2);
-    head_row<1, true>(A.s1.z2 + (size_t)r * H2, A.q1net, A.m, 0.0f, xh, y, mean_, rstd_, q1);
-    if (lane == 0) { A.s1.st2[r * 2] = mean_; A.s1.st2[r * 2 + 1] = rstd_; }
-    head_row<1, true>(A.s2.z2 + (size_t)r * H2, A.q2net, A.m, 0.0f, xh, y, mean_, rstd_, q2);
+    float qmin, q1, q2;
+    sac_td_heads<true>(A.m, r, {A.t1net, A.z2_t1, nullptr}, {A.t2net, A.z2_t2, nullptr}, {A.q1net, A.s1.z2, A.s1.st2}, {A.q2net, A.s2.z2, A.s2.st2}, qmin, q1, q2);
     if (lane == 0) {
-        A.s2.st2[r * 2] = mean_; A.s2.st2[r * 2 + 1] = rstd_;
         const float lab0 = A.rows[(size_t)r * 32 + 30], lab1 = A.rows[(size_t)r * 32 + 31];
-        const float qmin = fminf(t1[0], t2[0]);
-        const float target = lab0 + (1.0f - lab1) * (A.gamma * (qmin + A.ent_next[r] * A.alpha_state[3]));  // (bwd_l2<0>'s expression)
+        const float target = sac_td_target(lab0, lab1, A.gamma, qmin, A.ent_next[r], A.alpha_state[3]);
         const float wb = A.weights[r] * A.inv_batch;
-        const float d1 = q1[0] - target, d2 = q2[0] - target;
+        const float d1 = q1 - target, d2 = q2 - target;
         A.errors[r] = fabsf(d1);
         A.s1.dout[(size_t)r * OW] = 2.0f * d1 * wb;
         A.s2.dout[(size_t)r * OW] = 2.0f * d2 * wb;
@@ -262,22 +253,15 @@ __global__ __launch_bounds__(kThreads) void td_head_weighted_kernel(TdHeadArgs A
         atomicAdd(&A.losses[1], d2 * d2 * wb);
     }
 }
-// entropy_loss = -mean(log_alpha (target_entropy - H) w) and alpha_optim.step() (agent.py:322-325, 408-414): what thread 0 of the policy's
-// weight-gradient launch does in the unweighted call, with the gradient mean(w H) - target_entropy mean(w).  One thread.
+// entropy_loss = -mean(log_alpha (target_entropy - H) w) and alpha_optim.step() (agent.py:322-325, 408-414): sac_alpha_step on mean(w H) and
+// target_entropy mean(w) (wsum[0], wsum[1]: policy_dout_kernel<true>'s).  One thread.
 struct AlphaStepArgs {
     float* alpha_state; float* losses; const float* wsum;
     float target_entropy, b1, b2, eps, step_size, bc2_sqrt;
 };
 __global__ __launch_bounds__(64) void alpha_step_weighted_kernel(AlphaStepArgs A) {
     if (threadIdx.x != 0) return;
-    const float mean_wh = A.wsum[0], mean_w = A.wsum[1];
-    const float te = A.target_entropy * mean_w;
-    float la = A.alpha_state[0], m = A.alpha_state[1], v = A.alpha_state[2];
-    A.losses[3] = -(la * (te - mean_wh));  // entropy_loss with the log_alpha BEFORE its step
-    adam_update(la, m, v, mean_wh - te, A.b1, A.b2, A.eps, A.step_size, A.bc2_sqrt);
-    A.alpha_state[0] = la; A.alpha_state[1] = m; A.alpha_state[2] = v;
-    A.alpha_state[3] = expf(la);  // self.alpha = self.log_alpha.exp()
-    A.losses[5] = A.alpha_state[3];
+    sac_alpha_step(A.alpha_state, A.losses, A.wsum[0], A.target_entropy * A.wsum[1], A.b1, A.b2, A.eps, A.step_size, A.bc2_sqrt);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -452,9 +436,68 @@ static void sac_launch_1(const SacCtx& C, FwdArgs& F) {
 static GaussArgs gauss_cur(const SacCtx& C) {
     return GaussArgs{C.N->policy, kPolicy, C.s[SS_PC].z2, C.Bt->eps_cur, C.B, C.Bt->eps_cur ? 1 : 2, C.X.act_c, nullptr, C.X.aux_c, C.Bt->seed, 0x80000000u, C.Bt->call};
 }
+// a', H' = policy.sample(s') for the TD target
+static GaussArgs gauss_next(const SacCtx& C) {
+    return GaussArgs{C.N->policy, kPolicy, C.s[SS_PN].z2, C.Bt->eps_next, C.B, C.Bt->eps_next ? 1 : 2, C.X.act_n, C.X.ent_n, nullptr, C.Bt->seed, 0x40000000u, C.Bt->call};
+}
+// the one call's Gaussian launch: policy.sample(s') and policy.sample(s) together, the Polyak step of the targets (and their bf16 images) behind them
+static void launch_gauss_both(const SacCtx& C, const HxHyper* Hy, bool polyak) {
+    const GaussArgs G2 = gauss_cur(C);
+    launch_gauss(gauss_next(C), &G2, C.N->target_critic, C.N->critic, polyak ? 2 * kQs.padded() : 0, Hy->tau, C.st, C.im);
+}
+// Both critics' backward launch down to dh1 on slots s[slot0], s[slot0 + 1].  BM_CRITIC_TD (bwd_l2<0>): y, losses and the head gradient in the prologue,
+// from the target slots and H'; BM_SAC_QMIN (<4>): the min(Q1, Q2) selection in the prologue; BM_GIVEN (<3>): a per-row kernel left the head gradient
+static int launch_critics_bwd(const SacCtx& C, int slot0, int mode, const HxHyper* Hy = nullptr) {
+    const float* t1 = C.N->target_critic; const float* t2 = C.N->target_critic + kQs.padded();
+    BwdArgs G{};
+    G.njobs = 2; G.slope = 0.0f; G.inv_batch = 1.0f / C.B; G.losses = C.N->losses;
+    for (int h = 0; h < 2; ++h) {
+        BwdJob& J = G.job[h];
+        J = BwdJob{};
+        J.net = h ? C.q2 : C.q1; J.m = kQs; J.ws = C.s[slot0 + h]; J.rows = C.B; J.mode = mode;
+        if (mode == BM_CRITIC_TD) {
+            J.t1 = Head{t1, kQs, C.s[SS_T1]}; J.t2 = Head{t2, kQs, C.s[SS_T2]}; J.src = C.src; J.gamma = Hy->gamma;
+            J.bonus = C.X.ent_n; J.bonus_scale = C.N->alpha_state + 3; J.loss_slot = h;
+        }
+        if (mode == BM_SAC_QMIN) { J.t1 = Head{h ? C.q1 : C.q2, kQs, C.s[slot0 + (1 - h)]}; J.loss_slot = h; }
+        J.img_t = IM_C1_T + h;
+    }
+    G.images = C.im;
+    return launch_bwd(mode == BM_CRITIC_TD ? 0 : mode == BM_SAC_QMIN ? 4 : 3, G, C.st);
+}
+// grad_critic from the slots of Q1 / Q2 (s, a).  adam_step > 0 (one GPU): q1_optim.step() / q2_optim.step() ride in the launch — the thread that
+// produced a gradient steps it, and the critic's images follow its step
+static void launch_critics_wg(const SacCtx& C, const HxHyper* Hy, int adam_step) {
+    const HxSacNets* N = C.N;
+    WgArgs W{};
+    W.njobs = 2; W.slope = 0.0f; W.w_kind = 0; W.inv_batch = 1.0f / C.B;
+    W.bf16 = C.im != nullptr;
+    for (int h = 0; h < 2; ++h) {
+        WgJob& J = W.job[h];
+        J = WgJob{};
+        J.net = h ? C.q2 : C.q1; J.grad = N->grad_critic + h * kQs.padded(); J.m = kQs;
+        J.ws[0] = C.s[SS_Q1 + h]; J.rows[0] = C.B; J.nslots = 1; J.wmode[0] = 0;
+        if (adam_step > 0) {
+            J.p = N->critic + h * kQs.padded();
+            J.mom = N->m_critic + h * kQs.padded(); J.var = N->v_critic + h * kQs.padded();
+            if (C.im) { J.w2b = C.im + (IM_C1 + h) * kImgElems; J.w2tb = C.im + (IM_C1_T + h) * kImgElems; }
+        }
+    }
+    if (adam_step > 0) {
+        set_adam_scalars(W.ad, Hy->lr_critic, adam_step);
+        W.ad.losses = N->losses;
+    }
+    launch_wg(W, adam_step > 0, C.st);
+}
+// hx_sac_learn_weighted[_clipped]'s departures from the critic half: the TD head as a per-row kernel with the importance weights (the critics'
+// backward then runs with the head gradient given), and with clip_ws the weight-gradient launch without Adam, then the norm and the clipped step
+struct SacWeighted {
+    const float* weights; float* errors_out;
+    float* clip_ws; float max_norm, target_entropy;
+};
 // skip_first: launch 1 has run already (as workgroups of hx_sac_front's launch)
 static int sac_critic_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, const HxSample* S, int32_t polyak_first, void* stream,
-                                 int adam_step = 0, bool one_call = false, bool skip_first = false) {
+                                 int adam_step = 0, bool one_call = false, bool skip_first = false, const SacWeighted* Wt = nullptr) {
     HX_REQUIRE(N && Bt && Hy && Bt->rows && Bt->batch > 0 && Bt->batch % 16 == 0, "hx_sac_critic_grads: bad arguments");
     if (int rc = sac_check_formats(N, "hx_sac_critic_grads")) return rc;
     const SacCtx C(N, Bt, stream);
@@ -467,74 +510,33 @@ static int sac_critic_grads_impl(const HxSacNets* N, const HxSacBatch* Bt, const
         HX_REQUIRE(!S->bc_table && !S->idx_bc, "hx_sac_critic_grads_sampled: SAC has no BC minibatch");
         if (int rc = prepare_draw(S, B, const_cast<float*>(Bt->rows), nullptr, nullptr, stream, &SD, &fused)) return rc;
     }
-    const Slot* s = C.s;
-    const SacAux& X = C.X;
-    const int nq = 2 * kQs.padded();
     if (polyak_first && !one_call) {  // soft_update(critic_target, critic) BEFORE the update, agent.py:278-279
-        launch_polyak(N->target_critic, N->critic, nq, Hy->tau, nullptr, nullptr, 0, st);
+        launch_polyak(N->target_critic, N->critic, 2 * kQs.padded(), Hy->tau, nullptr, nullptr, 0, st);
         if (im)  // ... and the targets' bf16 images follow it
             for (int h = 0; h < 2; ++h) launch_pack_bf16(N->target_critic + h * kQs.padded() + kQs.W2(), im + (IM_TC1 + h) * kImgElems, false, st);
     }
-    const float* t1 = N->target_critic; const float* t2 = N->target_critic + kQs.padded();
     if (!skip_first) {   // policy(s'), policy(s), Q1/Q2(s, a)
         FwdArgs F;
         sac_launch_1(C, F);
         F.sample = fused ? &SD : nullptr;
         launch_fwd(F, st);
     }
-    {   // a', H' = policy.sample(s')
-        const GaussArgs G{N->policy, kPolicy, s[SS_PN].z2, Bt->eps_next, B, Bt->eps_next ? 1 : 2, X.act_n, X.ent_n, nullptr, Bt->seed, 0x40000000u, Bt->call};
-        if (one_call) {
-            const GaussArgs G2 = gauss_cur(C);
-            launch_gauss(G, &G2, N->target_critic, N->critic, polyak_first ? nq : 0, Hy->tau, st, im);
-        } else {
-            launch_gauss(G, nullptr, nullptr, nullptr, 0, 0.0f, st);
-        }
+    if (one_call) launch_gauss_both(C, Hy, polyak_first != 0);
+    else launch_gauss(gauss_next(C), nullptr, nullptr, nullptr, 0, 0.0f, st);
+    launch_target_q(C.s + SS_T1, N->target_critic, C.src, C.X.act_n, B, im, st);
+    if (Wt) {  // y, errors, losses and the head gradients per row, with the weights; then both critics backward from them
+        const TdHeadArgs T{C.q1, C.q2, N->target_critic, N->target_critic + kQs.padded(), kQs, C.s[SS_Q1], C.s[SS_Q2], C.s[SS_T1].z2, C.s[SS_T2].z2, Bt->rows,
+                           C.X.ent_n, N->alpha_state, Wt->weights, B, Hy->gamma, 1.0f / B, Wt->errors_out, N->losses};
+        hipLaunchKernelGGL(td_head_weighted_kernel, dim3((unsigned)((B + 3) / 4)), dim3(kThreads), 0, st, T);
     }
-    {   // target Q1/Q2 (s', a')
-        FwdArgs F{};
-        F.njobs = 2; F.slope = 0.0f;
-        F.job[0] = FwdJob{t1, kQs, C.src, 17, 3, Head{}, X.act_n, 0.f, s[SS_T1], B, 0, IM_TC1};
-        F.job[1] = FwdJob{t2, kQs, C.src, 17, 3, Head{}, X.act_n, 0.f, s[SS_T2], B, 0, IM_TC2};
-        F.images = im;
-        launch_fwd(F, st);
+    if (int rc = launch_critics_bwd(C, SS_Q1, Wt ? BM_GIVEN : BM_CRITIC_TD, Hy)) return rc;  // (BM_CRITIC_TD: y, losses, dq in its prologue)
+    const bool clip = Wt && Wt->clip_ws;
+    launch_critics_wg(C, Hy, clip ? 0 : adam_step);
+    if (clip) {
+        if (int rc = sac_grad_norm(N, 0, Wt->clip_ws, st, "hx_sac_learn_weighted_clipped")) return rc;
+        if (int rc = sac_clipped_step(N, Hy, 0, adam_step, 1.0f, Wt->target_entropy, Wt->max_norm, Wt->clip_ws, false, st, "hx_sac_learn_weighted_clipped")) return rc;
     }
-    {   // y, losses, dq, dh1
-        BwdArgs G{};
-        G.njobs = 2; G.slope = 0.0f; G.inv_batch = 1.0f / B; G.losses = N->losses; G.soft_count = nullptr;
-        for (int h = 0; h < 2; ++h) {
-            BwdJob& J = G.job[h];
-            J = BwdJob{};
-            J.net = h ? C.q2 : C.q1; J.m = kQs; J.ws = s[SS_Q1 + h]; J.rows = B; J.mode = BM_CRITIC_TD;
-            J.t1 = Head{t1, kQs, s[SS_T1]}; J.t2 = Head{t2, kQs, s[SS_T2]}; J.src = C.src; J.gamma = Hy->gamma;
-            J.bonus = X.ent_n; J.bonus_scale = N->alpha_state + 3; J.loss_slot = h;
-            J.img_t = IM_C1_T + h;
-        }
-        G.images = im;
-        if (int rc = launch_bwd(0, G, st)) return rc;
-    }
-    {
-        WgArgs W{};
-        W.njobs = 2; W.slope = 0.0f; W.w_kind = 0; W.inv_batch = 1.0f / B; W.soft_count = nullptr; W.wstate = nullptr;
-        W.bf16 = im != nullptr;
-        for (int h = 0; h < 2; ++h) {
-            WgJob& J = W.job[h];
-            J = WgJob{};
-            J.net = h ? C.q2 : C.q1; J.grad = N->grad_critic + h * kQs.padded(); J.m = kQs;
-            J.ws[0] = s[SS_Q1 + h]; J.rows[0] = B; J.nslots = 1; J.wmode[0] = 0;
-            if (adam_step > 0) {  // q1_optim.step() / q2_optim.step() ride in the wgrad launch (one GPU): the thread that produced a gradient steps it
-                J.p = N->critic + h * kQs.padded();
-                J.mom = N->m_critic + h * kQs.padded(); J.var = N->v_critic + h * kQs.padded();
-                if (im) { J.w2b = im + (IM_C1 + h) * kImgElems; J.w2tb = im + (IM_C1_T + h) * kImgElems; }  // the critic's images follow its step
-            }
-        }
-        if (adam_step > 0) {
-            set_adam_scalars(W.ad, Hy->lr_critic, adam_step);
-            W.ad.losses = N->losses;
-        }
-        launch_wg(W, adam_step > 0, st);
-    }
-    HX_CHECK_LAUNCH("hx_sac_critic_grads");
+    HX_CHECK_LAUNCH(Wt ? "hx_sac_learn_weighted" : "hx_sac_critic_grads");
     return 0;
 }
 int hx_sac_critic_grads(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* Hy, int32_t polyak_first, void* stream) {
@@ -587,19 +589,7 @@ static int launch_policy_tail(const SacCtx& C, bool one_call, const float* weigh
         if (weights) hipLaunchKernelGGL(q_select_kernel<true>, dim3(nb), dim3(kThreads), 0, C.st, Q);
         else hipLaunchKernelGGL(q_select_kernel<false>, dim3(nb), dim3(kThreads), 0, C.st, Q);
     }
-    {   // both critics backward down to dh1
-        BwdArgs G{};
-        G.njobs = 2; G.slope = 0.0f; G.inv_batch = 1.0f / B; G.losses = N->losses;
-        for (int h = 0; h < 2; ++h) {
-            BwdJob& J = G.job[h];
-            J = BwdJob{};
-            J.net = h ? C.q2 : C.q1; J.m = kQs; J.ws = s[SS_Q1P + h]; J.rows = B; J.mode = fold ? BM_SAC_QMIN : BM_GIVEN;
-            if (fold) { J.t1 = Head{h ? C.q1 : C.q2, kQs, s[SS_Q1P + (1 - h)]}; J.loss_slot = h; }
-            J.img_t = IM_C1_T + h;
-        }
-        G.images = C.im;
-        if (int rc = launch_bwd(fold ? 4 : 3, G, C.st)) return rc;
-    }
+    if (int rc = launch_critics_bwd(C, SS_Q1P, fold ? BM_SAC_QMIN : BM_GIVEN)) return rc;  // both critics backward down to dh1
     if (!fold) {
         PDoutArgs P{C.q1, C.q2, kQs, s[SS_Q1P], s[SS_Q2P], s[SS_PC], C.X.aux_c, N->alpha_state, B, 1.0f / B, N->losses, weights, wsum};
         if (weights) hipLaunchKernelGGL(policy_dout_kernel<true>, dim3(nb), dim3(kThreads), 0, C.st, P);
@@ -689,70 +679,11 @@ static int sac_learn_weighted_impl(const HxSacNets* N, const HxSacBatch* Bt, con
     HX_REQUIRE(N && Bt && Hy && Bt->rows && Bt->batch > 0 && Bt->batch % 16 == 0 && weights && errors_out, "hx_sac_learn_weighted: bad arguments (nets, batch, hyper, weights, errors_out)");
     HX_REQUIRE(!N->w2_bf16_all, "hx_sac_learn_weighted: the weighted update is fp32 only (nets->w2_bf16_all must be NULL)");
     if (int rc = sac_check_formats(N, "hx_sac_learn_weighted")) return rc;
+    const SacWeighted Wt{weights, errors_out, clip_ws, max_norm, target_entropy};
+    if (int rc = sac_critic_grads_impl(N, Bt, Hy, nullptr, polyak_first, stream, step, /*one_call=*/true, /*skip_first=*/false, &Wt)) return rc;
     const SacCtx C(N, Bt, stream);
     hipStream_t st = C.st;
-    const int B = C.B;
-    const Slot* s = C.s;
-    const SacAux& X = C.X;
-    const int nq = 2 * kQs.padded();
-    const float* t1 = N->target_critic; const float* t2 = N->target_critic + kQs.padded();
-    float* const wsum = X.aux_c + 16 * (size_t)B;  // two of the workspace's spare words behind the Gaussian heads' row buffers
-    const unsigned nb = (unsigned)((B + 3) / 4);
-    {   // policy(s'), policy(s), Q1/Q2(s, a)
-        FwdArgs F;
-        sac_launch_1(C, F);
-        launch_fwd(F, st);
-    }
-    {   // both Gaussian heads, the Polyak step of the targets behind them (agent.py:278-279: before the update)
-        const GaussArgs G{N->policy, kPolicy, s[SS_PN].z2, Bt->eps_next, B, Bt->eps_next ? 1 : 2, X.act_n, X.ent_n, nullptr, Bt->seed, 0x40000000u, Bt->call};
-        const GaussArgs G2 = gauss_cur(C);
-        launch_gauss(G, &G2, N->target_critic, N->critic, polyak_first ? nq : 0, Hy->tau, st, nullptr);
-    }
-    {   // target Q1/Q2 (s', a')
-        FwdArgs F{};
-        F.njobs = 2; F.slope = 0.0f;
-        F.job[0] = FwdJob{t1, kQs, C.src, 17, 3, Head{}, X.act_n, 0.f, s[SS_T1], B, 0, IM_TC1};
-        F.job[1] = FwdJob{t2, kQs, C.src, 17, 3, Head{}, X.act_n, 0.f, s[SS_T2], B, 0, IM_TC2};
-        launch_fwd(F, st);
-    }
-    {
-        TdHeadArgs T{C.q1, C.q2, t1, t2, kQs, s[SS_Q1], s[SS_Q2], s[SS_T1].z2, s[SS_T2].z2, Bt->rows, X.ent_n, N->alpha_state, weights, B, Hy->gamma, 1.0f / B,
-                     errors_out, N->losses};
-        hipLaunchKernelGGL(td_head_weighted_kernel, dim3(nb), dim3(kThreads), 0, st, T);
-    }
-    {   // both critics backward from the given head gradient
-        BwdArgs G{};
-        G.njobs = 2; G.slope = 0.0f; G.inv_batch = 1.0f / B; G.losses = N->losses;
-        for (int h = 0; h < 2; ++h) {
-            BwdJob& J = G.job[h];
-            J = BwdJob{};
-            J.net = h ? C.q2 : C.q1; J.m = kQs; J.ws = s[SS_Q1 + h]; J.rows = B; J.mode = BM_GIVEN; J.img_t = IM_C1_T + h;
-        }
-        if (int rc = launch_bwd(3, G, st)) return rc;
-    }
-    {   // grad_critic and q1_optim.step() / q2_optim.step() in one launch (sac_critic_grads_impl's)
-        WgArgs W{};
-        W.njobs = 2; W.slope = 0.0f; W.w_kind = 0; W.inv_batch = 1.0f / B; W.soft_count = nullptr; W.wstate = nullptr;
-        for (int h = 0; h < 2; ++h) {
-            WgJob& J = W.job[h];
-            J = WgJob{};
-            J.net = h ? C.q2 : C.q1; J.grad = N->grad_critic + h * kQs.padded(); J.m = kQs;
-            J.ws[0] = s[SS_Q1 + h]; J.rows[0] = B; J.nslots = 1; J.wmode[0] = 0;
-            if (!clip_ws) {
-                J.p = N->critic + h * kQs.padded();
-                J.mom = N->m_critic + h * kQs.padded(); J.var = N->v_critic + h * kQs.padded();
-            }
-        }
-        if (!clip_ws) {
-            set_adam_scalars(W.ad, Hy->lr_critic, step);
-            W.ad.losses = N->losses;
-        }
-        launch_wg(W, !clip_ws, st);
-        if (clip_ws) {
-            if (int rc = sac_grad_norm(N, 0, clip_ws, st, "hx_sac_learn_weighted_clipped")) return rc;
-            if (int rc = sac_clipped_step(N, Hy, 0, step, 1.0f, target_entropy, max_norm, clip_ws, false, st, "hx_sac_learn_weighted_clipped")) return rc;
-        }
-    }
+    float* const wsum = C.X.aux_c + 16 * (size_t)C.B;  // two of the workspace's spare words behind the Gaussian heads' row buffers
     launch_q_pi(C);
     if (int rc = launch_policy_tail(C, false, weights, wsum)) return rc;
     {
@@ -952,7 +883,14 @@ int hx_sac_learn_back(const HxSacNets* N, const HxSacBatch* Bt, const HxHyper* H
 }  // extern "C"
 
 namespace hxu {
-// (host code only: the device code of this file is what it was)
+// (host code only)
+void launch_target_q(const Slot* slots, const float* target_critic, const RowSrc& src, const float* act, int rows, const uint16_t* images, hipStream_t st) {
+    FwdArgs F{};
+    F.njobs = 2; F.slope = 0.0f;
+    for (int h = 0; h < 2; ++h) F.job[h] = FwdJob{target_critic + h * kQs.padded(), kQs, src, 17, 3, Head{}, act, 0.f, slots[h], rows, 0, IM_TC1 + h};
+    F.images = images;
+    launch_fwd(F, st);
+}
 void launch_sac_gauss_rows(const float* policy, const float* z2, const float* eps, int rows, float* act, float* ent, uint64_t seed, uint32_t row0,
                            uint32_t call, hipStream_t st) {
     launch_gauss(GaussArgs{policy, kPolicy, z2, eps, rows, eps ? 1 : 2, act, ent, nullptr, seed, row0, call}, nullptr, nullptr, nullptr, 0, 0.0f, st);

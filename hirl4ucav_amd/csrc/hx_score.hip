@@ -14,34 +14,14 @@
 // draw, not on how many rows were stored with it.  fwd_l2's compact job form carries no row index (pack_fwd), hence the gathered tile.
 #include <cmath>
 
-#include "hx_update.h"
+#include "hx_per_dev.h"
 
 using namespace hxnn;
 using namespace hxu;
 
 namespace {
 
-constexpr int kPerBlock = 1024;     // slots per block sum      (hx_per.hip's)
-constexpr int kPerThreads = 256;    // workgroup of the store kernels: one float4 of the block per thread
 constexpr uint32_t kScoreRow0 = 0xC0000000u;  // the scorer's Philox rows: learn() draws at 0x40000000 + r and 0x80000000 + r, acting at env ids from 0
-
-struct PerDev {
-    float* prio; float* bsum; float* pmax;
-    unsigned long long* marked; unsigned* ticket;
-    const unsigned long long* total;
-    long long cap;
-    int nblocks;
-};
-
-// the same fixed order as hx_per.hip's resum_block: (x + y) + (z + w) per thread, the DPP tree per wave, ((w0 + w1) + (w2 + w3)) over the four waves
-__device__ __forceinline__ void resum_block(const PerDev& P, int b, float* part) {
-    const int tid = threadIdx.x;
-    const float4 v = reinterpret_cast<const float4*>(P.prio + (size_t)b * kPerBlock)[tid];
-    const float s = wave_sum((v.x + v.y) + (v.z + v.w));
-    if ((tid & 63) == 0) part[tid >> 6] = s;
-    __syncthreads();
-    if (tid == 0) P.bsum[b] = (part[0] + part[1]) + (part[2] + part[3]);
-}
 
 // What a call covers, from the device words as they stand when it starts (`marked` moves only in the last chunk's commit, `total` not at all while the
 // call's launches run): rows i < len, row i in slot (start + i) mod cap.  More than cap new rows ("whole"): only the last cap of them are still in
@@ -88,7 +68,7 @@ __global__ __launch_bounds__(kPerThreads) void per_new_index_kernel(IndexArgs A)
     reinterpret_cast<float4*>(A.tile)[e] = reinterpret_cast<const float4*>(A.ring + (size_t)slot * 32)[c];
 }
 
-// y and error per row (td_head_weighted_kernel's expressions on the three critic z2 rows; no gradients, no sums).  One wave per row.
+// y and error per row from the three critic z2 rows (sac_td_heads, sac_td_target; no gradients, no sums).  One wave per row.
 struct TdScoreArgs {
     const float* q1net; const float* t1net; const float* t2net;
     Mlp m;
@@ -107,16 +87,11 @@ __global__ __launch_bounds__(kThreads) void td_score_kernel(TdScoreArgs A) {
     const int r = blockIdx.x * 4 + wave;
     const int len = reinterpret_cast<const int*>(A.hdr)[0];
     if (r >= A.rows || A.row_base + r >= len) return;
-    RowReg<H2> xh, y;
-    float mean_, rstd_, t1[1], t2[1], q1[1];
-    head_row<1, true>(A.z2_t1 + (size_t)r * H2, A.t1net, A.m, 0.0f, xh, y, mean_, rstd_, t1);
-    head_row<1, true>(A.z2_t2 + (size_t)r * H2, A.t2net, A.m, 0.0f, xh, y, mean_, rstd_, t2);
-    head_row<1, true>(A.z2_q1 + (size_t)r * H2, A.q1net, A.m, 0.0f, xh, y, mean_, rstd_, q1);
+    float qmin, q1, q2;
+    sac_td_heads<false>(A.m, r, {A.t1net, A.z2_t1, nullptr}, {A.t2net, A.z2_t2, nullptr}, {A.q1net, A.z2_q1, nullptr}, {}, qmin, q1, q2);
     if (lane == 0) {
         const float lab0 = A.tile[(size_t)r * 32 + 30], lab1 = A.tile[(size_t)r * 32 + 31];
-        const float qmin = fminf(t1[0], t2[0]);
-        const float target = lab0 + (1.0f - lab1) * (A.gamma * (qmin + A.ent_next[r] * A.alpha_state[3]));
-        const float e = fabsf(q1[0] - target);
+        const float e = fabsf(q1 - sac_td_target(lab0, lab1, A.gamma, qmin, A.ent_next[r], A.alpha_state[3]));
         A.err[r] = e;
         if (A.errors_out) A.errors_out[A.row_base + r] = e;
     }
@@ -156,8 +131,9 @@ __global__ __launch_bounds__(kPerThreads) void per_score_commit_kernel(CommitArg
             const unsigned long long off = sl >= s0 ? sl - s0 : sl + cap - s0;
             if (sl < cap && off < n) {
                 const float x = A.err[off];
-                const float p = powf(x + 1e-4f, A.alpha);
-                const bool ok = x >= 0.0f && x <= 3.0e38f && p >= 0.0f && p <= 3.0e38f;  // (false for NaN)
+                float p;
+                const bool storable = per_priority(x, A.alpha, p);
+                const bool ok = x >= 0.0f && x <= 3.0e38f && storable;  // (the error itself finite too: with alpha 0 any x gives p = 1)
                 e[c] = ok ? p : pm;  // never skipped: a live slot holds a priority
                 if (ok) top = fmaxf(top, p);
                 touched = true;
@@ -190,10 +166,8 @@ int64_t hx_per_score_workspace_floats(int32_t chunk_rows) { return chunk_rows > 
 
 int hx_per_score_new(const HxPer* per, const float* ring, const HxSacNets* N, const HxHyper* Hy, int64_t max_new, int32_t chunk_rows, float per_alpha,
                      const float* eps, uint64_t seed, uint32_t call, float* ws, float* errors_out, void* stream) {
-    HX_REQUIRE(per && per->prio && per->bsum && per->pmax && per->marked && per->ticket && per->total && per->cap > 0,
-               "hx_per_score_new: per needs prio, bsum, pmax, marked, ticket, total and cap > 0");
-    HX_REQUIRE(per->cap <= ((int64_t)1 << 24), "hx_per_score_new: prioritized replay holds at most 2^24 slots (cap = %lld)", (long long)per->cap);
-    HX_REQUIRE((reinterpret_cast<uintptr_t>(per->prio) & 15u) == 0, "hx_per_score_new: prio must be 16-byte aligned");
+    PerDev P;
+    if (int rc = per_dev(per, "hx_per_score_new", &P)) return rc;
     HX_REQUIRE(ring && N && Hy && ws, "hx_per_score_new: ring, nets, hyper and ws (hx_per_score_workspace_floats(chunk_rows) floats)");
     HX_REQUIRE(N->policy && N->critic && N->target_critic && N->alpha_state, "hx_per_score_new: nets needs policy, critic, target_critic and alpha_state");
     HX_REQUIRE(!N->w2_bf16_all, "hx_per_score_new: scoring is fp32 only (nets->w2_bf16_all must be NULL)");
@@ -203,8 +177,6 @@ int hx_per_score_new(const HxPer* per, const float* ring, const HxSacNets* N, co
     HX_REQUIRE((reinterpret_cast<uintptr_t>(ring) & 15u) == 0 && (reinterpret_cast<uintptr_t>(ws) & 15u) == 0, "hx_per_score_new: ring and ws must be 16-byte aligned");
     if (int rc = sac_check_formats(N, "hx_per_score_new")) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const PerDev P{per->prio, per->bsum, per->pmax, (unsigned long long*)per->marked, per->ticket, (const unsigned long long*)per->total, (long long)per->cap,
-                   (int)((per->cap + kPerBlock - 1) / kPerBlock)};
     const int C = chunk_rows;
     const long long rows_all = max_new < per->cap ? (long long)max_new : (long long)per->cap;  // (a call never covers more than the ring holds)
     const int nchunks = (int)((rows_all + C - 1) / C);
@@ -237,13 +209,7 @@ int hx_per_score_new(const HxPer* per, const float* ring, const HxSacNets* N, co
         }
         // a', H' = policy.sample(s'): per-row waves, so the rows behind `given` (padding: dropped) may keep what an earlier chunk left
         launch_sac_gauss_rows(N->policy, s[SC_PN].z2, eps ? eps + 4 * (size_t)base : nullptr, given, act, ent, seed, kScoreRow0 + (uint32_t)base, call, st);
-        {   // target Q1 / Q2 (s', a')
-            FwdArgs F{};
-            F.njobs = 2; F.slope = 0.0f;
-            F.job[0] = FwdJob{t1, kQs, src, 17, 3, Head{}, act, 0.f, s[SC_T1], C, 0, IM_TC1};
-            F.job[1] = FwdJob{t2, kQs, src, 17, 3, Head{}, act, 0.f, s[SC_T2], C, 0, IM_TC2};
-            launch_fwd(F, st);
-        }
+        launch_target_q(s + SC_T1, N->target_critic, src, act, C, nullptr, st);
         {
             const TdScoreArgs T{q1, t1, t2, kQs, s[SC_Q1].z2, s[SC_T1].z2, s[SC_T2].z2, tile, ent, N->alpha_state, hdr, base, given, Hy->gamma, err, errors_out};
             hipLaunchKernelGGL(td_score_kernel, dim3((unsigned)((C + 3) / 4)), dim3(kThreads), 0, st, T);

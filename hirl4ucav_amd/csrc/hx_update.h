@@ -553,6 +553,11 @@ __device__ __forceinline__ uint4 pack8_bf16(const float (&v)[8]) {
     q.w = __builtin_bit_cast(unsigned, v2bf{(__bf16)v[6], (__bf16)v[7]});
     return q;
 }
+// four floats -> four bf16 (round to nearest even): four consecutive k of one column, adjacent in a W2 image
+__device__ __forceinline__ uint2 pack4_bf16(float a, float b, float c, float d) {
+    typedef __bf16 v4bf __attribute__((ext_vector_type(4)));
+    return __builtin_bit_cast(uint2, v4bf{(__bf16)a, (__bf16)b, (__bf16)c, (__bf16)d});
+}
 
 enum { BM_CRITIC_TD = 0, BM_CRITIC_PI = 1, BM_ACTOR_PI = 2, BM_ACTOR_BC = 3, BM_GIVEN = 4,
        BM_SAC_QMIN = 5,     // SAC policy loss, a critic's side: dq = -w / B, w = 1 for the smaller of Q1 / Q2 (s, a~), 1/2 each on a tie  (SAC/agent.py:380-383)
@@ -570,6 +575,34 @@ __device__ __forceinline__ void sac_policy_dout(float da, float a, float se, flo
     d_logstd = (dLdx * se - ab) * mask;
 }
 #pragma clang fp contract(fast)
+// SAC's TD target y = r + (1 - d) gamma (min Q_target(s', a') + alpha H')  (SAC/agent.py:202-210): lab0 = reward, lab1 = done
+__device__ __forceinline__ float sac_td_target(float lab0, float lab1, float gamma, float qmin, float h_next, float alpha) {
+    return lab0 + (1.0f - lab1) * (gamma * (qmin + h_next * alpha));
+}
+// The heads a TD error of row r needs, by one wave: the two target critics on (s', a') -> their minimum, then Q1 (s, a) — and with BOTH also Q2 (s, a),
+// each head's LayerNorm stats stored for the backward pass that follows (st2_*: [rows][2]).  Without BOTH nothing of Q2 is evaluated and nothing stored.
+struct QHeadIn {
+    const float* net; const float* z2; float* st2;  // the critic's block, its z2 rows, and (BOTH) where its LayerNorm stats go
+};
+template <bool BOTH>
+__device__ __forceinline__ void sac_td_heads(const Mlp m, int r, const QHeadIn t1, const QHeadIn t2, const QHeadIn c1, const QHeadIn c2, float& qmin, float& q1,
+                                             float& q2) {
+    const int lane = threadIdx.x & 63;
+    RowReg<H2> xh, y;
+    float mean_, rstd_, a[1], b[1], o[1];
+    head_row<1, true>(t1.z2 + (size_t)r * H2, t1.net, m, 0.0f, xh, y, mean_, rstd_, a);
+    head_row<1, true>(t2.z2 + (size_t)r * H2, t2.net, m, 0.0f, xh, y, mean_, rstd_, b);
+    head_row<1, true>(c1.z2 + (size_t)r * H2, c1.net, m, 0.0f, xh, y, mean_, rstd_, o);
+    q1 = o[0];
+    q2 = 0.0f;
+    if (BOTH) {
+        if (lane == 0) { c1.st2[r * 2] = mean_; c1.st2[r * 2 + 1] = rstd_; }
+        head_row<1, true>(c2.z2 + (size_t)r * H2, c2.net, m, 0.0f, xh, y, mean_, rstd_, o);
+        q2 = o[0];
+        if (lane == 0) { c2.st2[r * 2] = mean_; c2.st2[r * 2 + 1] = rstd_; }
+    }
+    qmin = fminf(a[0], b[0]);
+}
 
 struct BwdJob {
     const float* net;
@@ -659,6 +692,18 @@ __device__ __forceinline__ void adam_update(float& p, float& m, float& v, float 
 }
 __device__ __forceinline__ float polyak_update(float target, float p, float tau) { return target * (1.0f - tau) + p * tau; }  // HIRL.py:13
 #pragma clang fp contract(fast)
+// SAC's log-alpha step by ONE thread (SAC/agent.py:322-325, 408-414): entropy_loss = -(log_alpha (te - mean_h)) with the log_alpha BEFORE its step
+// -> losses[3], alpha_optim.step() on the gradient mean_h - te, alpha = exp(log_alpha) -> alpha_state[3] and losses[5].  alpha_state: log_alpha, m, v,
+// alpha.  mean_h / te: the mean entropy and the target entropy; with importance weights mean(w H) and target_entropy mean(w).
+__device__ __forceinline__ void sac_alpha_step(float* alpha_state, float* losses, float mean_h, float te, float b1, float b2, float eps, float step_size,
+                                               float bc2_sqrt) {
+    float la = alpha_state[0], m = alpha_state[1], v = alpha_state[2];
+    losses[3] = -(la * (te - mean_h));
+    adam_update(la, m, v, mean_h - te, b1, b2, eps, step_size, bc2_sqrt);
+    alpha_state[0] = la; alpha_state[1] = m; alpha_state[2] = v;
+    alpha_state[3] = expf(la);  // self.alpha = self.log_alpha.exp()
+    losses[5] = alpha_state[3];
+}
 __device__ __forceinline__ float effective_w(int kind, float given, float warm, float inv_batch, const int* count, const float* wstate) {
     float w = given;
     if (kind == 1) w = (float)(*count) * inv_batch + warm;
@@ -700,6 +745,61 @@ struct AdamArgs {
     const float* countf;
     const uint32_t* guard;  // nullptr, or a word that must be 0 for the step to happen (HxNets.xchg_status: a failed exchange)
 };
+// The optimizer step on the float4 at word i of the flat buffers (16-B aligned, i + 4 <= n) with everything that follows it: g4 is the gradient as it
+// enters Adam (combined, scaled, clipped by the caller).  p, m, v stepped and stored; then the images of a W2 this float4 lies in (W2 starts at a
+// multiple of 4 floats: a float4 is inside or outside) — bf16 (and the other two parts of the exact split), fp32 —, the target's Polyak step, and on
+// the bf16 update path the forward, transposed and target images per segment.
+__device__ __forceinline__ void adam_step4(const AdamArgs& A, int i, const float4 g4) {
+    float4 p4 = *reinterpret_cast<const float4*>(A.p + i);
+    float4 m4 = *reinterpret_cast<const float4*>(A.m + i), v4 = *reinterpret_cast<const float4*>(A.v + i);
+    adam_update(p4.x, m4.x, v4.x, g4.x, A.b1, A.b2, A.eps, A.step_size, A.bc2_sqrt);
+    adam_update(p4.y, m4.y, v4.y, g4.y, A.b1, A.b2, A.eps, A.step_size, A.bc2_sqrt);
+    adam_update(p4.z, m4.z, v4.z, g4.z, A.b1, A.b2, A.eps, A.step_size, A.bc2_sqrt);
+    adam_update(p4.w, m4.w, v4.w, g4.w, A.b1, A.b2, A.eps, A.step_size, A.bc2_sqrt);
+    *reinterpret_cast<float4*>(A.p + i) = p4;
+    *reinterpret_cast<float4*>(A.m + i) = m4;
+    *reinterpret_cast<float4*>(A.v + i) = v4;
+    const uint2 pb = pack4_bf16(p4.x, p4.y, p4.z, p4.w);
+    if (A.w2b && i >= A.w2_lo && i < A.w2_lo + H2 * H1) {
+        const uint32_t e = (uint32_t)(i - A.w2_lo);  // four consecutive k of one column: adjacent in the image too
+        const uint32_t ix = w2_image_index(e / H1, e % H1);
+        *reinterpret_cast<uint2*>(A.w2b + ix) = pb;
+        if (A.w2b_x9) {  // the other two parts of the exact split (split3_bf16)
+            const float pv[4] = {p4.x, p4.y, p4.z, p4.w};
+            uint16_t md[4], lw[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { uint16_t h; split3_bf16(pv[q], h, md[q], lw[q]); }
+            *reinterpret_cast<uint2*>(A.w2b + kImgElems + ix) = make_uint2((uint32_t)md[0] | ((uint32_t)md[1] << 16), (uint32_t)md[2] | ((uint32_t)md[3] << 16));
+            *reinterpret_cast<uint2*>(A.w2b + 2 * kImgElems + ix) = make_uint2((uint32_t)lw[0] | ((uint32_t)lw[1] << 16), (uint32_t)lw[2] | ((uint32_t)lw[3] << 16));
+        }
+    }
+    if (A.w2f && i >= A.w2_lo && i < A.w2_lo + H2 * H1) {
+        const uint32_t e = (uint32_t)(i - A.w2_lo);
+        *reinterpret_cast<float4*>(A.w2f + w2f_image_index(e / H1, e % H1)) = p4;
+    }
+    float4 t4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (A.target) {  // soft_update with the new parameters
+        t4 = *reinterpret_cast<const float4*>(A.target + i);
+        t4.x = polyak_update(t4.x, p4.x, A.tau);
+        t4.y = polyak_update(t4.y, p4.y, A.tau);
+        t4.z = polyak_update(t4.z, p4.z, A.tau);
+        t4.w = polyak_update(t4.w, p4.w, A.tau);
+        *reinterpret_cast<float4*>(A.target + i) = t4;
+    }
+    for (int sg = 0; sg < A.nseg; ++sg) {
+        if (i < A.seg_lo[sg] || i >= A.seg_lo[sg] + H2 * H1) continue;
+        const uint32_t e = (uint32_t)(i - A.seg_lo[sg]), col = e / H1, k = e % H1;  // four consecutive k of one column
+        if (A.seg_w2b[sg]) *reinterpret_cast<uint2*>(A.seg_w2b[sg] + w2_image_index(col, k)) = pb;
+        if (A.seg_w2tb[sg]) {
+            uint16_t* tb = A.seg_w2tb[sg];
+            tb[w2t_image_index(k, col)] = (uint16_t)(pb.x & 0xFFFFu);
+            tb[w2t_image_index(k + 1, col)] = (uint16_t)(pb.x >> 16);
+            tb[w2t_image_index(k + 2, col)] = (uint16_t)(pb.y & 0xFFFFu);
+            tb[w2t_image_index(k + 3, col)] = (uint16_t)(pb.y >> 16);
+        }
+        if (A.target && A.seg_tgt_w2b[sg]) *reinterpret_cast<uint2*>(A.seg_tgt_w2b[sg] + w2_image_index(col, k)) = pack4_bf16(t4.x, t4.y, t4.z, t4.w);
+    }
+}
 // torch.optim.Adam's per-step scalars (defaults: betas (0.9, 0.999), eps 1e-8; step is 1-based) into the fields of that name of a WgAdam (the fused
 // wgrad + Adam launch) or an AdamArgs (adam_kernel).  Formed in double and rounded once: every path that steps a network rounds alike.
 template <typename A>
@@ -822,6 +922,9 @@ void launch_pack_bf16(const float* w2, uint16_t* image, bool transposed, hipStre
 // Philox4x32-10(seed; row0 + row, call).  What hx_score.hip runs between its two forward launches.
 void launch_sac_gauss_rows(const float* policy, const float* z2, const float* eps, int rows, float* act, float* ent, uint64_t seed, uint32_t row0,
                            uint32_t call, hipStream_t st);
+// hx_sac.hip: target Q1 / Q2 (s', a') — src's columns 17.., the action rows `act` [rows][4] — into slots[0] / slots[1], values only; images: the bf16
+// update path's (NULL: fp32)
+void launch_target_q(const Slot* slots, const float* target_critic, const RowSrc& src, const float* act, int rows, const uint16_t* images, hipStream_t st);
 // hx_clip.hip: per-segment sums of squares of grad_critic (which 0) / grad_policy (which 1) into clip_ws, then the optimizer step on g * coef[segment]
 int sac_grad_norm(const HxSacNets* N, int which, float* clip_ws, hipStream_t st, const char* who);
 int sac_clipped_step(const HxSacNets* N, const HxHyper* Hy, int which, int step, float grad_scale, float target_entropy, float max_norm, float* clip_ws,

@@ -176,15 +176,8 @@ __global__ __launch_bounds__(kWide) void wgrad_kernel(WgArgsC AC) {
             A.ad.losses[1] = A.ad.losses[3];  // TD3.py:236
         }
     }
-    if (ADAM && A.ad.alpha_state && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {  // what adam_kernel's thread 0 does on a SAC policy step
-        const float mean_h = A.ad.losses[4];
-        float la = A.ad.alpha_state[0], m = A.ad.alpha_state[1], v = A.ad.alpha_state[2];
-        A.ad.losses[3] = -(la * (A.ad.target_entropy - mean_h));  // entropy_loss with the log_alpha BEFORE its step
-        adam_update(la, m, v, mean_h - A.ad.target_entropy, A.ad.b1, A.ad.b2, A.ad.eps, A.ad.alpha_step_size, A.ad.bc2_sqrt);
-        A.ad.alpha_state[0] = la; A.ad.alpha_state[1] = m; A.ad.alpha_state[2] = v;
-        A.ad.alpha_state[3] = expf(la);  // self.alpha = self.log_alpha.exp()
-        A.ad.losses[5] = A.ad.alpha_state[3];
-    }
+    if (ADAM && A.ad.alpha_state && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0)  // a SAC policy step: the log-alpha step with the mean entropy
+        sac_alpha_step(A.ad.alpha_state, A.ad.losses, A.ad.losses[4], A.ad.target_entropy, A.ad.b1, A.ad.b2, A.ad.eps, A.ad.alpha_step_size, A.ad.bc2_sqrt);
 
     if (b < kWgTilesPerBlock) {
         // dW2[n][k] = sum_r scale dz2[r][n] h1[r][k].  Tile 16 (n) x 16 (k) per wave PAIR (w, w + 8): each wave reduces over half of the
@@ -557,15 +550,8 @@ __device__ __forceinline__ float adam_w(const AdamArgs& A) {
 
 __global__ __launch_bounds__(kThreads) void adam_kernel(AdamArgs A) {
     if (A.guard && __hip_atomic_load(A.guard, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u) return;  // failed exchange: fail-stop
-    if (A.alpha_state && blockIdx.x == 0 && threadIdx.x == 0) {
-        const float mean_h = A.losses[4];
-        float la = A.alpha_state[0], m = A.alpha_state[1], v = A.alpha_state[2];
-        A.losses[3] = -(la * (A.target_entropy - mean_h));  // entropy_loss with the log_alpha BEFORE its step
-        adam_update(la, m, v, mean_h - A.target_entropy, A.b1, A.b2, A.eps, A.alpha_step_size, A.bc2_sqrt);
-        A.alpha_state[0] = la; A.alpha_state[1] = m; A.alpha_state[2] = v;
-        A.alpha_state[3] = expf(la);  // self.alpha = self.log_alpha.exp()
-        A.losses[5] = A.alpha_state[3];
-    }
+    if (A.alpha_state && blockIdx.x == 0 && threadIdx.x == 0)  // a SAC policy step: the log-alpha step with the mean entropy
+        sac_alpha_step(A.alpha_state, A.losses, A.losses[4], A.target_entropy, A.b1, A.b2, A.eps, A.alpha_step_size, A.bc2_sqrt);
     const float wmix = A.g2 ? adam_w(A) : 0.0f;  // (read before thread 0 of block 0 may store the new weight: same value either way)
     if (A.finish_actor && blockIdx.x == 0 && threadIdx.x == 0) {
         if (A.use_bc) {
@@ -580,8 +566,7 @@ __global__ __launch_bounds__(kThreads) void adam_kernel(AdamArgs A) {
     const int i = (blockIdx.x * kThreads + threadIdx.x) * 4;
     if (i >= A.n) return;
     if (i + 4 <= A.n) {  // the flat buffers are 16-B aligned and a multiple of 4 floats long: one 16-B access per array
-        float4 p4 = *reinterpret_cast<const float4*>(A.p + i), g4 = *reinterpret_cast<const float4*>(A.g + i);
-        float4 m4 = *reinterpret_cast<const float4*>(A.m + i), v4 = *reinterpret_cast<const float4*>(A.v + i);
+        float4 g4 = *reinterpret_cast<const float4*>(A.g + i);
         if (A.g2) {  // g = w dL_bc + (1 - w) dL_rl  (HIRL.py:321), combined AFTER the exchange
             const float4 b4 = *reinterpret_cast<const float4*>(A.g2 + i);
             g4.x = wmix * b4.x + (1.0f - wmix) * g4.x;
@@ -589,61 +574,7 @@ __global__ __launch_bounds__(kThreads) void adam_kernel(AdamArgs A) {
             g4.z = wmix * b4.z + (1.0f - wmix) * g4.z;
             g4.w = wmix * b4.w + (1.0f - wmix) * g4.w;
         }
-        adam_update(p4.x, m4.x, v4.x, g4.x * A.gscale, A.b1, A.b2, A.eps, A.step_size, A.bc2_sqrt);
-        adam_update(p4.y, m4.y, v4.y, g4.y * A.gscale, A.b1, A.b2, A.eps, A.step_size, A.bc2_sqrt);
-        adam_update(p4.z, m4.z, v4.z, g4.z * A.gscale, A.b1, A.b2, A.eps, A.step_size, A.bc2_sqrt);
-        adam_update(p4.w, m4.w, v4.w, g4.w * A.gscale, A.b1, A.b2, A.eps, A.step_size, A.bc2_sqrt);
-        *reinterpret_cast<float4*>(A.p + i) = p4;
-        *reinterpret_cast<float4*>(A.m + i) = m4;
-        *reinterpret_cast<float4*>(A.v + i) = v4;
-        if (A.w2b && i >= A.w2_lo && i < A.w2_lo + H2 * H1) {  // W2 starts at a multiple of 4 floats: the float4 is inside or outside
-            typedef __bf16 v4bf __attribute__((ext_vector_type(4)));
-            const v4bf r = {(__bf16)p4.x, (__bf16)p4.y, (__bf16)p4.z, (__bf16)p4.w};
-            const uint32_t e = (uint32_t)(i - A.w2_lo);  // four consecutive k of one column: adjacent in the image too
-            const uint32_t ix = w2_image_index(e / H1, e % H1);
-            *reinterpret_cast<uint2*>(A.w2b + ix) = __builtin_bit_cast(uint2, r);
-            if (A.w2b_x9) {  // the other two parts of the exact split (split3_bf16)
-                const float pv[4] = {p4.x, p4.y, p4.z, p4.w};
-                uint16_t md[4], lw[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { uint16_t h; split3_bf16(pv[q], h, md[q], lw[q]); }
-                *reinterpret_cast<uint2*>(A.w2b + kImgElems + ix) = make_uint2((uint32_t)md[0] | ((uint32_t)md[1] << 16), (uint32_t)md[2] | ((uint32_t)md[3] << 16));
-                *reinterpret_cast<uint2*>(A.w2b + 2 * kImgElems + ix) = make_uint2((uint32_t)lw[0] | ((uint32_t)lw[1] << 16), (uint32_t)lw[2] | ((uint32_t)lw[3] << 16));
-            }
-        }
-        if (A.w2f && i >= A.w2_lo && i < A.w2_lo + H2 * H1) {
-            const uint32_t e = (uint32_t)(i - A.w2_lo);
-            *reinterpret_cast<float4*>(A.w2f + w2f_image_index(e / H1, e % H1)) = p4;
-        }
-        float4 t4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (A.target) {
-            t4 = *reinterpret_cast<const float4*>(A.target + i);
-            t4.x = polyak_update(t4.x, p4.x, A.tau);
-            t4.y = polyak_update(t4.y, p4.y, A.tau);
-            t4.z = polyak_update(t4.z, p4.z, A.tau);
-            t4.w = polyak_update(t4.w, p4.w, A.tau);
-            *reinterpret_cast<float4*>(A.target + i) = t4;
-        }
-        // bf16 update path: the images of every W2 this step changes follow it (forward, transposed, and the target's when it moved)
-        for (int sg = 0; sg < A.nseg; ++sg) {
-            if (i < A.seg_lo[sg] || i >= A.seg_lo[sg] + H2 * H1) continue;
-            typedef __bf16 v4bf __attribute__((ext_vector_type(4)));
-            const uint32_t e = (uint32_t)(i - A.seg_lo[sg]), col = e / H1, k = e % H1;  // four consecutive k of one column
-            const v4bf r = {(__bf16)p4.x, (__bf16)p4.y, (__bf16)p4.z, (__bf16)p4.w};
-            if (A.seg_w2b[sg]) *reinterpret_cast<uint2*>(A.seg_w2b[sg] + w2_image_index(col, k)) = __builtin_bit_cast(uint2, r);
-            if (A.seg_w2tb[sg]) {
-                const uint2 q = __builtin_bit_cast(uint2, r);
-                uint16_t* tb = A.seg_w2tb[sg];
-                tb[w2t_image_index(k, col)] = (uint16_t)(q.x & 0xFFFFu);
-                tb[w2t_image_index(k + 1, col)] = (uint16_t)(q.x >> 16);
-                tb[w2t_image_index(k + 2, col)] = (uint16_t)(q.y & 0xFFFFu);
-                tb[w2t_image_index(k + 3, col)] = (uint16_t)(q.y >> 16);
-            }
-            if (A.target && A.seg_tgt_w2b[sg]) {
-                const v4bf rt = {(__bf16)t4.x, (__bf16)t4.y, (__bf16)t4.z, (__bf16)t4.w};
-                *reinterpret_cast<uint2*>(A.seg_tgt_w2b[sg] + w2_image_index(col, k)) = __builtin_bit_cast(uint2, rt);
-            }
-        }
+        adam_step4(A, i, make_float4(g4.x * A.gscale, g4.y * A.gscale, g4.z * A.gscale, g4.w * A.gscale));
         return;
     }
     for (int c = 0; c < A.n - i; ++c) {  // ragged tail

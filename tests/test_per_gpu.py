@@ -17,6 +17,7 @@ from oracle import sac_oracle as S  # noqa: E402
 from tests import _hirl_data as D  # noqa: E402
 from tests import _per_check as P  # noqa: E402
 from tests import _sac_bits  # noqa: E402
+from tests import _sac_fold_bits  # noqa: E402
 from tests.test_oracle_sac import sac_params  # noqa: E402
 from tests.test_sac_gpu import grad_bad, sync  # noqa: E402
 
@@ -397,6 +398,13 @@ def test_unchanged_paths_give_the_parents_bits(SE, golden_dir):
     assert sorted(now) == sorted(g.files) and len(now) == 2 * len(_sac_bits.NAMES)
     for k in g.files:
         np.testing.assert_array_equal(now[k], g[k], err_msg=k)
+
+
+def test_weighted_paths_give_the_parents_bits(SE, golden_dir):
+    """hx_sac_learn_weighted from a fixed start (B = 48, non-unit weights, the Polyak step in call 3 of 4): the same bits as the recording made with
+    the library of the commit before the weighted, clipped and scoring paths were folded into the shared code (tests/golden/sac_fold_bits.npz,
+    tests/_sac_fold_bits.py) — networks, moments, alpha state, acting image, errors_out, the priorities hx_per_update leaves"""
+    _sac_fold_bits.assert_replays(SE, sac_params(), np.load(os.path.join(golden_dir, "sac_fold_bits.npz")), ("weighted",))
 
 
 def build_loop(SE, annealing=0.001):

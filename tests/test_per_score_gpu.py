@@ -258,6 +258,15 @@ def test_philox_key(SE, world):
     assert np.abs(a - learns).max() > 0.05 and (np.abs(a - learns) > 1e-2).mean() > 0.5
 
 
+def test_scoring_gives_the_parents_bits(SE, golden_dir):
+    """score_new on 40 new rows in chunks of 16 (three chunks, the last one padded) written across the block boundary at slot 1,024 of a 4,096-slot
+    store: prio and bsum of the two touched blocks, pmax, marked and errors_out carry the bits of the recording made with the library of the commit
+    before the scoring path was folded into the shared code (tests/golden/sac_fold_bits.npz, tests/_sac_fold_bits.py)"""
+    from tests import _sac_fold_bits
+
+    _sac_fold_bits.assert_replays(SE, sac_params(), np.load(os.path.join(golden_dir, "sac_fold_bits.npz")), ("score",))
+
+
 def test_score_new_through_a_real_env(SE):
     """64 envs, act_step -> score_new -> sample -> learn (step_learn under new_rows="td"), a 2,048-slot ring that wraps"""
     from hirl4ucav_amd.environments.batched import BatchedHarfangEnv

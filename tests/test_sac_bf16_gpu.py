@@ -332,6 +332,15 @@ def test_sac_bf16_learn_in_one_call_is_bit_identical_to_the_staged_sequence(SE, 
     check_images(SE, a, "after 7 calls")
 
 
+def test_staged_bf16_update_gives_the_parents_bits(SE, golden_dir):
+    """the staged bf16 update (hx_sac_critic_grads + hx_sac_adam(0) + hx_sac_policy_grads + hx_sac_adam(1): adam_kernel with segment images) at
+    B = 48, four calls from a fixed start: networks, moments, alpha state and the whole image block carry the bits of the recording made with the
+    library of the commit before adam_kernel's float4 step became shared code (tests/golden/sac_fold_bits.npz, tests/_sac_fold_bits.py)"""
+    from tests import _sac_fold_bits
+
+    _sac_fold_bits.assert_replays(SE, sac_params(), np.load(os.path.join(golden_dir, "sac_fold_bits.npz")), ("staged_bf16",))
+
+
 @pytest.mark.parametrize("n,cap,esac", [(16384, 40000, False), (9000, 20000, True)])
 def test_sac_bf16_front_launch_equals_act_step_then_guarded_learn(SE, n, cap, esac):
     """step_learn in bf16 (actps_sac_front_kernel<2>: MODE 2 acting + the bf16 first launch of learn()) == act_step_bf16, then learn() on a minibatch

@@ -208,6 +208,16 @@ def test_never_binding_clip_gives_hx_sac_adam_bits(SE, fmt):
     assert torch.equal(a.losses[3:6], b.losses[3:6])
 
 
+def test_clipped_paths_give_the_parents_bits(SE, golden_dir):
+    """hx_sac_learn_weighted_clipped, and the clipped staged sequence (gradients -> hx_sac_grad_norm -> hx_sac_adam_clipped) with entropy tuning and
+    with a fixed alpha, from a fixed start (B = 48, four calls, a max_norm that clips 7 of the 8 critic steps and never the policy in the weighted run): the same
+    bits as the recording made with the library of the commit before these paths were folded into the shared code
+    (tests/golden/sac_fold_bits.npz, tests/_sac_fold_bits.py) — networks, moments, alpha state, acting image, the norms and coefficients of every call"""
+    from tests import _sac_fold_bits
+
+    _sac_fold_bits.assert_replays(SE, sac_params(), np.load(os.path.join(golden_dir, "sac_fold_bits.npz")), ("weighted_clipped", "clipped"))
+
+
 # ---- learn() with a clip against the oracle --------------------------------------------------------------------------------------------------------
 
 def unclipped_norms(SE, e, make_oracle, run):

@@ -60,6 +60,18 @@ int main() {
     REFUSED(hx_sac_learn_weighted(&N16, &Bt, &Hy, f, f, 1, 3, -4.0f, nullptr));
     HxSacBatch odd = Bt; odd.batch = 40;
     REFUSED(hx_sac_learn_weighted(&N, &odd, &Hy, f, f, 1, 3, -4.0f, nullptr));
+    // priorities at insert: 40 new rows in chunks of 16
+    float* sws = (float*)dev(hx_per_score_workspace_floats(16) * 4); float* serr = (float*)dev(40 * 4); float* seps = (float*)dev(40 * 16);
+    OK(hx_per_score_new(&P, ring, &N, &Hy, 40, 16, 0.6f, nullptr, 7, 1, sws, serr, nullptr));
+    OK(hx_per_score_new(&P, ring, &N, &Hy, 40, 16, 0.6f, seps, 7, 2, sws, nullptr, nullptr));
+    REFUSED(hx_per_score_new(nullptr, ring, &N, &Hy, 40, 16, 0.6f, nullptr, 7, 1, sws, serr, nullptr));
+    REFUSED(hx_per_score_new(&hole, ring, &N, &Hy, 40, 16, 0.6f, nullptr, 7, 1, sws, serr, nullptr));
+    REFUSED(hx_per_score_new(&big, ring, &N, &Hy, 40, 16, 0.6f, nullptr, 7, 1, sws, serr, nullptr));
+    REFUSED(hx_per_score_new(&P, nullptr, &N, &Hy, 40, 16, 0.6f, nullptr, 7, 1, sws, serr, nullptr));
+    REFUSED(hx_per_score_new(&P, ring, &N16, &Hy, 40, 16, 0.6f, nullptr, 7, 1, sws, serr, nullptr));
+    REFUSED(hx_per_score_new(&P, ring, &N, &Hy, 40, 10, 0.6f, nullptr, 7, 1, sws, serr, nullptr));
+    REFUSED(hx_per_score_new(&P, ring, &N, &Hy, 0, 16, 0.6f, nullptr, 7, 1, sws, serr, nullptr));
+    REFUSED(hx_per_score_new(&P, ring, &N, &Hy, 40, 16, 1.5f, nullptr, 7, 1, sws, serr, nullptr));
     printf(fails ? "FAILED: %d\n" : "per entry points ran their host paths under the sanitizer (%d failures)\n", fails);
     return fails ? 1 : 0;
 }
