@@ -56,10 +56,10 @@ def slot_fields(e, name, B=128):
     return out
 
 
-def kernel_masks(e, name, ln2_w, ln2_b):
+def kernel_masks(e, name, ln2_w, ln2_b, B=128):
     """(layer-1 mask, layer-2 mask) the kernel used for the net evaluated in slot `name`: h1 > 0 as saved; y2 = g2 xhat2 + be2 > 0
     from the saved z2 and LayerNorm statistics with the LayerNorm parameters in force at that forward pass"""
-    f = slot_fields(e, name)
+    f = slot_fields(e, name, B)
     xhat = (f["z2"] - f["st2"][:, 0:1]) * f["st2"][:, 1:2]
     return f["h1"] > 0, (ln2_w * xhat + ln2_b) > 0
 
@@ -185,7 +185,7 @@ def check_params(e, o, E_, what, was_actor_call):
             assert not (d > bound).any(), f"{what} {k}: {int((d > bound).sum())} entries beyond their bound, worst {d.max():.2e}"
 
 
-def learn_masks(e, E_, pre, was_actor_call, soft, use_bc=True):
+def learn_masks(e, E_, pre, was_actor_call, soft, use_bc=True, B=128):
     """{activation call number of HirlOracle.learn: the kernel's mask} for the calls whose subgradient reaches a parameter gradient:
     calls 0-5 are the target networks (no gradient), 6/7 8/9 the critic's two heads, then on an actor call 10/11 actor(s), 12/13
     Q1(s, pi) with the UPDATED critic, [14-17 the soft estimate, no gradient], and last actor(s_bc)."""
@@ -193,14 +193,14 @@ def learn_masks(e, E_, pre, was_actor_call, soft, use_bc=True):
     now_critic = E_.unpack(e.critic, E_.CRITIC_LAYOUT)
     cpu = lambda t: t.cpu()  # noqa: E731
     m = {}
-    m[6], m[7] = kernel_masks(e, "C1", cpu(pre_critic["layernorm2.weight"]), cpu(pre_critic["layernorm2.bias"]))
-    m[8], m[9] = kernel_masks(e, "C2", cpu(pre_critic["layernorm4.weight"]), cpu(pre_critic["layernorm4.bias"]))
+    m[6], m[7] = kernel_masks(e, "C1", cpu(pre_critic["layernorm2.weight"]), cpu(pre_critic["layernorm2.bias"]), B)
+    m[8], m[9] = kernel_masks(e, "C2", cpu(pre_critic["layernorm4.weight"]), cpu(pre_critic["layernorm4.bias"]), B)
     if was_actor_call:
-        m[10], m[11] = kernel_masks(e, "API", cpu(pre_actor["layernorm2.weight"]), cpu(pre_actor["layernorm2.bias"]))
-        m[12], m[13] = kernel_masks(e, "CPI", cpu(now_critic["layernorm2.weight"]), cpu(now_critic["layernorm2.bias"]))
+        m[10], m[11] = kernel_masks(e, "API", cpu(pre_actor["layernorm2.weight"]), cpu(pre_actor["layernorm2.bias"]), B)
+        m[12], m[13] = kernel_masks(e, "CPI", cpu(now_critic["layernorm2.weight"]), cpu(now_critic["layernorm2.bias"]), B)
         if use_bc:
             c = 18 if soft else 14
-            m[c], m[c + 1] = kernel_masks(e, "ABC", cpu(pre_actor["layernorm2.weight"]), cpu(pre_actor["layernorm2.bias"]))
+            m[c], m[c + 1] = kernel_masks(e, "ABC", cpu(pre_actor["layernorm2.weight"]), cpu(pre_actor["layernorm2.bias"]), B)
     return m
 
 

@@ -371,7 +371,7 @@ def test_learn_ragged_batches_and_outlier_rows(eng_mod):
     params, data = D.make_params(11), D.make_data(12, outliers=True)
     ring, exp, bc = device_tables(data)
     rng = np.random.default_rng(1)
-    for B in (16, 48, 256):
+    for B in (16, 48, 256, 272, 512):
         e = eng_mod.HirlEngine(batch=B)
         e.load_params(params["actor"], params["critic"], params["bc_actor"])
         o = H.HirlOracle(params["actor"], params["critic"], params["bc_actor"])

@@ -235,13 +235,13 @@ class RoundedSac:
         S.mlp, S._act = self._mlp, self._act
 
 
-def kernel_masks(e):
+def kernel_masks(e, B=128):
     """per activation call of the oracle's learn(): the kernel's masks (layer 1: h1 > 0 where the forward saved it — not for policy(s') and the
     targets, which nothing differentiates; layer 2: z2 > 0, z2 with its bias, the LayerNorm slots being (1, 0))"""
     order = [0, 4, 5, 2, 3, 1, 6, 7]  # slots in the oracle's evaluation order (see RoundedSac)
     masks = {}
     for i, k in enumerate(order):
-        f = slot(e, k)
+        f = slot(e, k, B=B)
         if k not in (0, 4, 5):
             masks[2 * i] = f["h1"] > 0
         masks[2 * i + 1] = f["z2"] > 0
