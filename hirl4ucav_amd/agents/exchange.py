@@ -144,6 +144,16 @@ def negotiate_rccl_direct(group=None, flag_device="cpu", available=None, make_id
     return conn, ("" if conn is not None else why)
 
 
+def epoch_word(count):
+    """The flag word of a message kind's `count`-th exchange (count >= 1): 1, 2, ..., 0xFFFFFFFE, then 1 again — never 0 (what a fresh flag holds)
+    and never 0xFFFFFFFF (the poison value, which the entry points refuse).  Across the wrap a peer one exchange ahead or behind stays at a signed
+    distance of at most 3, which the kernels' (int)(flag - epoch) >= 0 reads correctly.  The buffer parity is NOT this word's business (the wrap
+    skips values; a skipped word must never skip a parity): OneShotExchange keeps its unbounded counter for that."""
+    if count < 1:
+        raise ValueError("epoch_word: exchanges are counted from 1")
+    return 1 + (count - 1) % 0xFFFFFFFE
+
+
 class _DeviceWords:
     """raw device memory as a torch tensor (no copy): the __cuda_array_interface__ protocol"""
 
@@ -222,13 +232,13 @@ class OneShotExchange:
     def allreduce(self, kind):
         """sum of every rank's message written into write_buffer(kind) -> a local tensor (the same bits on every rank)"""
         self.epoch[kind] += 1
-        e = self.epoch[kind]
+        e = self.epoch[kind]  # unbounded: its parity selects the buffer, epoch_word(e) is what the flags carry
         if self.two_stage:
             _lib.call("hx_allreduce_twostage", self.reduced[kind].data_ptr(), self.bufs[kind, e & 1], self.reds[kind], self.flags[kind], self.flags2[kind],
-                      self.status_ptr, self.world, self.rank, self.n[kind], e & 0xFFFFFFFF, self.timeout_ms, int(self.bf16), _lib.stream_ptr())
+                      self.status_ptr, self.world, self.rank, self.n[kind], epoch_word(e), self.timeout_ms, int(self.bf16), _lib.stream_ptr())
         else:
             _lib.call("hx_allreduce_oneshot", self.reduced[kind].data_ptr(), self.bufs[kind, e & 1], self.flags[kind], self.status_ptr, self.world,
-                      self.rank, self.n[kind], e & 0xFFFFFFFF, self.timeout_ms, _lib.stream_ptr())
+                      self.rank, self.n[kind], epoch_word(e), self.timeout_ms, _lib.stream_ptr())
         return self.reduced[kind]
 
     def check(self):

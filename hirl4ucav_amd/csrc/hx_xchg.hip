@@ -52,7 +52,8 @@ __global__ __launch_bounds__(kThreads) void oneshot_allreduce_kernel(OneShotArgs
         __hip_atomic_store(A.flag[A.rank], s_fail ? kPoison : A.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     if (s_fail) return;
-    // 2. wait for every peer (one polling lane per peer and workgroup; epochs only grow: signed distance handles the wrap)
+    // 2. wait for every peer (one polling lane per peer and workgroup; epoch words run 1 .. 0xFFFFFFFE and start over at 1, peers are at most one
+    //    exchange apart: the signed distance handles the wrap)
     if ((int)threadIdx.x < A.world && (int)threadIdx.x != A.rank) {
         const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
         for (;;) {
@@ -216,8 +217,10 @@ int hx_ipc_close(void* dev_ptr) {
  * bufs / flags: HOST arrays of `world` device pointers (own memory at index `rank`, peers' hipIpc mappings elsewhere); status: a device
  * word (fine-grained memory, starts at 0) that becomes 1 if a peer did not arrive within `timeout_ms`, 2 if a peer reported failure; it is
  * STICKY: from then on dst is left untouched, this rank's flag carries a poison value that fails every peer too, and every later call
- * returns at once (pass the word as HxNets.xchg_status and the optimizer steps are skipped as well).  epoch: this exchange's number,
- * increasing by 1 per call on every rank (each rank's flag word must start at 0, the first epoch is 1; 0xFFFFFFFF is reserved). */
+ * returns at once (pass the word as HxNets.xchg_status and the optimizer steps are skipped as well).  epoch: this exchange's flag word, the
+ * same on every rank: 1 at the first call (each rank's flag word must start at 0), then 2, 3, ..., 0xFFFFFFFE, then 1 again — never 0 and never
+ * 0xFFFFFFFF (reserved: the poison value).  Ranks are at most one exchange apart, and the waits compare by signed distance, (int)(flag - epoch)
+ * >= 0, so the step from 0xFFFFFFFE to 1 (a distance of 3) is read like any other (exchange.py epoch_word). */
 int hx_allreduce_oneshot(float* dst, const float* const* bufs, uint32_t* const* flags, uint32_t* status, int32_t world, int32_t rank,
                          int64_t n, uint32_t epoch, int32_t timeout_ms, void* stream) {
     HX_REQUIRE(dst && bufs && flags && status && world >= 1 && world <= kMaxWorld && rank >= 0 && rank < world && n > 0 && n % 4 == 0,

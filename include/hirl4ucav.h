@@ -712,8 +712,8 @@ int hx_ipc_export(void* dev_ptr, void* handle64 /* host, out */);
 int hx_ipc_import(const void* handle64 /* host */, void** dev_ptr);
 int hx_ipc_close(void* dev_ptr);
 /* dst[i] = bufs[0][i] + bufs[1][i] + ... (rank order: bit-identical on every rank), n floats (multiple of 4).  bufs / flags: host arrays of
- * `world` (<= 8) device pointers, own memory at index `rank`; every rank calls with the same epoch = 1, 2, 3, ...; messages are
- * double-buffered by the CALLER (epoch parity), see hx_xchg.hip.  *status != 0 afterwards: a peer did not arrive within timeout_ms (1) or
+ * `world` (<= 8) device pointers, own memory at index `rank`; every rank calls with the same epoch word = 1, 2, 3, ..., 0xFFFFFFFE, then 1
+ * again (never 0, never 0xFFFFFFFF: refused); messages are double-buffered by the CALLER (the parity of its own call count), see hx_xchg.hip. *status != 0 afterwards: a peer did not arrive within timeout_ms (1) or
  * reported failure (2) — sticky and global (fail-stop): see hx_xchg.hip.  EXPERIMENTAL until it has run on two physical GPUs. */
 int hx_allreduce_oneshot(float* dst, const float* const* bufs, uint32_t* const* flags, uint32_t* status, int32_t world, int32_t rank,
                          int64_t n, uint32_t epoch, int32_t timeout_ms, void* stream);
