@@ -28,7 +28,7 @@
 //            sums, parity at 1e-5); the first forward launch can also draw and gather the minibatch (SAMPLE);
 //   bwd_l2   head + loss gradient + LN2 backward in the prologue (8 rows per workgroup, a wave pair per row), dh1 = dz2 W2 on MFMA;
 //   wgrad    dW2 = dz2^T h1 on MFMA (16 x 128 per workgroup, a tile per wave pair over row halves) + the vector / LN / layer-1 gradients
-//            (16 columns x 64 row groups per workgroup): 112 workgroups per job, written into a flat gradient buffer with the parameter layout (one all-reduce message per phase when
+//            (16 columns x 64 row groups per workgroup): 112 workgroups per job (a lone two-slot fp32 job: 224, a slot per half workgroup), written into a flat gradient buffer with the parameter layout (one all-reduce message per phase when
 //            sharded); on one GPU the same threads apply Adam, the Polyak step of the target and refresh the W2 images (ADAM);
 //   adam / polyak  elementwise over the flat buffers, 16 B per lane (sharded path, SAC).
 // The kernels issue an instruction nearly every cycle of their life (16 waves per CU): their run time follows the instruction count — and the

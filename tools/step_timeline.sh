@@ -17,11 +17,22 @@ import csv, glob, sys, collections, re
 O = sys.argv[1]
 def short(n):
     n = re.sub(r"\(anonymous namespace\)::", "", n); n = re.sub(r"^void ", "", n)
-    return n.split("(")[0][:70]
+    return n.split("(")[0][:60]
+def keyed(r):
+    # (kernel, workgroups of the launch): one kernel on two grids — the critics' and the actor's wgrad launch — is two populations
+    if "Grid_Size_X" in r:
+        wgs = 1
+        for a in "XYZ":
+            wgs *= max(1, int(r["Grid_Size_" + a])) // max(1, int(r["Workgroup_Size_" + a]))
+    elif "Grid_Size" in r and "Workgroup_Size" in r:
+        wgs = int(r["Grid_Size"]) // max(1, int(r["Workgroup_Size"]))
+    else:
+        return short(r["Kernel_Name"])
+    return f"{short(r['Kernel_Name'])} [{wgs} wg]"
 rows = []
 for f in glob.glob(O + "/trace/**/*kernel_trace.csv", recursive=True):
     for r in csv.DictReader(open(f)):
-        rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), short(r["Kernel_Name"])))
+        rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), keyed(r)))
 rows.sort()
 rows = rows[len(rows) // 3:]  # steady state
 dur, gap, prev = collections.defaultdict(list), collections.defaultdict(list), collections.defaultdict(collections.Counter)
@@ -33,7 +44,7 @@ for c in ("FETCH_SIZE", "WRITE_SIZE"):
     for f in glob.glob(O + f"/pmc_{c}/**/*counter_collection.csv", recursive=True):
         for r in csv.DictReader(open(f)):
             if r["Counter_Name"] == c:
-                acc[short(r["Kernel_Name"])].append(float(r["Counter_Value"]))
+                acc[keyed(r)].append(float(r["Counter_Value"]))
     pmc[c] = {k: sum(v) / len(v) for k, v in acc.items()}
 print("# rocprofv3 --kernel-trace: per kernel [begin, end] on the device clock; gap = previous kernel's end -> this kernel's begin (same queue)")
 print("# FETCH_SIZE / WRITE_SIZE: separate --pmc passes, raw counter units (KB on gfx950: FETCH in 64-B x 2 per the guide's calibration -> tools/pmc_traffic_json.py)")
