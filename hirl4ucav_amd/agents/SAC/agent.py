@@ -4,7 +4,9 @@ expert_data), .expert_memory, .writer, .model_dir / .plot_dir, .save_models — 
 imitative=True (agent.py:315-318, 385-403): load_bc_actor, then learn() draws a second batch from .expert_memory for the
 BC-gated policy loss and logs loss/bc and loss/bc_weight.  With per=True (agent.py:112-118, 281-284, 329-331): .memory is a prioritized
 device memory — append(..., error), sample(n) -> (batch, indices, weights), update_priority(indices, errors) — and learn() carries the
-weights through the three losses (the store and the draw rule are this project's: rltorch.PrioritizedMemory is un-vendored).
+weights through the three losses (the store and the draw rule are this project's: rltorch.PrioritizedMemory is un-vendored).  With multi_step=n
+(2..8, uniform replay, not imitative; agent.py:121-124): .memory applies this project's truncated n-step rule on the host (rltorch.MultiStepMemory is
+un-vendored too: include/hirl4ucav.h "n-step returns"), each row's discount folded into its done column, and the engine keeps the one-step gamma.
 
 The networks are the Linear-ReLU stacks of the reference's un-vendored rltorch builder (initialisation: xavier-uniform
 weights, zero biases — that builder is not in /root/reference, so its exact initialiser is not claimed).  The known crashes of
@@ -16,7 +18,7 @@ import os
 import numpy as np
 import torch
 
-from ...utils.buffer import PER_EPS, DeviceReplay, PrioritizedReplay, device
+from ...utils.buffer import NSTEP_MAX, PER_EPS, DeviceReplay, HostNStep, PrioritizedReplay, device
 from .. import sac_engine as SE
 
 
@@ -28,19 +30,31 @@ class _Writer:
 
 
 class DeviceMemory(DeviceReplay):
-    """rltorch MultiStepMemory's append / sample / len on the device ring (multi_step = 1, SAC/agent.py:121-124)."""
+    """rltorch MultiStepMemory's append / sample / len on the device ring (SAC/agent.py:121-124).  multi_step > 1: this project's truncated n-step
+    rule (include/hirl4ucav.h "n-step returns") on the host, one transition per append — a row leaves the window once it holds multi_step steps, or
+    with fewer at the episode's end (done: terminal; episode_done without done, or a next append that does not continue from the last next_state:
+    truncated, bootstrapping from the last state seen), its discount folded into the done column."""
 
-    def __init__(self, capacity):
+    def __init__(self, capacity, multi_step=1, gamma=0.99):
         super().__init__(int(capacity), device)
         self._len, self._pos = 0, 0
+        self.multi_step = int(multi_step)
+        self._window = HostNStep(self.multi_step, gamma) if self.multi_step > 1 else None
 
-    def append(self, state, action, reward, next_state, done, episode_done=None):  # train_sac.py:242
-        row = np.zeros(32, np.float32)
-        row[0:13], row[13:17], row[17:30], row[30], row[31] = state, action, next_state, reward, float(done)
+    def _store(self, row):
         self.ring[self._pos] = torch.from_numpy(row).to(self.device)
         self._pos = (self._pos + 1) % self.capacity
         self._len = min(self._len + 1, self.capacity)
         self.total += 1
+
+    def append(self, state, action, reward, next_state, done, episode_done=None):  # train_sac.py:242
+        if self._window is not None:
+            for row, _ in self._window.append(state, action, reward, next_state, done, episode_done):
+                self._store(row)
+            return
+        row = np.zeros(32, np.float32)
+        row[0:13], row[13:17], row[17:30], row[30], row[31] = state, action, next_state, reward, float(done)
+        self._store(row)
 
     def __len__(self):
         return self._len
@@ -112,13 +126,17 @@ class SacAgent:
                  target_update_interval=3, eval_interval=1000, cuda=True):
         if tuple(observation_space.shape) != (13,) or tuple(action_space.shape) != (4,) or list(hidden_units) != [256, 512]:
             raise NotImplementedError("the HIP kernels are built for train_sac.py's shape: 13 / 4 / hidden [256, 512]")
-        if (per and imitative) or multi_step != 1 or (imitative and (not entropy_tuning or grad_clip is not None)):
-            raise NotImplementedError("built: uniform replay (with or without imitative=True) or prioritized replay (per=True, without imitative), multi_step 1; "
-                                      "without imitative also entropy_tuning=False (a fixed ent_coef) and grad_clip; per with imitative=True, multi_step != 1, and "
+        multi_step = int(multi_step)
+        if ((per and imitative) or not 1 <= multi_step <= NSTEP_MAX or (multi_step != 1 and (per or imitative))
+                or (imitative and (not entropy_tuning or grad_clip is not None))):
+            raise NotImplementedError("built: uniform replay (with or without imitative=True) or prioritized replay (per=True, without imitative); multi_step 1, or "
+                                      f"2..{NSTEP_MAX} with uniform replay and without imitative; without imitative also entropy_tuning=False (a fixed ent_coef) and "
+                                      "grad_clip; per with imitative=True, multi_step != 1 with per=True or imitative=True, and "
                                       "entropy_tuning=False or grad_clip with imitative=True (SacEngine.set_grad_clip / set_entropy_tuning take them) are not")
         self.observation_space, self.action_space = observation_space, action_space
         self.device = device
-        self.eng = SE.SacEngine(batch=batch_size, lr=lr, gamma=gamma ** multi_step, tau=tau, target_entropy=-float(np.prod(action_space.shape)),
+        # multi_step > 1: every row carries its own discount in the done column ((1 - d') gamma = gamma^m), so the engine keeps the one-step gamma
+        self.eng = SE.SacEngine(batch=batch_size, lr=lr, gamma=gamma, tau=tau, target_entropy=-float(np.prod(action_space.shape)),
                                 target_update_interval=target_update_interval, device=device)
         self.eng.load_params(_xavier_mlp(13, 8), _xavier_mlp(17, 1), _xavier_mlp(17, 1))
         if grad_clip is not None:  # update_params(optim, network, loss, grad_clip), agent.py:310-320
@@ -131,7 +149,7 @@ class SacAgent:
             self.memory = PrioritizedDeviceMemory(memory_size, alpha=alpha, beta=beta, beta_annealing=beta_annealing)
             self.eng.set_prioritized(self.memory)
         else:
-            self.memory = DeviceMemory(memory_size)
+            self.memory = DeviceMemory(memory_size, multi_step=multi_step, gamma=gamma)
         self.expert_memory = None
         self.imitative = bool(imitative)  # the BC gate needs load_bc_actor(...) and an expert_memory before the first learn()
         self.log_dir = log_dir

@@ -168,6 +168,7 @@ class SacEngine:
         self.prioritized, self.per_weights, self.per_errors = None, None, None  # set_prioritized
         self.per_new_rows = "max"  # set_prioritized(new_rows=...): how step_learn gives a step's rows their first priority
         self.grad_clip, self.clip_ws = None, None  # set_grad_clip
+        self.multi_step = None  # set_multi_step: the n-step inserter behind act_step
         self.entropy_tuning, self.ent_coef = True, None  # set_entropy_tuning
 
     def set_grad_clip(self, max_norm):
@@ -231,9 +232,37 @@ class SacEngine:
             raise _lib.HxError("prioritized replay runs on one GPU (priorities and block sums are not exchanged between ranks): run it with --gpus 1")
         if self.imitative:
             raise _lib.HxError("prioritized replay does not go with the imitative branch (not built: SacAgent(imitative=True, per=True)): build a SacEngine without set_imitative")
+        if new_rows == "td" and self.multi_step is not None:
+            raise _lib.HxError("prioritized replay with n-step rows: new_rows='td' is not built (the scoring pass and its chunks are sized by the envs per "
+                               "step, a step of n-step rows stores up to n * num_envs): use new_rows='max'")
+        if self.multi_step is not None and self.multi_step.replay is not replay:
+            raise _lib.HxError("set_prioritized: the n-step inserter given to set_multi_step writes into another replay")
         self.prioritized, self.per_new_rows = replay, new_rows
         self.per_weights = torch.ones(self.batch, dtype=torch.float32, device=self.device)
         self.per_errors = torch.zeros(self.batch, dtype=torch.float32, device=self.device)
+
+    def set_multi_step(self, inserter):
+        """SacAgent(multi_step=n) for the vector loop: from now on step_learn runs act_step on an env WITHOUT a replay ring, then inserter.push
+        (utils.buffer.NStepInserter: finished n-step rows into inserter.replay), then sample(inserter.replay) and learn() — the reference's order; there
+        is no front form, as for prioritized replay.  learn() itself is unchanged in fp32 and bf16: a row's discount sits in its done column and
+        hyper.gamma stays the one-step gamma, which must be the inserter's.  With set_prioritized the step's rows enter at pmax (mark_new with the bound
+        n * num_envs); new_rows='td' is refused.  None: back to one-step rows.  One GPU."""
+        if inserter is None:
+            self.multi_step = None
+            return
+        from ..utils.buffer import NStepInserter
+
+        if not isinstance(inserter, NStepInserter):
+            raise TypeError("set_multi_step takes a utils.buffer.NStepInserter")
+        if self.world > 1:
+            raise _lib.HxError("n-step returns run on one GPU (not built for sharded ranks): run it with --gpus 1")
+        if self.imitative:
+            raise _lib.HxError("n-step returns do not go with the imitative branch (not built: SacAgent(imitative=True, multi_step=n))")
+        if self.prioritized is not None and (self.per_new_rows != "max" or inserter.replay is not self.prioritized):
+            raise _lib.HxError("n-step returns with prioritized replay: new_rows='max' only, and the inserter writes into the prioritized replay")
+        if abs(inserter.gamma - float(self.hyper.gamma)) > 1e-7:
+            raise ValueError(f"set_multi_step: the inserter folds gamma = {inserter.gamma} into its rows, the update bootstraps with gamma = {float(self.hyper.gamma)}")
+        self.multi_step = inserter
 
     def score_new(self, replay, max_new, eps=None, seed=0):
         """the rows stored in `replay` since its last mark_new / score_new enter at |Q1(s, a) - y| of their own, computed with the networks as they
@@ -568,11 +597,16 @@ class SacEngine:
         learn(), batch <= 256, Philox draws.  Acting and update in one format: fp32, or bf16 for both (a bf16 policy beside the fp32 update runs act_step,
         then the sampled learn(); so does the imitative branch).  After set_prioritized there is no front form either: act_step -> mark_new -> sample ->
         learn, the reference's order.  -> (actions, obs, reward, done, success)."""
-        replay, n, B = env.replay, env.n, self.batch
+        ms = self.multi_step
+        replay, n, B = (env.replay if ms is None else ms.replay), env.n, self.batch
+        if ms is not None and env.replay is not None:
+            raise _lib.HxError("SacEngine.step_learn after set_multi_step: the env inserts one-step rows itself: build it with replay=None")
         if self.world > 1 or replay is None or self.separate_critic_adam or self.staged_policy:
             raise _lib.HxError("SacEngine.step_learn: one GPU, the one-call learn(), envs with a replay ring attached")
         if self._pending is not None:
             raise _lib.HxError("step_learn draws its own minibatch: a sample(defer=True) is still pending")
+        if ms is not None and self.imitative:
+            raise _lib.HxError("n-step returns do not go with the imitative branch (not built)")
         if self.prioritized is not None:
             # no front form: the front loop draws BEFORE the step's insert, so update() could hit slots the step has overwritten.  The reference's order:
             # act_step -> mark_new -> sample -> learn (which ends in update)
@@ -582,6 +616,8 @@ class SacEngine:
                 raise _lib.HxError("prioritized replay does not mix expert rows into the minibatch (the reference's learn() drops them when per is on: "
                                    "agent.py:281-284): run step_learn without expert rows")
             return self._step_then_learn(env, explore, act_seed, out, sample_seed, new_rows=self.per_new_rows)
+        if ms is not None:  # no front form: the front launch's acting workgroups insert one-step rows; the reference's order (E-SAC's expert rows are mixed in as ever)
+            return self._step_then_learn(env, explore, act_seed, out, sample_seed, expert=expert, n_main=n_main, defer=True)
         if self.imitative:  # no front form: the reference's order; `expert` is the imitative branch's expert memory, the minibatch is not expert-mixed
             if expert is None:
                 raise _lib.HxError("SacEngine.step_learn: the imitative branch needs the expert memory (expert=...)")
@@ -622,14 +658,17 @@ class SacEngine:
         return out, env.obs, env.reward, env.done, env.success
 
     def _step_then_learn(self, env, explore, act_seed, out, sample_seed, expert=None, n_main=None, defer=False, new_rows=None, imit_expert=None):
-        """step_learn without a front form, the reference's order: act_step, [the step's rows get their first priority: new_rows "max" | "td"],
+        """step_learn without a front form, the reference's order: act_step, [set_multi_step: the inserter's push], [the step's rows get their first priority: new_rows "max" | "td"],
         sample(env.replay, expert, n_main), [sample_expert(imit_expert)], learn()"""
-        replay = env.replay
+        ms = self.multi_step
+        replay = env.replay if ms is None else ms.replay
         res = self.act_step(env, explore=explore, seed=act_seed, out=out)
+        if ms is not None:  # the acting launch ran without a ring: the step's finished n-step rows enter behind it (at most n * num_envs of them)
+            ms.push(env, res[0])
         if new_rows == "td":
             self.score_new(replay, env.n, seed=sample_seed)
         elif new_rows == "max":
-            replay.mark_new(env.n)
+            replay.mark_new(env.n if ms is None else ms.max_rows)
         self.sample(replay, expert, n_main=n_main, seed=sample_seed, defer=defer)
         if imit_expert is not None:
             self.sample_expert(imit_expert, seed=sample_seed, defer=defer)

@@ -291,6 +291,9 @@ def main(config):
     per_new = getattr(config, "per_new", "max")  # how a step's rows get their first priority: at pmax, or at a TD error of their own (agent.py:234-246)
     if not per and per_refusal(config, world):  # (--per_new td without --per)
         raise SystemExit("train_all: " + per_refusal(config, world))
+    multi_step = int(getattr(config, "multi_step", 1))  # SacAgent(multi_step=n): truncated n-step returns (utils.buffer.NStepInserter)
+    if nstep_refusal(config, world):
+        raise SystemExit("train_all: " + nstep_refusal(config, world))
     grad_clip, fixed_alpha = getattr(config, "grad_clip", None), getattr(config, "fixed_alpha", None)  # SacAgent(grad_clip=c) / (entropy_tuning=False, ent_coef=x)
     if clip_refusal(config, world):
         raise SystemExit("train_all: " + clip_refusal(config, world))
@@ -305,7 +308,12 @@ def main(config):
     else:
         replay = DeviceReplay(buffer_size, device)
     env = BatchedHarfangEnv(n, scenario=env_type, device=device, seed=seed, max_step=max_step, auto_reset=True,
-                            random_reset=config.random, env_id0=rank * n, replay=replay)
+                            random_reset=config.random, env_id0=rank * n, replay=replay if multi_step == 1 else None)
+    inserter = None
+    if multi_step > 1:  # the acting launches run without a ring; the inserter's launch behind each step writes the finished n-step rows
+        from .utils.buffer import NStepInserter
+
+        inserter = NStepInserter(replay, n, multi_step, 0.99)  # (SacEngine's gamma, SAC/agent.py:60)
     sac = config.agent == "SAC"
     torch.manual_seed(seed)  # identical initial networks on every rank
     if sac:  # train_sac.py:187-215: lr 1e-3, hidden [256, 512], batch 128, target_update_interval 3
@@ -320,6 +328,8 @@ def main(config):
             eng.set_grad_clip(grad_clip)
         if fixed_alpha is not None:  # SAC/agent.py:108-110
             eng.set_entropy_tuning(False, fixed_alpha)
+        if inserter is not None:
+            eng.set_multi_step(inserter)
     else:
         eng = E.HirlEngine(batch=batch, slope=0.0 if hirl else 0.01, use_bc=hirl, device=device)
         eng.load_params(init_actor_state_dict(), init_critic_state_dict(), init_actor_state_dict() if hirl else None)
@@ -386,8 +396,13 @@ def main(config):
     else:
         # RANDOM EXPLORATION: 20 episodes of uniform actions in the reference (train_all.py:266-282) = 20*maxStep transitions
         env.reset()
+        if inserter is not None:
+            inserter.reset(env)
         for _ in range(math.ceil(20 * max_step / (n * world))):
-            env.step(torch.rand((n, 4), device=device) * 2 - 1)
+            a0 = torch.rand((n, 4), device=device) * 2 - 1
+            env.step(a0)
+            if inserter is not None:
+                inserter.push(env, a0)
         if per and per_new == "td":  # the exploration rows are appended with an error of their own too (SAC/agent.py:176-177, 234-246: the start_steps rows are scored as well)
             eng.score_new(replay, math.ceil(20 * max_step / (n * world)) * n, seed=seed + 3 + rank)
         elif per:
@@ -408,11 +423,14 @@ def main(config):
     shared_gpu = world > torch.cuda.device_count() and not os.environ.get("HX_FRONT_SHARED_GPU")
     front = (config.loop == "front" and not sac and not config.separate_launches and config.updates_per_step == 1 and batch <= 256
              and getattr(config, "dtype", "f32") in ("f32", "f32x9", "bf16") and not shared_gpu)
-    front_sac = (config.loop == "front" and sac and world == 1 and not config.separate_launches and config.updates_per_step == 1 and batch <= 256 and not per and grad_clip is None)
+    front_sac = (config.loop == "front" and sac and world == 1 and not config.separate_launches and config.updates_per_step == 1 and batch <= 256 and not per and grad_clip is None
+                 and inserter is None)
     if rank == 0:
         which = "front launch (env step + first launches of learn() in one launch; draw before the insert)" if (front or front_sac) else "reference order"
         if per:  # the front loop draws before the step's insert: update_priority could then hit slots the step has overwritten
             which += " (--per: the front launch draws before the step's insert, so the priorities of the drawn rows could be written into overwritten slots)"
+        if inserter is not None:  # the front launch's acting workgroups insert one-step rows themselves
+            which += f" (--multi_step {multi_step}: the n-step rows are written by a launch of their own behind the acting launch)"
         if sac and grad_clip is not None and not per:  # the clipped update is the staged sequence (gradients -> norm -> clipped step): its first launch is its own
             which += " (--grad_clip: the clipped update runs as stages, which have no front form)"
         print(f"vector loop: {which}" + (f" ({world} ranks share a GPU: the front launch is for one process per GPU)" if (shared_gpu and config.loop == "front") else ""),
@@ -481,6 +499,8 @@ def main(config):
                 eng.act_step(env, seed=seed + 1, out=actions)              # replay ring depends on the workgroup schedule)
             else:
                 eng.act_step(env, sigma=0.1, seed=seed + 1, out=actions)
+            if inserter is not None:
+                inserter.push(env, actions)  # this step's finished n-step rows (at most multi_step * n of them)
             if per and per_new == "td":
                 log_new = writer is not None and step % log_rate == 0
                 marked0 = replay.marked if log_new else 0  # (a host read, at the logging step only)
@@ -489,7 +509,7 @@ def main(config):
                     k = min(max(replay.marked - marked0, 1), n)
                     writer.add_scalar("stats/per_mean_new_error", float(replay.errors[:k].mean()), step + episode * max_step)
             elif per:
-                replay.mark_new(n)  # this step's rows enter at the running maximum priority (one launch, no host sync)
+                replay.mark_new(n if inserter is None else inserter.max_rows)  # this step's rows enter at the running maximum priority (one launch, no host sync)
             if ret is not None:
                 ret += env.reward
             if step == max_step - 1:
@@ -645,6 +665,26 @@ def per_refusal(config, world=1):
     return None
 
 
+def nstep_refusal(config, world=1):
+    """why `--multi_step` cannot run as asked, or None"""
+    n = getattr(config, "multi_step", 1)
+    if n == 1:
+        return None
+    if not 2 <= n <= 8:
+        return f"--multi_step {n}: the number of steps is 1 (off) or 2..8"
+    if config.agent != "SAC":
+        return f"--multi_step goes with --agent SAC (n-step returns are SacAgent's: SAC/agent.py:121-124), not --agent {config.agent}"
+    if config.type == "ISAC":
+        return "--multi_step with --type ISAC: n-step returns with the imitative branch are not built: use --type SAC or ESAC"
+    if config.type not in ("SAC", "ESAC"):
+        return f"--multi_step goes with --agent SAC --type SAC | ESAC, not --type {config.type}"
+    if getattr(config, "per_new", "max") != "max":
+        return f"--multi_step with --per_new {config.per_new}: scoring n-step rows at insert is not built: use --per_new max"
+    if (config.gpus and config.gpus > 1) or world > 1:
+        return "--multi_step runs on one GPU (the per-env windows are not built for sharded ranks): use --gpus 1"
+    return None
+
+
 def clip_refusal(config, world=1):
     """why `--grad_clip` / `--fixed_alpha` cannot run as asked, or None"""
     clip, fixed = getattr(config, "grad_clip", None), getattr(config, "fixed_alpha", None)
@@ -667,7 +707,7 @@ def parse_args(argv=None):
     """parser().parse_args with the cross-flag checks that are argparse errors"""
     p = parser()
     cfg = p.parse_args(argv)
-    why = per_refusal(cfg) or clip_refusal(cfg)
+    why = per_refusal(cfg) or clip_refusal(cfg) or nstep_refusal(cfg)
     if why:
         p.error(why)
     if cfg.type == "ISAC" and cfg.agent != "SAC":
@@ -731,6 +771,11 @@ def parser():
     p.add_argument("--per_alpha", type=float, default=0.6, help="--per: priority exponent (SAC/agent.py:62)")
     p.add_argument("--per_beta", type=float, default=0.4, help="--per: importance-weight exponent at the start (SAC/agent.py:62)")
     p.add_argument("--per_beta_annealing", type=float, default=0.0001, help="--per: beta <- min(1, beta + this) per sample call (SAC/agent.py:63)")
+    p.add_argument("--multi_step", type=int, default=1,
+                   help="SAC / E-SAC: truncated n-step returns (SacAgent(multi_step=N)), N in 2..8; 1 (default): one-step rows.  A launch of its own behind "
+                        "every acting launch keeps the last N steps per env and stores finished rows with r = sum gamma^k r_k and the row's discount folded "
+                        "into the done column; no transition is dropped.  Any --dtype, --per with --per_new max; one GPU; the vector loop runs in the "
+                        "reference's order.  Stored in the snapshot: --resume refuses another value")
     p.add_argument("--grad_clip", type=float, default=None, help="SAC: clip each network's gradient (Q1, Q2, policy) to this global L2 norm before its Adam step "
                                                                  "(SacAgent(grad_clip=C), SAC/utils.py:15-21); one GPU; the vector loop runs in the reference's "
                                                                  "order.  Stored in the snapshot: --resume refuses another value")

@@ -173,6 +173,127 @@ class PrioritizedReplay(DeviceReplay):
         return beta
 
 
+class HxNStep(ctypes.Structure):
+    """the n-step window's buffers (include/hirl4ucav.h HxNStep)"""
+    _fields_ = [("win", ctypes.c_void_p), ("hc", ctypes.c_void_p), ("obs_prev", ctypes.c_void_p), ("last_ctr", ctypes.c_void_p),
+                ("n_envs", ctypes.c_int64), ("n", ctypes.c_int32), ("gamma", ctypes.c_float)]
+
+
+_lib.register("hx_nstep_reset", [ctypes.POINTER(HxNStep), _vp, _vp, _vp])
+_lib.register("hx_nstep_push", [ctypes.POINTER(HxNStep), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp])
+
+NSTEP_MAX, NSTEP_FIELDS = 8, 20  # HX_NSTEP_MAX, HX_NSTEP_FIELDS
+
+
+class NStepInserter:
+    """Truncated n-step returns for the vector loop (SacAgent(multi_step=n); the rule is this project's: include/hirl4ucav.h "n-step returns").  The
+    env is built with replay=None; push(env, actions) behind every step keeps up to n pending heads per env and writes finished rows into `replay`
+    in the ordinary format, r = sum_k gamma^k r_k and the row's discount folded into the done column, so sample() / learn() run unchanged with the
+    one-step gamma.  reset(env) after env.reset().  One call stores at most max_rows = n * num_envs rows.  Everything enqueues on the current stream."""
+
+    def __init__(self, replay, num_envs, n, gamma):
+        self.replay, self.num_envs, self.n, self.gamma = replay, int(num_envs), int(n), float(gamma)
+        if not 1 <= self.n <= NSTEP_MAX:
+            raise ValueError(f"multi_step is 1..{NSTEP_MAX}, got {n}")
+        if self.num_envs <= 0:
+            raise ValueError(f"NStepInserter: num_envs > 0, got {num_envs}")
+        if replay.capacity < self.n * self.num_envs:
+            raise ValueError(f"NStepInserter: one step can store n * num_envs = {self.n * self.num_envs} rows, the replay holds {replay.capacity}")
+        L = _lib.load()
+        if L.hx_nstep_sizeof() != ctypes.sizeof(HxNStep):
+            raise _lib.HxError(f"ABI mismatch: HxNStep is {ctypes.sizeof(HxNStep)} bytes here, {L.hx_nstep_sizeof()} in {_lib.SO_PATH}")
+        L.hx_nstep_workspace_floats.restype = ctypes.c_int64
+        L.hx_nstep_workspace_floats.argtypes = [ctypes.c_int64, ctypes.c_int32]
+        N, k = self.num_envs, NSTEP_FIELDS * self.n * self.num_envs
+        words = int(L.hx_nstep_workspace_floats(N, self.n))
+        assert words == k + 15 * N
+        self.ws = torch.zeros(words, dtype=torch.float32, device=replay.device)  # the whole state: what a snapshot carries
+        self.win = self.ws[:k].view(NSTEP_FIELDS, self.n, N)
+        self.hc = self.ws[k:k + N].view(torch.int32)            # oldest head's position | pending heads << 8
+        self.obs_prev = self.ws[k + N:k + 14 * N].view(13, N)
+        self.last_ctr = self.ws[k + 14 * N:].view(torch.int32)
+        self.ns = HxNStep(self.win.data_ptr(), self.hc.data_ptr(), self.obs_prev.data_ptr(), self.last_ctr.data_ptr(), N, self.n, self.gamma)
+
+    @property
+    def max_rows(self):
+        return self.n * self.num_envs
+
+    def reset_arrays(self, obs, episode_ctr):
+        _lib.call("hx_nstep_reset", ctypes.byref(self.ns), obs.data_ptr(), episode_ctr.data_ptr(), _lib.stream_ptr())
+
+    def push_arrays(self, obs_new, actions, reward, done, success, episode_ctr):
+        r = self.replay
+        _lib.call("hx_nstep_push", ctypes.byref(self.ns), obs_new.data_ptr(), actions.data_ptr(), reward.data_ptr(), done.data_ptr(), success.data_ptr(),
+                  episode_ctr.data_ptr(), r.ring.data_ptr(), r.success.data_ptr(), r.capacity, r.total.data_ptr(), _lib.stream_ptr())
+
+    def _check(self, env):
+        if env.n != self.num_envs:
+            raise ValueError(f"NStepInserter was built for {self.num_envs} envs, the env has {env.n}")
+        if env.replay is not None:
+            raise ValueError("NStepInserter: the env inserts one-step rows itself (replay=...): build it with replay=None")
+
+    def reset(self, env):
+        """after env.reset(): every window empty, the next step starts from env.obs"""
+        self._check(env)
+        self.reset_arrays(env.obs, env.episode_ctr)
+
+    def push(self, env, actions):
+        """the step env has just taken with `actions` [num_envs, 4] (fp32, contiguous, on the device), as act_step / env.step left it"""
+        self._check(env)
+        if actions.dtype != torch.float32 or not actions.is_contiguous() or actions.numel() != self.num_envs * 4:
+            raise ValueError("NStepInserter.push: actions are a contiguous fp32 [num_envs, 4] tensor")
+        self.push_arrays(env.obs, actions, env.reward, env.done, env.success, env.episode_ctr)
+
+    def state(self):
+        return {"n": self.n, "num_envs": self.num_envs, "gamma": self.gamma, "ws": self.ws.cpu().clone()}
+
+    def load_state(self, st):
+        if st["n"] != self.n:
+            raise ValueError(f"snapshot was written under --multi_step {st['n']}, this run has --multi_step {self.n}: resume with the flag the run was started with")
+        if st["num_envs"] != self.num_envs or st["ws"].numel() != self.ws.numel():
+            raise ValueError(f"snapshot's n-step windows hold {st['num_envs']} envs, this run {self.num_envs}")
+        self.ws.copy_(st["ws"])
+
+
+class HostNStep:
+    """the same rule on the host for ONE env, one transition per append (SacAgent(multi_step=n).memory): fp32 numpy arithmetic in the kernel's order.
+    append -> the finished rows [(row[32], step_success)], oldest first."""
+
+    def __init__(self, n, gamma):
+        self.n, self.gamma = int(n), np.float32(gamma)
+        self.heads, self.obs_prev = [], None  # a head: [s, a, acc, boot, age, step_success]
+
+    def _row(self, h, s_next, d):
+        row = np.zeros(32, np.float32)
+        row[0:13], row[13:17], row[17:30], row[30], row[31] = h[0], h[1], s_next, h[2], d
+        return row, int(h[5])
+
+    def append(self, state, action, reward, next_state, done, episode_done=None, step_success=0):
+        state, next_state = np.asarray(state, np.float32).reshape(13), np.asarray(next_state, np.float32).reshape(13)
+        out = []
+        one = np.float32(1.0)
+        if self.heads and not np.array_equal(state.view(np.uint32), self.obs_prev.view(np.uint32)):
+            # the stream broke off (the driver's time-limit step is never appended): the pending heads leave as truncated rows
+            out += [self._row(h, self.obs_prev, one - h[3]) for h in self.heads]
+            self.heads = []
+        self.heads.append([state.copy(), np.asarray(action, np.float32).reshape(4).copy(), np.float32(0.0), np.float32(0.0), 0, step_success])
+        r = np.float32(reward)
+        for h in self.heads:
+            w = one if h[4] == 0 else np.float32(h[3] * self.gamma)
+            h[2], h[3], h[4] = np.float32(h[2] + np.float32(w * r)), w, h[4] + 1
+        if done:
+            out += [self._row(h, next_state, one) for h in self.heads]
+            self.heads = []
+        elif episode_done:  # the episode ends behind this step without a terminal state: bootstrap from next_state
+            out += [self._row(h, next_state, one - h[3]) for h in self.heads]
+            self.heads = []
+        elif self.heads[0][4] == self.n:
+            h = self.heads.pop(0)
+            out.append(self._row(h, next_state, one - h[3]))
+        self.obs_prev = next_state.copy()
+        return out
+
+
 # ---- reference-API façade -------------------------------------------------------------------------------------------
 import random  # noqa: E402
 from collections import namedtuple  # noqa: E402

@@ -29,6 +29,8 @@ def engine_state(eng):
         st["grad_clip"] = float(eng.grad_clip)
     if not getattr(eng, "entropy_tuning", True):
         st["fixed_alpha"] = float(eng.ent_coef)
+    if getattr(eng, "multi_step", None) is not None:  # (a one-step snapshot carries no such key) the n-step inserter's windows, obs_prev and counters
+        st["multi_step"] = eng.multi_step.state()
     return st
 
 
@@ -54,9 +56,16 @@ def load_engine_state(eng, st):
     if st.get("fixed_alpha") != now_fixed:
         raise ValueError(f"snapshot was written under --fixed_alpha {st.get('fixed_alpha')}, this engine runs under {now_fixed} (None: entropy tuning): "
                          "resume with the flag the run was started with")
+    was_n = st["multi_step"]["n"] if "multi_step" in st else 1
+    now_n = eng.multi_step.n if getattr(eng, "multi_step", None) is not None else 1
+    if was_n != now_n or ("multi_step" in st) != (getattr(eng, "multi_step", None) is not None):
+        raise ValueError(f"snapshot was written under --multi_step {was_n}, this engine runs under --multi_step {now_n}: resume with the flag the run was "
+                         "started with")
     if ("imitative" in st) != bool(getattr(eng, "imitative", False)):
         raise ValueError("snapshot and engine disagree about SAC's imitative branch (--type ISAC): resume with the type the run was started with")
     eng.arena.copy_(st["arena"])
+    if "multi_step" in st:
+        eng.multi_step.load_state(st["multi_step"])
     if "imitative" in st:
         eng.bc_actor.copy_(st["imitative"]["bc_actor"])
         eng.expert_calls = st["imitative"]["expert_calls"]

@@ -78,8 +78,9 @@ const char* hx_last_error(void);
  * 118: prioritized replay for SAC (HxPer, hx_per_*, hx_sac_learn_weighted).
  * 119: gradient-norm clipping and the fixed entropy coefficient for SAC (HX_SAC_FIXED_ALPHA, hx_sac_grad_norm, hx_sac_adam_clipped,
  * hx_sac_learn_weighted_clipped).
- * 120: priorities at insert for SAC's prioritized replay (hx_per_score_workspace_floats, hx_per_score_new). */
-#define HX_ABI_VERSION 120
+ * 120: priorities at insert for SAC's prioritized replay (hx_per_score_workspace_floats, hx_per_score_new).
+ * 121: n-step returns for SAC (HxNStep, hx_nstep_*). */
+#define HX_ABI_VERSION 121
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -699,6 +700,52 @@ int hx_per_score_new(const HxPer* per, const float* ring, const HxSacNets* nets,
  * hx_sac_grad_norm and the clipped step (4 launches more); the log-alpha step stays the launch of its own, unclipped. */
 int hx_sac_learn_weighted_clipped(const HxSacNets* nets, const HxSacBatch* batch, const HxHyper* hyper, const float* weights, float* errors_out,
                                   int32_t polyak_first, int32_t step, float target_entropy, float max_norm, float* clip_ws, void* stream);
+
+
+/* ------------------------------------------------------------------------------------------------------------
+ * n-step returns (SacAgent(multi_step=n): SAC/agent.py:121-124).  The reference's rltorch.MultiStepMemory is un-vendored, so the rule is THIS
+ * project's definition — truncated n-step returns, no transition dropped (rltorch drops an episode's last n - 1 windows and discounts every row by
+ * one scalar gamma^n; neither is done here and its bits are not claimed).  The acting launch runs WITHOUT a ring (HxStepOpts.ring = NULL);
+ * hx_nstep_push behind it keeps up to n pending heads per env and writes finished rows into the ordinary ring in the ordinary 32-word format with
+ * the per-row discount folded into the done column: a row of m steps has r = sum_k gamma^k r_k and (1 - d') gamma = gamma^m, so every consumer of
+ * the ring (hx_sac_learn*, the samplers, hx_per_score_new) runs unchanged with the ONE-step gamma in HxHyper.
+ * Per env and call, fp32 without contraction, in this order (tests/_nstep_model.py is the same in numpy, bit for bit):
+ *     trunc = episode_ctr != last_ctr && !done          (the time-limit step: executed, not stored — HxStepOpts.max_step)
+ *     trunc: every pending head, oldest first, leaves as (s_j, a_j, s' = obs_prev, r = acc_j, d' = 1 - boot_j); the window is cleared; no push
+ *     else:  push (s = obs_prev, a = action, acc = 0, age = 0, step_success); then for every head, the new one included,
+ *                w = age == 0 ? 1 : boot * gamma;  acc = acc + w * reward;  boot = w;  age += 1
+ *            done: every head, oldest first, leaves with s' = obs_new and d' = 1 (that s' is the next episode's first observation under
+ *                  auto_reset; it is multiplied by 1 - d' = 0), the window is cleared
+ *            else, the oldest head at age n: it leaves with s' = obs_new and d' = 1 - boot
+ *     obs_prev = obs_new; last_ctr = episode_ctr
+ * At n = 1: w = 1, acc = 0 + r, d' = 0 or 1 — the rows hx_env_step's insert writes, apart from the s' of terminal rows (and a done ON the time-limit
+ * step, which the insert drops and this rule stores as terminal).  Actions are stored as given.
+ * State, all device memory owned by the caller, hx_nstep_workspace_floats(n_envs, n) 4-byte words in all:
+ *     win       [HX_NSTEP_FIELDS][n][n_envs]  field-major, then head position, then env: s[13] a[4] acc boot step_success(as a float); a head's
+ *               age is not stored — heads enter one per stored step, so head j of `count` (oldest = 0) has age count - j
+ *     hc        [n_envs]  position of the oldest head (bits 0-7) | pending heads << 8 (0 .. n - 1 between calls): a circular index, nothing moves
+ *     obs_prev  [13][n_envs]      last_ctr  [n_envs]
+ * ------------------------------------------------------------------------------------------------------------ */
+#define HX_NSTEP_MAX 8
+#define HX_NSTEP_FIELDS 20
+typedef struct HxNStep {
+    float* win; uint32_t* hc; float* obs_prev; uint32_t* last_ctr;
+    int64_t n_envs;
+    int32_t n;   /* 1 .. HX_NSTEP_MAX */
+    float gamma; /* the one-step discount, HxHyper.gamma */
+} HxNStep;
+int hx_nstep_sizeof(void); /* sizeof(HxNStep) of the loaded library (hx_abi_sizes has no free word) */
+int64_t hx_nstep_workspace_floats(int64_t n_envs, int32_t n); /* 0 for n outside 1 .. HX_NSTEP_MAX or n_envs <= 0 */
+/* after env.reset(): every window empty (win zeroed), obs_prev <- obs [n_envs][13], last_ctr <- episode_ctr */
+int hx_nstep_reset(const HxNStep* ns, const float* obs, const uint32_t* episode_ctr, void* stream);
+/* One step of every env, exactly as an acting launch or hx_env_step left it: obs_new [n_envs][13] (16-byte aligned), actions [n_envs][4], reward,
+ * done, success, episode_ctr [n_envs].  One launch, one env per lane, 64 envs per workgroup.  Ring slots as hx_env_step's insert claims them: the
+ * workgroup's rows are counted (a prefix over its lanes), ONE atomicAdd on *total per workgroup, rows laid out by env, then oldest head first, and
+ * written as whole 128-byte lines; with one workgroup (n_envs <= 64) the slot order is therefore the same for the same inputs, beyond that it
+ * depends on the order in which workgroups reach the counter.  No workgroup waits for another, no float atomics.  One call can emit n * n_envs
+ * rows: cap >= n * n_envs (and < 2^31).  ring_success may be NULL.  Enqueues only. */
+int hx_nstep_push(const HxNStep* ns, const float* obs_new, const float* actions, const float* reward, const uint8_t* done, const int8_t* success,
+                  const uint32_t* episode_ctr, float* ring, int8_t* ring_success, int64_t cap, uint64_t* total, void* stream);
 
 
 /* ------------------------------------------------------------------------------------------------------------
