@@ -35,6 +35,15 @@ def layout(pair, envs_per_block):
     return ((1 if pair else 0) << 8) | (int(envs_per_block) // 4)
 
 
+class HxTrace(ctypes.Structure):
+    """the episode record's buffers (include/hirl4ucav.h HxTrace; utils/trace.py carves them out of one workspace)"""
+    _fields_ = [("log", _vp), ("total", _vp), ("nrec", _vp), ("end_step", _vp), ("end_flags", _vp), ("launches", _vp), ("hits", _vp), ("alive", _vp),
+                ("k", _i64), ("cap_steps", _i32)]
+
+
+TRACE_FIELDS, TRACE_SUMMARIES = 8, 6  # HX_TRACE_FIELDS, HX_TRACE_SUMMARIES
+
+
 class HxError(RuntimeError):
     pass
 
@@ -44,12 +53,14 @@ _SIGNATURES = {
     "hx_env_step": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(HxStepOpts), _vp],
     "hx_env_rearm": [_vp, _i64, _i64, _vp, _vp],
     "hx_label_transitions": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
+    "hx_trace_reset": [ctypes.POINTER(HxTrace), _vp],
+    "hx_trace_push": [ctypes.POINTER(HxTrace), _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp],
     "hx_event_destroy": [_vp],
     "hx_event_elapsed_us": [_vp, _vp, ctypes.POINTER(ctypes.c_float)],
 }
 
 _lib = None
-ABI_VERSION = 121  # HX_ABI_VERSION of include/hirl4ucav.h
+ABI_VERSION = 122  # HX_ABI_VERSION of include/hirl4ucav.h
 _ABI_STRUCTS = {}  # name -> (index in hx_abi_sizes, ctypes class): filled by the binding modules (check_struct)
 
 
@@ -86,6 +97,8 @@ def load():
                       f"HX_ABI_VERSION): rebuild the library (make -C hirl4ucav_amd/csrc)")
     L.hx_event_create.restype = ctypes.c_void_p
     L.hx_event_create.argtypes = []
+    L.hx_trace_workspace_words.restype = ctypes.c_int64
+    L.hx_trace_workspace_words.argtypes = [_i64, _i32]
     for name, args in _SIGNATURES.items():
         fn = getattr(L, name)
         fn.argtypes = args

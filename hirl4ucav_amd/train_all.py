@@ -106,12 +106,13 @@ def label_expert(states, actions, device):
     return rows, sc[keep]
 
 
-def validate(engine, scenario, episodes, max_step, if_random, seed, device, sac=False, env=None):
+def validate(engine, scenario, episodes, max_step, if_random, seed, device, sac=False, env=None, recorder=None):
     """validate() of train_all.py:22-102 (train_sac.py:24-68 for SAC) as ONE batch: `episodes` envs stepped with
     chooseActionNoNoise / exploit until done or the step limit.  The kernels keep simulating an env after its `done` (no auto
     reset here), so everything the reference reads when it SEES done — the score so far, env.episode_success, env.fire_success
     (train_all.py:59-64) — is latched at the first step with done != 0: a missile that is still in flight when the aircraft leaves
-    the altitude band must not turn that episode into a kill afterwards.  `env`: a prepared BatchedHarfangEnv (tests)."""
+    the altitude band must not turn that episode into a kill afterwards.  `env`: a prepared BatchedHarfangEnv (tests, --plot).
+    `recorder`: an EpisodeRecorder over `env` (utils/trace.py) — one more launch behind every env step; None: none, and the return is the same."""
     if env is None:
         env = BatchedHarfangEnv(episodes, scenario=scenario, device=device, seed=seed, auto_reset=False, random_reset=if_random, collect_stats=False)
         obs = env.reset()
@@ -122,9 +123,13 @@ def validate(engine, scenario, episodes, max_step, if_random, seed, device, sac=
     alive = torch.ones(episodes, dtype=torch.bool, device=device)
     kill = torch.zeros(episodes, dtype=torch.bool, device=device)
     fired = torch.zeros(episodes, dtype=torch.bool, device=device)
+    if recorder is not None:
+        recorder.reset()
     for step in range(max_step):
         a = engine.act(obs, explore=False) if sac else engine.act(obs)
         obs, r, d, s = env.step(a)
+        if recorder is not None:
+            recorder.push()
         total += torch.where(alive, r, torch.zeros_like(r))
         ending = alive & (d != 0)
         flags = env.state[35].view(torch.int32)
@@ -137,6 +142,17 @@ def validate(engine, scenario, episodes, max_step, if_random, seed, device, sac=
         engine.act_calls = calls
     scores = total.cpu().numpy()
     return float(scores.mean()), float(scores.std()), int(kill.sum()), int(fired.sum())
+
+
+def validate_plotting(plot, engine, scenario, episodes, max_step, if_random, seed, device, sac=False):
+    """validate(), and with --plot the record of its last episode -> (validate()'s tuple, the EpisodeRecorder or None).  Without --plot: the call as it
+    always was, no launch more."""
+    if not plot:
+        return validate(engine, scenario, episodes, max_step, if_random, seed, device, sac), None
+    from .utils.trace import validation_recorder
+
+    env, rec = validation_recorder(episodes, scenario, seed, if_random, max_step, device)
+    return validate(engine, scenario, episodes, max_step, if_random, seed, device, sac, env=env, recorder=rec), rec
 
 
 def load_expert(config, rng_seed=0):
@@ -201,6 +217,9 @@ def train_bc(config, device, seed, max_step):
     log_dir = os.path.join(config.result_dir, env_type, config.agent, config.model_name, time.strftime("%Y_%m_%d_%H_%M"))
     model_dir = os.path.join(log_dir, "model")
     os.makedirs(model_dir, exist_ok=True)
+    plot_dir = os.path.join(log_dir, "plot")  # train_all.py:217-219: beside model and summary
+    if config.plot:
+        os.makedirs(plot_dir, exist_ok=True)
     save_hparams(log_dir, actorLR=1e-3, batchSize=batch, maxStep=max_step, hiddenLayer1=256, hiddenLayer2=512, agent="BC", model_dir=model_dir,
                  data_dir=config.expert_csv)
     writer = make_writer(os.path.join(log_dir, "summary"))
@@ -213,10 +232,12 @@ def train_bc(config, device, seed, max_step):
         writer.add_scalar("Loss/BC_Loss", bc_loss, (episode + 1) * max_step)  # train_all.py:250-251
         print(f"Episode {episode + 1}: bc_loss {bc_loss:.6f}", flush=True)
         if (episode + 1) % config.checkpoint_rate == 0 and (episode + 1) >= config.bc_validate_from:  # train_all.py:259
-            mean, std, succ, fire = validate(eng, env_type, 50, max_step, config.random, seed + 12345, device)
+            (mean, std, succ, fire), rec = validate_plotting(config.plot, eng, env_type, 50, max_step, config.random, seed + 12345, device)
             if mean > high_score or succ / 50 >= success_rate or arttir % 5 == 0:
                 torch.save({k: v.cpu().clone() for k, v in E.unpack(eng.actor, E.ACTOR_LAYOUT).items()},
                            os.path.join(model_dir, checkpoint_tag(arttir, succ, 50, mean) + "Actor_Harfang_GYM"))
+                if rec is not None:  # train_all.py:70-89: only beside a checkpoint
+                    rec.write_reference_files(plot_dir, arttir)
                 high_score, success_rate = max(high_score, mean), max(success_rate, succ / 50)
             print(f"Validation {arttir}: avg reward {mean:.2f} (std {std:.2f}) success {succ / 50:.2f} fire success {fire / 50:.2f}", flush=True)
             log_validation(writer, episode, mean, std, succ / 50, fire / 50)
@@ -373,8 +394,11 @@ def main(config):
     log_dir = shared_value(os.path.join(config.result_dir, env_type, config.agent, config.model_name, time.strftime("%Y_%m_%d_%H_%M")), world)
     model_dir = os.path.join(log_dir, "model")
     os.makedirs(model_dir, exist_ok=True)
+    plot_dir = os.path.join(log_dir, "plot")  # train_all.py:217-219: beside model and summary
     writer = None
     if rank == 0:
+        if config.plot:
+            os.makedirs(plot_dir, exist_ok=True)
         save_hparams(log_dir, bufferSize=buffer_size, criticLR=1e-3, actorLR=1e-3, batchSize=batch, maxStep=max_step, validationStep=max_step,
                      hiddenLayer1=256, hiddenLayer2=512, agent=config.agent, model_dir=model_dir, hirl_type=config.type, data_dir=config.expert_csv,
                      num_envs=n, world=world, seed=seed, dtype=getattr(config, "dtype", "f32"))
@@ -584,9 +608,11 @@ def main(config):
                     ret.zero_()
                 last_stats = st
         if (episode + 1) % checkpoint_rate == 0 and rank == 0:  # VALIDATION, train_all.py:400-402 / train_sac.py:431-433
-            mean, std, succ, fire = validate(eng, env_type, 50, max_step, config.random, seed + 12345, device, sac)
+            (mean, std, succ, fire), rec = validate_plotting(config.plot, eng, env_type, 50, max_step, config.random, seed + 12345, device, sac)
             if mean > high_score or succ / 50 >= success_rate or arttir % 5 == 0:
                 tag = checkpoint_tag(arttir, succ, 50, mean)
+                if rec is not None:  # train_all.py:70-89: the last validation episode's track, only beside a checkpoint
+                    rec.write_reference_files(plot_dir, arttir)
                 if sac:  # SacAgent.save_models, SAC/agent.py:440-444
                     eng.save_models(model_dir, tag)
                 else:    # Agent.saveCheckpoints, HIRL.py:336-342

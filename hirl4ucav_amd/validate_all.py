@@ -14,7 +14,10 @@ What the reference does (validate_all.py:79-212, validate_sac.py:79-186) and wha
 One deviation, forced by batching: the reference's every-60th-call counter runs on across the episodes of a round (an env attribute, never reset), so an
 episode's first re-arm comes 60 - (steps of the episodes before it) mod 60 calls in; here every episode is its own env and re-arms at ITS steps 60, 120, ...
 (the first episode of a reference round does exactly that).  An episode that is still running at the step limit counts neither as a kill nor as a fire success
-(validate_all.py:59-66: both are read only when `done` is seen)."""
+(validate_all.py:59-66: both are read only when `done` is seen).
+An extension: the reference collects the last episode's track in validate() with --plot but never writes it (validate_all.py:30-58); here `--plot` writes it per
+round — the reference's five CSVs and two figures of train_all.py:70-89 with the tag round<k> — into `--plot_dir` (default <model_dir>/../plot), from the device
+record of utils/trace.py."""
 import argparse
 import os
 import statistics
@@ -31,9 +34,10 @@ VALIDATION_STEP = 1200   # validate_all.py:187,190
 REARM_EVERY = 60         # HarfangEnv_GYM.py:484-486
 
 
-def validate_round(engine, episodes, steps, if_random, seed, device, infinite=False, sac=False, scenario="serpentine", env=None):
+def validate_round(engine, episodes, steps, if_random, seed, device, infinite=False, sac=False, scenario="serpentine", env=None, recorder=None):
     """validate() of validate_all.py:25-77 / validate_sac.py:26-77 as ONE batch of `episodes` envs -> (mean score, fire-success rate, locked launches per launch or 0).
-    An env is simulated on after its `done` (no auto reset), so score and counters only accumulate while its episode lasts."""
+    An env is simulated on after its `done` (no auto reset), so score and counters only accumulate while its episode lasts.
+    `recorder`: an EpisodeRecorder over `env` (utils/trace.py) — one more launch behind every env step; None: none, and the return is the same."""
     if env is None:
         env = BatchedHarfangEnv(episodes, scenario=scenario, device=device, seed=seed, auto_reset=False, random_reset=if_random, collect_stats=False)
         obs = env.reset()
@@ -45,11 +49,15 @@ def validate_round(engine, episodes, steps, if_random, seed, device, infinite=Fa
     fire_success = torch.zeros(episodes, dtype=torch.bool, device=device)
     launches = torch.zeros((), dtype=torch.int64, device=device)
     hits = torch.zeros((), dtype=torch.int64, device=device)
+    if recorder is not None:
+        recorder.reset()
     for step in range(steps):
         if infinite and (step + 1) % REARM_EVERY == 0:  # the call counter is incremented first, then tested (:483-486)
             env.rearm(alive.to(torch.uint8))
         a = engine.act(obs, explore=False) if sac else engine.act(obs)  # exploit / chooseActionNoNoise
         obs, r, d, s = env.step(a)
+        if recorder is not None:
+            recorder.push()
         total += torch.where(alive, r, torch.zeros_like(r))
         launches += (alive & (s != 0)).sum()   # success != 0: a missile left the rail on this step (:517, :523)
         hits += (alive & (s == 1)).sum()       # ... with the target locked (:524)
@@ -65,6 +73,11 @@ def validate_round(engine, episodes, steps, if_random, seed, device, infinite=Fa
     n_launch = int(launches)
     rate = (int(hits) / n_launch) if (infinite and n_launch > 0) else 0.0  # (the reference divides by zero when nothing was launched)
     return float(total.mean()), int(fire_success.sum()) / episodes, rate
+
+
+def plot_dir_of(config):
+    """--plot_dir, or `plot` beside the checkpoint directory (the run layout of train_all: <run>/model, <run>/summary, <run>/plot)"""
+    return config.plot_dir or os.path.normpath(os.path.join(config.model_dir, os.pardir, "plot"))
 
 
 def load_agent(config, device):
@@ -104,8 +117,15 @@ def main(config):
     scenario = config.scenario or "serpentine"
     returns, success, hit_rate = [], [], []
     for k in range(config.nums):
+        env = rec = None
+        if config.plot:
+            from .utils.trace import validation_recorder
+
+            env, rec = validation_recorder(config.episodes, scenario, seed + 12345 + k, config.random, config.validation_step, device)
         r, s, f = validate_round(eng, config.episodes, config.validation_step, config.random, seed + 12345 + k, device, infinite=config.infinite, sac=sac,
-                                 scenario=scenario)
+                                 scenario=scenario, env=env, recorder=rec)
+        if rec is not None:
+            rec.write_reference_files(plot_dir_of(config), f"round{k + 1}")
         returns.append(r)
         success.append(s)
         hit_rate.append(f)
@@ -135,6 +155,7 @@ def parser():
     p.add_argument("--infinite", action="store_true")
     # not in the reference
     p.add_argument("--model_dir", type=str, required=True, help="directory of the checkpoint files (the reference hard-codes one)")
+    p.add_argument("--plot_dir", type=str, default=None, help="--plot: where the last episode's CSVs and figures of every round go (default: <model_dir>/../plot)")
     p.add_argument("--scenario", type=str, default=None, choices=["straight_line", "serpentine", "circular"], help="validate here instead of in serpentine")
     p.add_argument("--nums", type=int, default=2)
     p.add_argument("--episodes", type=int, default=50)

@@ -79,8 +79,9 @@ const char* hx_last_error(void);
  * 119: gradient-norm clipping and the fixed entropy coefficient for SAC (HX_SAC_FIXED_ALPHA, hx_sac_grad_norm, hx_sac_adam_clipped,
  * hx_sac_learn_weighted_clipped).
  * 120: priorities at insert for SAC's prioritized replay (hx_per_score_workspace_floats, hx_per_score_new).
- * 121: n-step returns for SAC (HxNStep, hx_nstep_*). */
-#define HX_ABI_VERSION 121
+ * 121: n-step returns for SAC (HxNStep, hx_nstep_*).
+ * 122: the record of validation episodes (HxTrace, hx_trace_*). */
+#define HX_ABI_VERSION 122
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -747,6 +748,43 @@ int hx_nstep_reset(const HxNStep* ns, const float* obs, const uint32_t* episode_
 int hx_nstep_push(const HxNStep* ns, const float* obs_new, const float* actions, const float* reward, const uint8_t* done, const int8_t* success,
                   const uint32_t* episode_ctr, float* ring, int8_t* ring_success, int64_t cap, uint64_t* total, void* stream);
 
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Episode record (validate() with --plot: train_all.py:22-102, train_sac.py:24-91).  The reference collects the last validation episode's track on
+ * the host, one get_pos() per step_test; here the state stays on the device and validation steps all its episodes in one launch, so a launch of its
+ * own behind every env step appends to a device log and latches what the reference reads when it SEES done.  k tracked envs (env_ids, or envs
+ * 0..k-1), steps t = 0, 1, ... < cap_steps.  Rule per tracked env j at hx_trace_push(t) (tests/_trace_model.py is the same in numpy, bit for bit):
+ *     end_step[j] >= 0: nothing is written — the kernels keep simulating an env after its done, and everything after the first done stays out of
+ *                       the record and out of the score
+ *     else:  log[.][t][j] <- the eight words below;  total = total + reward (fp32, step order);  launches += success != 0;  hits += success == 1;
+ *            nrec = t + 1;  done != 0: end_step = t, end_flags = the flags word, the env leaves `alive`
+ * The step that raises done IS recorded (the reference appends before it looks at done, train_all.py:38-57).  An id outside [0, n) records nothing.
+ * State, all device memory owned by the caller, hx_trace_workspace_words(k, cap_steps) 4-byte words in all:
+ *     log       [HX_TRACE_FIELDS][cap_steps][k]  field-major, then step, then tracked env: 0..2 ally position (state words 0..2), 3..5 opponent
+ *               position (state words 13..15), 6 reward, 7 bits 0..15 of the flags word (state word 35) | (uint8)success << 16; the words are copied
+ *               as bits; hx_trace_reset does not clear it (nrec says how much of it holds)
+ *     total (fp32), nrec, end_step (-1: running), end_flags (u32), launches, hits   [k] each, in this order behind the log
+ *     alive     [1]  tracked envs whose episode is still running: the host's early exit reads this one word
+ * ------------------------------------------------------------------------------------------------------------ */
+#define HX_TRACE_FIELDS 8
+#define HX_TRACE_SUMMARIES 6
+typedef struct HxTrace {
+    uint32_t* log;
+    float* total; int32_t* nrec; int32_t* end_step; uint32_t* end_flags; int32_t* launches; int32_t* hits;
+    int32_t* alive;
+    int64_t k;
+    int32_t cap_steps;
+} HxTrace;
+int hx_trace_sizeof(void); /* sizeof(HxTrace) of the loaded library */
+int64_t hx_trace_workspace_words(int64_t k, int32_t cap_steps); /* 0 for k <= 0 (or >= 2^31) or cap_steps <= 0 */
+/* every summary zero, end_step = -1, alive = k */
+int hx_trace_reset(const HxTrace* tr, void* stream);
+/* Step t of every tracked env, from the env's buffers exactly as hx_env_step or an acting launch left them: state (word w of env i at
+ * state[w * stride + i]), reward, done, success [n]; env_ids: k device ints, or NULL = envs 0..k-1 (then k <= n).  One launch, one tracked env per
+ * lane, 64 per workgroup; at most one integer atomic per wave (alive -= the wave's ending lanes), no float atomics, no workgroup waits for another.
+ * t < 0 or t >= cap_steps: HX_ERR_ARG, nothing is launched.  Enqueues only. */
+int hx_trace_push(const HxTrace* tr, const float* state, int64_t n, int64_t stride, const float* reward, const uint8_t* done, const int8_t* success,
+                  const int32_t* env_ids, int32_t t, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Exchange step of a sharded update without a collective library (selectable beside RCCL): one-shot all-reduce over hipIpc peer
