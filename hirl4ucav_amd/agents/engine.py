@@ -554,7 +554,8 @@ class HirlEngine:
         _lib.call("hx_adam", nets, hyper, 0 | pk, self.critic_step, gs, 0, 0.0, 0.0, B, st)
         self.nets.grad_critic = own_critic
         if actor_phase:
-            _lib.call("hx_hirl_actor_backward", nets, ctypes.byref(batch), hyper, int(w_kind == 1), 1, st)
+            # (fwd_done = 2: critic_grads() carried the actor call's forwards AND the heads launch G feeds on)
+            _lib.call("hx_hirl_actor_backward", nets, ctypes.byref(batch), hyper, int(w_kind == 1), 2, st)
             if self.world > 1 or self.sharded_sequence:   # [dL_rl | dL_bc | count] in one message, w formed from the global count after the exchange
                 if self.actor_msg is None:
                     self.actor_msg = torch.zeros(int(_lib.load().hx_actor_message_floats()), dtype=torch.float32, device=self.device)
@@ -667,7 +668,9 @@ class HirlEngine:
             _lib.call("hx_hirl_learn_back", nets, ctypes.byref(batch), hyper, self.critic_step, int(actor_phase), self.actor_step, int(do_polyak), w_kind, w_given,
                       float(bc_warm_up_weight), ctypes.byref(nxt_draw), ctypes.byref(nxt_tiles), with_c, st)
         else:  # a sharded rank: the same front launch (every rank draws from its own ring), then the stages with the exchanges in between
-            self._learn_staged(lambda: _lib.call("hx_hirl_critic_grads_back", nets, ctypes.byref(batch), hyper, ctypes.byref(nxt_draw), ctypes.byref(nxt_tiles), with_c, st),
+            heads = ((4 if (w_kind == 1 and self.use_bc) else 2) if actor_phase else 0)  # + 2: actor(s)'s head rides in this call's last launch, + 4: bc_actor(s)'s too
+            self._learn_staged(lambda: _lib.call("hx_hirl_critic_grads_back", nets, ctypes.byref(batch), hyper, ctypes.byref(nxt_draw), ctypes.byref(nxt_tiles),
+                                                 with_c | heads, st),
                                batch, actor_phase, do_polyak, w_kind, w_given, bc_warm_up_weight)
         self._front_drawn = (env, env.steps_issued, replay, expert, bc_table, n_main, int(sample_seed), float(smooth_sigma), self.sample_calls + 1, n)
         self._front_tiles = [nxt, cur]

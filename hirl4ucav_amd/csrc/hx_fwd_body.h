@@ -154,7 +154,7 @@ __device__ __forceinline__ void fwd_l2_body(const FwdArgsC& A, const SAT& SA, co
     const float bias2 = J.net[J.m.b2() + nt * NTW + (WIDE ? wave * 16 : (wave % CT) * 16) + (lane & 15)];
     // 1. input tile xs[16][XP]: thread -> (row, column); columns 13..16 carry the action of a 17-wide net, the rest is zero
     const int xr = tid / XP, xc = tid % XP;
-    const bool head_mode = in == 17 && J.act_mode != 0 && J.act_mode != 3;
+    const bool head_mode = in == 17 && J.act_mode == 1;
     float xv = 0.0f;
     float4 tile_piece = make_float4(0.f, 0.f, 0.f, 0.f);  // SAMPLE: this thread's 16 bytes of the row tile its workgroup publishes
     if constexpr (SAMPLE) {
@@ -176,6 +176,7 @@ __device__ __forceinline__ void fwd_l2_body(const FwdArgsC& A, const SAT& SA, co
         else if (in == 17 && xc < 17) {
             if (J.act_mode == 0) xv = src_row(J.src, r0 + xr)[xc];                             // replayed action, row cols 13..16
             else if (J.act_mode == 3) xv = J.noise[(size_t)(r0 + xr) * 4 + (xc - 13)];        // action rows of an earlier kernel (SAC)
+            else if (J.act_mode == 2) xv = J.prev.ws.outv[(size_t)(r0 + xr) * OW + (xc - 13)];  // the previous net's head, evaluated once by a head rider (hx_wgrad.hip)
         }
     }
     // the W2 fragment of the MFMA phase: 64 separate 16-byte requests per load (adjacent lanes are adjacent COLUMNS, 1 KB apart in the
@@ -211,7 +212,7 @@ __device__ __forceinline__ void fwd_l2_body(const FwdArgsC& A, const SAT& SA, co
         const int r = wave;
         RowReg<H2> xh, y;
         float mean, rstd, o[4];
-        if (J.prev.m.out == 4) head_row4<RELU>(J.prev.ws.z2 + (size_t)(r0 + r) * H2, J.prev.net, J.prev.m, slope, xh, y, mean, rstd, o);
+        if (J.prev.m.out == 4) head_row4<RELU, false, true>(J.prev.ws.z2 + (size_t)(r0 + r) * H2, J.prev.net, J.prev.m, slope, xh, y, mean, rstd, o);
         else head_row<4, RELU>(J.prev.ws.z2 + (size_t)(r0 + r) * H2, J.prev.net, J.prev.m, slope, xh, y, mean, rstd, o);
         if (lane < 4) {
             float a = fast_tanh(lane == 0 ? o[0] : lane == 1 ? o[1] : lane == 2 ? o[2] : o[3]);  // Actor.forward's tanh, HIRL.py:140
@@ -409,7 +410,7 @@ __device__ __forceinline__ void fwd_l2_body(const FwdArgsC& A, const SAT& SA, co
                     const int r = wave;
                     RowReg<H2> xh, y;
                     float mean, rstd, o[4];
-                    if (J.m.out == 4) head_row4<RELU, true>(J.ws.z2 + (size_t)(r0 + r) * H2, J.net, J.m, slope, xh, y, mean, rstd, o);
+                    if (J.m.out == 4) head_row4<RELU, true, true>(J.ws.z2 + (size_t)(r0 + r) * H2, J.net, J.m, slope, xh, y, mean, rstd, o);
                     else head_row<4, RELU, true>(J.ws.z2 + (size_t)(r0 + r) * H2, J.net, J.m, slope, xh, y, mean, rstd, o);
                     if (lane < 4) {
                         float a = fast_tanh(lane == 0 ? o[0] : lane == 1 ? o[1] : lane == 2 ? o[2] : o[3]);  // Actor.forward's tanh, HIRL.py:140

@@ -130,7 +130,11 @@ static bool front_has_c(bool asked) {
 // launches C and D: y, loss, dq, LN2 backward, dh1 for both heads; all critic parameter gradients.
 // adam_step > 0: the critic's optimizer step (and, with polyak, the soft_update of its target) rides in the wgrad launch
 // skip_c: launch C ran inside the front launch
-static int critic_back(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy, void* stream, int adam_step, bool polyak, const SampleDev* predraw = nullptr, bool skip_c = false) {
+// heads: an actor call — 1: actor(s)'s head rides in launch D (its z2 rows are in S_API since launch A), 2: bc_actor(s)'s too (S_BCS, launch B); launch G
+// then reads the finished action rows (hx_hirl_actor_backward, fwd_done = 2).  Launch D changes the critic only.  HX_HEAD_RIDER=0: no riders.
+static int heads_of(const HxHyper* Hy, int actor_fwd) { return actor_fwd ? ((actor_fwd == 2 && Hy->use_bc) ? 2 : 1) : 0; }
+static int critic_back(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy, void* stream, int adam_step, bool polyak, int heads, const SampleDev* predraw = nullptr,
+                       bool skip_c = false) {
     hipStream_t st = (hipStream_t)stream;
     const Mlp mQ{17, 1, Hy->no_layernorm ? 1 : 0};
     const int B = Bt->batch;
@@ -161,6 +165,11 @@ static int critic_back(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy, vo
         }
         W.bf16 = N->w2_bf16_all != nullptr;
         W.predraw = predraw; W.predraw_batch = B;
+        if (heads && head_rider_on()) {
+            const Mlp mA{13, 4, Hy->no_layernorm ? 1 : 0};
+            W.head[0] = Head{N->actor, mA, s[S_API]}; W.head_rows[0] = B; W.nhead = 1;
+            if (heads == 2) { W.head[1] = Head{N->bc_actor, mA, s[S_BCS]}; W.head_rows[1] = B; W.nhead = 2; }
+        }
         if (adam_step > 0) {
             W.ad = make_adam(N, Hy, Hy->lr_critic, adam_step, false);
             launch_wg(W, true, st);
@@ -188,7 +197,7 @@ static int critic_grads_impl(const HxNets* N, const HxBatch* Bt, const HxHyper* 
     launch_fwd(F, st);
     make_launch_b(N, Bt, Hy, actor_fwd, F);
     launch_fwd(F, st);
-    return critic_back(N, Bt, Hy, stream, adam_step, polyak);
+    return critic_back(N, Bt, Hy, stream, adam_step, polyak, heads_of(Hy, actor_fwd));
 }
 int hx_hirl_critic_grads(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy, int32_t actor_fwd, void* stream) {
     return critic_grads_impl(N, Bt, Hy, actor_fwd, stream, 0, false);
@@ -211,6 +220,8 @@ int hx_hirl_actor_backward(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy
     const RowSrc src{Bt->rows, nullptr, nullptr, 0, 32};
     const RowSrc bcsrc{Bt->bc_rows ? Bt->bc_rows : Bt->rows, nullptr, nullptr, 0, 32};
     const bool bc = Hy->use_bc != 0, soft = bc && estimate_soft;
+    // fwd_done = 2: the forwards AND the heads of actor(s) [and bc_actor(s)] are done (head riders of launch D): launch G reads the action rows
+    const int act_g = (fwd_done == 2 && head_rider_on()) ? 2 : 1;
     if (!fwd_done) {   // launch F: actor(s), actor(s_bc), bc_actor(s)  (hx_hirl_critic_grads(actor_fwd) can carry them instead)
         FwdArgs F{};
         F.slope = Hy->slope;
@@ -227,8 +238,8 @@ int hx_hirl_actor_backward(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy
         FwdArgs F{};
         F.slope = Hy->slope;
         int n = 0;
-        F.job[n++] = FwdJob{N->critic, mQ, src, 0, 1, Head{N->actor, mA, s[S_API]}, nullptr, 0.f, s[S_CPI], B, 1, IM_C1};
-        if (soft) F.job[n++] = FwdJob{N->critic, mQ, src, 0, 1, Head{N->bc_actor, mA, s[S_BCS]}, nullptr, 0.f, s[S_CSOFT], B, 0, IM_C1};
+        F.job[n++] = FwdJob{N->critic, mQ, src, 0, act_g, Head{N->actor, mA, s[S_API]}, nullptr, 0.f, s[S_CPI], B, 1, IM_C1};
+        if (soft) F.job[n++] = FwdJob{N->critic, mQ, src, 0, act_g, Head{N->bc_actor, mA, s[S_BCS]}, nullptr, 0.f, s[S_CSOFT], B, 0, IM_C1};
         F.njobs = n;
         F.images = N->w2_bf16_all;
         launch_fwd(F, st);
@@ -359,7 +370,7 @@ int hx_hirl_learn_sampled(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy,
     HX_REQUIRE(critic_step >= 1 && (!actor_phase || actor_step >= 1), "hx_hirl_learn: Adam steps are 1-based");
     int rc = critic_grads_impl(N, Bt, Hy, actor_phase ? (w_kind == 1 ? 2 : 1) : 0, stream, critic_step, do_polyak != 0, S);
     if (rc || !actor_phase) return rc;
-    if ((rc = hx_hirl_actor_backward(N, Bt, Hy, w_kind == 1, 1, stream))) return rc;
+    if ((rc = hx_hirl_actor_backward(N, Bt, Hy, w_kind == 1, 2, stream))) return rc;
     return actor_wgrad_impl(N, Hy, Bt->batch, Bt->batch, w_kind, w_given, warm, stream, actor_step, do_polyak != 0);
 }
 
@@ -408,9 +419,11 @@ static int make_predraw(const HxNets* N, const HxBatch* Bt, const HxSample* next
 int hx_hirl_critic_grads_back(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy, const HxSample* next, const HxBatch* next_tiles, int32_t c_in_front,
                               void* stream) {
     HX_REQUIRE(N && Bt && Hy && Bt->batch > 0 && Bt->batch % 16 == 0, "hx_hirl_critic_grads_back: batch must be a positive multiple of 16");
+    HX_REQUIRE(c_in_front >= 0 && c_in_front < 6 && (c_in_front < 4 || (Hy->use_bc && N->bc_actor)),
+               "hx_hirl_critic_grads_back: c_in_front is 0 / 1 (+ 2: actor(s)'s head rides, + 4: bc_actor(s)'s too — a BC agent's soft-estimate call)");
     SampleDev SD{};
     if (next) if (int rc = make_predraw(N, Bt, next, next_tiles, stream, &SD)) return rc;
-    return critic_back(N, Bt, Hy, stream, 0, false, next ? &SD : nullptr, front_has_c(c_in_front != 0));
+    return critic_back(N, Bt, Hy, stream, 0, false, (c_in_front >> 1) & 3, next ? &SD : nullptr, front_has_c((c_in_front & 1) != 0));
 }
 int hx_hirl_learn_back(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy, int32_t critic_step, int32_t actor_phase, int32_t actor_step, int32_t do_polyak,
                        int32_t w_kind, float w_given, float warm, const HxSample* next, const HxBatch* next_tiles, int32_t c_in_front, void* stream) {
@@ -418,9 +431,10 @@ int hx_hirl_learn_back(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy, in
     HX_REQUIRE(critic_step >= 1 && (!actor_phase || actor_step >= 1), "hx_hirl_learn_back: Adam steps are 1-based");
     SampleDev SD{};
     if (next) if (int rc = make_predraw(N, Bt, next, next_tiles, stream, &SD)) return rc;
-    int rc = critic_back(N, Bt, Hy, stream, critic_step, do_polyak != 0, next ? &SD : nullptr, front_has_c(c_in_front != 0));
+    int rc = critic_back(N, Bt, Hy, stream, critic_step, do_polyak != 0, heads_of(Hy, actor_phase ? (w_kind == 1 ? 2 : 1) : 0), next ? &SD : nullptr,
+                         front_has_c(c_in_front != 0));
     if (rc || !actor_phase) return rc;
-    if ((rc = hx_hirl_actor_backward(N, Bt, Hy, w_kind == 1, 1, stream))) return rc;
+    if ((rc = hx_hirl_actor_backward(N, Bt, Hy, w_kind == 1, 2, stream))) return rc;
     return actor_wgrad_impl(N, Hy, Bt->batch, Bt->batch, w_kind, w_given, warm, stream, actor_step, do_polyak != 0);
 }
 

@@ -23,7 +23,8 @@
 // Structure (DESIGN.md "update kernels"): B = 128 is 0.49 GFLOP per learn(), so the ~1,770 eager ops of the reference collapse into
 // 4 launches (critic-only call) or 8 (call with the delayed actor step), minibatch draw and optimizer steps included.  Every launch is
 //   fwd_l2   z2 = act(LN(x W1^T + b1)) W2^T + b2 for up to 4 independent nets; layer 1 (K = 13 / 17) on MFMA from LDS-staged operands, the
-//            previous net's LN2/final/tanh "head" recomputed per workgroup when the input action is another net's output, the
+//            previous net's LN2/final/tanh "head" recomputed per workgroup when the input action is another net's output (act_mode 1; act_mode 2
+//            reads the action rows a head rider of an earlier wgrad launch left: the actor call's launch G), the
 //            256 -> 512 GEMM tiled 16 rows x 32 / 64 columns per workgroup on fp32 MFMA (v_mfma_f32_16x16x4_f32: fp32 products and
 //            sums, parity at 1e-5); the first forward launch can also draw and gather the minibatch (SAMPLE);
 //   bwd_l2   head + loss gradient + LN2 backward in the prologue (8 rows per workgroup, a wave pair per row), dh1 = dz2 W2 on MFMA;
@@ -224,11 +225,43 @@ __device__ __forceinline__ void head_row(const float* __restrict__ z2row, const 
     }
 }
 
+// One lane's eight terms of a head_row4 dot product, every rounding spelled out.  Under fp contract(fast) the compiler decides term by term whether
+// a product is fused into the running sum, and it decides by what surrounds the inlined function: in the forward kernels the first two terms were fused
+// and the other six multiplied (in pairs, v_pk_mul_f32) and then added; inlined into the weight-gradient kernel's head rider one of the four chains fused
+// four — last bits of the action rows differed between two kernels that call the same function.  This is the forward kernels' form, fixed.
+#pragma clang fp contract(off)
+__device__ __forceinline__ float head_dot8(const float (&h)[8], const float (&w)[8]) {
+    float a = __builtin_fmaf(h[0], w[0], 0.0f);
+    a = __builtin_fmaf(h[1], w[1], a);
+#pragma unroll
+    for (int i = 2; i < 8; ++i) {
+        const float p = h[i] * w[i];
+        a = a + p;
+    }
+    return a;
+}
+// ... and the eight squares of a lane's LayerNorm variance: there the forward kernels fuse the FIRST square into the rounded SECOND one
+// (v_mul_f32 d1 d1, v_fmac_f32 d0 d0), then add the other six
+__device__ __forceinline__ float head_var8(const float (&d)[8]) {
+    const float p1 = d[1] * d[1];
+    float q = __builtin_fmaf(d[0], d[0], p1);
+#pragma unroll
+    for (int i = 2; i < 8; ++i) {
+        const float p = d[i] * d[i];
+        q = q + p;
+    }
+    return q;
+}
+#pragma clang fp contract(fast)
+
 // The same head with EVERY operand requested before the first one is used (four outputs: the deterministic actor).  head_row asks for W3's
 // rows one at a time under `if (j < m.out)`: dependent round trips to L2 on the critical path of a forward workgroup whose input action
 // is another net's output (-0.2 us per step; staging the 12 KB through LDS as bwd_l2 does costs a barrier more than it saves: +0.35 us).
 // Same arithmetic in the same order: same bits.
-template <bool RELU, bool AGENT = false>
+// PIN: the roundings of everything between z2 and o[] are those of head_dot8 / head_var8 and explicit multiply-adds —
+// for the callers whose results meet across kernels: the forward workgroups' prologue (hx_fwd_body.h), the front launch's once-per-tile head, and the
+// head riders of the weight-gradient launch (hx_wgrad.hip), which must leave the action rows the forward prologue would have computed, bit for bit.
+template <bool RELU, bool AGENT = false, bool PIN = false>
 __device__ __forceinline__ void head_row4(const float* __restrict__ z2row, const float* __restrict__ net, const Mlp m, float slope,
                                           RowReg<H2>& xhat, RowReg<H2>& y, float& mean, float& rstd, float (&o)[4]) {
     RowReg<H2> z, g, be, w0, w1, w2, w3;
@@ -242,22 +275,40 @@ __device__ __forceinline__ void head_row4(const float* __restrict__ z2row, const
     w3.load(net + m.W3() + 3 * H2);
     const int lane = threadIdx.x & 63;
     const float b3 = net[m.b3() + (lane & 3)];
-    row_stats<8>(z.v, H2, mean, rstd);
-    if (m.no_ln) { mean = 0.0f; rstd = 1.0f; }
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    if constexpr (PIN) {
+        float s = 0.0f, d[8], h[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        xhat.v[i] = (z.v[i] - mean) * rstd;
-        y.v[i] = g.v[i] * xhat.v[i] + be.v[i];
+        for (int i = 0; i < 8; ++i) s += z.v[i];
+        mean = wave_sum(s) / (float)H2;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d[i] = z.v[i] - mean;
+        rstd = __builtin_amdgcn_rsqf(wave_sum(head_var8(d)) / (float)H2 + LN_EPS);  // (row_stats<8>; a division by 512 is exact, fused or not)
+        if (m.no_ln) { mean = 0.0f; rstd = 1.0f; }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            xhat.v[i] = (z.v[i] - mean) * rstd;
+            y.v[i] = __builtin_fmaf(g.v[i], xhat.v[i], be.v[i]);
+            h[i] = act_f<RELU>(y.v[i], slope);
+        }
+        a0 = head_dot8(h, w0.v); a1 = head_dot8(h, w1.v); a2 = head_dot8(h, w2.v); a3 = head_dot8(h, w3.v);
+    } else {
+        row_stats<8>(z.v, H2, mean, rstd);
+        if (m.no_ln) { mean = 0.0f; rstd = 1.0f; }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            xhat.v[i] = (z.v[i] - mean) * rstd;
+            y.v[i] = g.v[i] * xhat.v[i] + be.v[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) a0 += act_f<RELU>(y.v[i], slope) * w0.v[i];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) a1 += act_f<RELU>(y.v[i], slope) * w1.v[i];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) a2 += act_f<RELU>(y.v[i], slope) * w2.v[i];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) a3 += act_f<RELU>(y.v[i], slope) * w3.v[i];
     }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) a0 += act_f<RELU>(y.v[i], slope) * w0.v[i];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) a1 += act_f<RELU>(y.v[i], slope) * w1.v[i];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) a2 += act_f<RELU>(y.v[i], slope) * w2.v[i];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) a3 += act_f<RELU>(y.v[i], slope) * w3.v[i];
     o[0] = wave_sum(a0) + __shfl(b3, 0);
     o[1] = wave_sum(a1) + __shfl(b3, 1);
     o[2] = wave_sum(a2) + __shfl(b3, 2);
@@ -423,6 +474,7 @@ struct FwdJob {
     RowSrc src;
     int col0;      // state columns [col0, col0+13) of the source row (0 = s, 17 = s')
     int act_mode;  // in == 17 only: 0 = action from source row cols 13..16, 1 = tanh(head(prev)) (+ clamped noise, clamp +-1),
+                   // 2 = the finished action rows prev.ws.outv [rows][OW] (a head rider of an earlier launch wrote them: WgArgs::head),
                    // 3 = action rows [rows][4] given through `noise`
     Head prev;
     const float* noise;  // [4] one draw shared by the whole batch (HIRL.py:265) or nullptr
@@ -678,7 +730,15 @@ struct WgArgs {
     float* count_out;  // nullptr, or where thread 0 of the launch leaves (float)*soft_count: the merged actor message's count word
     const SampleDev* predraw;  // hx_hirl_learn_back: one more workgroup draws and gathers the NEXT front launch's minibatch (predraw_wg), or null
     int predraw_batch;
+    // head riders (wgrad_kernel only): up to two nets this launch does NOT change whose z2 rows an earlier launch left in a slot — one more
+    // workgroup per 16-row tile evaluates the net's head (LayerNorm 2, final layer, tanh) ONCE and leaves outv[row][0..3] and st2[row] in that slot
+    // for a later forward job with act_mode 2 (the actor call's launch G, which otherwise repeats it in each of its column workgroups)
+    Head head[2];
+    int head_rows[2];
+    int nhead;
 };
+// HX_HEAD_RIDER (read once per process): 1 = the actor call's heads ride in the critics' weight-gradient launch, 0 = launch G evaluates them itself
+bool head_rider_on();  // hx_wgrad.hip
 
 // torch.optim.Adam (defaults) on one element, and soft_update.  Contraction is OFF in these two: HIP's __fmul_rn / __fsub_rn are plain
 // operators, which the compiler may or may not fuse depending on the surrounding kernel — and the fused wgrad + Adam launch must

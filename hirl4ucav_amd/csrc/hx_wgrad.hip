@@ -3,6 +3,8 @@
 //            the target and refresh the W2 images                                   (loss.backward() + optimizer.step(), HIRL.py:284-288,322-330)
 //   wgrad2   the same for ONE job with TWO slots of at most 256 rows together (the actor step, SAC's imitative policy step; fp32): each slot on
 //            its own threads, 224 workgroups instead of 112, bit-identical (launch_wg chooses; HX_WGRAD_TWO_SLOT=0 keeps wgrad)
+//   head riders  (wgrad only) workgroups beyond the jobs' own evaluate the head of up to two nets the launch does not change, once per row: the actor
+//            call's actor(s) [and bc_actor(s)] in the critics' launch, for launch G to read instead of repeating it per column workgroup (HX_HEAD_RIDER=0: off)
 //   adam     torch.optim.Adam defaults over a flat buffer (sharded path, SAC, BC)   (HIRL.py:50,123; SAC/agent.py:310-325)
 //   polyak   soft_update                                                             (HIRL.py:11-13)
 #include <cmath>
@@ -30,8 +32,15 @@ struct WgJobC {
     float* count_out;                    // job 0 only: (float)*soft_count goes here (the merged actor message of a sharded run)
 };
 static_assert(sizeof(WgJobC) == 176, "WgJobC layout");
+// a head rider's job: the net, the slot that holds its z2 rows, and how many
+struct HeadJobC {
+    const float* net; float* ws;
+    int32_t rows;     // 0: no such job
+    uint32_t cfg;     // m:10
+};
 struct WgArgsC {
     WgJobC job[2];
+    HeadJobC head[2];
     // hx_hirl_learn_back: workgroup (kWgPerJob, 0) — one beyond the jobs' own, on a CU this launch leaves idle — assembles the next front launch's minibatch
     int has_pre, pre_batch;
     SampleDev pre;
@@ -260,6 +269,46 @@ __device__ __forceinline__ void l1_row(L1Acc& a, const float* rrow, const float*
     a.dw1[16] += dz * xrow[16];
 }
 
+// The workgroups of wgrad_kernel's columns beyond the jobs' own (blockIdx.x >= kWgPerJob) are numbered so that slot s sits on XCD s % 8: column
+// group c / 8 first, then the job row, then c % 8.  Slot 0 is the predraw's when there is one; the head riders' tiles follow from slot 8 then (a row
+// tile t on XCD t % 8, where launch G's workgroups of that tile run), else from slot 0.
+__device__ __forceinline__ int extra_slot() {
+    const int c = (int)blockIdx.x - kWgPerJob;
+    return ((c >> 3) * (int)gridDim.y + (int)blockIdx.y) * 8 + (c & 7);
+}
+inline int extra_columns(int slots, int njobs) { return 8 * ((slots + 8 * njobs - 1) / (8 * njobs)); }
+// Head rider: row tile t of the launch's head jobs (job 0's tiles, then job 1's) — one wave per row evaluates the net's head exactly as a forward
+// workgroup with act_mode 1 does in its prologue (hx_fwd_body.h: the same head_row4 / head_row, the same fast_tanh, no smoothing noise) and writes what
+// that job's first column workgroups write: outv[row][0..3] and st2[row].  No LDS, no barrier; a slot beyond the tiles exits.
+template <bool RELU>
+__device__ __forceinline__ void head_rider_wg(const WgArgsC& AC, int t) {
+    if (t < 0) return;
+    const float slope = AC.job[0].slope;
+    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const HeadJobC& hj = AC.head[h];
+        const int tiles = (hj.rows + RT - 1) / RT;
+        if (t < tiles) {
+            const int r = t * RT + wave;
+            if (r >= hj.rows) return;
+            const Mlp m = mlp_of(hj.cfg & 1023u);
+            const Slot S = carve_slot(hj.ws, hj.rows);
+            RowReg<H2> xh, y;
+            float mean, rstd, o[4];
+            if (m.out == 4) head_row4<RELU, false, true>(S.z2 + (size_t)r * H2, hj.net, m, slope, xh, y, mean, rstd, o);
+            else head_row<4, RELU>(S.z2 + (size_t)r * H2, hj.net, m, slope, xh, y, mean, rstd, o);
+            if (lane < 4) S.outv[(size_t)r * OW + lane] = fast_tanh(lane == 0 ? o[0] : lane == 1 ? o[1] : lane == 2 ? o[2] : o[3]);  // Actor.forward's tanh, HIRL.py:140
+            if (lane == 0) {
+                S.st2[(size_t)r * 2] = mean;
+                S.st2[(size_t)r * 2 + 1] = rstd;
+            }
+            return;
+        }
+        t -= tiles;
+    }
+}
+
 // BF16 (the bf16 update path): dW2 = dz2^T h1 on v_mfma_f32_16x16x32_bf16 — both operands rounded to bf16 as they are loaded (32 batch rows
 // per MFMA instead of 4), fp32 accumulation per slot, the slot's BC weight applied to the fp32 sum; every other gradient (biases, LayerNorm,
 // layer 1, the head) is fp32 arithmetic on fp32 values.  With ADAM the step also refreshes the bf16 images of W2 (forward, transposed,
@@ -280,8 +329,10 @@ __global__ __launch_bounds__(kWide) void wgrad_kernel(WgArgsC AC) {
 
     {
         static_assert(sizeof(lds) >= (4 * kFusedSlots + 2 * kFusedBatchMax) * 4, "predraw_wg's tables fit");
-        if (AC.has_pre && blockIdx.x >= kWgPerJob) {  // (eight columns beyond the jobs' own: the XCD of every other workgroup stays what it was)
-            if (blockIdx.x == kWgPerJob && blockIdx.y == 0) predraw_wg(AC.pre, AC.pre_batch, lds);
+        if (blockIdx.x >= kWgPerJob) {  // (columns beyond the jobs' own, eight at a time: the XCD of every other workgroup stays what it was)
+            const int s = extra_slot();
+            if (AC.has_pre && s == 0) predraw_wg(AC.pre, AC.pre_batch, lds);
+            else head_rider_wg<RELU>(AC, s - (AC.has_pre ? 8 : 0));
             return;
         }
     }
@@ -922,13 +973,26 @@ __global__ __launch_bounds__(kThreads) void polyak_kernel(float* target, const f
 
 namespace hxu {
 
+// HX_HEAD_RIDER=0 (read once): launch G evaluates the heads it feeds on itself, in every column workgroup — for A/B timing and the bit-for-bit test
+bool head_rider_on() {
+    static const bool on = !(getenv("HX_HEAD_RIDER") && atoi(getenv("HX_HEAD_RIDER")) == 0);
+    return on;
+}
+
 void launch_wg(const WgArgs& W, bool adam, hipStream_t st) {
     WgArgsC C{};
     for (int j = 0; j < W.njobs; ++j) C.job[j] = pack_wg(W.job[j], W);
     const bool pre = W.predraw != nullptr;
     C.has_pre = pre ? 1 : 0;
     if (pre) { C.pre = *W.predraw; C.pre_batch = W.predraw_batch; }
-    const dim3 grid(kWgPerJob + (pre ? 8 : 0), W.njobs);
+    // head riders: the tiles take the slots the predraw's eight columns leave free, and as many more columns (eight at a time) as they need
+    int head_tiles = 0;
+    for (int h = 0; h < W.nhead && h < 2; ++h) {
+        C.head[h] = HeadJobC{W.head[h].net, W.head[h].ws.x, W.head_rows[h], mlp_bits(W.head[h].m)};
+        head_tiles += (W.head_rows[h] + RT - 1) / RT;
+    }
+    const int extra = (pre || head_tiles) ? extra_columns((pre ? 8 : 0) + head_tiles, W.njobs) : 0;
+    const dim3 grid(kWgPerJob + extra, W.njobs);
     const bool relu = W.slope == 0.0f;
 #define HX_WG(ADAM_, RELU_, BF16_) hipLaunchKernelGGL((wgrad_kernel<ADAM_, RELU_, BF16_>), grid, dim3(kWide), 0, st, C)
     static const int dbg_off = getenv("HX_DBG_BF16_OFF") ? atoi(getenv("HX_DBG_BF16_OFF")) : 0;
@@ -938,7 +1002,7 @@ void launch_wg(const WgArgs& W, bool adam, hipStream_t st) {
     if (W.bf16 && !(dbg_off & 4)) {
         if (adam) { if (relu) HX_WG(true, true, true); else HX_WG(true, false, true); }
         else { if (relu) HX_WG(false, true, true); else HX_WG(false, false, true); }
-    } else if (two_on && W.njobs == 1 && J0.nslots == 2 && J0.rows[0] > 0 && J0.rows[1] > 0 && J0.rows[0] + J0.rows[1] <= kWgRowChunk) {
+    } else if (two_on && head_tiles == 0 && W.njobs == 1 && J0.nslots == 2 && J0.rows[0] > 0 && J0.rows[1] > 0 && J0.rows[0] + J0.rows[1] <= kWgRowChunk) {
         // one job, two slots whose rows fit the LDS tiles together: each slot on its own threads, 224 workgroups (wgrad2_kernel)
         const dim3 grid2(kWg2PerJob + (pre ? 8 : 0), 1);
 #define HX_WG2(ADAM_, RELU_) hipLaunchKernelGGL((wgrad2_kernel<ADAM_, RELU_>), grid2, dim3(kWide), 0, st, C)

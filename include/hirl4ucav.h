@@ -289,7 +289,12 @@ typedef struct HxHyper {
  *   hx_adam(which = 1)      actor.optimizer.step(); actor_loss, bc_weight   HIRL.py:325,334
  *   hx_polyak               every 3rd actor step (HIRL.py:327-330) */
 /* actor_fwd: 0 = critic phase only; 1 = also run the delayed actor step's critic-independent forward passes actor(s),
- * actor(s_bc) in the same first launch; 2 = plus bc_actor(s) for the soft estimate (then pass fwd_done = 1 below). */
+ * actor(s_bc) in the same first launch; 2 = plus bc_actor(s) for the soft estimate (then pass fwd_done = 1 or 2 below).
+ * With actor_fwd != 0 the call's last launch (the critics' parameter gradients) also evaluates the HEAD of actor(s) [and of bc_actor(s)] once
+ * per row — LayerNorm 2, final layer, tanh — on workgroups of its own, and leaves the action rows in the workspace (HX_HEAD_RIDER=0: not).
+ * hx_hirl_actor_backward's fwd_done: 0 = it runs the actor call's forward passes itself; 1 = they are done, its Q1(s, pi(s)) launch evaluates
+ * the heads it feeds on in each of its workgroups; 2 = forwards and heads are done (this call's actor_fwd != 0, or hx_hirl_critic_grads_back's
+ * c_in_front + 2 / + 4), the launch reads the action rows — same bits either way. */
 int hx_hirl_critic_grads(const HxNets* nets, const HxBatch* batch, const HxHyper* hyper, int32_t actor_fwd, void* stream);
 int hx_hirl_actor_backward(const HxNets* nets, const HxBatch* batch, const HxHyper* hyper, int32_t estimate_soft,
                            int32_t fwd_done, void* stream);
@@ -415,7 +420,9 @@ int hx_hirl_front(float* state, int64_t n, int64_t stride, float* obs_io, float*
 int hx_hirl_learn_back(const HxNets* nets, const HxBatch* batch, const HxHyper* hyper, int32_t critic_step, int32_t actor_phase, int32_t actor_step,
                        int32_t do_polyak, int32_t w_kind, float w_given, float warm, const HxSample* next, const HxBatch* next_tiles, int32_t c_in_front,
                        void* stream);
-/* A sharded rank's form: what hx_hirl_critic_grads leaves behind (grad_critic, ready for the exchange; no optimizer step) after a front launch, + the predraw. */
+/* A sharded rank's form: what hx_hirl_critic_grads leaves behind (grad_critic, ready for the exchange; no optimizer step) after a front launch, + the predraw.
+ * c_in_front: 0 / 1 as above, + 2 on an actor call (the head of actor(s) rides in the gradient launch, as with hx_hirl_critic_grads' actor_fwd = 1),
+ * + 4 instead on a soft-estimate call of a BC agent (bc_actor(s)'s head too, actor_fwd = 2); then hx_hirl_actor_backward takes fwd_done = 2. */
 int hx_hirl_critic_grads_back(const HxNets* nets, const HxBatch* batch, const HxHyper* hyper, const HxSample* next, const HxBatch* next_tiles, int32_t c_in_front,
                               void* stream);
 
