@@ -44,6 +44,14 @@ class HxTrace(ctypes.Structure):
 TRACE_FIELDS, TRACE_SUMMARIES = 8, 6  # HX_TRACE_FIELDS, HX_TRACE_SUMMARIES
 
 
+class HxEpStat(ctypes.Structure):
+    """the episode statistics' buffers (include/hirl4ucav.h HxEpStat; utils/epstat.py carves them out of one workspace)"""
+    _fields_ = [("part", _vp), ("acc", _vp), ("len", _vp), ("last_ctr", _vp), ("n_envs", _i64)]
+
+
+EPSTAT_BINS, EPSTAT_SUMS, EPSTAT_SLOT_WORDS = 4, 8, 36  # HX_EPSTAT_BINS, HX_EPSTAT_SUMS, HX_EPSTAT_SLOT_WORDS
+
+
 class HxError(RuntimeError):
     pass
 
@@ -55,12 +63,15 @@ _SIGNATURES = {
     "hx_label_transitions": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
     "hx_trace_reset": [ctypes.POINTER(HxTrace), _vp],
     "hx_trace_push": [ctypes.POINTER(HxTrace), _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp],
+    "hx_epstat_reset": [ctypes.POINTER(HxEpStat), _vp, _vp],
+    "hx_epstat_clear": [ctypes.POINTER(HxEpStat), _vp],
+    "hx_epstat_push": [ctypes.POINTER(HxEpStat), _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
     "hx_event_destroy": [_vp],
     "hx_event_elapsed_us": [_vp, _vp, ctypes.POINTER(ctypes.c_float)],
 }
 
 _lib = None
-ABI_VERSION = 122  # HX_ABI_VERSION of include/hirl4ucav.h
+ABI_VERSION = 123  # HX_ABI_VERSION of include/hirl4ucav.h
 _ABI_STRUCTS = {}  # name -> (index in hx_abi_sizes, ctypes class): filled by the binding modules (check_struct)
 
 
@@ -99,6 +110,10 @@ def load():
     L.hx_event_create.argtypes = []
     L.hx_trace_workspace_words.restype = ctypes.c_int64
     L.hx_trace_workspace_words.argtypes = [_i64, _i32]
+    L.hx_epstat_workspace_words.restype = ctypes.c_int64
+    L.hx_epstat_workspace_words.argtypes = [_i64]
+    if L.hx_epstat_sizeof() != ctypes.sizeof(HxEpStat):
+        raise HxError(f"ABI mismatch: HxEpStat is {ctypes.sizeof(HxEpStat)} bytes here, {L.hx_epstat_sizeof()} in {SO_PATH}")
     for name, args in _SIGNATURES.items():
         fn = getattr(L, name)
         fn.argtypes = args

@@ -30,9 +30,54 @@ from .utils.scalars import make_writer
 from .utils.seed import set_seed
 
 MAX_STEP = {"straight_line": 1500, "serpentine": 1500, "circular": 1900}  # train_all.py:159-183
+MIXED = "mixed"  # --env mixed: one population over all of SCENARIOS (BASELINE.json configs[4]); an extension, the reference trains one scenario per run
+MIXED_MAX_STEP = max(MAX_STEP.values())  # HxStepOpts.max_step is one word: a mixed population trains under the longest of its scenarios' limits
 
 
 # ---- pure host logic (unit-tested on CPU) ----------------------------------------------------------------------------
+def mixed_scenarios(n, env_id0=0):
+    """per-env scenario ids of a mixed shard of n envs whose first env has the global id env_id0: contiguous thirds, so that wavefronts never
+    mix scenarios (the rule of bench.py --scenario mixed)"""
+    return np.sort((env_id0 + np.arange(n)) % 3)
+
+
+def scenarios_of(env_type):
+    """the scenario names a --env value covers, in bin order"""
+    return list(SCENARIOS) if env_type == MIXED else [env_type]
+
+
+def default_max_step(env_type):
+    return MIXED_MAX_STEP if env_type == MIXED else MAX_STEP[env_type]
+
+
+def expert_paths(arg):
+    """--expert_csv: one path, or a comma-separated list of them (one file per scenario, say) -> the list; empty items are an error"""
+    if not arg:
+        return []
+    paths = [p.strip() for p in arg.split(",")]
+    if any(not p for p in paths):
+        raise ValueError(f"--expert_csv {arg!r}: an empty item in the list")
+    return paths
+
+
+def pool_validation(results, episodes=50):
+    """The reference's four validation numbers over several validate() calls of `episodes` episodes each, from their (mean, std, successes, fire
+    successes) tuples alone -> the same tuple for the pooled episodes: the mean of means, the population std of the pooled scores
+    (sqrt(mean(std_k^2 + mean_k^2) - mean^2), equal groups), the summed counts (the caller divides by len(results) * episodes)."""
+    means = np.asarray([r[0] for r in results], np.float64)
+    stds = np.asarray([r[1] for r in results], np.float64)
+    mean = float(means.mean())
+    var = float((stds * stds + means * means).mean() - mean * mean)
+    return mean, math.sqrt(max(var, 0.0)), int(sum(r[2] for r in results)), int(sum(r[3] for r in results))
+
+
+def mixed_refusal(config):
+    """why `--env mixed` cannot run as asked, or None"""
+    if config.env == MIXED and config.num_envs < len(SCENARIOS):
+        return f"--env mixed with --num_envs {config.num_envs}: a mixed population holds every scenario, so at least {len(SCENARIOS)} envs"
+    return None
+
+
 def bc_weight_schedule(hirl_type, episode, bc_weight, bc_warm_up=False):
     """(bc_weight_now, bc_warm_up_weight) at the start of `episode` — train_all.py:328-339."""
     warm = 0.0
@@ -155,6 +200,74 @@ def validate_plotting(plot, engine, scenario, episodes, max_step, if_random, see
     return validate(engine, scenario, episodes, max_step, if_random, seed, device, sac, env=env, recorder=rec), rec
 
 
+def validate_mixed(plot, engine, episodes, if_random, seed, device, sac=False):
+    """--env mixed: the existing validate() once per scenario — `episodes` episodes each, that scenario's OWN step limit (MAX_STEP), the same seed — so
+    every tuple is what a single-scenario run would get from the same networks -> ({scenario: validate()'s tuple}, {scenario: recorder or None})."""
+    results, recorders = {}, {}
+    for name in SCENARIOS:
+        results[name], recorders[name] = validate_plotting(plot, engine, name, episodes, MAX_STEP[name], if_random, seed, device, sac)
+    return results, recorders
+
+
+def validate_env(config, engine, env_type, max_step, seed, device, sac=False, episodes=50):
+    """The periodic validation of a training run -> (the tuple the checkpoint rule reads, {scenario: tuple}, {scenario: recorder or None}).
+    One scenario: validate_plotting as ever.  mixed: validate_mixed, pooled over the three scenarios' episodes (pool_validation)."""
+    if env_type != MIXED:
+        res, rec = validate_plotting(config.plot, engine, env_type, episodes, max_step, config.random, seed, device, sac)
+        return res, {env_type: res}, {env_type: rec}
+    results, recorders = validate_mixed(config.plot, engine, episodes, config.random, seed, device, sac)
+    return pool_validation([results[k] for k in SCENARIOS], episodes), results, recorders
+
+
+def write_validation_plots(recorders, plot_dir, arttir):
+    """--plot: the last validation episode's files beside a checkpoint; under mixed one set per scenario with the tag <arttir>_<scenario>"""
+    for name, rec in recorders.items():
+        if rec is not None:
+            rec.write_reference_files(plot_dir, arttir if len(recorders) == 1 else f"{arttir}_{name}")
+
+
+def log_validation_by_scenario(writer, episode, results, episodes=50):
+    """mixed: Validation/<scenario>/{Avg Reward, Std Reward, Success Rate, Fire Success Rate} beside the four pooled reference tags"""
+    if writer is None or len(results) == 1:
+        return
+    for name, (mean, std, succ, fire) in results.items():
+        for tag, v in (("Avg Reward", mean), ("Std Reward", std), ("Success Rate", succ / episodes), ("Fire Success Rate", fire / episodes)):
+            writer.add_scalar(f"Validation/{name}/{tag}", v, episode)
+
+
+def log_episode_stats(writer, episode, stats, last100):
+    """The per-scenario Training/* scalars of one driver episode from EpisodeStats.read_and_clear(), for every scenario in which an episode ended,
+    and Training/Last 100 Episode Average Reward (train_all.py:384) from the (sum, count) window, to which this episode is added first."""
+    last100.add(sum(s["sum_ret"] for s in stats.values()), sum(s["count"] for s in stats.values()))
+    if writer is None:
+        return
+    for name, s in stats.items():
+        if not s["count"]:
+            continue
+        writer.add_scalar(f"Training/{name}/Episode Reward", s["mean"], episode)
+        writer.add_scalar(f"Training/{name}/Episode Reward Std", s["std"], episode)
+        writer.add_scalar(f"Training/{name}/Episode Length", s["mean_len"], episode)
+        writer.add_scalar(f"Training/{name}/Average Step Reward", s["sum_ret"] / max(s["sum_len"], 1.0), episode)
+        writer.add_scalar(f"Training/{name}/Ended By Done", s["done"], episode)
+        writer.add_scalar(f"Training/{name}/Ended By Time Limit", s["time_limit"], episode)
+    if not math.isnan(last100.mean()):
+        writer.add_scalar("Training/Last 100 Episode Average Reward", last100.mean(), episode)
+
+
+def load_expert_files(config):
+    """load_expert per file of --expert_csv's list -> [(states, actions), ...]: each file is read, and later labelled, on its own, so that no
+    transition spans two files.  One path (or none: --synthetic_expert) gives the one table load_expert gives."""
+    paths = expert_paths(config.expert_csv)
+    if len(paths) <= 1:
+        return [load_expert(config)]
+    out = []
+    for p in paths:
+        if not os.path.exists(p):
+            raise FileNotFoundError(f"--expert_csv {p}: no such file")
+        out.append(read_data(p))
+    return out
+
+
 def load_expert(config, rng_seed=0):
     """read_data(data_dir) (train_all.py:222-228).  The reference raises when the file is missing, and so does this: a mistyped path must
     not turn into a run that trains on noise.  `--synthetic_expert` (benchmarks, tests; the Drive data is not available, README.md:6,30)
@@ -208,7 +321,8 @@ def train_bc(config, device, seed, max_step):
     env_type, batch = config.env, 128
     eng = E.HirlEngine(batch=batch, lr_actor=1e-3, slope=0.01, use_bc=True, device=device)  # BC.py:129-135 leaky_relu
     eng.load_params(init_actor_state_dict(), init_critic_state_dict())
-    es, ea = load_expert(config)
+    tables = load_expert_files(config)
+    es, ea = np.concatenate([t[0] for t in tables]), np.concatenate([t[1] for t in tables])
     tab = np.zeros((es.shape[0], 32), np.float32)
     tab[:, 0:13], tab[:, 13:17] = es, ea
     bc_table = torch.from_numpy(tab).to(device)
@@ -232,15 +346,16 @@ def train_bc(config, device, seed, max_step):
         writer.add_scalar("Loss/BC_Loss", bc_loss, (episode + 1) * max_step)  # train_all.py:250-251
         print(f"Episode {episode + 1}: bc_loss {bc_loss:.6f}", flush=True)
         if (episode + 1) % config.checkpoint_rate == 0 and (episode + 1) >= config.bc_validate_from:  # train_all.py:259
-            (mean, std, succ, fire), rec = validate_plotting(config.plot, eng, env_type, 50, max_step, config.random, seed + 12345, device)
-            if mean > high_score or succ / 50 >= success_rate or arttir % 5 == 0:
+            (mean, std, succ, fire), by_scenario, recs = validate_env(config, eng, env_type, max_step, seed + 12345, device)
+            val_n = 50 * len(by_scenario)  # (mixed: the pooled episodes of the three scenarios)
+            if mean > high_score or succ / val_n >= success_rate or arttir % 5 == 0:
                 torch.save({k: v.cpu().clone() for k, v in E.unpack(eng.actor, E.ACTOR_LAYOUT).items()},
-                           os.path.join(model_dir, checkpoint_tag(arttir, succ, 50, mean) + "Actor_Harfang_GYM"))
-                if rec is not None:  # train_all.py:70-89: only beside a checkpoint
-                    rec.write_reference_files(plot_dir, arttir)
-                high_score, success_rate = max(high_score, mean), max(success_rate, succ / 50)
-            print(f"Validation {arttir}: avg reward {mean:.2f} (std {std:.2f}) success {succ / 50:.2f} fire success {fire / 50:.2f}", flush=True)
-            log_validation(writer, episode, mean, std, succ / 50, fire / 50)
+                           os.path.join(model_dir, checkpoint_tag(arttir, succ, val_n, mean) + "Actor_Harfang_GYM"))
+                write_validation_plots(recs, plot_dir, arttir)  # train_all.py:70-89: only beside a checkpoint
+                high_score, success_rate = max(high_score, mean), max(success_rate, succ / val_n)
+            print(f"Validation {arttir}: avg reward {mean:.2f} (std {std:.2f}) success {succ / val_n:.2f} fire success {fire / val_n:.2f}", flush=True)
+            log_validation_by_scenario(writer, episode, by_scenario)
+            log_validation(writer, episode, mean, std, succ / val_n, fire / val_n)
             arttir += 1
     writer.close()
     return log_dir
@@ -298,7 +413,13 @@ def main(config):
     if rank == 0:
         print(f"seed {seed}" + (" (from the snapshot)" if snap_seed is not None else "" if config.seed is not None else " (drawn: no --seed given)"), flush=True)
     env_type, n = config.env, config.num_envs
-    max_step = (int(config.max_step) if getattr(config, "max_step", None) else MAX_STEP[env_type]) * (8 if config.render else 1)
+    max_step = (int(config.max_step) if getattr(config, "max_step", None) else default_max_step(env_type)) * (8 if config.render else 1)
+    if mixed_refusal(config):
+        raise SystemExit("train_all: " + mixed_refusal(config))
+    snap_env = snap["driver"].get("env") if snap is not None else None  # (a snapshot from before --env mixed does not record it: it is not a mixed one)
+    if snap is not None and (snap_env != env_type if snap_env is not None else env_type == MIXED):
+        raise SystemExit(f"train_all: --resume {config.resume} was run with --env {snap_env if snap_env is not None else 'of one scenario (unrecorded)'}, "
+                         f"--env {env_type} given")
     if config.agent == "BC":
         return train_bc(config, device, seed, max_step)
     hirl = config.agent == "HIRL"
@@ -328,13 +449,41 @@ def main(config):
         replay.score_chunk = score_chunk_for(n)  # --per_new td: rows per chunk of the scoring pass, by the envs per step (measured: DESIGN.md section 8)
     else:
         replay = DeviceReplay(buffer_size, device)
-    env = BatchedHarfangEnv(n, scenario=env_type, device=device, seed=seed, max_step=max_step, auto_reset=True,
+    env = BatchedHarfangEnv(n, scenario=mixed_scenarios(n, rank * n).astype(np.int32) if env_type == MIXED else env_type, device=device, seed=seed, max_step=max_step, auto_reset=True,
                             random_reset=config.random, env_id0=rank * n, replay=replay if multi_step == 1 else None)
     inserter = None
     if multi_step > 1:  # the acting launches run without a ring; the inserter's launch behind each step writes the finished n-step rows
         from .utils.buffer import NStepInserter
 
         inserter = NStepInserter(replay, n, multi_step, 0.99)  # (SacEngine's gamma, SAC/agent.py:60)
+    # Episode statistics by scenario (utils/epstat.py): one small launch behind every acting launch.  On under --env mixed, opt-in (--episode_stats) for
+    # one scenario; off, the run is launch for launch what it was.  Every rank keeps its own shard's statistics; rank 0 writes its own.
+    estats = last100 = None
+    if env_type == MIXED or getattr(config, "episode_stats", False):
+        from .utils.epstat import EpisodeStats, Last100
+
+        estats, last100 = EpisodeStats(env), Last100()
+
+    def stats_record():
+        """what every snapshot's driver record carries beside the driver's scalars"""
+        rec = {"env": env_type}
+        if estats is not None:
+            rec["episode_stats"] = {"device": estats.state(), "last100": last100.state()}
+        return rec
+
+    def restore_stats(record):
+        """after CK.load_run: the statistics workspace and the last-100 window of the snapshot; a snapshot without them starts them at zero"""
+        if estats is None:
+            return
+        st = record.get("episode_stats")
+        last100.pairs.clear()
+        if st is None:
+            estats.reset()
+            return
+        estats.load_state(st["device"])
+        for s_, c_ in st["last100"]:
+            last100.add(s_, c_)
+
     sac = config.agent == "SAC"
     torch.manual_seed(seed)  # identical initial networks on every rank
     if sac:  # train_sac.py:187-215: lr 1e-3, hidden [256, 512], batch 128, target_update_interval 3
@@ -357,8 +506,10 @@ def main(config):
     expert_len = bc_len = 0
     expert = bc_table = None
     if hirl or esac or isac:
-        es, ea = load_expert(config)
-        rows, succ = label_expert(es, ea, device)
+        tables = load_expert_files(config)
+        labelled = [label_expert(es_k, ea_k, device) for es_k, ea_k in tables]  # each file on its own: no transition spans two files
+        rows, succ = torch.cat([r for r, _ in labelled]), torch.cat([s_ for _, s_ in labelled])
+        es, ea = np.concatenate([t[0] for t in tables]), np.concatenate([t[1] for t in tables])
         expert = DeviceReplay(rows.shape[0] + 10, device)
         expert.store_rows(rows, succ)
         expert_len, bc_len = rows.shape[0], es.shape[0]
@@ -416,17 +567,22 @@ def main(config):
     run = {"episode": 0, "expert_num": batch if (hirl or esac) else 0, "high_score": -math.inf, "success_rate": 0.0, "arttir": 1}
     if config.resume:  # every rank restores its own shard: <resume>/state_rank<r>.pt
         run = CK.load_run(snap, eng, env, replay)
+        restore_stats(run)
         del snap
     else:
         # RANDOM EXPLORATION: 20 episodes of uniform actions in the reference (train_all.py:266-282) = 20*maxStep transitions
         env.reset()
         if inserter is not None:
             inserter.reset(env)
+        if estats is not None:
+            estats.reset()
         for _ in range(math.ceil(20 * max_step / (n * world))):
             a0 = torch.rand((n, 4), device=device) * 2 - 1
             env.step(a0)
             if inserter is not None:
                 inserter.push(env, a0)
+            if estats is not None:
+                estats.push()
         if per and per_new == "td":  # the exploration rows are appended with an error of their own too (SAC/agent.py:176-177, 234-246: the start_steps rows are scored as well)
             eng.score_new(replay, math.ceil(20 * max_step / (n * world)) * n, seed=seed + 3 + rank)
         elif per:
@@ -481,7 +637,7 @@ def main(config):
             torch.distributed.barrier()
         snap_path = os.path.join(log_dir, f"state_rank{rank}.pt")
         CK.save_run(snap_path, eng, env, replay, {"episode": episode0, "expert_num": expert_num, "high_score": high_score, "success_rate": success_rate,
-                                                  "arttir": arttir, "seed": seed, "dtype": dtype, **dtype_mark})
+                                                  "arttir": arttir, "seed": seed, "dtype": dtype, **dtype_mark, **stats_record()})
         if world > 1:
             torch.distributed.barrier()
     episode = episode0
@@ -501,6 +657,8 @@ def main(config):
                 eng.step_learn(env, expert, bc_table, n_main=batch - expert_num, act_sigma=0.1, act_seed=seed + 1, out=actions, sample_seed=seed + 2 + rank,
                                bc_weight_now=w_now, bc_warm_up_weight=warm)
                 w_now = None  # afterwards learn()'s own returned weight is fed back (train_all.py:361): the stored device value
+                if estats is not None:
+                    estats.push()
                 if ret is not None:
                     ret += env.reward
                 if writer is not None and step % log_rate == 0:  # Loss/* every 300 steps, train_all.py:362-367
@@ -511,6 +669,8 @@ def main(config):
             if front_sac and step < max_step - 1:  # SAC / E-SAC: explore + env step + the first forward launch of learn() in one launch (SacEngine.step_learn)
                 expert_num = expert_num_after(expert_num, step, warm_up_rate)
                 eng.step_learn(env, expert if (esac or isac) else None, n_main=batch - expert_num, act_seed=seed + 1, out=actions, sample_seed=seed + 2 + rank)
+                if estats is not None:
+                    estats.push()
                 if ret is not None:
                     ret += env.reward
                 if isac and writer is not None and step % log_rate == 0:  # SAC/agent.py:353-359
@@ -525,6 +685,8 @@ def main(config):
                 eng.act_step(env, sigma=0.1, seed=seed + 1, out=actions)
             if inserter is not None:
                 inserter.push(env, actions)  # this step's finished n-step rows (at most multi_step * n of them)
+            if estats is not None:
+                estats.push()
             if per and per_new == "td":
                 log_new = writer is not None and step % log_rate == 0
                 marked0 = replay.marked if log_new else 0  # (a host read, at the logging step only)
@@ -572,6 +734,7 @@ def main(config):
                           ": stopping.  `--loop reference` runs the same update without in-launch waits", flush=True)
                 raise SystemExit(3)
             run = CK.load_run(snap_path, eng, env, replay)  # every rank its own shard; all shards of a snapshot come from the same episode
+            restore_stats(run)
             eng.front_reset()
             expert_num, high_score, success_rate, arttir = run["expert_num"], run["high_score"], run["success_rate"], run["arttir"]
             episode = episode0 = run["episode"]
@@ -587,6 +750,12 @@ def main(config):
                 if writer is not None:
                     writer.add_scalar("Others/Front_trip_rollback_to_episode", episode, episode)
             continue
+        if estats is not None:  # the env episodes that ended during this driver episode, by scenario (one device-to-host copy, then the partials are cleared)
+            by_scenario = estats.read_and_clear()
+            log_episode_stats(writer, episode, by_scenario, last100)
+            if rank == 0:
+                print(f"Episode {episode + 1}: " + " | ".join(f"{k} ended {v['count']} (done {v['done']}, time limit {v['time_limit']}) return {v['mean']:.2f} "
+                                                              f"length {v['mean_len']:.1f}" for k, v in by_scenario.items() if v["count"]), flush=True)
         if rank == 0:
             c, a, b, r_, f, w = eng.losses_host()
             st = env.stats_dict()
@@ -608,20 +777,24 @@ def main(config):
                     ret.zero_()
                 last_stats = st
         if (episode + 1) % checkpoint_rate == 0 and rank == 0:  # VALIDATION, train_all.py:400-402 / train_sac.py:431-433
-            (mean, std, succ, fire), rec = validate_plotting(config.plot, eng, env_type, 50, max_step, config.random, seed + 12345, device, sac)
-            if mean > high_score or succ / 50 >= success_rate or arttir % 5 == 0:
-                tag = checkpoint_tag(arttir, succ, 50, mean)
-                if rec is not None:  # train_all.py:70-89: the last validation episode's track, only beside a checkpoint
-                    rec.write_reference_files(plot_dir, arttir)
+            (mean, std, succ, fire), val_by_scenario, recs = validate_env(config, eng, env_type, max_step, seed + 12345, device, sac)
+            val_n = 50 * len(val_by_scenario)  # (mixed: the pooled episodes of the three scenarios)
+            if mean > high_score or succ / val_n >= success_rate or arttir % 5 == 0:
+                tag = checkpoint_tag(arttir, succ, val_n, mean)
+                write_validation_plots(recs, plot_dir, arttir)  # train_all.py:70-89: the last validation episode's track, only beside a checkpoint
                 if sac:  # SacAgent.save_models, SAC/agent.py:440-444
                     eng.save_models(model_dir, tag)
                 else:    # Agent.saveCheckpoints, HIRL.py:336-342
                     for name, flat, layout in (("Critic_", eng.critic, E.CRITIC_LAYOUT), ("Actor_", eng.actor, E.ACTOR_LAYOUT),
                                                ("TargetCritic_", eng.target_critic, E.CRITIC_LAYOUT), ("TargetActor_", eng.target_actor, E.ACTOR_LAYOUT)):
                         torch.save({k: v.cpu().clone() for k, v in E.unpack(flat, layout).items()}, os.path.join(model_dir, tag + name + "Harfang_GYM"))
-                high_score, success_rate = max(high_score, mean), max(success_rate, succ / 50)
-            print(f"Validation {arttir}: avg reward {mean:.2f} (std {std:.2f}) success {succ / 50:.2f} fire success {fire / 50:.2f}", flush=True)
-            log_validation(writer, episode, mean, std, succ / 50, fire / 50)
+                high_score, success_rate = max(high_score, mean), max(success_rate, succ / val_n)
+            print(f"Validation {arttir}: avg reward {mean:.2f} (std {std:.2f}) success {succ / val_n:.2f} fire success {fire / val_n:.2f}", flush=True)
+            if len(val_by_scenario) > 1:
+                for k_, (m_, s_, k2_, f_) in val_by_scenario.items():
+                    print(f"  {k_}: avg reward {m_:.2f} (std {s_:.2f}) success {k2_ / 50:.2f} fire success {f_ / 50:.2f}", flush=True)
+            log_validation_by_scenario(writer, episode, val_by_scenario)
+            log_validation(writer, episode, mean, std, succ / val_n, fire / val_n)
             arttir += 1
         # sharded run: the replicas must not have drifted apart
         check_due = (episode + 1) % checkpoint_rate == 0 or (config.replica_check_every and (episode + 1) % config.replica_check_every == 0)
@@ -636,7 +809,7 @@ def main(config):
                 torch.distributed.barrier()  # every shard of a snapshot comes from the same episode ...
             CK.save_run(os.path.join(log_dir, f"state_rank{rank}.pt"), eng, env, replay,
                         {"episode": episode + 1, "expert_num": expert_num, "high_score": high_score, "success_rate": success_rate, "arttir": arttir,
-                         "seed": seed, "dtype": dtype, **dtype_mark})
+                         "seed": seed, "dtype": dtype, **dtype_mark, **stats_record()})
             if world > 1:
                 torch.distributed.barrier()  # ... and nobody runs ahead while a shard is still being written
             snap_path = os.path.join(log_dir, f"state_rank{rank}.pt")
@@ -733,7 +906,7 @@ def parse_args(argv=None):
     """parser().parse_args with the cross-flag checks that are argparse errors"""
     p = parser()
     cfg = p.parse_args(argv)
-    why = per_refusal(cfg) or clip_refusal(cfg) or nstep_refusal(cfg)
+    why = per_refusal(cfg) or clip_refusal(cfg) or nstep_refusal(cfg) or mixed_refusal(cfg)
     if why:
         p.error(why)
     if cfg.type == "ISAC" and cfg.agent != "SAC":
@@ -755,14 +928,17 @@ def parser():
     p.add_argument("--render", action="store_true")
     p.add_argument("--plot", action="store_true")
     p.add_argument("--seed", type=int, default=None)
-    p.add_argument("--env", type=str, default="straight_line", choices=list(SCENARIOS))
+    p.add_argument("--env", type=str, default="straight_line", choices=list(SCENARIOS) + [MIXED],
+                   help="mixed (an extension): one population over all three scenarios in contiguous thirds (mixed_scenarios), under the longest step limit "
+                        "(1,900) unless --max_step says otherwise; episode statistics and validation are reported per scenario and pooled")
     p.add_argument("--random", action="store_true")
     # additions of the vectorised driver
     p.add_argument("--num_envs", type=int, default=4096)
     p.add_argument("--episodes", type=int, default=6000)
     p.add_argument("--updates_per_step", type=int, default=1)
     p.add_argument("--buffer_size", type=int, default=1 << 20)
-    p.add_argument("--expert_csv", type=str, default=None)
+    p.add_argument("--expert_csv", type=str, default=None, help="the expert table; a comma-separated list of files is read and labelled file by file "
+                                                                "(no transition spans two files) and concatenated")
     p.add_argument("--bc_actor", type=str, default=None)
     p.add_argument("--result_dir", type=str, default="results")
     p.add_argument("--checkpoint_rate", type=int, default=25, help="episodes between validations (train_all.py:206)")
@@ -788,6 +964,9 @@ def parser():
     p.add_argument("--load_dir", type=str, default=None, help="--load_model: directory of the checkpoint files (default: this run's model dir)")
     p.add_argument("--load_tag", type=str, default="Agent20_successRate0.64", help="--load_model: checkpoint tag (train_all.py:240 hard-codes this one)")
     p.add_argument("--log_rewards", action="store_true", help="also log Training/Episode Reward (one more small launch per vector step)")
+    p.add_argument("--episode_stats", action="store_true",
+                   help="per-episode training statistics by scenario (return, length, how the episode ended: Training/<scenario>/*, Training/Last 100 Episode "
+                        "Average Reward): one small launch behind every acting launch (utils/epstat.py).  Always on under --env mixed")
     p.add_argument("--per", action="store_true", help="SAC: prioritized replay (SacAgent(per=True)): proportional draws with importance weights, priorities from "
                                                       "|Q1 - y|; fp32, one GPU, --type SAC; the vector loop runs in the reference's order")
     p.add_argument("--per_new", choices=("max", "td"), default="max",

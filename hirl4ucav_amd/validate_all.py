@@ -17,7 +17,10 @@ episode's first re-arm comes 60 - (steps of the episodes before it) mod 60 calls
 (validate_all.py:59-66: both are read only when `done` is seen).
 An extension: the reference collects the last episode's track in validate() with --plot but never writes it (validate_all.py:30-58); here `--plot` writes it per
 round — the reference's five CSVs and two figures of train_all.py:70-89 with the tag round<k> — into `--plot_dir` (default <model_dir>/../plot), from the device
-record of utils/trace.py."""
+record of utils/trace.py.
+Another: `--scenario mixed` runs every round over the three scenarios (`episodes` episodes each, the same seed), prints a line per scenario and the pooled
+line, and the final statistics are over the rounds' pooled numbers; it has no --infinite form (that env is the serpentine one).  main()'s returned lists then hold the
+pooled numbers of each round."""
 import argparse
 import os
 import statistics
@@ -31,6 +34,8 @@ from .environments.batched import BatchedHarfangEnv
 from .utils.seed import set_seed
 
 VALIDATION_STEP = 1200   # validate_all.py:187,190
+SCENARIO_NAMES = ("straight_line", "serpentine", "circular")
+MIXED = "mixed"
 REARM_EVERY = 60         # HarfangEnv_GYM.py:484-486
 
 
@@ -115,17 +120,31 @@ def main(config):
     print(("random" if config.random else "fixed") + f" initial positions; seed {seed}" + ("" if config.seed is not None else " (drawn: no --seed given)"), flush=True)
     eng, sac = load_agent(config, device)
     scenario = config.scenario or "serpentine"
+    why = mixed_refusal(config)
+    if why:
+        raise SystemExit("validate_all: " + why)
     returns, success, hit_rate = [], [], []
-    for k in range(config.nums):
+
+    def one_round(k, scenario, tag):
         env = rec = None
         if config.plot:
             from .utils.trace import validation_recorder
 
             env, rec = validation_recorder(config.episodes, scenario, seed + 12345 + k, config.random, config.validation_step, device)
-        r, s, f = validate_round(eng, config.episodes, config.validation_step, config.random, seed + 12345 + k, device, infinite=config.infinite, sac=sac,
-                                 scenario=scenario, env=env, recorder=rec)
+        out = validate_round(eng, config.episodes, config.validation_step, config.random, seed + 12345 + k, device, infinite=config.infinite, sac=sac,
+                             scenario=scenario, env=env, recorder=rec)
         if rec is not None:
-            rec.write_reference_files(plot_dir_of(config), f"round{k + 1}")
+            rec.write_reference_files(plot_dir_of(config), tag)
+        return out
+
+    for k in range(config.nums):
+        if scenario == MIXED:  # every scenario with the round's seed; the round's numbers are the pooled ones (equal groups: the mean of the three)
+            per = {name: one_round(k, name, f"round{k + 1}_{name}") for name in SCENARIO_NAMES}
+            for name, (r, s, _) in per.items():
+                print(f"round {k + 1} {name}: avg reward {r:.2f} fire success {s:.2f}", flush=True)
+            r, s, f = statistics.mean(v[0] for v in per.values()), statistics.mean(v[1] for v in per.values()), 0.0
+        else:
+            r, s, f = one_round(k, scenario, f"round{k + 1}")
         returns.append(r)
         success.append(s)
         hit_rate.append(f)
@@ -137,6 +156,22 @@ def main(config):
         print(statistics.mean(returns), sd(returns))
         print(statistics.mean(success), sd(success))
     return returns, success, hit_rate
+
+
+def mixed_refusal(config):
+    """why `--scenario mixed` cannot run as asked, or None"""
+    if config.scenario == MIXED and config.infinite:
+        return "--scenario mixed with --infinite: the re-arming env is the serpentine one (HarfangSerpentineInfiniteEnv): drop one of the two"
+    return None
+
+
+def parse_args(argv=None):
+    """parser().parse_args with the cross-flag check that is an argparse error"""
+    p = parser()
+    cfg = p.parse_args(argv)
+    if mixed_refusal(cfg):
+        p.error(mixed_refusal(cfg))
+    return cfg
 
 
 def parser():
@@ -156,7 +191,8 @@ def parser():
     # not in the reference
     p.add_argument("--model_dir", type=str, required=True, help="directory of the checkpoint files (the reference hard-codes one)")
     p.add_argument("--plot_dir", type=str, default=None, help="--plot: where the last episode's CSVs and figures of every round go (default: <model_dir>/../plot)")
-    p.add_argument("--scenario", type=str, default=None, choices=["straight_line", "serpentine", "circular"], help="validate here instead of in serpentine")
+    p.add_argument("--scenario", type=str, default=None, choices=list(SCENARIO_NAMES) + [MIXED],
+                   help="validate here instead of in serpentine; mixed: every round over all three, per-scenario and pooled lines")
     p.add_argument("--nums", type=int, default=2)
     p.add_argument("--episodes", type=int, default=50)
     p.add_argument("--validation_step", type=int, default=VALIDATION_STEP)
@@ -165,4 +201,4 @@ def parser():
 
 
 if __name__ == "__main__":
-    main(parser().parse_args())
+    main(parse_args())

@@ -80,8 +80,9 @@ const char* hx_last_error(void);
  * hx_sac_learn_weighted_clipped).
  * 120: priorities at insert for SAC's prioritized replay (hx_per_score_workspace_floats, hx_per_score_new).
  * 121: n-step returns for SAC (HxNStep, hx_nstep_*).
- * 122: the record of validation episodes (HxTrace, hx_trace_*). */
-#define HX_ABI_VERSION 122
+ * 122: the record of validation episodes (HxTrace, hx_trace_*).
+ * 123: per-episode statistics by scenario (HxEpStat, hx_epstat_*). */
+#define HX_ABI_VERSION 123
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -792,6 +793,52 @@ int hx_trace_reset(const HxTrace* tr, void* stream);
  * t < 0 or t >= cap_steps: HX_ERR_ARG, nothing is launched.  Enqueues only. */
 int hx_trace_push(const HxTrace* tr, const float* state, int64_t n, int64_t stride, const float* reward, const uint8_t* done, const int8_t* success,
                   const int32_t* env_ids, int32_t t, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Episode statistics (the reference's totalReward and step of a training episode, train_all.py:341-354, 383-385), binned by scenario: what a mixed
+ * population (per-env scenario ids, hx_env_reset) needs to tell which manoeuvre the policy fails.  AUTO-RESET ENVS ONLY: the rule reads an episode's
+ * end off done and off episode_ctr moving, which is what an acting launch with HxStepOpts.auto_reset = 1 leaves.  hx_epstat_push runs behind every
+ * acting launch (a front launch or hx_env_step).  Per env and call, fp32 without contraction, in this order (tests/_epstat_model.py is the same in
+ * numpy, bit for bit):
+ *     bin   = (flags word, state word 35, >> 8) & 3        (the scenario id survives every auto-reset)
+ *     fire_good[bin] += success == +1;  fire_bad[bin] += success == -1        (every executed step, the time-limit step too)
+ *     trunc = episode_ctr != last_ctr && !done             (the time-limit step: executed, not stored — HxStepOpts.max_step)
+ *     trunc: the episode leaves with (acc, len) as they are — the reference breaks before `totalReward += reward` on that step
+ *            (train_all.py:346-354), so its reward is not in the return
+ *     else:  acc = acc + reward;  len += 1;  done: the episode leaves           (a done ON the time-limit step is a done: n_done)
+ *     an episode that leaves adds to its bin count, n_done or n_time_limit, sum_len, sum_ret, sum_ret_sq, min_ret, max_ret; then acc = 0, len = 0
+ *     last_ctr = episode_ctr
+ * Kills cannot be attributed here: HX_F_EPISODE_SUCCESS is cleared by the auto-reset inside the same acting launch, before this launch reads the
+ * flags word.  Per-scenario kill rates come from validation.
+ * Accumulation: workgroup g (envs 64 g .. 64 g + 63, the same on every call) owns slot g of `part` and adds the call's contribution to it: for each
+ * word of the slot, c = 0, then the lanes of that bin in lane order 0..63 (c = c + value), then word = word + c.  Sums are float64 (return and
+ * return squared are the fp32 return widened first; the counts are exact integers held as float64), min / max are fp32 and start at +inf / -inf.
+ * No atomics, no workgroup waits for another, the same inputs give the same bits.  The host reads `part` and adds the slots in index order.
+ * State, all device memory owned by the caller, hx_epstat_workspace_words(n_envs) 4-byte words in all, in this order:
+ *     part      [ceil(n_envs / 64)][HX_EPSTAT_SLOT_WORDS] 8-byte words (8-byte aligned).  Words 0..31 of a slot: [bin][HX_EPSTAT_SUMS] float64 —
+ *               count, n_done, n_time_limit, sum_len, sum_ret, sum_ret_sq, fire_good, fire_bad; words 32..35: [bin] min_ret (low half) and
+ *               max_ret (high half) as fp32
+ *     acc (fp32), len (u32), last_ctr (u32)   [n_envs] each
+ * ------------------------------------------------------------------------------------------------------------ */
+#define HX_EPSTAT_BINS 4
+#define HX_EPSTAT_SUMS 8
+#define HX_EPSTAT_SLOT_WORDS 36
+typedef struct HxEpStat {
+    double* part;
+    float* acc; uint32_t* len; uint32_t* last_ctr;
+    int64_t n_envs;
+} HxEpStat;
+int hx_epstat_sizeof(void); /* sizeof(HxEpStat) of the loaded library */
+int64_t hx_epstat_workspace_words(int64_t n_envs); /* 0 for n_envs <= 0 (or >= 2^31) */
+/* after env.reset(): every slot cleared, acc = 0, len = 0, last_ctr <- episode_ctr [n_envs] */
+int hx_epstat_reset(const HxEpStat* es, const uint32_t* episode_ctr, void* stream);
+/* the partial sums only (sums 0, min +inf, max -inf): the host has read them; running episodes keep their acc, len and last_ctr */
+int hx_epstat_clear(const HxEpStat* es, void* stream);
+/* One step of every env, from the env's buffers exactly as an acting launch or hx_env_step left them: state (word w of env i at
+ * state[w * stride + i]; only word 35 is read), reward, done, success, episode_ctr [n], n = n_envs.  One launch, one env per lane, 64 per
+ * workgroup; plain vector stores, each one contiguous run per wave.  Enqueues only. */
+int hx_epstat_push(const HxEpStat* es, const float* state, int64_t n, int64_t stride, const float* reward, const uint8_t* done, const int8_t* success,
+                   const uint32_t* episode_ctr, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Exchange step of a sharded update without a collective library (selectable beside RCCL): one-shot all-reduce over hipIpc peer
