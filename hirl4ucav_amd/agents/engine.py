@@ -518,12 +518,7 @@ class HirlEngine:
         smp = ctypes.byref(pending[0]) if pending is not None else None
         nets, hyper = ctypes.byref(self.nets), ctypes.byref(self.hyper)
         w_kind, w_given = _bc_weight_kind(bc_weight_now)
-        actor_phase = self.actor_trainable  # HIRL.py:291
-        self.critic_step += 1
-        if actor_phase:
-            self.actor_step += 1
-            self.update_count += 1
-        do_polyak = actor_phase and self.update_count % self.target_update_freq == 0  # HIRL.py:327-330
+        actor_phase, do_polyak = self._begin_call()
         if not self.staged:
             _lib.call("hx_hirl_learn_sampled", nets, ctypes.byref(batch), hyper, smp, self.critic_step, int(actor_phase), self.actor_step,
                       int(do_polyak), w_kind, w_given, float(bc_warm_up_weight), st)
@@ -536,37 +531,65 @@ class HirlEngine:
             self._learn_staged(grads, batch, actor_phase, do_polyak, w_kind, w_given, bc_warm_up_weight, before_exchange)
         self.actor_trainable = not self.actor_trainable  # HIRL.py:332
 
+    def _begin_call(self):
+        """The host counters of one learn() call, advanced before its launches (HIRL.py:291,327-330) -> (actor_phase, do_polyak); the caller flips
+        `actor_trainable` when the call has been issued (HIRL.py:332)."""
+        actor_phase = self.actor_trainable  # HIRL.py:291
+        self.critic_step += 1
+        if actor_phase:
+            self.actor_step += 1
+            self.update_count += 1
+        return actor_phase, actor_phase and self.update_count % self.target_update_freq == 0  # HIRL.py:327-330
+
     def _learn_staged(self, critic_grads, batch, actor_phase, do_polyak, w_kind, w_given, bc_warm_up_weight, before_exchange=None):
         """sharded: the stages of learn() with the exchanges of SURVEY.md 8e in between — ONE message per phase.  critic_grads() issues the launches
-        that leave the critics' gradient behind (all of them, or — after a front launch — the rest of them)."""
-        B, st = self.batch, _lib.stream_ptr()
-        nets, hyper = ctypes.byref(self.nets), ctypes.byref(self.hyper)
-        gs = 1.0 / self.world
-        own_critic = self.grad_critic.data_ptr()
+        that leave the critics' gradient behind (all of them, or — after a front launch — the rest of them).  The stages are methods of their own
+        (_stage_*) so that tests/_sharded_lockstep.py can run several ranks' stages in lockstep in one process; `world` there overrides this
+        engine's (1 / world scales the summed gradients, batch x world divides the summed soft count)."""
         if self.xchg is not None:  # peers read this rank's gradient straight out of its message buffer: wgrad writes there
             self.nets.grad_critic = self.xchg.write_buffer("critic").data_ptr()
         critic_grads()
         if before_exchange is not None:
             before_exchange()
-        summed = self._allreduce(self.grad_critic, "critic")
+        self._stage_critic_step(self._allreduce(self.grad_critic, "critic"), do_polyak)
+        if actor_phase:
+            self._stage_actor_backward(batch, w_kind)
+            if self.world > 1 or self.sharded_sequence:   # [dL_rl | dL_bc | count] in one message, w formed from the global count after the exchange
+                msg = self._stage_actor_message()
+                self._stage_actor_step(self._allreduce(msg, "actor"), do_polyak, w_kind, w_given, bc_warm_up_weight)
+            else:                # one rank running the staged sequence (tests): the weight is known locally, bit-identical to the one-call path
+                B, st, nets, hyper = self.batch, _lib.stream_ptr(), ctypes.byref(self.nets), ctypes.byref(self.hyper)
+                _lib.call("hx_hirl_actor_wgrad", nets, hyper, B, B, w_kind, w_given, float(bc_warm_up_weight), st)
+                _lib.call("hx_adam", nets, hyper, 1 | (16 if do_polyak else 0), self.actor_step, 1.0 / self.world, w_kind, w_given,
+                          float(bc_warm_up_weight), B, st)
+
+    def _stage_critic_step(self, summed, do_polyak, world=None):
+        """the critics' Adam step on the SUMMED gradient (`summed`: a tensor), scaled by 1 / world"""
+        own_critic = self.grad_critic.data_ptr()
         self.nets.grad_critic = summed.data_ptr()
         pk = 16 if do_polyak else 0  # + 16: soft_update of the target in the same launch (nothing reads it in between)
-        _lib.call("hx_adam", nets, hyper, 0 | pk, self.critic_step, gs, 0, 0.0, 0.0, B, st)
+        _lib.call("hx_adam", ctypes.byref(self.nets), ctypes.byref(self.hyper), 0 | pk, self.critic_step, 1.0 / (self.world if world is None else world),
+                  0, 0.0, 0.0, self.batch, _lib.stream_ptr())
         self.nets.grad_critic = own_critic
-        if actor_phase:
-            # (fwd_done = 2: critic_grads() carried the actor call's forwards AND the heads launch G feeds on)
-            _lib.call("hx_hirl_actor_backward", nets, ctypes.byref(batch), hyper, int(w_kind == 1), 2, st)
-            if self.world > 1 or self.sharded_sequence:   # [dL_rl | dL_bc | count] in one message, w formed from the global count after the exchange
-                if self.actor_msg is None:
-                    self.actor_msg = torch.zeros(int(_lib.load().hx_actor_message_floats()), dtype=torch.float32, device=self.device)
-                msg = self.xchg.write_buffer("actor") if self.xchg is not None else self.actor_msg
-                _lib.call("hx_hirl_actor_wgrad_split", nets, hyper, B, msg.data_ptr(), st)
-                summed = self._allreduce(msg, "actor")
-                _lib.call("hx_adam_mixed", nets, hyper, int(do_polyak), self.actor_step, gs, w_kind, w_given, float(bc_warm_up_weight),
-                          B * self.world, summed.data_ptr(), st)
-            else:                # one rank running the staged sequence (tests): the weight is known locally, bit-identical to the one-call path
-                _lib.call("hx_hirl_actor_wgrad", nets, hyper, B, B, w_kind, w_given, float(bc_warm_up_weight), st)
-                _lib.call("hx_adam", nets, hyper, 1 | pk, self.actor_step, gs, w_kind, w_given, float(bc_warm_up_weight), B, st)
+
+    def _stage_actor_backward(self, batch, w_kind):
+        # (fwd_done = 2: critic_grads() carried the actor call's forwards AND the heads launch G feeds on)
+        _lib.call("hx_hirl_actor_backward", ctypes.byref(self.nets), ctypes.byref(batch), ctypes.byref(self.hyper), int(w_kind == 1), 2, _lib.stream_ptr())
+
+    def _stage_actor_message(self, msg=None):
+        """this rank's merged actor message [dL_rl | dL_bc | count words] (`msg`: where; default the exchange's write buffer or the engine's own) -> msg"""
+        if msg is None:
+            if self.actor_msg is None:
+                self.actor_msg = torch.zeros(int(_lib.load().hx_actor_message_floats()), dtype=torch.float32, device=self.device)
+            msg = self.xchg.write_buffer("actor") if self.xchg is not None else self.actor_msg
+        _lib.call("hx_hirl_actor_wgrad_split", ctypes.byref(self.nets), ctypes.byref(self.hyper), self.batch, msg.data_ptr(), _lib.stream_ptr())
+        return msg
+
+    def _stage_actor_step(self, summed, do_polyak, w_kind, w_given, bc_warm_up_weight, world=None):
+        """the actor's Adam step from the SUMMED message: w from the global count over batch x world rows, gradient scaled by 1 / world"""
+        world = self.world if world is None else world
+        _lib.call("hx_adam_mixed", ctypes.byref(self.nets), ctypes.byref(self.hyper), int(do_polyak), self.actor_step, 1.0 / world, w_kind, w_given,
+                  float(bc_warm_up_weight), self.batch * world, summed.data_ptr(), _lib.stream_ptr())
 
     def step_learn(self, env, expert=None, bc_table=None, n_main=None, act_noise=None, act_sigma=0.0, act_seed=0, out=None, sample_seed=0,
                    smooth_sigma=0.2, bc_weight_now=0.0, bc_warm_up_weight=0.0):

@@ -53,7 +53,9 @@ class RcclDirect:
         self.comm = comm
 
     def allreduce(self, t):
-        """t <- sum over the ranks of t (fp32), in place, on the current stream"""
+        """t <- sum over the ranks of t (fp32), in place, on the current stream.  bf16: EVERY word is rounded to bf16 and summed in bf16 (a length that
+        is no multiple of 4 travels as fp32) — integer words are exact only while every partial sum stays within 256, which is what the merged actor
+        message's digit words are for (include/hirl4ucav.h hx_hirl_actor_wgrad_split)"""
         n = t.numel()
         if self.bf16 and n % 4 == 0:
             if self._scratch is None or self._scratch.numel() < n:

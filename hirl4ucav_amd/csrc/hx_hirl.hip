@@ -329,8 +329,9 @@ int hx_hirl_actor_wgrad(const HxNets* N, const HxHyper* Hy, int32_t batch, int32
 }
 
 /* Stage 2b of a sharded run with ONE exchange for the actor phase: the UNWEIGHTED gradients of the two actor losses and the local soft
- * count go into one message, msg = [dL_rl | dL_bc | count, 0...] (hx_actor_message_floats()); after its all-reduce hx_adam_mixed
- * forms w from the global count and combines.  TD3 (use_bc = 0): dL_rl only. */
+ * count go into one message, msg = [dL_rl | dL_bc | count, its base-32 digits, 0...] (hx_actor_message_floats()); after its all-reduce
+ * hx_adam_mixed forms w from the global count — rebuilt from the summed digit words, exact on bf16 transports too (hx_update.h kCountDigits) —
+ * and combines.  TD3 (use_bc = 0): dL_rl and zero count words; the dL_bc half is not written. */
 int hx_hirl_actor_wgrad_split(const HxNets* N, const HxHyper* Hy, int32_t batch, float* msg, void* stream) {
     HX_REQUIRE(N && Hy && batch > 0 && msg && (reinterpret_cast<uintptr_t>(msg) & 15u) == 0, "hx_hirl_actor_wgrad_split: bad arguments");
     const Mlp mA{13, 4, Hy->no_layernorm ? 1 : 0}, mQ{17, 1, Hy->no_layernorm ? 1 : 0};  // layerNorm = False: HIRL.py:70-80,92-97,135-138

@@ -727,7 +727,7 @@ struct WgArgs {
     const int* soft_count;
     const float* wstate;
     int bf16;  // dW2 = dz2^T h1 with both operands rounded to bf16 (fp32 accumulate): the bf16 update path
-    float* count_out;  // nullptr, or where thread 0 of the launch leaves (float)*soft_count: the merged actor message's count word
+    float* count_out;  // nullptr, or where thread 0 of the launch leaves (float)*soft_count and its base-32 digits: the merged actor message's count words
     const SampleDev* predraw;  // hx_hirl_learn_back: one more workgroup draws and gathers the NEXT front launch's minibatch (predraw_wg), or null
     int predraw_batch;
     // head riders (wgrad_kernel only): up to two nets this launch does NOT change whose z2 rows an earlier launch left in a slot — one more
@@ -771,6 +771,18 @@ __device__ __forceinline__ float effective_w(int kind, float given, float warm, 
     return w > 1.0f ? 1.0f : w;  // HIRL.py:308
 }
 
+// The soft count inside the merged actor message (hx_actor_message_floats(): 64 words behind the two gradients).  Word 0 holds (float)count; words
+// 1..kCountDigits hold the count's base-32 digits, least significant first, and THEY are what the optimizer step reads: a digit is at most 31, so every
+// partial sum over up to 8 ranks (kMaxWorld) is at most 248 — an integer below 256 is exact in bf16 as well as in fp32, in any order of summation.
+// Word 0 alone would lose its low bits on a bf16 transport once the global count passes 256.  7 digits = 35 bits: every non-negative int32 count.
+constexpr int kCountDigits = 7;
+__device__ __forceinline__ unsigned long long count_from_digits(const float* words) {
+    unsigned long long c = 0;
+#pragma unroll
+    for (int k = 0; k < kCountDigits; ++k) c += (unsigned long long)(uint32_t)words[1 + k] << (5 * k);
+    return c;
+}
+
 struct AdamArgs {
     float* p; const float* g; float* m; float* v;
     int n;
@@ -799,8 +811,8 @@ struct AdamArgs {
     uint16_t* seg_w2b[2];
     uint16_t* seg_w2tb[2];
     uint16_t* seg_tgt_w2b[2];
-    // merged actor message of a sharded run: g holds the summed dL_rl, g2 the summed dL_bc, *countf the summed
-    // soft count; the step uses g = w g2 + (1 - w) g with w from the GLOBAL count.  nullptr: g is the finished gradient.
+    // merged actor message of a sharded run: g holds the summed dL_rl, g2 the summed dL_bc, countf the summed
+    // count words (count_from_digits); the step uses g = w g2 + (1 - w) g with w from the GLOBAL count.  nullptr: g is the finished gradient.
     const float* g2;
     const float* countf;
     const uint32_t* guard;  // nullptr, or a word that must be 0 for the step to happen (HxNets.xchg_status: a failed exchange)

@@ -142,7 +142,13 @@ inline WgJobC pack_wg(const WgJob& J, const WgArgs& A) {
 // what thread 0 of the launch does besides its gradients
 template <bool ADAM>
 __device__ __forceinline__ void wg_thread0(const WgArgs& A, float w) {
-    if (A.count_out) *A.count_out = A.soft_count ? (float)*A.soft_count : 0.0f;
+    if (A.count_out) {  // word 0: the count itself; words 1..kCountDigits: its base-32 digits, what adam_w reads (count_from_digits)
+        const int c = A.soft_count ? *A.soft_count : 0;
+        A.count_out[0] = (float)c;
+        uint32_t u = (uint32_t)c;
+#pragma unroll
+        for (int k = 0; k < kCountDigits; ++k, u >>= 5) A.count_out[1 + k] = (float)(u & 31u);
+    }
     if (ADAM && A.ad.finish_actor) {  // what adam_kernel's thread 0 does on an actor step
         if (A.ad.use_bc) {
             A.ad.losses[1] = A.ad.losses[2] * w + A.ad.losses[3] * (1.0f - w);  // HIRL.py:321
@@ -897,10 +903,10 @@ __global__ __launch_bounds__(kWide) void wgrad2_kernel(WgArgsC AC) {
     }
 }
 
-// the BC weight of this call (HIRL.py:299-308); countf: the soft count as a float word of the all-reduced message
+// the BC weight of this call (HIRL.py:299-308); countf: the count words of the all-reduced message (the global count from its digit words)
 __device__ __forceinline__ float adam_w(const AdamArgs& A) {
     if (A.countf && A.w_kind == 1) {
-        const float w = *A.countf * A.inv_batch + A.warm;
+        const float w = __builtin_fmaf((float)count_from_digits(A.countf), A.inv_batch, A.warm);  // one rounding, as effective_w's count * inv_batch + warm compiles
         return w > 1.0f ? 1.0f : w;
     }
     return effective_w(A.w_kind, A.w_given, A.warm, A.inv_batch, A.soft_count, A.wstate);

@@ -81,8 +81,9 @@ const char* hx_last_error(void);
  * 120: priorities at insert for SAC's prioritized replay (hx_per_score_workspace_floats, hx_per_score_new).
  * 121: n-step returns for SAC (HxNStep, hx_nstep_*).
  * 122: the record of validation episodes (HxTrace, hx_trace_*).
- * 123: per-episode statistics by scenario (HxEpStat, hx_epstat_*). */
-#define HX_ABI_VERSION 123
+ * 123: per-episode statistics by scenario (HxEpStat, hx_epstat_*).
+ * 124: the merged actor message carries the soft count as base-32 digit words too, and hx_adam_mixed reads those (exact on the bf16 transports). */
+#define HX_ABI_VERSION 124
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -309,10 +310,16 @@ int hx_adam(const HxNets* nets, const HxHyper* hyper, int32_t which, int32_t ste
             float w_given, float warm, int32_t batch, void* stream);
 int hx_polyak(const HxNets* nets, const HxHyper* hyper, void* stream); /* both targets in a launch of their own */
 /* Sharded runs with ONE exchange for the actor phase (SURVEY.md 8e "all-reduce dL_bc, dL_rl and the count in one message and combine
- * locally"): hx_hirl_actor_wgrad_split writes msg = [dL_rl | dL_bc | soft count as a float, 0...] (hx_actor_message_floats() floats, each
- * gradient hx_actor_param_count() floats padded to a multiple of 4), unweighted; after the all-reduce of msg, hx_adam_mixed forms
+ * locally"): hx_hirl_actor_wgrad_split writes msg = [dL_rl | dL_bc | tail] (hx_actor_message_floats() floats, each gradient
+ * hx_actor_param_count() floats padded to a multiple of 4; the padding is not written), unweighted; after the all-reduce of msg, hx_adam_mixed forms
  * w = count / batch + warm from the GLOBAL count (w_kind 1; given / stored weight otherwise), g = w dL_bc + (1 - w) dL_rl (HIRL.py:321),
- * and steps the actor (grad_scale = 1 / world; polyak != 0: soft_update of targetActor in the same launch). */
+ * and steps the actor (grad_scale = 1 / world; polyak != 0: soft_update of targetActor in the same launch).
+ * The 64-word tail: word 0 = the local soft count as a float (for the reader of a dump; nothing computes with it), words 1..7 = the count's base-32
+ * digits as floats, least significant first, words 8..63 are not written (keep them 0).  hx_adam_mixed rebuilds the global count from the SUMMED digit
+ * words: a digit is at most 31, so every partial sum over up to 8 ranks is at most 248, and integers up to 256 are exact in bf16 — the count arrives
+ * exactly through every transport and summation order, the bf16 ones included (word 0 does not: bf16 keeps 8 bits, 8 ranks x 128 rows need 11).
+ * The launch writes grad_actor nowhere.  TD3 (hyper->use_bc == 0): dL_rl and the eight count words (all 0) are written, the dL_bc half is left as it
+ * was, and hx_adam_mixed reads neither the dL_bc half nor the tail. */
 int64_t hx_actor_message_floats(void);
 int hx_hirl_actor_wgrad_split(const HxNets* nets, const HxHyper* hyper, int32_t batch, float* msg, void* stream);
 int hx_adam_mixed(const HxNets* nets, const HxHyper* hyper, int32_t polyak, int32_t step, float grad_scale, int32_t w_kind, float w_given,
@@ -876,7 +883,9 @@ int hx_rccl_init(const uint8_t* id128 /* host */, int32_t world, int32_t rank, v
 int hx_rccl_allreduce(void* comm, void* buf, int64_t n, int32_t dtype, void* stream);
 /* The same exchange with the message on the wire as bf16 (half the bytes; RCCL sums in bf16): buf[i] (fp32) -> scratch[i] (bf16, round to nearest even) ->
  * ncclAllReduce(bf16) -> buf[i] (fp32), three enqueues on `stream`.  Every rank receives the same bits (replicas stay identical); opt-in
- * (`--exchange rccl-bf16`), n a multiple of 4, scratch: n bf16 device words. */
+ * (`--exchange rccl-bf16`), n a multiple of 4, scratch: n bf16 device words.  EVERY word of the message is rounded and summed as bf16, whatever it
+ * means: an integer travels exactly only while every partial sum stays within 256.  The merged actor message is built for that (its soft count as
+ * base-32 digit words, see hx_hirl_actor_wgrad_split); a caller's own integer words need the same care or hx_rccl_allreduce. */
 int hx_rccl_allreduce_bf16(void* comm, float* buf, uint16_t* scratch, int64_t n, void* stream);
 int hx_rccl_destroy(void* comm);
 

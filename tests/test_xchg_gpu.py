@@ -70,9 +70,11 @@ def ranks():
 class Case:
     """one (W, n): the messages, dst with its guard floats and the red buffers on the device, the model's answers on the host"""
 
-    def __init__(self, W, n, seed):
+    def __init__(self, W, n, seed, messages=None):
+        """messages: fp32 [W, n] to send instead of the seeded X.messages(W, n, seed)"""
         self.W, self.n = W, n
-        self.host = X.messages(W, n, seed)
+        self.host = X.messages(W, n, seed) if messages is None else np.ascontiguousarray(messages, np.float32)
+        assert self.host.shape == (W, n)
         self.sum = X.rank_order_sum(self.host)
         self.msg = torch.from_numpy(self.host).cuda()
         self.dst = torch.full((W, n + X.GUARD), -7.0, dtype=torch.float32, device="cuda")
@@ -107,10 +109,11 @@ class Case:
             assert np.array_equal(X.bits(got[r, :self.n]), X.bits(got[0, :self.n])), (variant, self.W, self.n, "rank", r, "differs from rank 0")
 
 
-def run_case(ranks, variant, W, n, seed, epoch=1, ahead=None):
+def run_case(ranks, variant, W, n, seed, epoch=1, ahead=None, messages=None):
     """Every rank in turn.  Two-stage: one call launches both stages, so pass A leaves every red[r] slice written (checked: the partition itself) and
-    pass B, one epoch later on the same messages, gives the dst to compare.  `ahead`: what the PEERS' flags hold at each call (a peer one exchange ahead)."""
-    c = Case(W, n, seed)
+    pass B, one epoch later on the same messages, gives the dst to compare.  `ahead`: what the PEERS' flags hold at each call (a peer one exchange ahead).
+    -> the Case (its dst rows hold every rank's result)"""
+    c = Case(W, n, seed, messages)
     ranks.zero()
     passes = [epoch] if variant == "oneshot" else [epoch, epoch + 1]
     for k, e in enumerate(passes):
@@ -121,6 +124,7 @@ def run_case(ranks, variant, W, n, seed, epoch=1, ahead=None):
         if variant != "oneshot" and k == 0:
             c.check_red(variant)
     c.check_dst(variant)
+    return c
 
 
 @pytest.mark.parametrize("variant", ["oneshot", "twostage", "twostage-bf16"])
