@@ -15,6 +15,7 @@ import argparse
 import math
 import os
 import time
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -349,8 +350,7 @@ def train_bc(config, device, seed, max_step):
             (mean, std, succ, fire), by_scenario, recs = validate_env(config, eng, env_type, max_step, seed + 12345, device)
             val_n = 50 * len(by_scenario)  # (mixed: the pooled episodes of the three scenarios)
             if mean > high_score or succ / val_n >= success_rate or arttir % 5 == 0:
-                torch.save({k: v.cpu().clone() for k, v in E.unpack(eng.actor, E.ACTOR_LAYOUT).items()},
-                           os.path.join(model_dir, checkpoint_tag(arttir, succ, val_n, mean) + "Actor_Harfang_GYM"))
+                CK.save_hirl_nets(eng, model_dir, checkpoint_tag(arttir, succ, val_n, mean), names=("Actor_",))
                 write_validation_plots(recs, plot_dir, arttir)  # train_all.py:70-89: only beside a checkpoint
                 high_score, success_rate = max(high_score, mean), max(success_rate, succ / val_n)
             print(f"Validation {arttir}: avg reward {mean:.2f} (std {std:.2f}) success {succ / val_n:.2f} fire success {fire / val_n:.2f}", flush=True)
@@ -382,7 +382,12 @@ def launch_ranks(n, argv):
                             "--master-port", str(port), "-m", "hirl4ucav_amd.train_all"] + list(argv), env=env)
 
 
-def main(config):
+# ---- the training run: one plain state object, filled by the functions below in main()'s order -----------------------------------------------------
+Run = SimpleNamespace  # config, rank / world / device / seed, the agent flags, env / replay / inserter / eng / expert tables, writer and directories, driver scalars
+
+
+def start_run(config):
+    """process / device / process-group setup, the seed and snapshot negotiation, the step limit -> Run"""
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     if getattr(config, "gpus", None) and config.gpus != world:
@@ -412,7 +417,7 @@ def main(config):
     set_seed(seed + rank)
     if rank == 0:
         print(f"seed {seed}" + (" (from the snapshot)" if snap_seed is not None else "" if config.seed is not None else " (drawn: no --seed given)"), flush=True)
-    env_type, n = config.env, config.num_envs
+    env_type = config.env
     max_step = (int(config.max_step) if getattr(config, "max_step", None) else default_max_step(env_type)) * (8 if config.render else 1)
     if mixed_refusal(config):
         raise SystemExit("train_all: " + mixed_refusal(config))
@@ -420,155 +425,185 @@ def main(config):
     if snap is not None and (snap_env != env_type if snap_env is not None else env_type == MIXED):
         raise SystemExit(f"train_all: --resume {config.resume} was run with --env {snap_env if snap_env is not None else 'of one scenario (unrecorded)'}, "
                          f"--env {env_type} given")
-    if config.agent == "BC":
-        return train_bc(config, device, seed, max_step)
-    hirl = config.agent == "HIRL"
-    esac = config.agent == "SAC" and config.type == "ESAC"
-    isac = config.agent == "SAC" and config.type == "ISAC"  # SacAgent(imitative=True): the BC-gated policy loss; the minibatch is NOT expert-mixed
-    if isac and (world > 1 or getattr(config, "dtype", "f32") != "f32" or not config.bc_actor):
-        raise SystemExit("train_all: " + isac_refusal(config, world))
-    per = bool(getattr(config, "per", False))  # SacAgent(per=True): prioritized replay, the importance weights through the three losses
-    if per and per_refusal(config, world):
-        raise SystemExit("train_all: " + per_refusal(config, world))
-    per_new = getattr(config, "per_new", "max")  # how a step's rows get their first priority: at pmax, or at a TD error of their own (agent.py:234-246)
-    if not per and per_refusal(config, world):  # (--per_new td without --per)
-        raise SystemExit("train_all: " + per_refusal(config, world))
-    multi_step = int(getattr(config, "multi_step", 1))  # SacAgent(multi_step=n): truncated n-step returns (utils.buffer.NStepInserter)
-    if nstep_refusal(config, world):
-        raise SystemExit("train_all: " + nstep_refusal(config, world))
-    grad_clip, fixed_alpha = getattr(config, "grad_clip", None), getattr(config, "fixed_alpha", None)  # SacAgent(grad_clip=c) / (entropy_tuning=False, ent_coef=x)
-    if clip_refusal(config, world):
-        raise SystemExit("train_all: " + clip_refusal(config, world))
-    batch, buffer_size, checkpoint_rate = 128, config.buffer_size, config.checkpoint_rate  # train_all.py:190-208
-    warm_up_rate = 20 if config.agent == "SAC" else 10  # train_sac.py:203 / train_all.py:207
+    return Run(config=config, rank=rank, world=world, device=device, seed=seed, snap=snap, env_type=env_type, n=config.num_envs, max_step=max_step)
 
-    if per:  # SAC/agent.py:112-118 (alpha 0.6, beta 0.4, beta_annealing 0.0001 are the reference's defaults)
+
+def check_agent_flags(run):
+    """the agent flags, each with its refusal check"""
+    config, world = run.config, run.world
+    run.sac, run.hirl = config.agent == "SAC", config.agent == "HIRL"
+    run.esac = run.sac and config.type == "ESAC"
+    run.isac = run.sac and config.type == "ISAC"  # SacAgent(imitative=True): the BC-gated policy loss; the minibatch is NOT expert-mixed
+    if run.isac and (world > 1 or getattr(config, "dtype", "f32") != "f32" or not config.bc_actor):
+        raise SystemExit("train_all: " + isac_refusal(config, world))
+    run.per = bool(getattr(config, "per", False))  # SacAgent(per=True): prioritized replay, the importance weights through the three losses
+    run.per_new = getattr(config, "per_new", "max")  # how a step's rows get their first priority: at pmax, or at a TD error of their own (agent.py:234-246)
+    run.multi_step = int(getattr(config, "multi_step", 1))  # SacAgent(multi_step=n): truncated n-step returns (utils.buffer.NStepInserter)
+    run.grad_clip, run.fixed_alpha = getattr(config, "grad_clip", None), getattr(config, "fixed_alpha", None)  # SacAgent(grad_clip=c) / (entropy_tuning=False, ent_coef=x)
+    for refusal in (per_refusal, nstep_refusal, clip_refusal):  # (per_refusal without --per: --per_new td on its own)
+        if refusal(config, world):
+            raise SystemExit("train_all: " + refusal(config, world))
+    run.batch = 128  # train_all.py:190-208
+    run.warm_up_rate = 20 if run.sac else 10  # train_sac.py:203 / train_all.py:207
+
+
+def build_env(run):
+    """replay ring, envs, the n-step inserter and the episode statistics"""
+    config, device, n, env_type = run.config, run.device, run.n, run.env_type
+    if run.per:  # SAC/agent.py:112-118 (alpha 0.6, beta 0.4, beta_annealing 0.0001 are the reference's defaults)
         from .utils.buffer import PrioritizedReplay, score_chunk_for
 
-        replay = PrioritizedReplay(buffer_size, device, alpha=config.per_alpha, beta=config.per_beta, beta_annealing=config.per_beta_annealing)
-        replay.score_chunk = score_chunk_for(n)  # --per_new td: rows per chunk of the scoring pass, by the envs per step (measured: DESIGN.md section 8)
+        run.replay = PrioritizedReplay(config.buffer_size, device, alpha=config.per_alpha, beta=config.per_beta, beta_annealing=config.per_beta_annealing)
+        run.replay.score_chunk = score_chunk_for(n)  # --per_new td: rows per chunk of the scoring pass, by the envs per step (measured: DESIGN.md section 8)
     else:
-        replay = DeviceReplay(buffer_size, device)
-    env = BatchedHarfangEnv(n, scenario=mixed_scenarios(n, rank * n).astype(np.int32) if env_type == MIXED else env_type, device=device, seed=seed, max_step=max_step, auto_reset=True,
-                            random_reset=config.random, env_id0=rank * n, replay=replay if multi_step == 1 else None)
-    inserter = None
-    if multi_step > 1:  # the acting launches run without a ring; the inserter's launch behind each step writes the finished n-step rows
+        run.replay = DeviceReplay(config.buffer_size, device)
+    run.env = BatchedHarfangEnv(n, scenario=mixed_scenarios(n, run.rank * n).astype(np.int32) if env_type == MIXED else env_type, device=device, seed=run.seed,
+                                max_step=run.max_step, auto_reset=True, random_reset=config.random, env_id0=run.rank * n,
+                                replay=run.replay if run.multi_step == 1 else None)
+    run.inserter = None
+    if run.multi_step > 1:  # the acting launches run without a ring; the inserter's launch behind each step writes the finished n-step rows
         from .utils.buffer import NStepInserter
 
-        inserter = NStepInserter(replay, n, multi_step, 0.99)  # (SacEngine's gamma, SAC/agent.py:60)
+        run.inserter = NStepInserter(run.replay, n, run.multi_step, 0.99)  # (SacEngine's gamma, SAC/agent.py:60)
     # Episode statistics by scenario (utils/epstat.py): one small launch behind every acting launch.  On under --env mixed, opt-in (--episode_stats) for
     # one scenario; off, the run is launch for launch what it was.  Every rank keeps its own shard's statistics; rank 0 writes its own.
-    estats = last100 = None
+    run.estats = run.last100 = None
     if env_type == MIXED or getattr(config, "episode_stats", False):
         from .utils.epstat import EpisodeStats, Last100
 
-        estats, last100 = EpisodeStats(env), Last100()
+        run.estats, run.last100 = EpisodeStats(run.env), Last100()
 
-    def stats_record():
-        """what every snapshot's driver record carries beside the driver's scalars"""
-        rec = {"env": env_type}
-        if estats is not None:
-            rec["episode_stats"] = {"device": estats.state(), "last100": last100.state()}
-        return rec
 
-    def restore_stats(record):
-        """after CK.load_run: the statistics workspace and the last-100 window of the snapshot; a snapshot without them starts them at zero"""
-        if estats is None:
-            return
-        st = record.get("episode_stats")
-        last100.pairs.clear()
-        if st is None:
-            estats.reset()
-            return
-        estats.load_state(st["device"])
-        for s_, c_ in st["last100"]:
-            last100.add(s_, c_)
-
-    sac = config.agent == "SAC"
-    torch.manual_seed(seed)  # identical initial networks on every rank
-    if sac:  # train_sac.py:187-215: lr 1e-3, hidden [256, 512], batch 128, target_update_interval 3
+def build_engine(run):
+    """the engine of either agent family, with the networks every rank starts from"""
+    torch.manual_seed(run.seed)  # identical initial networks on every rank
+    if run.sac:  # train_sac.py:187-215: lr 1e-3, hidden [256, 512], batch 128, target_update_interval 3
         from .agents import sac_engine as SE
         from .agents.SAC.agent import _xavier_mlp
 
-        eng = SE.SacEngine(batch=batch, lr=1e-3, device=device)
+        eng = SE.SacEngine(batch=run.batch, lr=1e-3, device=run.device)
         eng.load_params(_xavier_mlp(13, 8), _xavier_mlp(17, 1), _xavier_mlp(17, 1))
-        if per:
-            eng.set_prioritized(replay, new_rows=per_new)
-        if grad_clip is not None:  # update_params(..., grad_clip), SAC/agent.py:310-320
-            eng.set_grad_clip(grad_clip)
-        if fixed_alpha is not None:  # SAC/agent.py:108-110
-            eng.set_entropy_tuning(False, fixed_alpha)
-        if inserter is not None:
-            eng.set_multi_step(inserter)
+        if run.per:
+            eng.set_prioritized(run.replay, new_rows=run.per_new)
+        if run.grad_clip is not None:  # update_params(..., grad_clip), SAC/agent.py:310-320
+            eng.set_grad_clip(run.grad_clip)
+        if run.fixed_alpha is not None:  # SAC/agent.py:108-110
+            eng.set_entropy_tuning(False, run.fixed_alpha)
+        if run.inserter is not None:
+            eng.set_multi_step(run.inserter)
     else:
-        eng = E.HirlEngine(batch=batch, slope=0.0 if hirl else 0.01, use_bc=hirl, device=device)
-        eng.load_params(init_actor_state_dict(), init_critic_state_dict(), init_actor_state_dict() if hirl else None)
-    expert_len = bc_len = 0
-    expert = bc_table = None
-    if hirl or esac or isac:
-        tables = load_expert_files(config)
-        labelled = [label_expert(es_k, ea_k, device) for es_k, ea_k in tables]  # each file on its own: no transition spans two files
-        rows, succ = torch.cat([r for r, _ in labelled]), torch.cat([s_ for _, s_ in labelled])
-        es, ea = np.concatenate([t[0] for t in tables]), np.concatenate([t[1] for t in tables])
-        expert = DeviceReplay(rows.shape[0] + 10, device)
-        expert.store_rows(rows, succ)
-        expert_len, bc_len = rows.shape[0], es.shape[0]
-        tab = np.zeros((bc_len, 32), np.float32)
-        tab[:, 0:13], tab[:, 13:17] = es, ea
-        bc_table = torch.from_numpy(tab).to(device)
-        if hirl and config.bc_actor:  # agent.load_bc_actor (train_all.py:311-312): a missing file is an error, as in the reference
-            if not os.path.exists(config.bc_actor):
-                raise FileNotFoundError(f"--bc_actor {config.bc_actor}: no such file")
-            eng.bc_actor.copy_(E.pack(torch.load(config.bc_actor, map_location="cpu"), E.ACTOR_LAYOUT, E.ACTOR_SIZE, device))
-        elif hirl and config.type == "soft" and rank == 0:
-            print("WARNING: HIRL-soft without --bc_actor: the soft weight is estimated against a randomly initialised bc_actor", flush=True)
-        if isac:  # agent.load_bc_actor (SAC/agent.py:158-160): a missing file is an error, as for HIRL
-            if not os.path.exists(config.bc_actor):
-                raise FileNotFoundError(f"--bc_actor {config.bc_actor}: no such file")
-            eng.set_imitative(torch.load(config.bc_actor, map_location="cpu"), slope=0.01)
-    dtype, warning, refusal, mark = resolve_dtype(sac, getattr(config, "dtype", "f32"), snap["driver"] if snap is not None else None)
-    dtype_mark = {"dtype_honoured": True} if mark else {}  # (in every snapshot's driver record)
-    if warning and rank == 0:
+        eng = E.HirlEngine(batch=run.batch, slope=0.0 if run.hirl else 0.01, use_bc=run.hirl, device=run.device)
+        eng.load_params(init_actor_state_dict(), init_critic_state_dict(), init_actor_state_dict() if run.hirl else None)
+    run.eng = eng
+
+
+def load_expert_tables(run):
+    """HIRL / E-SAC / ISAC: the labelled expert ring, the BC (s, a) table and the frozen bc_actor"""
+    config, device, eng = run.config, run.device, run.eng
+    run.expert = run.bc_table = None
+    if not (run.hirl or run.esac or run.isac):
+        return
+    tables = load_expert_files(config)
+    labelled = [label_expert(es_k, ea_k, device) for es_k, ea_k in tables]  # each file on its own: no transition spans two files
+    rows, succ = torch.cat([r for r, _ in labelled]), torch.cat([s_ for _, s_ in labelled])
+    es, ea = np.concatenate([t[0] for t in tables]), np.concatenate([t[1] for t in tables])
+    run.expert = DeviceReplay(rows.shape[0] + 10, device)
+    run.expert.store_rows(rows, succ)
+    tab = np.zeros((es.shape[0], 32), np.float32)
+    tab[:, 0:13], tab[:, 13:17] = es, ea
+    run.bc_table = torch.from_numpy(tab).to(device)
+    if (run.hirl or run.isac) and config.bc_actor and not os.path.exists(config.bc_actor):  # agent.load_bc_actor: a missing file is an error, as in the reference
+        raise FileNotFoundError(f"--bc_actor {config.bc_actor}: no such file")
+    if run.hirl and config.bc_actor:  # agent.load_bc_actor (train_all.py:311-312)
+        eng.bc_actor.copy_(E.pack(torch.load(config.bc_actor, map_location="cpu"), E.ACTOR_LAYOUT, E.ACTOR_SIZE, device))
+    elif run.hirl and config.type == "soft" and run.rank == 0:
+        print("WARNING: HIRL-soft without --bc_actor: the soft weight is estimated against a randomly initialised bc_actor", flush=True)
+    if run.isac:  # agent.load_bc_actor (SAC/agent.py:158-160)
+        eng.set_imitative(torch.load(config.bc_actor, map_location="cpu"), slope=0.01)
+
+
+def set_dtype(run):
+    """--dtype against the agent and the snapshot, then the engine's acting / update formats; the sharded update's transport"""
+    config, eng = run.config, run.eng
+    run.dtype, warning, refusal, mark = resolve_dtype(run.sac, getattr(config, "dtype", "f32"), run.snap["driver"] if run.snap is not None else None)
+    run.dtype_mark = {"dtype_honoured": True} if mark else {}  # (in every snapshot's driver record)
+    if warning and run.rank == 0:
         print(f"WARNING: {warning}", flush=True)
     if refusal:
         raise SystemExit(f"train_all: --resume {config.resume} {refusal}")
-    if world > 1 and os.environ.get("HX_DIST_BACKEND", "nccl") == "nccl" and hasattr(eng, "use_rccl_direct"):
+    if run.world > 1 and os.environ.get("HX_DIST_BACKEND", "nccl") == "nccl" and hasattr(eng, "use_rccl_direct"):
         eng.use_rccl_direct()  # ncclAllReduce enqueued by the library on the engine's stream (hx_rccl_*): no torch.distributed call inside learn()
-    if dtype == "f32x9" and not sac:  # fp32, the acting kernel's 256 -> 512 product through the exact three-way bf16 split of both operands (engine.set_act_dtype)
+    if run.dtype == "f32x9" and not run.sac:  # fp32, the acting kernel's 256 -> 512 product through the exact three-way bf16 split of both operands (engine.set_act_dtype)
         eng.set_act_dtype("f32x9")
-    elif dtype in ("bf16", "bf16_policy"):  # bf16: policy AND critics (BASELINE.json configs[4]; SAC: SacEngine's bf16 path); bf16_policy: policy inference only
+    elif run.dtype in ("bf16", "bf16_policy"):  # bf16: policy AND critics (BASELINE.json configs[4]; SAC: SacEngine's bf16 path); bf16_policy: policy inference only
         eng.set_act_dtype("bf16")
-        if dtype == "bf16":
+        if run.dtype == "bf16":
             eng.set_update_dtype("bf16")
 
+
+def open_run_dir(run):
+    """the run directory, log1.txt and the writer (rank 0); --load_model"""
+    config = run.config
     # ONE run directory for all ranks: rank 0 names it (a minute boundary between ranks would scatter the state_rank<r>.pt shards)
-    log_dir = shared_value(os.path.join(config.result_dir, env_type, config.agent, config.model_name, time.strftime("%Y_%m_%d_%H_%M")), world)
-    model_dir = os.path.join(log_dir, "model")
-    os.makedirs(model_dir, exist_ok=True)
-    plot_dir = os.path.join(log_dir, "plot")  # train_all.py:217-219: beside model and summary
-    writer = None
-    if rank == 0:
+    run.log_dir = shared_value(os.path.join(config.result_dir, run.env_type, config.agent, config.model_name, time.strftime("%Y_%m_%d_%H_%M")), run.world)
+    run.model_dir = os.path.join(run.log_dir, "model")
+    os.makedirs(run.model_dir, exist_ok=True)
+    run.plot_dir = os.path.join(run.log_dir, "plot")  # train_all.py:217-219: beside model and summary
+    run.writer = None
+    if run.rank == 0:
         if config.plot:
-            os.makedirs(plot_dir, exist_ok=True)
-        save_hparams(log_dir, bufferSize=buffer_size, criticLR=1e-3, actorLR=1e-3, batchSize=batch, maxStep=max_step, validationStep=max_step,
-                     hiddenLayer1=256, hiddenLayer2=512, agent=config.agent, model_dir=model_dir, hirl_type=config.type, data_dir=config.expert_csv,
-                     num_envs=n, world=world, seed=seed, dtype=getattr(config, "dtype", "f32"))
-        writer = make_writer(os.path.join(log_dir, "summary"))
-    if config.load_model and not sac:  # agent.loadCheckpoints(tag, model_dir), train_all.py:239-240 (the reference hard-codes the tag)
-        src = config.load_dir or model_dir
-        for name, flat, layout, size in (("Critic_", eng.critic, E.CRITIC_LAYOUT, E.CRITIC_SIZE), ("Actor_", eng.actor, E.ACTOR_LAYOUT, E.ACTOR_SIZE),
-                                         ("TargetCritic_", eng.target_critic, E.CRITIC_LAYOUT, E.CRITIC_SIZE),
-                                         ("TargetActor_", eng.target_actor, E.ACTOR_LAYOUT, E.ACTOR_SIZE)):
-            f = os.path.join(src, config.load_tag + name + "Harfang_GYM")
-            if not os.path.exists(f):
-                raise FileNotFoundError(f"--load_model: {f} not found (--load_dir / --load_tag name the checkpoint)")
-            flat.copy_(E.pack(torch.load(f, map_location="cpu"), layout, size, device))
-        eng.refresh_bf16()
-    run = {"episode": 0, "expert_num": batch if (hirl or esac) else 0, "high_score": -math.inf, "success_rate": 0.0, "arttir": 1}
+            os.makedirs(run.plot_dir, exist_ok=True)
+        save_hparams(run.log_dir, bufferSize=config.buffer_size, criticLR=1e-3, actorLR=1e-3, batchSize=run.batch, maxStep=run.max_step, validationStep=run.max_step,
+                     hiddenLayer1=256, hiddenLayer2=512, agent=config.agent, model_dir=run.model_dir, hirl_type=config.type, data_dir=config.expert_csv,
+                     num_envs=run.n, world=run.world, seed=run.seed, dtype=getattr(config, "dtype", "f32"))
+        run.writer = make_writer(os.path.join(run.log_dir, "summary"))
+    if config.load_model and not run.sac:  # agent.loadCheckpoints(tag, model_dir), train_all.py:239-240 (the reference hard-codes the tag)
+        CK.load_hirl_nets(run.eng, config.load_dir or run.model_dir, config.load_tag,
+                          missing="--load_model: {} not found (--load_dir / --load_tag name the checkpoint)")
+
+
+def stats_record(run):
+    """what every snapshot's driver record carries beside the driver's scalars"""
+    rec = {"env": run.env_type}
+    if run.estats is not None:
+        rec["episode_stats"] = {"device": run.estats.state(), "last100": run.last100.state()}
+    return rec
+
+
+def restore_stats(run, record):
+    """after CK.load_run: the statistics workspace and the last-100 window of the snapshot; a snapshot without them starts them at zero"""
+    if run.estats is None:
+        return
+    st = record.get("episode_stats")
+    run.last100.pairs.clear()
+    if st is None:
+        run.estats.reset()
+        return
+    run.estats.load_state(st["device"])
+    for s_, c_ in st["last100"]:
+        run.last100.add(s_, c_)
+
+
+def driver_record(run, episode):
+    """the driver's part of a whole-run snapshot taken with `episode` episodes finished"""
+    return {"episode": episode, "expert_num": run.expert_num, "high_score": run.high_score, "success_rate": run.success_rate, "arttir": run.arttir,
+            "seed": run.seed, "dtype": run.dtype, **run.dtype_mark, **stats_record(run)}
+
+
+def adopt_record(run, record):
+    """the driver scalars of a driver record (a fresh run's, or a loaded snapshot's); the throughput clock and the env counters' baseline start here"""
+    run.expert_num, run.high_score, run.success_rate, run.arttir = record["expert_num"], record["high_score"], record["success_rate"], record["arttir"]
+    run.episode = run.episode0 = record["episode"]
+    run.t0, run.last_stats = time.time(), run.env.stats_dict()
+
+
+def restore_or_explore(run):
+    """--resume: this rank's shard of the snapshot; a fresh run: the reference's random exploration"""
+    config, env, eng, inserter, estats, n = run.config, run.env, run.eng, run.inserter, run.estats, run.n
+    record = {"episode": 0, "expert_num": run.batch if (run.hirl or run.esac) else 0, "high_score": -math.inf, "success_rate": 0.0, "arttir": 1}
     if config.resume:  # every rank restores its own shard: <resume>/state_rank<r>.pt
-        run = CK.load_run(snap, eng, env, replay)
-        restore_stats(run)
-        del snap
+        record = CK.load_run(run.snap, eng, env, run.replay)
+        restore_stats(run, record)
     else:
         # RANDOM EXPLORATION: 20 episodes of uniform actions in the reference (train_all.py:266-282) = 20*maxStep transitions
         env.reset()
@@ -576,23 +611,27 @@ def main(config):
             inserter.reset(env)
         if estats is not None:
             estats.reset()
-        for _ in range(math.ceil(20 * max_step / (n * world))):
-            a0 = torch.rand((n, 4), device=device) * 2 - 1
+        for _ in range(math.ceil(20 * run.max_step / (n * run.world))):
+            a0 = torch.rand((n, 4), device=run.device) * 2 - 1
             env.step(a0)
             if inserter is not None:
                 inserter.push(env, a0)
             if estats is not None:
                 estats.push()
-        if per and per_new == "td":  # the exploration rows are appended with an error of their own too (SAC/agent.py:176-177, 234-246: the start_steps rows are scored as well)
-            eng.score_new(replay, math.ceil(20 * max_step / (n * world)) * n, seed=seed + 3 + rank)
-        elif per:
-            replay.mark_new()  # the exploration rows enter at the starting maximum priority
-    expert_num, high_score, success_rate, arttir = run["expert_num"], run["high_score"], run["success_rate"], run["arttir"]
-    actions = torch.zeros((n, 4), device=device)
-    t0, episode0 = time.time(), run["episode"]
-    log_rate = 300  # train_all.py:208
-    ret = torch.zeros(n, device=device) if config.log_rewards else None
-    last_stats = env.stats_dict()
+        if run.per and run.per_new == "td":  # the exploration rows are appended with an error of their own too (SAC/agent.py:176-177, 234-246: the start_steps rows are scored as well)
+            eng.score_new(run.replay, math.ceil(20 * run.max_step / (n * run.world)) * n, seed=run.seed + 3 + run.rank)
+        elif run.per:
+            run.replay.mark_new()  # the exploration rows enter at the starting maximum priority
+    run.snap = None  # (the snapshot's tensors are not kept for the length of the run)
+    adopt_record(run, record)
+
+
+def choose_loop(run):
+    """which form the vector step takes, the "vector loop: ..." line, and the starting snapshot a front trip can go back to"""
+    config, world, rank, sac = run.config, run.world, run.rank, run.sac
+    run.actions = torch.zeros((run.n, 4), device=run.device)
+    run.log_rate = 300  # train_all.py:208
+    run.ret = torch.zeros(run.n, device=run.device) if config.log_rewards else None
     # --loop front (default where it applies: HIRL / TD3 in fp32 or bf16 actor + critic, SAC / E-SAC on one GPU at every number of envs — up to 8,192 the
     # per-tile acting role measured faster than the reference's order in every size class, DESIGN.md §8; batch <= 256, one update per step): the env
     # step and the first two launches of learn() (SAC: its first forward launch) as ONE launch (HirlEngine / SacEngine.step_learn) — the minibatch is then drawn from the ring as it stood before
@@ -601,17 +640,17 @@ def main(config):
     # the waiting workgroups of processes that share a GPU add up; eight front-loop ranks on one GPU tripped in round 5).  HX_FRONT_SHARED_GPU=1 takes it
     # anyway (soak tests); the status word + fallback below stay armed either way.
     shared_gpu = world > torch.cuda.device_count() and not os.environ.get("HX_FRONT_SHARED_GPU")
-    front = (config.loop == "front" and not sac and not config.separate_launches and config.updates_per_step == 1 and batch <= 256
-             and getattr(config, "dtype", "f32") in ("f32", "f32x9", "bf16") and not shared_gpu)
-    front_sac = (config.loop == "front" and sac and world == 1 and not config.separate_launches and config.updates_per_step == 1 and batch <= 256 and not per and grad_clip is None
-                 and inserter is None)
+    run.front = (config.loop == "front" and not sac and not config.separate_launches and config.updates_per_step == 1 and run.batch <= 256
+                 and getattr(config, "dtype", "f32") in ("f32", "f32x9", "bf16") and not shared_gpu)
+    run.front_sac = (config.loop == "front" and sac and world == 1 and not config.separate_launches and config.updates_per_step == 1 and run.batch <= 256 and not run.per
+                     and run.grad_clip is None and run.inserter is None)
     if rank == 0:
-        which = "front launch (env step + first launches of learn() in one launch; draw before the insert)" if (front or front_sac) else "reference order"
-        if per:  # the front loop draws before the step's insert: update_priority could then hit slots the step has overwritten
+        which = "front launch (env step + first launches of learn() in one launch; draw before the insert)" if (run.front or run.front_sac) else "reference order"
+        if run.per:  # the front loop draws before the step's insert: update_priority could then hit slots the step has overwritten
             which += " (--per: the front launch draws before the step's insert, so the priorities of the drawn rows could be written into overwritten slots)"
-        if inserter is not None:  # the front launch's acting workgroups insert one-step rows themselves
-            which += f" (--multi_step {multi_step}: the n-step rows are written by a launch of their own behind the acting launch)"
-        if sac and grad_clip is not None and not per:  # the clipped update is the staged sequence (gradients -> norm -> clipped step): its first launch is its own
+        if run.inserter is not None:  # the front launch's acting workgroups insert one-step rows themselves
+            which += f" (--multi_step {run.multi_step}: the n-step rows are written by a launch of their own behind the acting launch)"
+        if sac and run.grad_clip is not None and not run.per:  # the clipped update is the staged sequence (gradients -> norm -> clipped step): its first launch is its own
             which += " (--grad_clip: the clipped update runs as stages, which have no front form)"
         print(f"vector loop: {which}" + (f" ({world} ranks share a GPU: the front launch is for one process per GPU)" if (shared_gpu and config.loop == "front") else ""),
               flush=True)
@@ -619,206 +658,269 @@ def main(config):
     # observed on gfx950, promised by nobody.  A wait that gives up sets a sticky status word: it is read every --status_check_every vector steps (one host
     # sync; every rank takes the same decision), and on a trip every rank goes back to the newest snapshot and continues in the reference's order INSIDE this
     # process (--on_front_trip fallback, the default), or the run exits with code 3 (no snapshot yet, or --on_front_trip exit).
-    check_every = max(int(config.status_check_every), 0)
-    snap_path = os.path.join(config.resume, f"state_rank{rank}.pt") if config.resume else None  # the newest whole-run snapshot this process can go back to
-    steps_since_check = 0
-
-    def front_tripped():
-        code = eng.front_status()
-        if world > 1:
-            t = torch.tensor([code], dtype=torch.int32, device=device if torch.distributed.get_backend() == "nccl" else "cpu")
-            torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-            code = int(t.item())
-        return code
-
-    if front and check_every and config.on_front_trip == "fallback" and config.snapshot_every and snap_path is None:
+    run.check_every = max(int(config.status_check_every), 0)
+    run.steps_since_check = 0
+    run.snap_path = os.path.join(config.resume, f"state_rank{rank}.pt") if config.resume else None  # the newest whole-run snapshot this process can go back to
+    if run.front and run.check_every and config.on_front_trip == "fallback" and config.snapshot_every and run.snap_path is None:
         # a trip before the first periodic snapshot would leave nothing to go back to: take one of the starting state (every rank its shard)
-        if world > 1:
-            torch.distributed.barrier()
-        snap_path = os.path.join(log_dir, f"state_rank{rank}.pt")
-        CK.save_run(snap_path, eng, env, replay, {"episode": episode0, "expert_num": expert_num, "high_score": high_score, "success_rate": success_rate,
-                                                  "arttir": arttir, "seed": seed, "dtype": dtype, **dtype_mark, **stats_record()})
-        if world > 1:
-            torch.distributed.barrier()
-    episode = episode0
-    while episode < config.episodes:
-        w_now, warm = bc_weight_schedule(config.type, episode, config.bc_weight) if hirl else (0.0, 0.0)
-        tripped = 0
-        for step in range(max_step):
-            if front and check_every:
-                steps_since_check += 1
-                if steps_since_check >= check_every:
-                    steps_since_check = 0
-                    tripped = front_tripped()
-                    if tripped:
-                        break
-            if front and step < max_step - 1:  # (the last step of an episode has no learn() behind it, train_all.py:346-347)
-                expert_num = expert_num_after(expert_num, step, warm_up_rate)
-                eng.step_learn(env, expert, bc_table, n_main=batch - expert_num, act_sigma=0.1, act_seed=seed + 1, out=actions, sample_seed=seed + 2 + rank,
-                               bc_weight_now=w_now, bc_warm_up_weight=warm)
-                w_now = None  # afterwards learn()'s own returned weight is fed back (train_all.py:361): the stored device value
-                if estats is not None:
-                    estats.push()
-                if ret is not None:
-                    ret += env.reward
-                if writer is not None and step % log_rate == 0:  # Loss/* every 300 steps, train_all.py:362-367
-                    c_, a_, b_, r__, f_, _w = eng.losses_host()
-                    for tag, v in (("Loss/Critic_Loss", c_), ("Loss/Actor_Loss", a_), ("Loss/BC_Loss", b_), ("Loss/RL_Loss", r__), ("Loss/BC_Fire_Loss", f_)):
-                        writer.add_scalar(tag, v, step + episode * max_step)
-                continue
-            if front_sac and step < max_step - 1:  # SAC / E-SAC: explore + env step + the first forward launch of learn() in one launch (SacEngine.step_learn)
-                expert_num = expert_num_after(expert_num, step, warm_up_rate)
-                eng.step_learn(env, expert if (esac or isac) else None, n_main=batch - expert_num, act_seed=seed + 1, out=actions, sample_seed=seed + 2 + rank)
-                if estats is not None:
-                    estats.push()
-                if ret is not None:
-                    ret += env.reward
-                if isac and writer is not None and step % log_rate == 0:  # SAC/agent.py:353-359
-                    log_imitative(writer, eng, step + episode * max_step)
-                continue
-            if config.separate_launches:  # chooseAction, then env.step: two launches
-                eng.act(env.obs, seed=seed + 1, row0=env.env_id0, out=actions) if sac else eng.act(env.obs, sigma=0.1, seed=seed + 1, row0=env.env_id0, out=actions)
-                env.step(actions)
-            elif sac:                     # the same in ONE launch (identical values; only the order in which a step's rows enter the
-                eng.act_step(env, seed=seed + 1, out=actions)              # replay ring depends on the workgroup schedule)
-            else:
-                eng.act_step(env, sigma=0.1, seed=seed + 1, out=actions)
-            if inserter is not None:
-                inserter.push(env, actions)  # this step's finished n-step rows (at most multi_step * n of them)
-            if estats is not None:
-                estats.push()
-            if per and per_new == "td":
-                log_new = writer is not None and step % log_rate == 0
-                marked0 = replay.marked if log_new else 0  # (a host read, at the logging step only)
-                eng.score_new(replay, n, seed=seed + 3 + rank)  # this step's rows enter at |Q1(s, a) - y| of their own (no host sync)
-                if log_new:  # the mean over the rows this call covered (a step stores at most n)
-                    k = min(max(replay.marked - marked0, 1), n)
-                    writer.add_scalar("stats/per_mean_new_error", float(replay.errors[:k].mean()), step + episode * max_step)
-            elif per:
-                replay.mark_new(n if inserter is None else inserter.max_rows)  # this step's rows enter at the running maximum priority (one launch, no host sync)
-            if ret is not None:
-                ret += env.reward
-            if step == max_step - 1:
-                break
-            expert_num = expert_num_after(expert_num, step, warm_up_rate)
-            for _ in range(config.updates_per_step):
-                if sac:  # train_sac.py:270-273 (SAC) / :401-403 (E-SAC: expert rows mixed in while expert_num > 0)
-                    eng.sample(replay, expert if esac else None, n_main=batch - expert_num, seed=seed + 2 + rank, defer=True)
-                    if isac:  # expert_memory.sample(batch_size), SAC/agent.py:392: the second batch, drawn inside learn() too
-                        eng.sample_expert(expert, seed=seed + 2 + rank, defer=True)
-                    eng.learn()
-                    continue
-                eng.sample(replay, expert, bc_table, n_main=batch - expert_num, seed=seed + 2 + rank, defer=True)  # drawn inside learn()'s first launch
-                eng.learn(bc_weight_now=w_now, bc_warm_up_weight=warm)
-                w_now = None  # afterwards learn()'s own returned weight is fed back (train_all.py:361): the stored device value
-            if writer is not None and step % log_rate == 0 and not sac:  # Loss/* every 300 steps, train_all.py:362-367
-                c_, a_, b_, r__, f_, _w = eng.losses_host()
-                for tag, v in (("Loss/Critic_Loss", c_), ("Loss/Actor_Loss", a_), ("Loss/BC_Loss", b_), ("Loss/RL_Loss", r__), ("Loss/BC_Fire_Loss", f_)):
-                    writer.add_scalar(tag, v, step + episode * max_step)
-            if isac and writer is not None and step % log_rate == 0:  # SAC/agent.py:353-359
-                log_imitative(writer, eng, step + episode * max_step)
-            if sac and grad_clip is not None and writer is not None and step % log_rate == 0:
-                for tag, v in zip(("q1", "q2", "policy"), eng.grad_norms_host()[0]):
-                    writer.add_scalar("stats/grad_norm_" + tag, v, step + episode * max_step)
-            if per and writer is not None and step % log_rate == 0:
-                writer.add_scalar("stats/per_beta", replay.beta, step + episode * max_step)
-                writer.add_scalar("stats/per_max_priority", replay.pmax, step + episode * max_step)
-        if front and not tripped:
-            tripped = front_tripped()  # ... and at every episode's end: nothing of a tripped episode reaches a validation, a checkpoint or a snapshot
-        if tripped:
-            why = (f"front launch: an in-launch wait gave up (status word {tripped}: " + " and ".join(w for b_, w in ((1, "launch B waiting for launch A's rows"),
-                   (2, "launch C waiting for launches A / B")) if tripped & b_) + f") in episode {episode + 1} — the minibatches read since the last check are suspect")
-            if config.on_front_trip != "fallback" or snap_path is None or not os.path.exists(snap_path):
-                if rank == 0:
-                    print(why + "; " + ("--on_front_trip exit" if config.on_front_trip != "fallback" else "no snapshot to go back to (--snapshot_every)") +
-                          ": stopping.  `--loop reference` runs the same update without in-launch waits", flush=True)
-                raise SystemExit(3)
-            run = CK.load_run(snap_path, eng, env, replay)  # every rank its own shard; all shards of a snapshot come from the same episode
-            restore_stats(run)
-            eng.front_reset()
-            expert_num, high_score, success_rate, arttir = run["expert_num"], run["high_score"], run["success_rate"], run["arttir"]
-            episode = episode0 = run["episode"]
-            t0, last_stats, front = time.time(), env.stats_dict(), False
-            if ret is not None:
-                ret.zero_()
-            if rank == 0:
-                print(why + f": back to the snapshot of episode {episode} ({snap_path}), continuing in the REFERENCE's order (no in-launch waits)", flush=True)
-                if dtype == "f32" and eng.front_x9 and (eng.x9_rows is None or n < eng.x9_rows):  # [ADVICE r5] say what else changes with the loop
-                    print(f"note: the front launch acted in the exact-split format at every size; in the reference's order {n} envs act on fp32 MFMA "
-                          f"(the split applies from {eng.x9_rows} rows on): fp32 results up to summation order from here on", flush=True)
-                print(f"note: scalars and checkpoints written for episodes {episode + 1}.. before the trip are written again from here", flush=True)
-                if writer is not None:
-                    writer.add_scalar("Others/Front_trip_rollback_to_episode", episode, episode)
+        write_snapshot(run, run.episode0)
+
+
+def write_snapshot(run, episode):
+    """whole-run state for --resume and for the way back after a front trip: one file per rank, `episode` episodes finished"""
+    if run.world > 1:
+        torch.distributed.barrier()  # every shard of a snapshot comes from the same episode ...
+    path = os.path.join(run.log_dir, f"state_rank{run.rank}.pt")
+    CK.save_run(path, run.eng, run.env, run.replay, driver_record(run, episode))
+    if run.world > 1:
+        torch.distributed.barrier()  # ... and nobody runs ahead while a shard is still being written
+    run.snap_path = path
+
+
+# ---- the vector step: two hooks every form shares, three forms --------------------------------------------------------------------------------------
+def after_env_step(run, step):
+    """Behind every acting launch, in this order: the n-step rows, the episode statistics, the new rows' first priorities, the reward sum.  (The front
+    forms run without an inserter and without --per: choose_loop.)"""
+    if run.inserter is not None:
+        run.inserter.push(run.env, run.actions)  # this step's finished n-step rows (at most multi_step * n of them)
+    if run.estats is not None:
+        run.estats.push()
+    if run.per and run.per_new == "td":
+        replay, n, writer = run.replay, run.n, run.writer
+        log_new = writer is not None and step % run.log_rate == 0
+        marked0 = replay.marked if log_new else 0  # (a host read, at the logging step only)
+        run.eng.score_new(replay, n, seed=run.seed + 3 + run.rank)  # this step's rows enter at |Q1(s, a) - y| of their own (no host sync)
+        if log_new:  # the mean over the rows this call covered (a step stores at most n)
+            k = min(max(replay.marked - marked0, 1), n)
+            writer.add_scalar("stats/per_mean_new_error", float(replay.errors[:k].mean()), step + run.episode * run.max_step)
+    elif run.per:
+        run.replay.mark_new(run.n if run.inserter is None else run.inserter.max_rows)  # this step's rows enter at the running maximum priority (one launch, no host sync)
+    if run.ret is not None:
+        run.ret += run.env.reward
+
+
+def log_step_scalars(run, step):
+    """Behind a step's learn(), every log_rate steps on rank 0.  (The front forms write neither grad norms nor stats/per_*: they never run with
+    --grad_clip or --per, choose_loop.)"""
+    writer, eng = run.writer, run.eng
+    if writer is None or step % run.log_rate != 0:
+        return
+    at = step + run.episode * run.max_step
+    if not run.sac:  # Loss/* every 300 steps, train_all.py:362-367
+        c_, a_, b_, r__, f_, _w = eng.losses_host()
+        for tag, v in (("Loss/Critic_Loss", c_), ("Loss/Actor_Loss", a_), ("Loss/BC_Loss", b_), ("Loss/RL_Loss", r__), ("Loss/BC_Fire_Loss", f_)):
+            writer.add_scalar(tag, v, at)
+    if run.isac:  # SAC/agent.py:353-359
+        log_imitative(writer, eng, at)
+    if run.sac and run.grad_clip is not None:
+        for tag, v in zip(("q1", "q2", "policy"), eng.grad_norms_host()[0]):
+            writer.add_scalar("stats/grad_norm_" + tag, v, at)
+    if run.per:
+        writer.add_scalar("stats/per_beta", run.replay.beta, at)
+        writer.add_scalar("stats/per_max_priority", run.replay.pmax, at)
+
+
+def step_front_hirl(run, step, w_now, warm):
+    """HIRL / TD3: env step + the first two launches of learn() as one launch (HirlEngine.step_learn)"""
+    run.expert_num = expert_num_after(run.expert_num, step, run.warm_up_rate)
+    run.eng.step_learn(run.env, run.expert, run.bc_table, n_main=run.batch - run.expert_num, act_sigma=0.1, act_seed=run.seed + 1, out=run.actions,
+                       sample_seed=run.seed + 2 + run.rank, bc_weight_now=w_now, bc_warm_up_weight=warm)
+    after_env_step(run, step)
+    log_step_scalars(run, step)
+
+
+def step_front_sac(run, step):
+    """SAC / E-SAC / ISAC: explore + env step + the first forward launch of learn() in one launch (SacEngine.step_learn); ISAC's expert batch rides in it"""
+    run.expert_num = expert_num_after(run.expert_num, step, run.warm_up_rate)
+    run.eng.step_learn(run.env, run.expert if (run.esac or run.isac) else None, n_main=run.batch - run.expert_num, act_seed=run.seed + 1, out=run.actions,
+                       sample_seed=run.seed + 2 + run.rank)
+    after_env_step(run, step)
+    log_step_scalars(run, step)
+
+
+def step_reference(run, step, w_now, warm):
+    """the reference's order: act -> env step -> insert -> draw -> learn (--updates_per_step times); an episode's last step only acts"""
+    config, eng, env, seed, sac = run.config, run.eng, run.env, run.seed, run.sac
+    if config.separate_launches:  # chooseAction, then env.step: two launches
+        eng.act(env.obs, seed=seed + 1, row0=env.env_id0, out=run.actions) if sac else eng.act(env.obs, sigma=0.1, seed=seed + 1, row0=env.env_id0, out=run.actions)
+        env.step(run.actions)
+    elif sac:                     # the same in ONE launch (identical values; only the order in which a step's rows enter the
+        eng.act_step(env, seed=seed + 1, out=run.actions)              # replay ring depends on the workgroup schedule)
+    else:
+        eng.act_step(env, sigma=0.1, seed=seed + 1, out=run.actions)
+    after_env_step(run, step)
+    if step == run.max_step - 1:
+        return
+    run.expert_num = expert_num_after(run.expert_num, step, run.warm_up_rate)
+    n_main, sample_seed = run.batch - run.expert_num, seed + 2 + run.rank
+    for _ in range(config.updates_per_step):
+        if sac:  # train_sac.py:270-273 (SAC) / :401-403 (E-SAC: expert rows mixed in while expert_num > 0)
+            eng.sample(run.replay, run.expert if run.esac else None, n_main=n_main, seed=sample_seed, defer=True)
+            if run.isac:  # expert_memory.sample(batch_size), SAC/agent.py:392: the second batch, drawn inside learn() too
+                eng.sample_expert(run.expert, seed=sample_seed, defer=True)
+            eng.learn()
             continue
-        if estats is not None:  # the env episodes that ended during this driver episode, by scenario (one device-to-host copy, then the partials are cleared)
-            by_scenario = estats.read_and_clear()
-            log_episode_stats(writer, episode, by_scenario, last100)
-            if rank == 0:
-                print(f"Episode {episode + 1}: " + " | ".join(f"{k} ended {v['count']} (done {v['done']}, time limit {v['time_limit']}) return {v['mean']:.2f} "
-                                                              f"length {v['mean_len']:.1f}" for k, v in by_scenario.items() if v["count"]), flush=True)
+        eng.sample(run.replay, run.expert, run.bc_table, n_main=n_main, seed=sample_seed, defer=True)  # drawn inside learn()'s first launch
+        eng.learn(bc_weight_now=w_now, bc_warm_up_weight=warm)
+        w_now = None  # afterwards learn()'s own returned weight is fed back (train_all.py:361): the stored device value
+    log_step_scalars(run, step)
+
+
+def front_tripped(run):
+    """the front launch's status word, the worst over the ranks (0: no in-launch wait gave up)"""
+    code = run.eng.front_status()
+    if run.world > 1:
+        t = torch.tensor([code], dtype=torch.int32, device=run.device if torch.distributed.get_backend() == "nccl" else "cpu")
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+        code = int(t.item())
+    return code
+
+
+def run_episode(run):
+    """max_step vector steps, each in the form that applies -> the front launch's status word (non-zero: the episode was left at that read)"""
+    config, max_step = run.config, run.max_step
+    w_now, warm = bc_weight_schedule(config.type, run.episode, config.bc_weight) if run.hirl else (0.0, 0.0)
+    front = run.front  # (read every episode: a trip turns it off)
+    for step in range(max_step):
+        if front and run.check_every:
+            run.steps_since_check += 1
+            if run.steps_since_check >= run.check_every:
+                run.steps_since_check = 0
+                tripped = front_tripped(run)
+                if tripped:
+                    return tripped
+        if front and step < max_step - 1:  # (the last step of an episode has no learn() behind it, train_all.py:346-347: it only acts)
+            step_front_hirl(run, step, w_now, warm)
+        elif run.front_sac and step < max_step - 1:
+            step_front_sac(run, step)
+        else:
+            step_reference(run, step, w_now, warm)
+        w_now = None  # given to an episode's first learn(); afterwards learn()'s own returned weight is fed back (train_all.py:361): the stored device value
+    return front_tripped(run) if front else 0  # ... and at every episode's end: nothing of a tripped episode reaches a validation, a checkpoint or a snapshot
+
+
+def roll_back(run, tripped):
+    """An in-launch wait of the front launch gave up: back to the newest snapshot and on in the reference's order, or exit code 3"""
+    config, eng, rank, snap_path = run.config, run.eng, run.rank, run.snap_path
+    why = (f"front launch: an in-launch wait gave up (status word {tripped}: " + " and ".join(w for b_, w in ((1, "launch B waiting for launch A's rows"),
+           (2, "launch C waiting for launches A / B")) if tripped & b_) + f") in episode {run.episode + 1} — the minibatches read since the last check are suspect")
+    if config.on_front_trip != "fallback" or snap_path is None or not os.path.exists(snap_path):
         if rank == 0:
-            c, a, b, r_, f, w = eng.losses_host()
-            st = env.stats_dict()
-            sps = (episode + 1 - episode0) * max_step * n * world / (time.time() - t0)
-            names = ("q1", "q2", "policy", "entropy_loss", "alpha") if sac else ("critic", "actor", "bc", "rl", "bc_weight")
-            vals = (c, a, b, r_, w)
-            print(f"Episode {episode + 1}: " + " ".join(f"{k} {v:.4f}" for k, v in zip(names, vals)) + f" | episodes {st['episodes']} "
-                  f"kills {st['kills']} fire-success {st['fire_success_episodes']} | {sps:,.0f} env steps/s", flush=True)
-            if writer is not None:  # Training/* per episode, train_all.py:383-388: rates over the env episodes that ENDED during this driver episode
-                ended = max(st["episodes"] - last_stats["episodes"], 1)
-                writer.add_scalar("Training/Last 50 Episode Train success rate", (st["kills"] - last_stats["kills"]) / ended, episode)
-                writer.add_scalar("Training/Last 50 Episode Fire success rate", (st["fire_success_episodes"] - last_stats["fire_success_episodes"]) / ended, episode)
-                writer.add_scalar("Others/BC_weight", w, episode)
-                writer.add_scalar("Others/Nonfinite_actions", st.get("nonfinite_actions", 0), episode)
-                if ret is not None:
-                    tot = float(ret.mean())
-                    writer.add_scalar("Training/Episode Reward", tot, episode)
-                    writer.add_scalar("Training/Average Step Reward", tot / max_step, episode)
-                    ret.zero_()
-                last_stats = st
-        if (episode + 1) % checkpoint_rate == 0 and rank == 0:  # VALIDATION, train_all.py:400-402 / train_sac.py:431-433
-            (mean, std, succ, fire), val_by_scenario, recs = validate_env(config, eng, env_type, max_step, seed + 12345, device, sac)
-            val_n = 50 * len(val_by_scenario)  # (mixed: the pooled episodes of the three scenarios)
-            if mean > high_score or succ / val_n >= success_rate or arttir % 5 == 0:
-                tag = checkpoint_tag(arttir, succ, val_n, mean)
-                write_validation_plots(recs, plot_dir, arttir)  # train_all.py:70-89: the last validation episode's track, only beside a checkpoint
-                if sac:  # SacAgent.save_models, SAC/agent.py:440-444
-                    eng.save_models(model_dir, tag)
-                else:    # Agent.saveCheckpoints, HIRL.py:336-342
-                    for name, flat, layout in (("Critic_", eng.critic, E.CRITIC_LAYOUT), ("Actor_", eng.actor, E.ACTOR_LAYOUT),
-                                               ("TargetCritic_", eng.target_critic, E.CRITIC_LAYOUT), ("TargetActor_", eng.target_actor, E.ACTOR_LAYOUT)):
-                        torch.save({k: v.cpu().clone() for k, v in E.unpack(flat, layout).items()}, os.path.join(model_dir, tag + name + "Harfang_GYM"))
-                high_score, success_rate = max(high_score, mean), max(success_rate, succ / val_n)
-            print(f"Validation {arttir}: avg reward {mean:.2f} (std {std:.2f}) success {succ / val_n:.2f} fire success {fire / val_n:.2f}", flush=True)
-            if len(val_by_scenario) > 1:
-                for k_, (m_, s_, k2_, f_) in val_by_scenario.items():
-                    print(f"  {k_}: avg reward {m_:.2f} (std {s_:.2f}) success {k2_ / 50:.2f} fire success {f_ / 50:.2f}", flush=True)
-            log_validation_by_scenario(writer, episode, val_by_scenario)
-            log_validation(writer, episode, mean, std, succ / val_n, fire / val_n)
-            arttir += 1
-        # sharded run: the replicas must not have drifted apart
-        check_due = (episode + 1) % checkpoint_rate == 0 or (config.replica_check_every and (episode + 1) % config.replica_check_every == 0)
-        if world > 1 and check_due:
-            mine = torch.tensor([eng.replica_checksum()], dtype=torch.int64, device=device)
-            every = [torch.zeros_like(mine) for _ in range(world)]
-            torch.distributed.all_gather(every, mine)
-            if any(int(c.item()) != int(mine.item()) for c in every):
-                raise RuntimeError(f"rank {rank}: network replicas diverged at episode {episode + 1}")
-        if config.snapshot_every and (episode + 1) % config.snapshot_every == 0:  # whole-run state for --resume (one file per rank)
-            if world > 1:
-                torch.distributed.barrier()  # every shard of a snapshot comes from the same episode ...
-            CK.save_run(os.path.join(log_dir, f"state_rank{rank}.pt"), eng, env, replay,
-                        {"episode": episode + 1, "expert_num": expert_num, "high_score": high_score, "success_rate": success_rate, "arttir": arttir,
-                         "seed": seed, "dtype": dtype, **dtype_mark, **stats_record()})
-            if world > 1:
-                torch.distributed.barrier()  # ... and nobody runs ahead while a shard is still being written
-            snap_path = os.path.join(log_dir, f"state_rank{rank}.pt")
-        episode += 1
-    if writer is not None:
-        writer.close()
-    if world > 1:
+            print(why + "; " + ("--on_front_trip exit" if config.on_front_trip != "fallback" else "no snapshot to go back to (--snapshot_every)") +
+                  ": stopping.  `--loop reference` runs the same update without in-launch waits", flush=True)
+        raise SystemExit(3)
+    record = CK.load_run(snap_path, eng, run.env, run.replay)  # every rank its own shard; all shards of a snapshot come from the same episode
+    restore_stats(run, record)
+    eng.front_reset()
+    adopt_record(run, record)
+    run.front = False
+    if run.ret is not None:
+        run.ret.zero_()
+    if rank == 0:
+        print(why + f": back to the snapshot of episode {run.episode} ({snap_path}), continuing in the REFERENCE's order (no in-launch waits)", flush=True)
+        if run.dtype == "f32" and eng.front_x9 and (eng.x9_rows is None or run.n < eng.x9_rows):  # [ADVICE r5] say what else changes with the loop
+            print(f"note: the front launch acted in the exact-split format at every size; in the reference's order {run.n} envs act on fp32 MFMA "
+                  f"(the split applies from {eng.x9_rows} rows on): fp32 results up to summation order from here on", flush=True)
+        print(f"note: scalars and checkpoints written for episodes {run.episode + 1}.. before the trip are written again from here", flush=True)
+        if run.writer is not None:
+            run.writer.add_scalar("Others/Front_trip_rollback_to_episode", run.episode, run.episode)
+
+
+# ---- an episode's end ---------------------------------------------------------------------------------------------------------------------------------
+def log_scenario_stats(run):
+    """the env episodes that ended during this driver episode, by scenario (one device-to-host copy, then the partials are cleared)"""
+    if run.estats is None:
+        return
+    by_scenario = run.estats.read_and_clear()
+    log_episode_stats(run.writer, run.episode, by_scenario, run.last100)
+    if run.rank == 0:
+        print(f"Episode {run.episode + 1}: " + " | ".join(f"{k} ended {v['count']} (done {v['done']}, time limit {v['time_limit']}) return {v['mean']:.2f} "
+                                                          f"length {v['mean_len']:.1f}" for k, v in by_scenario.items() if v["count"]), flush=True)
+
+
+def log_episode(run):
+    """rank 0: the `Episode N:` line, Training/* and Others/*"""
+    if run.rank != 0:
+        return
+    episode, writer, ret = run.episode, run.writer, run.ret
+    c, a, b, r_, f, w = run.eng.losses_host()
+    st = run.env.stats_dict()
+    sps = (episode + 1 - run.episode0) * run.max_step * run.n * run.world / (time.time() - run.t0)
+    names = ("q1", "q2", "policy", "entropy_loss", "alpha") if run.sac else ("critic", "actor", "bc", "rl", "bc_weight")
+    print(f"Episode {episode + 1}: " + " ".join(f"{k} {v:.4f}" for k, v in zip(names, (c, a, b, r_, w))) + f" | episodes {st['episodes']} "
+          f"kills {st['kills']} fire-success {st['fire_success_episodes']} | {sps:,.0f} env steps/s", flush=True)
+    if writer is not None:  # Training/* per episode, train_all.py:383-388: rates over the env episodes that ENDED during this driver episode
+        ended = max(st["episodes"] - run.last_stats["episodes"], 1)
+        writer.add_scalar("Training/Last 50 Episode Train success rate", (st["kills"] - run.last_stats["kills"]) / ended, episode)
+        writer.add_scalar("Training/Last 50 Episode Fire success rate", (st["fire_success_episodes"] - run.last_stats["fire_success_episodes"]) / ended, episode)
+        writer.add_scalar("Others/BC_weight", w, episode)
+        writer.add_scalar("Others/Nonfinite_actions", st.get("nonfinite_actions", 0), episode)
+        if ret is not None:
+            tot = float(ret.mean())
+            writer.add_scalar("Training/Episode Reward", tot, episode)
+            writer.add_scalar("Training/Average Step Reward", tot / run.max_step, episode)
+            ret.zero_()
+        run.last_stats = st
+
+
+def validate_and_checkpoint(run):
+    """rank 0: VALIDATION, train_all.py:400-402 / train_sac.py:431-433, and the checkpoint where the reference's rule asks for one"""
+    config, eng, episode, arttir = run.config, run.eng, run.episode, run.arttir
+    (mean, std, succ, fire), val_by_scenario, recs = validate_env(config, eng, run.env_type, run.max_step, run.seed + 12345, run.device, run.sac)
+    val_n = 50 * len(val_by_scenario)  # (mixed: the pooled episodes of the three scenarios)
+    if mean > run.high_score or succ / val_n >= run.success_rate or arttir % 5 == 0:
+        tag = checkpoint_tag(arttir, succ, val_n, mean)
+        write_validation_plots(recs, run.plot_dir, arttir)  # train_all.py:70-89: the last validation episode's track, only beside a checkpoint
+        if run.sac:  # SacAgent.save_models, SAC/agent.py:440-444
+            eng.save_models(run.model_dir, tag)
+        else:    # Agent.saveCheckpoints, HIRL.py:336-342
+            CK.save_hirl_nets(eng, run.model_dir, tag)
+        run.high_score, run.success_rate = max(run.high_score, mean), max(run.success_rate, succ / val_n)
+    print(f"Validation {arttir}: avg reward {mean:.2f} (std {std:.2f}) success {succ / val_n:.2f} fire success {fire / val_n:.2f}", flush=True)
+    if len(val_by_scenario) > 1:
+        for k_, (m_, s_, k2_, f_) in val_by_scenario.items():
+            print(f"  {k_}: avg reward {m_:.2f} (std {s_:.2f}) success {k2_ / 50:.2f} fire success {f_ / 50:.2f}", flush=True)
+    log_validation_by_scenario(run.writer, episode, val_by_scenario)
+    log_validation(run.writer, episode, mean, std, succ / val_n, fire / val_n)
+    run.arttir += 1
+
+
+def check_replicas(run):
+    """sharded run: the replicas must not have drifted apart"""
+    mine = torch.tensor([run.eng.replica_checksum()], dtype=torch.int64, device=run.device)
+    every = [torch.zeros_like(mine) for _ in range(run.world)]
+    torch.distributed.all_gather(every, mine)
+    if any(int(c.item()) != int(mine.item()) for c in every):
+        raise RuntimeError(f"rank {run.rank}: network replicas diverged at episode {run.episode + 1}")
+
+
+def main(config):
+    run = start_run(config)
+    if config.agent == "BC":
+        return train_bc(config, run.device, run.seed, run.max_step)
+    for phase in (check_agent_flags, build_env, build_engine, load_expert_tables, set_dtype, open_run_dir, restore_or_explore, choose_loop):
+        phase(run)
+    while run.episode < config.episodes:
+        tripped = run_episode(run)
+        if tripped:
+            roll_back(run, tripped)
+            continue
+        log_scenario_stats(run)
+        log_episode(run)
+        done = run.episode + 1
+        validation_due = done % config.checkpoint_rate == 0
+        if validation_due and run.rank == 0:
+            validate_and_checkpoint(run)
+        if run.world > 1 and (validation_due or (config.replica_check_every and done % config.replica_check_every == 0)):
+            check_replicas(run)
+        if config.snapshot_every and done % config.snapshot_every == 0:
+            write_snapshot(run, done)
+        run.episode += 1
+    if run.writer is not None:
+        run.writer.close()
+    if run.world > 1:
         torch.distributed.destroy_process_group()
-    return log_dir
+    return run.log_dir
 
 
 def log_imitative(writer, eng, at):

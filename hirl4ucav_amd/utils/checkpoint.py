@@ -7,10 +7,13 @@ the Philox streams of the sampler and of the exploration noise), the env state w
 the filled part of the replay ring, the host RNGs, and the driver's own scalars.  A run resumed from a snapshot
 continues bit-identically to the run that was never stopped (tests/test_facade_gpu.py).
 """
+import os
 import random
 
 import numpy as np
 import torch
+
+from ..agents import engine as E
 
 ENGINE_COUNTERS = ("critic_step", "actor_step", "update_count", "actor_trainable", "sample_calls", "act_calls", "learning_steps")
 
@@ -134,8 +137,6 @@ def load_env_state(env, st):
 
 def save_run(path, eng, env, replay, driver):
     """Written to a temporary file and renamed: a kill during the ~130 MB write leaves the previous snapshot intact."""
-    import os
-
     torch.cuda.synchronize()
     tmp = path + ".tmp"
     torch.save({"engine": engine_state(eng), "env": env_state(env), "replay": replay_state(replay), "driver": dict(driver),
@@ -159,3 +160,28 @@ def load_run(path, eng, env, replay):
     torch.set_rng_state(snap["rng"]["torch"])
     torch.cuda.set_rng_state(snap["rng"]["torch_cuda"], env.device)
     return snap["driver"]
+
+
+# ---- the reference's four network files (Agent.saveCheckpoints / loadCheckpoints, HIRL.py:336-350): <dir>/<tag><name>Harfang_GYM ----
+HIRL_NETS = (("Critic_", "critic", E.CRITIC_LAYOUT, E.CRITIC_SIZE), ("Actor_", "actor", E.ACTOR_LAYOUT, E.ACTOR_SIZE),  # (name, attribute, layout, size)
+             ("TargetCritic_", "target_critic", E.CRITIC_LAYOUT, E.CRITIC_SIZE), ("TargetActor_", "target_actor", E.ACTOR_LAYOUT, E.ACTOR_SIZE))
+ALL_NETS = tuple(net[0] for net in HIRL_NETS)
+
+
+def save_hirl_nets(eng, model_dir, tag, names=ALL_NETS):
+    """the state_dicts of a HirlEngine's networks `names` under the reference's key names, one file each"""
+    for name, attr, layout, _ in HIRL_NETS:
+        if name in names:
+            torch.save({k: v.cpu().clone() for k, v in E.unpack(getattr(eng, attr), layout).items()}, os.path.join(model_dir, tag + name + "Harfang_GYM"))
+
+
+def load_hirl_nets(eng, src_dir, tag, names=ALL_NETS, missing="{} not found"):
+    """the files save_hirl_nets writes into the engine's networks `names`; `missing`: the FileNotFoundError's text, {} standing for the file"""
+    for name, attr, layout, size in HIRL_NETS:
+        if name in names:
+            f = os.path.join(src_dir, tag + name + "Harfang_GYM")
+            if not os.path.exists(f):
+                raise FileNotFoundError(missing.format(f))
+            flat = getattr(eng, attr)
+            flat.copy_(E.pack(torch.load(f, map_location="cpu"), layout, size, flat.device))
+    eng.refresh_bf16()

@@ -31,6 +31,7 @@ from . import _lib
 from .agents import engine as E
 from .agents.HIRL import init_actor_state_dict, init_critic_state_dict
 from .environments.batched import BatchedHarfangEnv
+from .utils import checkpoint as CK
 from .utils.seed import set_seed
 
 VALIDATION_STEP = 1200   # validate_all.py:187,190
@@ -102,11 +103,8 @@ def load_agent(config, device):
     hirl = config.agent == "HIRL"
     eng = E.HirlEngine(batch=128, slope=0.0 if hirl else 0.01, use_bc=False, device=device)  # HIRL: ReLU; TD3 / BC: LeakyReLU(0.01)
     eng.load_params(init_actor_state_dict(), init_critic_state_dict(), None)
-    f = os.path.join(config.model_dir, config.model_name + "Actor_Harfang_GYM")
-    if not os.path.exists(f):
-        raise FileNotFoundError(f"{f} not found (--model_dir / --model_name name the checkpoint, e.g. Agent3_100_5_)")
-    eng.actor.copy_(E.pack(torch.load(f, map_location="cpu"), E.ACTOR_LAYOUT, E.ACTOR_SIZE, device))  # validation acts with the actor alone
-    eng.refresh_bf16()
+    CK.load_hirl_nets(eng, config.model_dir, config.model_name, names=("Actor_",),  # validation acts with the actor alone
+                      missing="{} not found (--model_dir / --model_name name the checkpoint, e.g. Agent3_100_5_)")
     if config.dtype != "f32":
         eng.set_act_dtype("f32x9" if config.dtype == "f32x9" else "bf16")
     return eng, False
