@@ -106,7 +106,9 @@ typedef struct HxStepOpts {
     float* ring;           /* [cap][HX_ROW_WORDS] replay ring or NULL: fused UniformMemory.store (buffer.py:20-36) */
     int8_t* ring_success;  /* [cap] step_success of each stored row, or NULL */
     int64_t cap;
-    uint64_t* total;       /* transitions ever stored; slot = total % cap (buffer.py:36 position) */
+    uint64_t* total;       /* transitions ever stored; slot = total % cap (buffer.py:36 position).  A 64-bit counter in every consumer (the
+                              inserts, the draws, PER's `marked`, the host): the documented domain is total < 2^52 — the inserts take total % cap
+                              from an fp64 quotient estimate with one correction step —, tested up to there (tests/test_ring_counter_*.py) */
     uint64_t* stats;       /* [HX_STAT_WAYS][HX_STAT_PITCH] or NULL: see HX_STAT_WAYS */
     void* ev_start;        /* measurement only (host handles from hx_event_create, or NULL): the launch stamps the kernel's own */
     void* ev_stop;         /* begin / end into them — the duration rocprofv3 reports, without the dispatch gap around it */

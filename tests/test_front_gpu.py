@@ -16,6 +16,7 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from tests import _hirl_data as D  # noqa: E402
+from tests._ring_model import allowed_slots  # noqa: E402
 
 NETS = ("actor", "critic", "target_actor", "target_critic", "m_actor", "v_actor", "m_critic", "v_critic")
 
@@ -27,14 +28,6 @@ def eng_mod():
     from hirl4ucav_amd.agents import engine
 
     return engine
-
-
-def allowed_slots(tot, cap, guard):
-    """The population of a guarded draw, restated: every slot that holds a transition before the env step (slots < min(tot, cap)) and is not one of
-    the `guard` slots behind the ring head tot % cap."""
-    live = np.arange(min(tot, cap))
-    window = (tot + np.arange(guard)) % cap
-    return np.setdiff1d(live, window)
 
 
 def make_pair(eng_mod, n, cap, use_bc, slope, seed, act="f32", staged=False):
@@ -150,7 +143,9 @@ def test_guarded_draw_covers_its_population(eng_mod):
     rep.ring.copy_(torch.from_numpy(rng.normal(size=(cap, 32)).astype(np.float32)))
     e = eng_mod.HirlEngine(batch=128, use_bc=False)
     e.load_params(params["actor"], params["critic"], None)
-    for tot in (400, 650, 700, 2 * 700 + 10, 3 * 700 + 620):  # not full; window past the end; just full; full; full with the window wrapped
+    # not full; window past the end; just full; full; full with the window wrapped; and the 64-bit counter past 2^32: 2^32 + 10 (head 406), 2^40 + 620
+    # (head 396), and a total congruent to 3 * 700 + 620 (the wrapped window again)
+    for tot in (400, 650, 700, 2 * 700 + 10, 3 * 700 + 620, (1 << 32) + 10, (1 << 40) + 620, ((1 << 32) // 700 + 1) * 700 + 620):
         rep.total.fill_(tot)
         seen = set()
         ok = allowed_slots(tot, cap, guard)

@@ -391,7 +391,10 @@ def test_learn_ragged_batches_and_outlier_rows(eng_mod):
             check_params(e, o, eng_mod, f"B={B} call {k} params", was_actor_call)
 
 
-@pytest.mark.parametrize("guard,tot", [(0, 700), (0, 431), (150, 3 * 700 + 620), (150, 400)])
+T_PAST_2_32 = ((1 << 32) // 700 + 1) * 700 + 620  # the 64-bit counter past 2^32, congruent to 3 * 700 + 620 mod 700
+
+
+@pytest.mark.parametrize("guard,tot", [(0, 700), (0, 431), (150, 3 * 700 + 620), (150, 400), (150, T_PAST_2_32), (0, T_PAST_2_32)])
 def test_device_draw_is_uniform(eng_mod, guard, tot):
     """UniformMemory.sample is random.sample(population, batchSize) (hirl/utils/buffer.py:45): every slot of the population equally likely, no duplicates
     inside a minibatch.  test_device_sampler / test_guarded_draw_covers_its_population prove support and distinctness; this is the FREQUENCY: 4,000 draws
