@@ -71,7 +71,7 @@ _SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 124  # HX_ABI_VERSION of include/hirl4ucav.h
+ABI_VERSION = 125  # HX_ABI_VERSION of include/hirl4ucav.h
 _ABI_STRUCTS = {}  # name -> (index in hx_abi_sizes, ctypes class): filled by the binding modules (check_struct)
 
 

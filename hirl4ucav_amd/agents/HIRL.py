@@ -114,6 +114,10 @@ class Agent:
             tab = np.zeros((len(self.expert_states), 32), np.float32)
             tab[:, 0:13], tab[:, 13:17] = self.expert_states, self.expert_actions
             self._bc_table = torch.from_numpy(tab).to(device)
+            self.target_indices = np.where(self.expert_actions[:, 3] == 1)[0]  # HIRL.py:168, 217-219
+        # HIRL.py:184-185.  expert_upsample = True: one row of learn()'s BC minibatch is a fire row (HIRL.py:253-257).  buffer_upsample is informational
+        # here, as the façade's buffer is built before anyone can set it; the vector loop's form of it is train_all --buffer_upsample
+        self.buffer_upsample, self.expert_upsample = False, False
         self._last = (0.0, 0.0, 0.0, 0.0, 0.0, bc_weight)
 
     @property
@@ -153,6 +157,9 @@ class Agent:
         else:
             idx, n_main = self.buffer.sample_indices(B), B
         idx_bc = np.random.choice(self.expert_states.shape[0], B, replace=False)  # HIRL.py:249
+        if self.expert_upsample:  # HIRL.py:253-257, the reference's call order: the fire row first, then the row it replaces
+            selected = np.random.choice(self.target_indices)
+            idx_bc[np.random.randint(B)] = selected
         noise = torch.normal(mean=torch.zeros(self.actionDim), std=torch.ones(self.actionDim) * self.TD3LearningNoise)  # :265
         was_actor_call = self.eng.actor_trainable
         self.eng.assemble(self.buffer.ring, torch.as_tensor(idx, dtype=torch.int32, device=device), expert_ring=self.expert_buffer.ring,

@@ -187,6 +187,7 @@ class HirlEngine:
         self.soft_count = self.soft_count[:1]
         self.sample_calls = 0
         self._pending = None  # a draw sample(defer=True) recorded for the next learn()
+        self.upsampler, self.fire_idx, self.upsample_calls = None, None, 0  # set_upsample()
         # step_learn: hand-off words (flags int32[64], status int32[1]) + the epoch counter; two sets of minibatch tiles (the rest of learn() k still
         # reads set k while its first launch fills set k + 1 for the next front launch) and what the set in waiting was drawn for
         # launch C inside the front launch (front_c_for()).  [r5] OFF by default: with the six-term acting format the one size class where it paid (8,192 envs
@@ -471,6 +472,16 @@ class HirlEngine:
                   idx.data_ptr(), _lib.ptr(idx_bc), None, self.rows.data_ptr(), self.bc_rows.data_ptr() if bc_table is not None else None,
                   _lib.stream_ptr())
 
+    def set_upsample(self, upsampler=None, fire_idx=None):
+        """The reference's two sampling switches for the vector loop (HIRL.py:184-185; include/hirl4ucav.h "Success upsampling").  upsampler: a
+        utils.buffer.SuccessUpsampler beside the replay ring sample() is given — rows [0, n_main) are then drawn 10 : 1 in favour of success rows,
+        with replacement (buffer_upsample).  fire_idx: int32 device tensor, the expert table's fire rows — one row of the BC minibatch is then
+        replaced by one of them (expert_upsample).  With either set, sample() runs the plain draw and hx_ups_draw behind it over the same tiles
+        (defer=True is ignored); learn() is untouched.  Both None: every path as before."""
+        if fire_idx is not None and (fire_idx.dtype != torch.int32 or fire_idx.numel() == 0 or not fire_idx.is_contiguous()):
+            raise _lib.HxError("set_upsample: fire_idx is a contiguous, non-empty int32 tensor (the expert table has no fire row?)")
+        self.upsampler, self.fire_idx = upsampler, fire_idx
+
     def sample(self, replay, expert=None, bc_table=None, n_main=None, seed=0, sigma=0.2, defer=False):
         """Draw AND gather the next minibatch on the device (no host sync): UniformMemory.sample (buffer.py:38-48), the
         buffer/expert mix and np.random.choice of HIRL.py:223-251, torch.normal(0, 0.2) of HIRL.py:265.
@@ -478,6 +489,13 @@ class HirlEngine:
         the same indices, noise, tiles and update bit for bit, one launch less); the returned tensors are filled by that learn()."""
         B = self.batch
         self.sample_calls += 1
+        ups = self.upsampler is not None or self.fire_idx is not None
+        if ups:
+            defer = False  # the draw behind it rewrites the tiles: they have to exist
+            if self.upsampler is not None and self.upsampler.replay is not replay:
+                raise _lib.HxError("sample: the upsampler given to set_upsample() stands beside another replay ring")
+            if self.fire_idx is not None and bc_table is None:
+                raise _lib.HxError("sample: set_upsample(fire_idx=...) replaces a row of the BC minibatch: bc_table is needed")
         if defer:
             # (the tensors are referenced by the record: they must outlive the launch)
             self._pending = (HxSample(replay.total.data_ptr(), replay.capacity, replay.ring.data_ptr(),
@@ -492,6 +510,15 @@ class HirlEngine:
                   bc_table.shape[0] if bc_table is not None else 0, B, B if n_main is None else int(n_main), 1, int(seed),
                   self.sample_calls, float(sigma), self._idx.data_ptr(), self._idx_bc.data_ptr() if bc_table is not None else None,
                   self._noise.data_ptr(), self.rows.data_ptr(), self.bc_rows.data_ptr() if bc_table is not None else None, _lib.stream_ptr())
+        if ups:
+            from ..utils.buffer import draw_call
+
+            self.upsample_calls += 1
+            fire = self.fire_idx
+            nm = (B if n_main is None else int(n_main)) if self.upsampler is not None else 0
+            if nm > 0 or fire is not None:  # (an all-expert minibatch without the fire row: nothing to redraw)
+                draw_call(self.upsampler if nm > 0 else None, replay.ring, B, nm, self._idx, self.rows, None, seed, self.upsample_calls, fire,
+                          bc_table if fire is not None else None, self._idx_bc if fire is not None else None, self.bc_rows if fire is not None else None)
         return self._idx, self._idx_bc, self._noise
 
     def learn(self, noise=None, bc_weight_now=0.0, bc_warm_up_weight=0.0, before_exchange=None):
@@ -608,6 +635,9 @@ class HirlEngine:
                                "the bf16 acting format, with a replay ring attached to the env")
         if self._pending is not None:
             raise _lib.HxError("step_learn draws its own minibatch: a sample(defer=True) is still pending")
+        if self.upsampler is not None or self.fire_idx is not None:
+            raise _lib.HxError("step_learn: the front launch draws its minibatch uniformly inside the launch; set_upsample() goes with sample() + learn() "
+                               "(the reference-order step)")
         if self._front is None:
             buf = torch.zeros(96, dtype=torch.int32, device=self.device)
             self._front = (buf[0:64], buf[64:65])

@@ -329,6 +329,15 @@ def train_bc(config, device, seed, max_step):
     bc_table = torch.from_numpy(tab).to(device)
     table = DeviceReplay(es.shape[0], device)  # the sampler wants a main ring as well; the BC step reads only the BC rows
     table.store_rows(bc_table)
+    if upsample_refusal(config):
+        raise SystemExit("train_all: " + upsample_refusal(config))
+    if getattr(config, "expert_upsample", False):  # BC.py:152-158, 171-176: one row of every minibatch is a fire row
+        from .utils.buffer import fire_rows
+
+        fire = fire_rows(bc_table)
+        if upsample_refusal(config, n_fire=fire.numel()):
+            raise SystemExit("train_all: " + upsample_refusal(config, n_fire=fire.numel()))
+        eng.set_upsample(None, fire)
     log_dir = os.path.join(config.result_dir, env_type, config.agent, config.model_name, time.strftime("%Y_%m_%d_%H_%M"))
     model_dir = os.path.join(log_dir, "model")
     os.makedirs(model_dir, exist_ok=True)
@@ -440,7 +449,10 @@ def check_agent_flags(run):
     run.per_new = getattr(config, "per_new", "max")  # how a step's rows get their first priority: at pmax, or at a TD error of their own (agent.py:234-246)
     run.multi_step = int(getattr(config, "multi_step", 1))  # SacAgent(multi_step=n): truncated n-step returns (utils.buffer.NStepInserter)
     run.grad_clip, run.fixed_alpha = getattr(config, "grad_clip", None), getattr(config, "fixed_alpha", None)  # SacAgent(grad_clip=c) / (entropy_tuning=False, ent_coef=x)
-    for refusal in (per_refusal, nstep_refusal, clip_refusal):  # (per_refusal without --per: --per_new td on its own)
+    # the reference's two sampling switches (HIRL.py:184-185): success rows of the replay drawn 10 : 1, one fire row forced into the BC minibatch
+    run.buffer_upsample, run.expert_upsample = bool(getattr(config, "buffer_upsample", False)), bool(getattr(config, "expert_upsample", False))
+    run.upsampler = None
+    for refusal in (per_refusal, nstep_refusal, clip_refusal, upsample_refusal):  # (per_refusal without --per: --per_new td on its own)
         if refusal(config, world):
             raise SystemExit("train_all: " + refusal(config, world))
     run.batch = 128  # train_all.py:190-208
@@ -460,6 +472,10 @@ def build_env(run):
     run.env = BatchedHarfangEnv(n, scenario=mixed_scenarios(n, run.rank * n).astype(np.int32) if env_type == MIXED else env_type, device=device, seed=run.seed,
                                 max_step=run.max_step, auto_reset=True, random_reset=config.random, env_id0=run.rank * n,
                                 replay=run.replay if run.multi_step == 1 else None)
+    if run.buffer_upsample:  # UniformMemory(capacity, upsample=True), HIRL.py:189: the counts beside the ring, kept current behind every acting launch
+        from .utils.buffer import SuccessUpsampler
+
+        run.upsampler = SuccessUpsampler(run.replay, int(config.upsample_boost))
     run.inserter = None
     if run.multi_step > 1:  # the acting launches run without a ring; the inserter's launch behind each step writes the finished n-step rows
         from .utils.buffer import NStepInserter
@@ -500,7 +516,9 @@ def build_engine(run):
 def load_expert_tables(run):
     """HIRL / E-SAC / ISAC: the labelled expert ring, the BC (s, a) table and the frozen bc_actor"""
     config, device, eng = run.config, run.device, run.eng
-    run.expert = run.bc_table = None
+    run.expert = run.bc_table = run.fire_idx = None
+    if run.upsampler is not None:  # (TD3 has no expert table: the engine hears of the upsampler here)
+        eng.set_upsample(run.upsampler, None)
     if not (run.hirl or run.esac or run.isac):
         return
     tables = load_expert_files(config)
@@ -520,6 +538,13 @@ def load_expert_tables(run):
         print("WARNING: HIRL-soft without --bc_actor: the soft weight is estimated against a randomly initialised bc_actor", flush=True)
     if run.isac:  # agent.load_bc_actor (SAC/agent.py:158-160)
         eng.set_imitative(torch.load(config.bc_actor, map_location="cpu"), slope=0.01)
+    if run.expert_upsample:  # target_indices, HIRL.py:217-219
+        from .utils.buffer import fire_rows
+
+        run.fire_idx = fire_rows(run.bc_table)
+        if upsample_refusal(config, run.world, n_fire=run.fire_idx.numel()):
+            raise SystemExit("train_all: " + upsample_refusal(config, run.world, n_fire=run.fire_idx.numel()))
+        eng.set_upsample(run.upsampler, run.fire_idx)
 
 
 def set_dtype(run):
@@ -618,6 +643,8 @@ def restore_or_explore(run):
                 inserter.push(env, a0)
             if estats is not None:
                 estats.push()
+            if getattr(run, "upsampler", None) is not None:
+                run.upsampler.mark_new(n)
         if run.per and run.per_new == "td":  # the exploration rows are appended with an error of their own too (SAC/agent.py:176-177, 234-246: the start_steps rows are scored as well)
             eng.score_new(run.replay, math.ceil(20 * run.max_step / (n * run.world)) * n, seed=run.seed + 3 + run.rank)
         elif run.per:
@@ -640,8 +667,9 @@ def choose_loop(run):
     # the waiting workgroups of processes that share a GPU add up; eight front-loop ranks on one GPU tripped in round 5).  HX_FRONT_SHARED_GPU=1 takes it
     # anyway (soak tests); the status word + fallback below stay armed either way.
     shared_gpu = world > torch.cuda.device_count() and not os.environ.get("HX_FRONT_SHARED_GPU")
+    upsampled = tuple(flag for flag in ("buffer_upsample", "expert_upsample") if getattr(run, flag, False))  # the weighted draw is a launch behind the plain one
     run.front = (config.loop == "front" and not sac and not config.separate_launches and config.updates_per_step == 1 and run.batch <= 256
-                 and getattr(config, "dtype", "f32") in ("f32", "f32x9", "bf16") and not shared_gpu)
+                 and getattr(config, "dtype", "f32") in ("f32", "f32x9", "bf16") and not shared_gpu and not upsampled)
     run.front_sac = (config.loop == "front" and sac and world == 1 and not config.separate_launches and config.updates_per_step == 1 and run.batch <= 256 and not run.per
                      and run.grad_clip is None and run.inserter is None)
     if rank == 0:
@@ -650,6 +678,8 @@ def choose_loop(run):
             which += " (--per: the front launch draws before the step's insert, so the priorities of the drawn rows could be written into overwritten slots)"
         if run.inserter is not None:  # the front launch's acting workgroups insert one-step rows themselves
             which += f" (--multi_step {run.multi_step}: the n-step rows are written by a launch of their own behind the acting launch)"
+        if upsampled:  # the front launch draws uniformly, inside the launch and before the step's insert
+            which += f" ({' '.join('--' + flag for flag in upsampled)}: the upsampled draw is a launch of its own between the acting launch and learn(), after the step's insert)"
         if sac and run.grad_clip is not None and not run.per:  # the clipped update is the staged sequence (gradients -> norm -> clipped step): its first launch is its own
             which += " (--grad_clip: the clipped update runs as stages, which have no front form)"
         print(f"vector loop: {which}" + (f" ({world} ranks share a GPU: the front launch is for one process per GPU)" if (shared_gpu and config.loop == "front") else ""),
@@ -695,6 +725,8 @@ def after_env_step(run, step):
             writer.add_scalar("stats/per_mean_new_error", float(replay.errors[:k].mean()), step + run.episode * run.max_step)
     elif run.per:
         run.replay.mark_new(run.n if run.inserter is None else run.inserter.max_rows)  # this step's rows enter at the running maximum priority (one launch, no host sync)
+    if getattr(run, "upsampler", None) is not None:
+        run.upsampler.mark_new(run.n)  # the blocks this step's rows fell into are recounted (one launch, no host sync)
     if run.ret is not None:
         run.ret += run.env.reward
 
@@ -986,6 +1018,29 @@ def nstep_refusal(config, world=1):
     return None
 
 
+def upsample_refusal(config, world=1, n_fire=None):
+    """why `--buffer_upsample` / `--expert_upsample` cannot run as asked, or None.  n_fire: the fire rows of the expert table, once it has been read"""
+    buf, exp = getattr(config, "buffer_upsample", False), getattr(config, "expert_upsample", False)
+    if not buf and not exp:
+        return None
+    flag = "--buffer_upsample" if buf else "--expert_upsample"
+    if config.agent == "SAC":
+        return (f"{flag} goes with --agent HIRL | TD3{'' if buf else ' | BC'} (the two switches are the HIRL agent's: HIRL.py:184-185; SacAgent has --per), "
+                "not --agent SAC")
+    if buf and config.agent == "BC":
+        return "--buffer_upsample goes with --agent HIRL | TD3 (BC has no replay ring); --expert_upsample is BC's switch (BC.py:152-158)"
+    if exp and config.agent == "TD3":
+        return "--expert_upsample goes with --agent HIRL | BC (TD3 reads no expert table)"
+    if (config.gpus and config.gpus > 1) or world > 1:
+        return f"{flag} runs on one GPU (the draw is rank-local and untested on sharded ranks): use --gpus 1"
+    boost = getattr(config, "upsample_boost", 10)
+    if buf and not 2 <= boost <= 255:
+        return f"--upsample_boost {boost}: the weight of a success row against 1 is 2..255 (10 = the reference's 1.0 : 0.1)"
+    if exp and n_fire is not None and n_fire == 0:
+        return "--expert_upsample: the expert table holds no row whose fire action is 1 (target_indices would be empty: HIRL.py:217-219)"
+    return None
+
+
 def clip_refusal(config, world=1):
     """why `--grad_clip` / `--fixed_alpha` cannot run as asked, or None"""
     clip, fixed = getattr(config, "grad_clip", None), getattr(config, "fixed_alpha", None)
@@ -1008,7 +1063,7 @@ def parse_args(argv=None):
     """parser().parse_args with the cross-flag checks that are argparse errors"""
     p = parser()
     cfg = p.parse_args(argv)
-    why = per_refusal(cfg) or clip_refusal(cfg) or nstep_refusal(cfg) or mixed_refusal(cfg)
+    why = per_refusal(cfg) or clip_refusal(cfg) or nstep_refusal(cfg) or mixed_refusal(cfg) or upsample_refusal(cfg)
     if why:
         p.error(why)
     if cfg.type == "ISAC" and cfg.agent != "SAC":
@@ -1078,6 +1133,15 @@ def parser():
     p.add_argument("--per_alpha", type=float, default=0.6, help="--per: priority exponent (SAC/agent.py:62)")
     p.add_argument("--per_beta", type=float, default=0.4, help="--per: importance-weight exponent at the start (SAC/agent.py:62)")
     p.add_argument("--per_beta_annealing", type=float, default=0.0001, help="--per: beta <- min(1, beta + this) per sample call (SAC/agent.py:63)")
+    p.add_argument("--buffer_upsample", action="store_true",
+                   help="HIRL (every --type) and TD3: the reference's UniformMemory(upsample=True) (HIRL.py:184, 189): a replay row whose step_success is 1 "
+                        "is drawn --upsample_boost times as often as any other, with replacement.  TD3 is an extension (the same engine draws for both).  "
+                        "The vector loop takes the reference's order")
+    p.add_argument("--expert_upsample", action="store_true",
+                   help="HIRL and BC: the reference's `bc fire upsample` (HIRL.py:185, 253-257; BC.py:171-176): one row of every BC minibatch is replaced "
+                        "by a uniformly chosen expert row whose fire action is 1")
+    p.add_argument("--upsample_boost", type=int, default=10, help="--buffer_upsample: the integer weight of a success row against 1, 2..255 "
+                                                                  "(10 = the reference's 1.0 : 0.1)")
     p.add_argument("--multi_step", type=int, default=1,
                    help="SAC / E-SAC: truncated n-step returns (SacAgent(multi_step=N)), N in 2..8; 1 (default): one-step rows.  A launch of its own behind "
                         "every acting launch keeps the last N steps per env and stores finished rows with r = sum gamma^k r_k and the row's discount folded "

@@ -173,6 +173,95 @@ class PrioritizedReplay(DeviceReplay):
         return beta
 
 
+class HxUps(ctypes.Structure):
+    """the success upsampler's buffers (include/hirl4ucav.h HxUps)"""
+    _fields_ = [("cnt", ctypes.c_void_p), ("marked", ctypes.c_void_p), ("total", ctypes.c_void_p), ("ring_success", ctypes.c_void_p),
+                ("cap", ctypes.c_int64), ("boost", ctypes.c_int32)]
+
+
+_lib.register("hx_ups_mark_new", [ctypes.POINTER(HxUps), ctypes.c_int64, _vp])
+_lib.register("hx_ups_recount", [ctypes.POINTER(HxUps), _vp])
+_lib.register("hx_ups_draw", [ctypes.POINTER(HxUps), _vp, _i32, _i32, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp])
+
+UPS_BLOCK, UPS_MAX_CAPACITY, UPS_BOOST, UPS_BOOST_RANGE = 1024, 1 << 24, 10, (2, 255)
+
+
+def check_ups_abi():
+    L = _lib.load()
+    if L.hx_ups_sizeof() != ctypes.sizeof(HxUps):
+        raise _lib.HxError(f"ABI mismatch: HxUps is {ctypes.sizeof(HxUps)} bytes here, {L.hx_ups_sizeof()} in {_lib.SO_PATH}")
+    L.hx_ups_words.restype = ctypes.c_int64
+    L.hx_ups_words.argtypes = [ctypes.c_int64]
+    return L
+
+
+def fire_rows(bc_table):
+    """the reference's target_indices (HIRL.py:217-219, BC.py:152-158): the rows of an expert table [n, 32] whose fire action (word 16) is 1 -> int32"""
+    return torch.nonzero(bc_table[:, 16] == 1).reshape(-1).to(torch.int32)
+
+
+class SuccessUpsampler:
+    """The reference's UniformMemory(upsample=True) draw (buffer.py:18-29, 39-43) beside a DeviceReplay, which stays as it is: a transition whose
+    step_success == 1 weighs `boost`, every other 1 (the reference's 1.0 : 0.1 as integers), drawn proportionally WITH replacement and without
+    importance weights (include/hirl4ucav.h "Success upsampling").  cnt = the live success rows per 1,024 slots; mark_new(n) behind every acting
+    launch keeps it current.  Everything enqueues on the current stream; nothing synchronises but weight_total() and marked."""
+
+    def __init__(self, replay, boost=UPS_BOOST):
+        boost = int(boost)
+        if not UPS_BOOST_RANGE[0] <= boost <= UPS_BOOST_RANGE[1]:
+            raise ValueError(f"upsample boost is {UPS_BOOST_RANGE[0]}..{UPS_BOOST_RANGE[1]} (the weight of a success row against 1), got {boost}")
+        if replay.capacity > UPS_MAX_CAPACITY:
+            raise ValueError(f"success upsampling holds at most 2^24 slots (capacity {replay.capacity}): the draw scans 16,384 block weights")
+        L = check_ups_abi()
+        self.replay, self.boost = replay, boost
+        self.nblocks = int(L.hx_ups_words(replay.capacity))
+        assert self.nblocks == (replay.capacity + UPS_BLOCK - 1) // UPS_BLOCK
+        self.cnt = torch.zeros(self.nblocks, dtype=torch.int32, device=replay.device)
+        self.marked_t = torch.zeros(1, dtype=torch.int64, device=replay.device)
+        self.ups = HxUps(self.cnt.data_ptr(), self.marked_t.data_ptr(), replay.total.data_ptr(), replay.success.data_ptr(), replay.capacity, boost)
+
+    @property
+    def marked(self):  # host sync
+        return int(self.marked_t.item())
+
+    def mark_new(self, max_new=None):
+        """the blocks touched by the rows stored since the last call are recounted.  max_new: an upper bound on their number (the envs stepped);
+        default: the whole ring"""
+        _lib.call("hx_ups_mark_new", ctypes.byref(self.ups), int(max_new) if max_new else self.replay.capacity, _lib.stream_ptr())
+
+    def recount(self):
+        _lib.call("hx_ups_recount", ctypes.byref(self.ups), _lib.stream_ptr())
+
+    def draw_into(self, batch, n_main, idx, rows, x=None, seed=0, call=0, fire=None, bc_table=None, idx_bc=None, bc_rows=None):
+        """hx_ups_draw: rows [0, n_main) of idx (int32) / rows <- proportional draws, the rest untouched.  x: injected 64-bit words (int64 tensor,
+        n_main of them, two more with `fire`), else Philox(seed; row, call).  fire: int32 indices of bc_table's fire rows -> one row of idx_bc /
+        bc_rows is replaced by one of them."""
+        draw_call(self, self.replay.ring, batch, n_main, idx, rows, x, seed, call, fire, bc_table, idx_bc, bc_rows)
+
+    def weight_total(self):
+        """W = n + (boost - 1) sum(cnt) (host sync: tests)"""
+        return min(int(self.replay.total.item()), self.replay.capacity) + (self.boost - 1) * int(self.cnt.sum().item())
+
+    def state(self):
+        return {"boost": self.boost, "marked": self.marked}
+
+    def load_state(self, st):
+        """after the ring has been restored: the counts are formed again from its labels"""
+        if int(st["boost"]) != self.boost:
+            raise ValueError(f"snapshot was written under --upsample_boost {st['boost']}, this run has --upsample_boost {self.boost}: resume with the "
+                             "value the run was started with")
+        self.recount()
+
+
+def draw_call(upsampler, ring, batch, n_main, idx, rows, x=None, seed=0, call=0, fire=None, bc_table=None, idx_bc=None, bc_rows=None):
+    """hx_ups_draw with or without an upsampler (None with n_main = 0: the BC minibatch's fire row alone)"""
+    if fire is not None and (fire.dtype != torch.int32 or not fire.is_contiguous() or fire.numel() == 0):
+        raise ValueError("fire is a contiguous, non-empty int32 tensor of expert-table rows")
+    _lib.call("hx_ups_draw", ctypes.byref(upsampler.ups) if upsampler is not None else None, _lib.ptr(ring), int(batch), int(n_main), _lib.ptr(x),
+              int(seed), int(call), _lib.ptr(idx), _lib.ptr(rows), _lib.ptr(fire), fire.numel() if fire is not None else 0, _lib.ptr(bc_table),
+              _lib.ptr(idx_bc), _lib.ptr(bc_rows), _lib.stream_ptr())
+
+
 class HxNStep(ctypes.Structure):
     """the n-step window's buffers (include/hirl4ucav.h HxNStep)"""
     _fields_ = [("win", ctypes.c_void_p), ("hc", ctypes.c_void_p), ("obs_prev", ctypes.c_void_p), ("last_ctr", ctypes.c_void_p),
@@ -311,7 +400,8 @@ class UniformMemory(DeviceReplay):
 
     def __init__(self, capacity, upsample=False):
         if upsample:
-            raise NotImplementedError("priority upsampling is disabled in the reference (HIRL.py:184,189)")
+            raise NotImplementedError("priority upsampling is disabled in the reference (HIRL.py:184,189); the vector loop's form of it is "
+                                      "SuccessUpsampler beside a DeviceReplay (train_all --buffer_upsample)")
         super().__init__(int(capacity), device)
         self.upsample = False
         self._len = 0

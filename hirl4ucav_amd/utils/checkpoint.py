@@ -34,7 +34,28 @@ def engine_state(eng):
         st["fixed_alpha"] = float(eng.ent_coef)
     if getattr(eng, "multi_step", None) is not None:  # (a one-step snapshot carries no such key) the n-step inserter's windows, obs_prev and counters
         st["multi_step"] = eng.multi_step.state()
+    if upsample_flags(eng) != (False, False):  # (a snapshot of a run without the two switches carries no such key)
+        st["upsample"] = {"buffer": eng.upsampler.state() if eng.upsampler is not None else None, "expert": eng.fire_idx is not None,
+                          "calls": eng.upsample_calls}
     return st
+
+
+def upsample_flags(eng):
+    """(buffer_upsample, expert_upsample) as the engine runs them (HirlEngine.set_upsample)"""
+    return getattr(eng, "upsampler", None) is not None, getattr(eng, "fire_idx", None) is not None
+
+
+def check_upsample(eng, st):
+    ups = st.get("upsample")
+    was = (ups["buffer"] is not None, bool(ups["expert"])) if ups else (False, False)
+    now = upsample_flags(eng)
+    for name, w, n in (("--buffer_upsample", was[0], now[0]), ("--expert_upsample", was[1], now[1])):
+        if w != n:
+            raise ValueError(f"snapshot was written {'under' if w else 'without'} {name}, this run is {'under' if n else 'without'} it: resume with the "
+                             "flags the run was started with")
+    if was[0] and int(ups["buffer"]["boost"]) != eng.upsampler.boost:
+        raise ValueError(f"snapshot was written under --upsample_boost {ups['buffer']['boost']}, this run has --upsample_boost {eng.upsampler.boost}: "
+                         "resume with the value the run was started with")
 
 
 def load_engine_state(eng, st):
@@ -66,7 +87,10 @@ def load_engine_state(eng, st):
                          "started with")
     if ("imitative" in st) != bool(getattr(eng, "imitative", False)):
         raise ValueError("snapshot and engine disagree about SAC's imitative branch (--type ISAC): resume with the type the run was started with")
+    check_upsample(eng, st)
     eng.arena.copy_(st["arena"])
+    if "upsample" in st:
+        eng.upsample_calls = st["upsample"]["calls"]
     if "multi_step" in st:
         eng.multi_step.load_state(st["multi_step"])
     if "imitative" in st:
@@ -155,6 +179,8 @@ def load_run(path, eng, env, replay):
     load_engine_state(eng, snap["engine"])
     load_env_state(env, snap["env"])
     load_replay_state(replay, snap["replay"])
+    if getattr(eng, "upsampler", None) is not None:  # the counts are formed again from the restored labels
+        eng.upsampler.load_state(snap["engine"]["upsample"]["buffer"])
     random.setstate(snap["rng"]["python"])
     np.random.set_state(snap["rng"]["numpy"])
     torch.set_rng_state(snap["rng"]["torch"])

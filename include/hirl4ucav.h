@@ -82,8 +82,9 @@ const char* hx_last_error(void);
  * 121: n-step returns for SAC (HxNStep, hx_nstep_*).
  * 122: the record of validation episodes (HxTrace, hx_trace_*).
  * 123: per-episode statistics by scenario (HxEpStat, hx_epstat_*).
- * 124: the merged actor message carries the soft count as base-32 digit words too, and hx_adam_mixed reads those (exact on the bf16 transports). */
-#define HX_ABI_VERSION 124
+ * 124: the merged actor message carries the soft count as base-32 digit words too, and hx_adam_mixed reads those (exact on the bf16 transports).
+ * 125: success upsampling of the replay draw and the BC minibatch's fire row (HxUps, hx_ups_*). */
+#define HX_ABI_VERSION 125
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -848,6 +849,56 @@ int hx_epstat_clear(const HxEpStat* es, void* stream);
  * workgroup; plain vector stores, each one contiguous run per wave.  Enqueues only. */
 int hx_epstat_push(const HxEpStat* es, const float* state, int64_t n, int64_t stride, const float* reward, const uint8_t* done, const int8_t* success,
                    const uint32_t* episode_ctr, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Success upsampling (the reference's buffer_upsample and expert_upsample switches: HIRL.py:184-185, 189, 217-219, 253-257; buffer.py:18-29,
+ * 39-43; BC.py:152-158, 171-176).  UniformMemory(upsample=True) stores priority 1.0 for a transition whose step_success == 1 and 0.1 for every
+ * other and draws np.random.choice(len, B, p = priorities / sum): proportional, with replacement, no importance weights.  Here the weights are
+ * INTEGERS — `boost` (default 10) for a success row, 1 for any other, the same distribution — so every sum is an exact count: no float
+ * arithmetic, the same labels and random words give the same indices on any run.
+ *     live length   n = min(*total, cap)
+ *     weight        slot i < n: boost if ring_success[i] == 1, else 1;  slot i >= n: 0, whatever stale label it holds
+ *     W             = n + (boost - 1) sum(cnt)                                   (fits 32 bits: cap <= 2^24, boost <= 255)
+ *     draw          row r takes a 64-bit word x_r -> target t = (x_r W) >> 64, an integer in [0, W) -> the slot whose interval of the
+ *                   running integer weight holds t: independent draws, WITH replacement (tests/_upsample_model.py is the same in Python integers)
+ * State beside a replay ring of `cap` <= 2^24 slots, all device memory owned by the caller:
+ *     cnt    [hx_ups_words(cap)] = ceil(cap / 1024) uint32: the live slots of each block of 1,024 consecutive slots whose label is exactly 1
+ *     marked one uint64: the `total` up to which the counts are current (start 0)
+ * ring_success is HxStepOpts.ring_success, cap bytes, 16-byte aligned; nothing behind cap is read.
+ * ------------------------------------------------------------------------------------------------------------ */
+typedef struct HxUps {
+    uint32_t* cnt;
+    uint64_t* marked;
+    const uint64_t* total;      /* the ring's counter (HxStepOpts.total) */
+    const int8_t* ring_success; /* the labels beside the ring (HxStepOpts.ring_success) */
+    int64_t cap;
+    int32_t boost;              /* 2 .. 255: the weight of a success row against 1; 10 = the reference's 1.0 : 0.1 */
+} HxUps;
+int hx_ups_sizeof(void); /* sizeof(HxUps) of the loaded library (hx_abi_sizes has no free word) */
+int64_t hx_ups_words(int64_t cap); /* ceil(cap / 1024); 0 for cap <= 0 or cap > 2^24 */
+/* Every block touched by the slots of [marked, *total) mod cap is RECOUNTED from the labels, masked by the live length (so slots overwritten
+ * after the ring wrapped are handled by construction), then marked advances.  max_new = the caller's upper bound on the rows stored since the
+ * last call; if more arrived, the first max_new are covered and `marked` advances by as much; cap or more rows to cover: the whole ring, and
+ * marked <- *total.  One launch of ONE workgroup: each of its 16 waves takes one touched block at a time (16 bytes of labels per lane, ballot /
+ * popcount), and the workgroup's barrier stands between every wave's read of `marked` and the one store to it — with one workgroup per block
+ * that store would need a ticket atomic or a launch of its own.  No atomics, nothing waits.  Enqueues only. */
+int hx_ups_mark_new(const HxUps* ups, int64_t max_new, void* stream);
+/* every block again from the labels, marked <- *total (a restored snapshot, labels written directly, tests); one wave per block */
+int hx_ups_recount(const HxUps* ups, void* stream);
+/* The draw, ONE workgroup (as hx_per_sample and hx_sample_batch), behind a plain hx_sample_batch over the same tiles:
+ *   rows r < n_main: x_r = x[r] when x is given, else the Philox4x32-10 words 0 (high half) and 1 (low half) of (key = seed; counter = (r, call,
+ *     a stream word of its own, 0)).  The block by binary search in an inclusive scan of the block weights live_in_block + (boost - 1) cnt held
+ *     in LDS (beyond 2^23 slots in pairs, as hx_per_sample holds its sums), the slot by one wave's scan of the block's 1,024 labels.
+ *     idx[r] <- the slot, rows[r] <- ring[slot] (whole 128-byte rows).  Rows [n_main, batch) of idx and rows are NOT touched.
+ *   fire_idx [n_fire] given (n_fire > 0): j = (w0 n_fire) >> 64, k = (w1 batch) >> 64 with w0 = x[n_main], w1 = x[n_main + 1] when x is given
+ *     (x then holds n_main + 2 words), else words (0, 1) and (2, 3) of Philox(seed; (0xFFFFFFF1, call, the stream word, 0));
+ *     idx_bc[k] <- fire_idx[j], bc_rows[k] <- bc_table[fire_idx[j]] (the reference replaces ONE row of the BC minibatch by a fire row).  Every
+ *     entry of fire_idx must index bc_table: the caller's promise.  ups may be NULL with n_main = 0: the BC replacement alone.
+ * batch <= 1024, 0 <= n_main <= batch.  Drawing while W == 0 (an empty ring) is the caller's error, which the device cannot refuse: every row
+ * is then slot 0.  If the counts are stale (rows stored since the last hx_ups_mark_new) a target can pass the end of its block's labels: it
+ * resolves to the block's last live slot, never to a slot beyond the live length. */
+int hx_ups_draw(const HxUps* ups, const float* ring, int32_t batch, int32_t n_main, const uint64_t* x, uint64_t seed, uint32_t call, int32_t* idx,
+                float* rows, const int32_t* fire_idx, int32_t n_fire, const float* bc_table, int32_t* idx_bc, float* bc_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Exchange step of a sharded update without a collective library (selectable beside RCCL): one-shot all-reduce over hipIpc peer
