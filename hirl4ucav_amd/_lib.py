@@ -66,12 +66,14 @@ _SIGNATURES = {
     "hx_epstat_reset": [ctypes.POINTER(HxEpStat), _vp, _vp],
     "hx_epstat_clear": [ctypes.POINTER(HxEpStat), _vp],
     "hx_epstat_push": [ctypes.POINTER(HxEpStat), _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
+    "hx_pilot_act": [_vp, _i64, _i64, _vp, _vp, _vp, _vp],
+    "hx_pilot_refresh": [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _u64, _vp],
     "hx_event_destroy": [_vp],
     "hx_event_elapsed_us": [_vp, _vp, ctypes.POINTER(ctypes.c_float)],
 }
 
 _lib = None
-ABI_VERSION = 125  # HX_ABI_VERSION of include/hirl4ucav.h
+ABI_VERSION = 126  # HX_ABI_VERSION of include/hirl4ucav.h
 _ABI_STRUCTS = {}  # name -> (index in hx_abi_sizes, ctypes class): filled by the binding modules (check_struct)
 
 

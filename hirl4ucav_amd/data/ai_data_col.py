@@ -21,9 +21,13 @@ from .expert_pilot import pursuit_actions
 MAX_EPISODE_STEP = 2000  # ai_data_col.py:86
 
 
-def collect(scenario, episodes, if_random, seed=0, noise_std=0.0, device="cuda"):
+def collect(scenario, episodes, if_random, seed=0, noise_std=0.0, device="cuda", pilot="torch"):
     """-> (states [M, 13], actions [M, 4], info): the valid episodes back to back, each from its reset observation to the
-    observation that shows the opponent destroyed (the IA loop records that last state too, ai_data_col.py:57-60)."""
+    observation that shows the opponent destroyed (the IA loop records that last state too, ai_data_col.py:57-60).
+    pilot: "torch" = expert_pilot.pursuit_actions; "device" = the same law as one launch (utils.pilot.device_pilot_actions), its noise drawn from
+    the same generator in the same shape."""
+    if pilot not in ("torch", "device"):
+        raise ValueError(f"collect: pilot is 'torch' or 'device', got {pilot!r}")
     env = BatchedHarfangEnv(episodes, scenario=scenario, device=device, seed=seed, auto_reset=False, random_reset=if_random, collect_stats=False)
     gen = torch.Generator(device=device)
     gen.manual_seed(seed)
@@ -32,7 +36,12 @@ def collect(scenario, episodes, if_random, seed=0, noise_std=0.0, device="cuda")
     A = torch.zeros((MAX_EPISODE_STEP + 1, episodes, 4), device=device)
     steps = 0
     for t in range(MAX_EPISODE_STEP + 1):
-        a = pursuit_actions(env.state, obs, noise_std, gen)
+        if pilot == "device":
+            from ..utils.pilot import device_pilot_actions
+
+            a = device_pilot_actions(env, noise_std * torch.randn((episodes, 3), device=device, generator=gen) if noise_std > 0 else None)
+        else:
+            a = pursuit_actions(env.state, obs, noise_std, gen)
         S[t], A[t] = obs, a
         steps = t + 1
         if t % 64 == 63 and bool((obs[:, 12] <= 0).all()):
@@ -71,10 +80,12 @@ def main(argv=None):
     p.add_argument("--episodes", type=int, default=20)  # ai_data_col.py:38
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--noise", type=float, default=0.0, help="std of Gaussian noise on the pilot's stick levels")
+    p.add_argument("--pilot", default="torch", choices=["torch", "device"],
+                   help="torch (default): the pilot as elementwise torch ops; device: the same law as one HIP launch per step (hx_pilot_act)")
     p.add_argument("--out", default=None)
     c = p.parse_args(argv)
     out = c.out or os.path.join("expert_data", c.env, "expert_data_ai_random.csv" if c.random else "expert_data_ai.csv")  # ai_data_col.py:104-105
-    s, a, info = collect(c.env, c.episodes, c.random, c.seed, c.noise)
+    s, a, info = collect(c.env, c.episodes, c.random, c.seed, c.noise, pilot=c.pilot)
     os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
     write_data(s, a, out)
     print(f"episode {info['episodes']}  step {len(s)}  invalid data {info['invalid']}")

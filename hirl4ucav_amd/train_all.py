@@ -329,8 +329,8 @@ def train_bc(config, device, seed, max_step):
     bc_table = torch.from_numpy(tab).to(device)
     table = DeviceReplay(es.shape[0], device)  # the sampler wants a main ring as well; the BC step reads only the BC rows
     table.store_rows(bc_table)
-    if upsample_refusal(config):
-        raise SystemExit("train_all: " + upsample_refusal(config))
+    if upsample_refusal(config) or expert_online_refusal(config):
+        raise SystemExit("train_all: " + (upsample_refusal(config) or expert_online_refusal(config)))
     if getattr(config, "expert_upsample", False):  # BC.py:152-158, 171-176: one row of every minibatch is a fire row
         from .utils.buffer import fire_rows
 
@@ -452,7 +452,7 @@ def check_agent_flags(run):
     # the reference's two sampling switches (HIRL.py:184-185): success rows of the replay drawn 10 : 1, one fire row forced into the BC minibatch
     run.buffer_upsample, run.expert_upsample = bool(getattr(config, "buffer_upsample", False)), bool(getattr(config, "expert_upsample", False))
     run.upsampler = None
-    for refusal in (per_refusal, nstep_refusal, clip_refusal, upsample_refusal):  # (per_refusal without --per: --per_new td on its own)
+    for refusal in (per_refusal, nstep_refusal, clip_refusal, upsample_refusal, expert_online_refusal):  # (per_refusal without --per: --per_new td on its own)
         if refusal(config, world):
             raise SystemExit("train_all: " + refusal(config, world))
     run.batch = 128  # train_all.py:190-208
@@ -516,7 +516,7 @@ def build_engine(run):
 def load_expert_tables(run):
     """HIRL / E-SAC / ISAC: the labelled expert ring, the BC (s, a) table and the frozen bc_actor"""
     config, device, eng = run.config, run.device, run.eng
-    run.expert = run.bc_table = run.fire_idx = None
+    run.expert = run.bc_table = run.fire_idx = run.online = None
     if run.upsampler is not None:  # (TD3 has no expert table: the engine hears of the upsampler here)
         eng.set_upsample(run.upsampler, None)
     if not (run.hirl or run.esac or run.isac):
@@ -545,6 +545,16 @@ def load_expert_tables(run):
         if upsample_refusal(config, run.world, n_fire=run.fire_idx.numel()):
             raise SystemExit("train_all: " + upsample_refusal(config, run.world, n_fire=run.fire_idx.numel()))
         eng.set_upsample(run.upsampler, run.fire_idx)
+    why = expert_online_resume_refusal(config, run.snap["driver"] if run.snap is not None else None)
+    if why:
+        raise SystemExit(f"train_all: --resume {config.resume} {why}")
+    if int(getattr(config, "expert_online", 0)) > 0:
+        # An extension (utils/pilot.py): the table grows by an online region that starts as a cyclic copy of the offline rows and is relabelled by the
+        # pilot behind every acting launch.  fire_idx above was taken from the offline rows, which stay where they are: it stays valid.
+        from .utils.pilot import OnlineExpert
+
+        run.online = OnlineExpert(run.env, run.bc_table, int(config.expert_online), int(config.expert_online_per_step))
+        run.bc_table = run.online.table
 
 
 def set_dtype(run):
@@ -592,11 +602,16 @@ def stats_record(run):
     rec = {"env": run.env_type}
     if run.estats is not None:
         rec["episode_stats"] = {"device": run.estats.state(), "last100": run.last100.state()}
+    if getattr(run, "online", None) is not None:  # (a snapshot of a run without --expert_online carries no such key)
+        rec["expert_online"] = run.online.state_dict()
     return rec
 
 
 def restore_stats(run, record):
-    """after CK.load_run: the statistics workspace and the last-100 window of the snapshot; a snapshot without them starts them at zero"""
+    """after CK.load_run: the statistics workspace and the last-100 window of the snapshot; a snapshot without them starts them at zero.  The online
+    region of the expert table and its call counter come back here too (load_expert_tables has refused a snapshot without them)."""
+    if getattr(run, "online", None) is not None:
+        run.online.load_state_dict(record["expert_online"])
     if run.estats is None:
         return
     st = record.get("episode_stats")
@@ -643,6 +658,8 @@ def restore_or_explore(run):
                 inserter.push(env, a0)
             if estats is not None:
                 estats.push()
+            if getattr(run, "online", None) is not None:
+                run.online.push()
             if getattr(run, "upsampler", None) is not None:
                 run.upsampler.mark_new(n)
         if run.per and run.per_new == "td":  # the exploration rows are appended with an error of their own too (SAC/agent.py:176-177, 234-246: the start_steps rows are scored as well)
@@ -709,12 +726,14 @@ def write_snapshot(run, episode):
 
 # ---- the vector step: two hooks every form shares, three forms --------------------------------------------------------------------------------------
 def after_env_step(run, step):
-    """Behind every acting launch, in this order: the n-step rows, the episode statistics, the new rows' first priorities, the reward sum.  (The front
-    forms run without an inserter and without --per: choose_loop.)"""
+    """Behind every acting launch, in this order: the n-step rows, the episode statistics, the pilot's relabelled rows, the new rows' first priorities,
+    the reward sum.  (The front forms run without an inserter and without --per: choose_loop.)"""
     if run.inserter is not None:
         run.inserter.push(run.env, run.actions)  # this step's finished n-step rows (at most multi_step * n of them)
     if run.estats is not None:
         run.estats.push()
+    if getattr(run, "online", None) is not None:
+        run.online.push()  # --expert_online: per_step envs relabelled by the pilot into the online region of bc_table (one launch, no host sync)
     if run.per and run.per_new == "td":
         replay, n, writer = run.replay, run.n, run.writer
         log_new = writer is not None and step % run.log_rate == 0
@@ -887,6 +906,8 @@ def log_episode(run):
         writer.add_scalar("Training/Last 50 Episode Fire success rate", (st["fire_success_episodes"] - run.last_stats["fire_success_episodes"]) / ended, episode)
         writer.add_scalar("Others/BC_weight", w, episode)
         writer.add_scalar("Others/Nonfinite_actions", st.get("nonfinite_actions", 0), episode)
+        if getattr(run, "online", None) is not None:
+            writer.add_scalar("Expert/Online Rows Written", run.online.rows_written(), episode)  # (host arithmetic: no device read)
         if ret is not None:
             tot = float(ret.mean())
             writer.add_scalar("Training/Episode Reward", tot, episode)
@@ -1041,6 +1062,42 @@ def upsample_refusal(config, world=1, n_fire=None):
     return None
 
 
+def expert_online_refusal(config, world=1):
+    """why `--expert_online` / `--expert_online_per_step` cannot run as asked, or None"""
+    rows, k = int(getattr(config, "expert_online", 0)), int(getattr(config, "expert_online_per_step", 64))
+    if rows == 0:
+        return None
+    if rows < 0:
+        return f"--expert_online {rows}: the rows of the online region, 0 (off) or more"
+    if config.agent == "SAC":
+        return (f"--expert_online goes with --agent HIRL (SAC / ESAC / ISAC draw expert TRANSITIONS from the labelled ring, not from the BC table, and "
+                f"relabelling r, s' and done there is not built), not --agent SAC --type {config.type}")
+    if config.agent == "TD3":
+        return "--expert_online goes with --agent HIRL (TD3 reads no expert table)"
+    if config.agent == "BC":
+        return "--expert_online goes with --agent HIRL (--agent BC has no rollouts whose states the pilot could label)"
+    if (config.gpus and config.gpus > 1) or world > 1:
+        return "--expert_online runs on one GPU (the refresh is rank-local and untested on sharded ranks): use --gpus 1"
+    if not 1 <= k <= min(rows, int(config.num_envs)):
+        return (f"--expert_online_per_step {k}: 1 <= rows per step <= min(--expert_online, --num_envs) = {min(rows, int(config.num_envs))} (the picks of a step "
+                "are distinct envs and distinct slots)")
+    return None
+
+
+def expert_online_resume_refusal(config, driver):
+    """why a snapshot's driver record cannot be resumed under this run's --expert_online / --expert_online_per_step, or None (driver None: a fresh run)"""
+    if driver is None:
+        return None
+    was = driver.get("expert_online")
+    was_rows, was_k = (int(was["online_rows"]), int(was["per_step"])) if was is not None else (0, None)
+    rows, k = int(getattr(config, "expert_online", 0)), int(getattr(config, "expert_online_per_step", 64))
+    if was_rows != rows:
+        return f"was run with --expert_online {was_rows}, --expert_online {rows} given"
+    if rows and was_k != k:
+        return f"was run with --expert_online_per_step {was_k}, --expert_online_per_step {k} given"
+    return None
+
+
 def clip_refusal(config, world=1):
     """why `--grad_clip` / `--fixed_alpha` cannot run as asked, or None"""
     clip, fixed = getattr(config, "grad_clip", None), getattr(config, "fixed_alpha", None)
@@ -1063,7 +1120,7 @@ def parse_args(argv=None):
     """parser().parse_args with the cross-flag checks that are argparse errors"""
     p = parser()
     cfg = p.parse_args(argv)
-    why = per_refusal(cfg) or clip_refusal(cfg) or nstep_refusal(cfg) or mixed_refusal(cfg) or upsample_refusal(cfg)
+    why = per_refusal(cfg) or clip_refusal(cfg) or nstep_refusal(cfg) or mixed_refusal(cfg) or upsample_refusal(cfg) or expert_online_refusal(cfg)
     if why:
         p.error(why)
     if cfg.type == "ISAC" and cfg.agent != "SAC":
@@ -1142,6 +1199,13 @@ def parser():
                         "by a uniformly chosen expert row whose fire action is 1")
     p.add_argument("--upsample_boost", type=int, default=10, help="--buffer_upsample: the integer weight of a success row against 1, 2..255 "
                                                                   "(10 = the reference's 1.0 : 0.1)")
+    p.add_argument("--expert_online", type=int, default=0, metavar="ROWS",
+                   help="HIRL (every --type, every --dtype, both loops; an extension, the reference can only replay recordings): the BC table grows by ROWS "
+                        "rows that start as a cyclic copy of the expert CSV's and are relabelled by the scripted pursuit pilot in the states the learner "
+                        "reaches (dataset aggregation): one small launch behind every acting launch (utils/pilot.py).  0 (default): off, the run is launch "
+                        "for launch what it was.  One GPU.  Stored in the snapshot: --resume refuses another value")
+    p.add_argument("--expert_online_per_step", type=int, default=64, metavar="K",
+                   help="--expert_online: envs relabelled per acting launch, 1 <= K <= min(ROWS, --num_envs); they replace the K oldest online rows")
     p.add_argument("--multi_step", type=int, default=1,
                    help="SAC / E-SAC: truncated n-step returns (SacAgent(multi_step=N)), N in 2..8; 1 (default): one-step rows.  A launch of its own behind "
                         "every acting launch keeps the last N steps per env and stores finished rows with r = sum gamma^k r_k and the row's discount folded "

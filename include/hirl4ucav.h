@@ -83,8 +83,9 @@ const char* hx_last_error(void);
  * 122: the record of validation episodes (HxTrace, hx_trace_*).
  * 123: per-episode statistics by scenario (HxEpStat, hx_epstat_*).
  * 124: the merged actor message carries the soft count as base-32 digit words too, and hx_adam_mixed reads those (exact on the bf16 transports).
- * 125: success upsampling of the replay draw and the BC minibatch's fire row (HxUps, hx_ups_*). */
-#define HX_ABI_VERSION 125
+ * 125: success upsampling of the replay draw and the BC minibatch's fire row (HxUps, hx_ups_*).
+ * 126: the pursuit pilot as a kernel and the online region of the BC table (hx_pilot_act, hx_pilot_refresh). */
+#define HX_ABI_VERSION 126
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -899,6 +900,34 @@ int hx_ups_recount(const HxUps* ups, void* stream);
  * resolves to the block's last live slot, never to a slot beyond the live length. */
 int hx_ups_draw(const HxUps* ups, const float* ring, int32_t batch, int32_t n_main, const uint64_t* x, uint64_t seed, uint32_t call, int32_t* idx,
                 float* rows, const int32_t* fire_idx, int32_t n_fire, const float* bc_table, int32_t* idx_bc, float* bc_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * The pilot as a kernel (an EXTENSION: the reference's expert is Harfang's IA inside an external simulator and can only be replayed from
+ * recordings).  data/expert_pilot.py pursuit_actions, the scripted pursuit law the expert CSVs of this build are flown by, on the state words in
+ * HBM — so the expert can label the states the learner reaches (dataset aggregation).  Per env, fp32 without contraction, correctly rounded divide
+ * and square root, in this order (tests/_pilot_model.py is the same in numpy, bit for bit):
+ *     w, x, y, z = state words 6..9;  d_i = state[13 + i] - state[i], i = 0..2
+ *     rows of R^T:  ax = (1 - 2 (yy + zz), 2 (xy + wz), 2 (xz - wy))
+ *                   ay = (2 (xy - wz), 1 - 2 (xx + zz), 2 (yz + wx))
+ *                   az = (2 (xz + wy), 2 (yz - wx), 1 - 2 (xx + yy))
+ *     b_r = (r0 d0 + r1 d1) + r2 d2 for r = ax, ay, az;  nrm = sqrt((b0 b0 + b1 b1) + b2 b2);  nrm < 1e-6: nrm = 1e-6 (a comparison: NaN stays NaN)
+ *     levels = (-4 (b1 / nrm), -2 (b0 / nrm), 4 (b0 / nrm)), + noise[i][0..2] when given, each clamped to [-1, 1] by comparisons
+ *     fire = +1 iff obs[7] > 0 && obs[8] > 0 (locked, and the missile still on the rail), else -1
+ * ------------------------------------------------------------------------------------------------------------ */
+/* actions[i] <- (levels, fire) of env i, i < n: state as hx_env_step leaves it (word w of env i at state[w * stride + i]), obs [n][13], noise NULL or
+ * [n][3] (already scaled), actions [n][4], 16-byte aligned.  One env per lane, 64 per workgroup; every state word one contiguous run per wave, one
+ * 16-byte store per lane.  Enqueues only. */
+int hx_pilot_act(const float* state, int64_t n, int64_t stride, const float* obs, const float* noise, float* actions, void* stream);
+/* The online region of a BC table [offline_rows + online_rows][HX_ROW_WORDS]: behind an acting launch, k = per_call envs are relabelled by the pilot and
+ * stored over the oldest online rows.  For j in [0, k):
+ *     env   e_j  = (call + j floor(n / k)) mod n            (k distinct envs spread over the population; the window moves by one env per call)
+ *     slot       = offline_rows + ((call k + j) mod M)      (M = online_rows; exact for every 64-bit call: FIFO over the online region)
+ *     row        = obs[e_j] (words 0..12), the pilot's NOISE-FREE action (13..16), zeros (17..31), written as one whole 128-byte line
+ *     a row with a non-finite word among its 17 is NOT written: the slot keeps what it had
+ * Rows [0, offline_rows) are never touched.  1 <= k <= min(n, M), table 128-byte aligned, else HX_ERR_ARG and nothing is launched.  Between launches
+ * every slot holds a complete row.  No atomics, no workgroup waits for another.  Enqueues only. */
+int hx_pilot_refresh(const float* state, int64_t n, int64_t stride, const float* obs, float* table, int64_t offline_rows, int64_t online_rows,
+                     int32_t per_call, uint64_t call, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Exchange step of a sharded update without a collective library (selectable beside RCCL): one-shot all-reduce over hipIpc peer
