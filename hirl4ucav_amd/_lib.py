@@ -6,28 +6,37 @@ There is NO fallback: if the HIP extension is missing or a call fails, this rais
 import ctypes
 import os
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # HX_LIBRARY selects another build of the same library (A/B timing of two builds on one box, the phase-stamp build); never a fallback
 SO_PATH = os.environ.get("HX_LIBRARY") or os.path.join(_HERE, "libhx_mi355.so")
 
-ENV_WORDS, OBS_DIM, ACT_DIM, ROW_WORDS = 37, 13, 4, 32
+_ABI = _abi.abi()  # structs, signatures and constants as include/hirl4ucav.h declares them: nothing below restates the header
+HxError = _abi.HxError
+DEFINES = _ABI.defines  # "HX_NAME" -> int
+
+
+def _defines(names):
+    return (DEFINES["HX_" + k] for k in names.split())
+
+
+ENV_WORDS, OBS_DIM, ACT_DIM, ROW_WORDS = _defines("ENV_WORDS OBS_DIM ACT_DIM ROW_WORDS")
 STAT_NAMES = ("episodes", "kills", "fire_success_episodes", "time_limit", "fires", "good_fires", "locked_steps", "env_steps", "nonfinite_actions")
-STAT_WAYS, STAT_PITCH = 32, 16  # HX_STAT_WAYS, HX_STAT_PITCH: the counters are kept 32 times (way = workgroup % 32, one 128-byte line each); a statistic = the sum
+STAT_WAYS, STAT_PITCH = _defines("STAT_WAYS STAT_PITCH")  # the counters are kept 32 times (way = workgroup % 32, one 128-byte line each); a statistic = the sum
 
-F_LOCKED_PREV, F_LOCKED, F_SLOT_PREV, F_SLOT, F_FIRED, F_FIRE_SUCCESS, F_EPISODE_SUCCESS, F_DONE = (1 << i for i in range(8))
-F_SCEN_SHIFT = 8
-F_SERP_POS, F_SERP_LONG, F_M_ACTIVE, F_M_GUIDED, F_SIM_SLOT = (1 << i for i in range(10, 15))
+F_LOCKED_PREV, F_LOCKED, F_SLOT_PREV, F_SLOT, F_FIRED, F_FIRE_SUCCESS, F_EPISODE_SUCCESS, F_DONE = _defines(
+    "F_LOCKED_PREV F_LOCKED F_SLOT_PREV F_SLOT F_FIRED F_FIRE_SUCCESS F_EPISODE_SUCCESS F_DONE")
+F_SCEN_SHIFT, F_SERP_POS, F_SERP_LONG, F_M_ACTIVE, F_M_GUIDED, F_SIM_SLOT = _defines("F_SCEN_SHIFT F_SERP_POS F_SERP_LONG F_M_ACTIVE F_M_GUIDED F_SIM_SLOT")
+LAYOUT_ORDERED_SLOTS, = _defines("LAYOUT_ORDERED_SLOTS")  # the ring behind HxStepOpts.total carries the slot header (DeviceReplay(ordered_slots=True))
+TRACE_FIELDS, TRACE_SUMMARIES = _defines("TRACE_FIELDS TRACE_SUMMARIES")
+EPSTAT_BINS, EPSTAT_SUMS, EPSTAT_SLOT_WORDS = _defines("EPSTAT_BINS EPSTAT_SUMS EPSTAT_SLOT_WORDS")
+ABI_VERSION, = _defines("ABI_VERSION")
 
-_vp, _i32, _i64, _u32, _u64, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float
-
-
-class HxStepOpts(ctypes.Structure):
-    _fields_ = [("max_step", _i32), ("auto_reset", _i32), ("randomize", _i32), ("env_id0", _u32), ("seed", _u64),
-                ("episode_ctr", _vp), ("ring", _vp), ("ring_success", _vp), ("cap", _i64), ("total", _vp), ("stats", _vp),
-                ("ev_start", _vp), ("ev_stop", _vp), ("layout", _i32)]
-
-
-LAYOUT_ORDERED_SLOTS = 1 << 16  # HX_LAYOUT_ORDERED_SLOTS: the ring behind HxStepOpts.total carries the slot header (DeviceReplay(ordered_slots=True))
+STRUCTS = _ABI.structs  # name -> the ONE ctypes class of a `typedef struct Hx…` (a POINTER(HxName) argument takes only that class)
+HxStepOpts = STRUCTS["HxStepOpts"]
+HxTrace = STRUCTS["HxTrace"]  # the episode record's buffers (utils/trace.py carves them out of one workspace)
+HxEpStat = STRUCTS["HxEpStat"]  # the episode statistics' buffers (utils/epstat.py carves them out of one workspace)
 
 
 def layout(pair, envs_per_block):
@@ -35,46 +44,7 @@ def layout(pair, envs_per_block):
     return ((1 if pair else 0) << 8) | (int(envs_per_block) // 4)
 
 
-class HxTrace(ctypes.Structure):
-    """the episode record's buffers (include/hirl4ucav.h HxTrace; utils/trace.py carves them out of one workspace)"""
-    _fields_ = [("log", _vp), ("total", _vp), ("nrec", _vp), ("end_step", _vp), ("end_flags", _vp), ("launches", _vp), ("hits", _vp), ("alive", _vp),
-                ("k", _i64), ("cap_steps", _i32)]
-
-
-TRACE_FIELDS, TRACE_SUMMARIES = 8, 6  # HX_TRACE_FIELDS, HX_TRACE_SUMMARIES
-
-
-class HxEpStat(ctypes.Structure):
-    """the episode statistics' buffers (include/hirl4ucav.h HxEpStat; utils/epstat.py carves them out of one workspace)"""
-    _fields_ = [("part", _vp), ("acc", _vp), ("len", _vp), ("last_ctr", _vp), ("n_envs", _i64)]
-
-
-EPSTAT_BINS, EPSTAT_SUMS, EPSTAT_SLOT_WORDS = 4, 8, 36  # HX_EPSTAT_BINS, HX_EPSTAT_SUMS, HX_EPSTAT_SLOT_WORDS
-
-
-class HxError(RuntimeError):
-    pass
-
-
-_SIGNATURES = {
-    "hx_env_reset": [_vp, _i64, _i64, _vp, _vp, _i32, _i32, _u64, _u32, _vp, _vp, _vp],
-    "hx_env_step": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(HxStepOpts), _vp],
-    "hx_env_rearm": [_vp, _i64, _i64, _vp, _vp],
-    "hx_label_transitions": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
-    "hx_trace_reset": [ctypes.POINTER(HxTrace), _vp],
-    "hx_trace_push": [ctypes.POINTER(HxTrace), _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp],
-    "hx_epstat_reset": [ctypes.POINTER(HxEpStat), _vp, _vp],
-    "hx_epstat_clear": [ctypes.POINTER(HxEpStat), _vp],
-    "hx_epstat_push": [ctypes.POINTER(HxEpStat), _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
-    "hx_pilot_act": [_vp, _i64, _i64, _vp, _vp, _vp, _vp],
-    "hx_pilot_refresh": [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _u64, _vp],
-    "hx_event_destroy": [_vp],
-    "hx_event_elapsed_us": [_vp, _vp, ctypes.POINTER(ctypes.c_float)],
-}
-
 _lib = None
-ABI_VERSION = 126  # HX_ABI_VERSION of include/hirl4ucav.h
-_ABI_STRUCTS = {}  # name -> (index in hx_abi_sizes, ctypes class): filled by the binding modules (check_struct)
 
 
 def check_struct(index, cls):
@@ -82,7 +52,6 @@ def check_struct(index, cls):
     would hand the kernels short buffers (a 9-word statistics buffer under a library that adds into 512 words)."""
     sizes = (ctypes.c_int32 * 8)()
     L = load()
-    L.hx_abi_sizes.argtypes = [ctypes.POINTER(ctypes.c_int32)]
     if L.hx_abi_sizes(sizes) != 0 or sizes[index] != ctypes.sizeof(cls):
         raise HxError(f"ABI mismatch: {cls.__name__} is {ctypes.sizeof(cls)} bytes here, {sizes[index]} in {SO_PATH}")
     if sizes[7] != STAT_WAYS * STAT_PITCH:
@@ -103,34 +72,25 @@ def load():
     import torch  # noqa: F401
 
     L = ctypes.CDLL(SO_PATH)
-    L.hx_last_error.restype = ctypes.c_char_p
-    L.hx_version.restype = ctypes.c_int
+    _abi.bind(L)  # argtypes and restype of every function the headers declare
     if L.hx_version() != ABI_VERSION:
-        raise HxError(f"{SO_PATH} implements ABI version {L.hx_version()}, this binding was written for {ABI_VERSION} (include/hirl4ucav.h "
+        raise HxError(f"{SO_PATH} implements ABI version {L.hx_version()}, the headers this binding is read from declare {ABI_VERSION} (include/hirl4ucav.h "
                       f"HX_ABI_VERSION): rebuild the library (make -C hirl4ucav_amd/csrc)")
-    L.hx_event_create.restype = ctypes.c_void_p
-    L.hx_event_create.argtypes = []
-    L.hx_trace_workspace_words.restype = ctypes.c_int64
-    L.hx_trace_workspace_words.argtypes = [_i64, _i32]
-    L.hx_epstat_workspace_words.restype = ctypes.c_int64
-    L.hx_epstat_workspace_words.argtypes = [_i64]
     if L.hx_epstat_sizeof() != ctypes.sizeof(HxEpStat):
         raise HxError(f"ABI mismatch: HxEpStat is {ctypes.sizeof(HxEpStat)} bytes here, {L.hx_epstat_sizeof()} in {SO_PATH}")
-    for name, args in _SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.argtypes = args
-        fn.restype = ctypes.c_int
     _lib = L
     return L
 
 
 def register(name, argtypes):
-    """Used by the other binding modules to add their entry points."""
-    _SIGNATURES[name] = argtypes
-    if _lib is not None:
-        fn = getattr(_lib, name)
-        fn.argtypes = argtypes
-        fn.restype = ctypes.c_int
+    """Callers outside the package that still state a signature: it is compared with the header's (any pointer but one to a struct of the
+    header counts as void*) and refused when it differs; nothing is overwritten."""
+    if name not in _ABI.functions:
+        raise HxError(f"{name} is not declared in the headers of {_abi.INCLUDE_DIR}")
+    declared = _ABI.functions[name][1]
+    given = [ctypes.c_void_p if issubclass(t, ctypes._Pointer) and t._type_ not in STRUCTS.values() else t for t in argtypes]
+    if given != declared:
+        raise HxError(f"{name}: the signature given, {[t.__name__ for t in argtypes]}, is not the header's, {[t.__name__ for t in declared]}")
 
 
 def call(name, *args):

@@ -14,76 +14,12 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .exchange import OneShotExchange, RcclDirect, _DeviceWords, negotiate_rccl_direct  # noqa: F401  (the transports of the sharded update)
 
 H1, H2 = 256, 512
-_vp, _i32, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-
-
-class HxBatch(ctypes.Structure):
-    _fields_ = [("rows", _vp), ("bc_rows", _vp), ("batch", _i32), ("noise", _vp)]
-
-
-class HxSample(ctypes.Structure):
-    """the minibatch draw as a description (include/hirl4ucav.h HxSample): launch A of the update draws and gathers"""
-    _fields_ = [("total", _vp), ("cap", ctypes.c_int64), ("ring", _vp), ("expert_ring", _vp), ("expert_len", ctypes.c_int64),
-                ("bc_table", _vp), ("bc_len", ctypes.c_int64), ("n_main", _i32), ("seed", ctypes.c_uint64), ("call", ctypes.c_uint32),
-                ("sigma", _f32), ("idx", _vp), ("idx_bc", _vp), ("guard", ctypes.c_uint32)]
-
-
-class HxFront(ctypes.Structure):
-    """in-launch hand-off state of the front launch (include/hirl4ucav.h HxFront)"""
-    _fields_ = [("flags", _vp), ("status", _vp), ("epoch", ctypes.c_uint32), ("with_c", ctypes.c_uint32)]
-
-
-class HxNets(ctypes.Structure):
-    _fields_ = [(k, _vp) for k in ("actor", "critic", "target_actor", "target_critic", "bc_actor", "grad_actor", "grad_critic",
-                                   "m_actor", "v_actor", "m_critic", "v_critic", "losses", "soft_count", "wstate", "ws", "actor_w2_bf16", "actor_w2_f32i",
-                                   "w2_bf16_all", "xchg_status", "actor_w2_x9")]
-
-
-class HxHyper(ctypes.Structure):
-    _fields_ = [(k, _f32) for k in ("gamma", "tau", "lr_actor", "lr_critic", "slope", "noise_clamp", "loss_lambda")] + [("use_bc", _i32), ("no_layernorm", _i32)]
-
-
-_P = ctypes.POINTER
-_lib.register("hx_actor_act", [_vp, _vp, ctypes.c_int64, _vp, _i32, _vp, _f32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _f32, _vp, _vp])
-_lib.register("hx_actor_act_step", [_vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _i32, _vp, _f32, ctypes.c_uint64, ctypes.c_uint32,
-                                     ctypes.c_uint32, _f32, _vp, _vp, _vp, _P(_lib.HxStepOpts), _vp])
-_lib.register("hx_pack_w2_bf16", [_vp, _i32, _vp, _vp])
-_lib.register("hx_pack_w2_f32i", [_vp, _i32, _vp, _vp])
-_lib.register("hx_pack_update_images", [_P(HxNets), _vp])
-_lib.register("hx_pack_w2_x9", [_vp, _i32, _vp, _vp])
-_lib.register("hx_actor_act_x9", [_vp, _vp, _vp, ctypes.c_int64, _vp, _i32, _vp, _f32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _f32, _vp])
-_lib.register("hx_actor_act_step_x9", [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _i32, _vp, _f32, ctypes.c_uint64, ctypes.c_uint32,
-                                        ctypes.c_uint32, _f32, _vp, _vp, _vp, _P(_lib.HxStepOpts), _vp])
-_lib.register("hx_actor_act_f32i", [_vp, _vp, _vp, ctypes.c_int64, _vp, _i32, _vp, _f32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _f32, _vp])
-_lib.register("hx_actor_act_step_f32i", [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _i32, _vp, _f32, ctypes.c_uint64, ctypes.c_uint32,
-                                          ctypes.c_uint32, _f32, _vp, _vp, _vp, _P(_lib.HxStepOpts), _vp])
-_lib.register("hx_actor_act_bf16", [_vp, _vp, _vp, ctypes.c_int64, _vp, _i32, _vp, _f32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _f32, _vp])
-_lib.register("hx_actor_act_step_bf16", [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _i32, _vp, _f32, ctypes.c_uint64, ctypes.c_uint32,
-                                          ctypes.c_uint32, _f32, _vp, _vp, _vp, _P(_lib.HxStepOpts), _vp])
-_lib.register("hx_hirl_critic_grads", [_P(HxNets), _P(HxBatch), _P(HxHyper), _i32, _vp])
-_lib.register("hx_hirl_actor_backward", [_P(HxNets), _P(HxBatch), _P(HxHyper), _i32, _i32, _vp])
-_lib.register("hx_hirl_actor_wgrad", [_P(HxNets), _P(HxHyper), _i32, _i32, _i32, _f32, _f32, _vp])
-_lib.register("hx_adam", [_P(HxNets), _P(HxHyper), _i32, _i32, _f32, _i32, _f32, _f32, _i32, _vp])
-_lib.register("hx_polyak", [_P(HxNets), _P(HxHyper), _vp])
-_lib.register("hx_hirl_actor_wgrad_split", [_P(HxNets), _P(HxHyper), _i32, _vp, _vp])
-_lib.register("hx_adam_mixed", [_P(HxNets), _P(HxHyper), _i32, _i32, _f32, _i32, _f32, _f32, _i32, _vp, _vp])
-from .exchange import OneShotExchange, RcclDirect, _DeviceWords, negotiate_rccl_direct  # noqa: E402,F401  (the transports of the sharded update)
-
-
-_lib.register("hx_bc_train_actor", [_P(HxNets), _P(HxBatch), _P(HxHyper), _i32, _vp])
-_lib.register("hx_hirl_learn", [_P(HxNets), _P(HxBatch), _P(HxHyper), _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp])
-_lib.register("hx_hirl_learn_sampled", [_P(HxNets), _P(HxBatch), _P(HxHyper), _P(HxSample), _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp])
-_lib.register("hx_hirl_front", [_vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _i32, _vp, _f32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp,
-                                 _P(_lib.HxStepOpts), _P(HxNets), _P(HxBatch), _P(HxHyper), _i32, _i32, _P(HxFront), _vp])
-_lib.register("hx_hirl_learn_back", [_P(HxNets), _P(HxBatch), _P(HxHyper), _i32, _i32, _i32, _i32, _i32, _f32, _f32, _P(HxSample), _P(HxBatch), _i32, _vp])
-_lib.register("hx_hirl_critic_grads_back", [_P(HxNets), _P(HxBatch), _P(HxHyper), _P(HxSample), _P(HxBatch), _i32, _vp])
-_lib.register("hx_sample_batch_guarded", [_vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _i32, _i32, _i32, ctypes.c_uint64,
-                                           ctypes.c_uint32, _f32, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp])
-_lib.register("hx_hirl_critic_grads_sampled", [_P(HxNets), _P(HxBatch), _P(HxHyper), _P(HxSample), _i32, _vp])
-_lib.register("hx_sample_batch", [_vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _i32, _i32, _i32, ctypes.c_uint64,
-                                   ctypes.c_uint32, _f32, _vp, _vp, _vp, _vp, _vp, _vp])
+HxBatch, HxNets, HxHyper = (_lib.STRUCTS[k] for k in ("HxBatch", "HxNets", "HxHyper"))
+HxSample = _lib.STRUCTS["HxSample"]  # the minibatch draw as a description: launch A of the update draws and gathers
+HxFront = _lib.STRUCTS["HxFront"]  # in-launch hand-off state of the front launch
 
 # ---- flat layout <-> reference state_dict keys (hirl/agents/HIRL.py:19-146) -------------------------------------
 
@@ -173,7 +109,6 @@ class HirlEngine:
         for i, cls in ((0, _lib.HxStepOpts), (1, HxNets), (2, HxHyper), (3, HxBatch), (4, HxSample)):
             _lib.check_struct(i, cls)  # this binding's structs against the loaded library's (include/hirl4ucav.h hx_abi_sizes)
         assert L.hx_actor_param_count() == ACTOR_SIZE and L.hx_critic_param_count() == CRITIC_SIZE
-        L.hx_hirl_workspace_floats.restype = ctypes.c_int64
         self.batch = int(batch)
         # ONE arena (carve) for the 5 nets, gradients, Adam moments, workspace and minibatch tiles
         ws_floats = int(L.hx_hirl_workspace_floats(self.batch))
@@ -288,7 +223,6 @@ class HirlEngine:
         if self.update_dtype == "bf16":
             if self.images is None:
                 L = _lib.load()
-                L.hx_bf16_images_elems.restype = ctypes.c_int64
                 self.images = torch.zeros(int(L.hx_bf16_images_elems()), dtype=torch.bfloat16, device=self.device)
             self.nets.w2_bf16_all = self.images.data_ptr()
             self.w2_bf16 = self.images[:H2 * H1]

@@ -8,23 +8,7 @@ import torch
 
 from .. import _lib
 
-_vp, _i32, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-_P = ctypes.POINTER
-_lib.register("hx_ipc_alloc", [ctypes.c_int64, _i32, _P(_vp)])
-_lib.register("hx_ipc_free", [_vp])
-_lib.register("hx_ipc_export", [_vp, _vp])
-_lib.register("hx_ipc_import", [_vp, _P(_vp)])
-_lib.register("hx_ipc_close", [_vp])
-_lib.register("hx_allreduce_oneshot", [_vp, _P(_vp), _P(_vp), _vp, _i32, _i32, ctypes.c_int64, ctypes.c_uint32, _i32, _vp])
-_lib.register("hx_allreduce_twostage", [_vp, _P(_vp), _P(_vp), _P(_vp), _P(_vp), _vp, _i32, _i32, ctypes.c_int64, ctypes.c_uint32, _i32, _i32, _vp])
-_lib.register("hx_rccl_unique_id", [_vp])
-_lib.register("hx_rccl_init", [_vp, _i32, _i32, _P(_vp)])
-_lib.register("hx_rccl_allreduce", [_vp, _vp, ctypes.c_int64, _i32, _vp])
-_lib.register("hx_rccl_allreduce_bf16", [_vp, _vp, _vp, ctypes.c_int64, _vp])
-_lib.register("hx_rccl_destroy", [_vp])
-
-
-_lib.register("hx_rccl_available", [])
+_vp = ctypes.c_void_p
 
 
 class RcclDirect:

@@ -10,54 +10,7 @@ import torch
 from .. import _lib
 from . import engine as E
 
-_vp, _i32, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-_P = ctypes.POINTER
-
-
-class HxSacNets(ctypes.Structure):
-    _fields_ = [(k, _vp) for k in ("policy", "critic", "target_critic", "grad_policy", "grad_critic", "m_policy", "v_policy", "m_critic",
-                                   "v_critic", "losses", "alpha_state", "ws", "policy_w2_f32i", "policy_w2_x9", "w2_bf16_all", "policy_w2_bf16")]
-
-
-class HxSacImit(ctypes.Structure):
-    """the imitative branch's buffers (include/hirl4ucav.h HxSacImit)"""
-    _fields_ = [("bc_actor", _vp), ("expert_rows", _vp), ("ws", _vp), ("count", _vp), ("bc_slope", _f32)]
-
-
-class HxSacBatch(ctypes.Structure):
-    _fields_ = [("rows", _vp), ("batch", _i32), ("eps_next", _vp), ("eps_cur", _vp), ("seed", ctypes.c_uint64), ("call", ctypes.c_uint32)]
-
-
-_lib.register("hx_sac_act", [_vp, _vp, ctypes.c_int64, _vp, _i32, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp])
-_lib.register("hx_sac_act_step", [_vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _i32, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
-                                   _vp, _vp, _vp, _P(_lib.HxStepOpts), _vp])
-_lib.register("hx_sac_act_f32i", [_vp, _vp, _vp, ctypes.c_int64, _vp, _i32, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp])
-_lib.register("hx_sac_act_step_f32i", [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _i32, _vp, ctypes.c_uint64, ctypes.c_uint32,
-                                        ctypes.c_uint32, _vp, _vp, _vp, _P(_lib.HxStepOpts), _vp])
-_lib.register("hx_sac_act_x9", [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _i32, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp])
-_lib.register("hx_sac_act_step_x9", [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _i32, _vp, ctypes.c_uint64, ctypes.c_uint32,
-                                      ctypes.c_uint32, _vp, _vp, _vp, _P(_lib.HxStepOpts), _vp])
-_lib.register("hx_sac_act_bf16", [_vp, _vp, _vp, ctypes.c_int64, _vp, _i32, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp])
-_lib.register("hx_sac_act_step_bf16", [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _i32, _vp, ctypes.c_uint64, ctypes.c_uint32,
-                                        ctypes.c_uint32, _vp, _vp, _vp, _P(_lib.HxStepOpts), _vp])
-_lib.register("hx_sac_pack_update_images", [_P(HxSacNets), _vp])
-_lib.register("hx_sac_critic_grads", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _i32, _vp])
-_lib.register("hx_sac_critic_grads_sampled", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _P(E.HxSample), _i32, _vp])
-_lib.register("hx_sac_critic_step", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _P(E.HxSample), _i32, _i32, _vp])
-_lib.register("hx_sac_front", [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _i32, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp,
-                                _P(_lib.HxStepOpts), _P(HxSacNets), _P(HxSacBatch), _vp])
-_lib.register("hx_sac_learn_back", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _i32, _i32, ctypes.c_float, _P(E.HxSample), _vp, _vp])
-_lib.register("hx_sac_learn", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _P(E.HxSample), _i32, _i32, ctypes.c_float, _vp])
-_lib.register("hx_sac_policy_grads", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _vp])
-_lib.register("hx_sac_adam", [_P(HxSacNets), _P(E.HxHyper), _i32, _i32, _f32, _f32, _vp])
-_lib.register("hx_sac_policy_grads_imitative", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _P(HxSacImit), _vp])
-_lib.register("hx_sac_learn_weighted", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _vp, _vp, _i32, _i32, ctypes.c_float, _vp])
-_lib.register("hx_sac_grad_norm", [_P(HxSacNets), _i32, _vp, _vp])
-_lib.register("hx_sac_adam_clipped", [_P(HxSacNets), _P(E.HxHyper), _i32, _i32, _f32, _f32, _f32, _vp, _vp])
-_lib.register("hx_sac_learn_weighted_clipped", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _vp, _vp, _i32, _i32, ctypes.c_float, _f32, _vp, _vp])
-_lib.register("hx_sac_learn_imitative", [_P(HxSacNets), _P(HxSacBatch), _P(E.HxHyper), _P(E.HxSample), _P(HxSacImit), _P(E.HxSample), _i32, _i32,
-                                          ctypes.c_float, _vp])
-
+HxSacNets, HxSacImit, HxSacBatch = (_lib.STRUCTS[k] for k in ("HxSacNets", "HxSacImit", "HxSacBatch"))
 H1, H2 = E.H1, E.H2
 SEQ_KEYS = ("0.weight", "0.bias", "2.weight", "2.bias", "4.weight", "4.bias")  # nn.Sequential(Linear, ReLU, Linear, ReLU, Linear)
 
@@ -126,7 +79,6 @@ class SacEngine:
         if self.device.type != "cuda":
             raise _lib.HxError("SacEngine runs on the GPU only (no CPU path in the product)")
         L = _lib.load()
-        L.hx_sac_workspace_floats.restype = ctypes.c_int64
         assert L.hx_sac_policy_param_count() == POLICY_SIZE
         self.batch = int(batch)
         ws = int(L.hx_sac_workspace_floats(self.batch))
@@ -186,7 +138,6 @@ class SacEngine:
             raise _lib.HxError("gradient clipping runs on one GPU (the norm is taken over this rank's gradient, before any exchange): run it with --gpus 1")
         if self.clip_ws is None:
             L = _lib.load()
-            L.hx_sac_clip_floats.restype = ctypes.c_int64
             self.clip_ws = torch.zeros(int(L.hx_sac_clip_floats()), dtype=torch.float32, device=self.device)
         self.grad_clip = max_norm
 
@@ -291,7 +242,6 @@ class SacEngine:
         if self.prioritized is not None:
             raise _lib.HxError("the imitative branch does not go with prioritized replay (not built: SacAgent(imitative=True, per=True)): build a SacEngine without set_prioritized")
         L = _lib.load()
-        L.hx_sac_imit_sizeof.restype, L.hx_sac_imit_workspace_floats.restype = ctypes.c_int, ctypes.c_int64
         if L.hx_sac_imit_sizeof() != ctypes.sizeof(HxSacImit):
             raise _lib.HxError(f"ABI mismatch: HxSacImit is {ctypes.sizeof(HxSacImit)} bytes here, {L.hx_sac_imit_sizeof()} in {_lib.SO_PATH}")
         if torch.is_tensor(bc_actor):
@@ -359,7 +309,6 @@ class SacEngine:
         if self.update_dtype == "bf16":
             if self.images is None:
                 L = _lib.load()
-                L.hx_bf16_images_elems.restype = ctypes.c_int64
                 self.images = torch.zeros(int(L.hx_bf16_images_elems()), dtype=torch.bfloat16, device=self.device)
             self.w2_bf16 = self.images[:H2 * H1]
             self.nets.w2_bf16_all, self.nets.policy_w2_bf16, self.nets.policy_w2_f32i = self.images.data_ptr(), None, None

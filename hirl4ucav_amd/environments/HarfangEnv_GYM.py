@@ -5,7 +5,6 @@ the batched HIP env-step kernel (one env resident on the GPU) instead of a Harfa
 For throughput use BatchedHarfangEnv (environments/batched.py); this façade exists so that the reference's drivers
 (train_all.py, validate_all.py) and data tools keep working call for call.
 """
-import ctypes
 import inspect
 import os
 import random
@@ -62,8 +61,6 @@ class HarfangEnv:
         self._np_action, self._np_row = self._h_action.numpy(), self._h_row.numpy()
         # (the stream current AT THE CALL: hx_env_step / hx_env_pack_row are enqueued on _lib.stream_ptr(), which follows torch.cuda.stream(...))
         self._stream_sync = lambda: torch.cuda.current_stream(self._env.device).synchronize()
-        _lib.register("hx_env_pack_row", [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p])
         self.state = None
 
     # ---- helpers ------------------------------------------------------------------------------------------------

@@ -47,8 +47,6 @@ class GpuSimBackend:
 
         self.torch, self.lib, self.ct = torch, _lib, ctypes
         _lib.load()
-        _lib.register("hx_sim_tick", [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p])
-        _lib.register("hx_sim_readback", [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p])
         d = torch.device(device)
         self.state = torch.zeros((_lib.ENV_WORDS, 1), dtype=torch.float32, device=d)
         self.cmd = {ALLY: [0.0, 0.0, 0.0], OPPO: [0.0, 0.0, 0.0]}

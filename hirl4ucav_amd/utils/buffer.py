@@ -46,21 +46,7 @@ class DeviceReplay:
         self.fixed_len = min(start + k, self.capacity)  # host-known live length (tables filled once: expert ring)
 
 
-
-class HxPer(ctypes.Structure):
-    """the prioritized store's buffers (include/hirl4ucav.h HxPer)"""
-    _fields_ = [("prio", ctypes.c_void_p), ("bsum", ctypes.c_void_p), ("pmax", ctypes.c_void_p), ("marked", ctypes.c_void_p), ("ticket", ctypes.c_void_p),
-                ("total", ctypes.c_void_p), ("cap", ctypes.c_int64)]
-
-
-_vp, _i32 = ctypes.c_void_p, ctypes.c_int32
-_lib.register("hx_per_mark_new", [ctypes.POINTER(HxPer), ctypes.c_int64, _vp])
-_lib.register("hx_per_set", [ctypes.POINTER(HxPer), _vp, _vp, _i32, _vp])
-_lib.register("hx_per_update", [ctypes.POINTER(HxPer), _vp, _vp, _i32, ctypes.c_float, _vp])
-_lib.register("hx_per_resum", [ctypes.POINTER(HxPer), _vp])
-_lib.register("hx_per_score_new", [ctypes.POINTER(HxPer), _vp, _vp, _vp, ctypes.c_int64, _i32, ctypes.c_float, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp])
-_lib.register("hx_per_sample", [ctypes.POINTER(HxPer), _vp, _i32, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_float, _vp, _vp, _vp, _vp])
-
+HxPer = _lib.STRUCTS["HxPer"]  # the prioritized store's buffers
 PER_BLOCK, PER_EPS, PER_MAX_CAPACITY = 1024, 1e-4, 1 << 24
 # rows per chunk of score_new's forward launches (include/hirl4ucav.h "Priorities at insert"); from 1,024 rows on a chunk has 128 row tiles per net:
 # the forward kernel's wide tiling.  A row's score depends on this value (the launch shape fixes the order of the forward kernel's sums), not on how
@@ -124,7 +110,6 @@ class PrioritizedReplay(DeviceReplay):
             raise ValueError("score_new: max_new is an upper bound on the rows stored since the last call (> 0)")
         if self._score_ws is None or self._score_ws_chunk != self.score_chunk:
             L = _lib.load()
-            L.hx_per_score_workspace_floats.restype = ctypes.c_int64
             words = int(L.hx_per_score_workspace_floats(int(self.score_chunk)))
             if words <= 0:
                 raise ValueError(f"score_new: score_chunk is a positive multiple of 16, got {self.score_chunk}")
@@ -173,16 +158,7 @@ class PrioritizedReplay(DeviceReplay):
         return beta
 
 
-class HxUps(ctypes.Structure):
-    """the success upsampler's buffers (include/hirl4ucav.h HxUps)"""
-    _fields_ = [("cnt", ctypes.c_void_p), ("marked", ctypes.c_void_p), ("total", ctypes.c_void_p), ("ring_success", ctypes.c_void_p),
-                ("cap", ctypes.c_int64), ("boost", ctypes.c_int32)]
-
-
-_lib.register("hx_ups_mark_new", [ctypes.POINTER(HxUps), ctypes.c_int64, _vp])
-_lib.register("hx_ups_recount", [ctypes.POINTER(HxUps), _vp])
-_lib.register("hx_ups_draw", [ctypes.POINTER(HxUps), _vp, _i32, _i32, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp])
-
+HxUps = _lib.STRUCTS["HxUps"]  # the success upsampler's buffers
 UPS_BLOCK, UPS_MAX_CAPACITY, UPS_BOOST, UPS_BOOST_RANGE = 1024, 1 << 24, 10, (2, 255)
 
 
@@ -190,8 +166,6 @@ def check_ups_abi():
     L = _lib.load()
     if L.hx_ups_sizeof() != ctypes.sizeof(HxUps):
         raise _lib.HxError(f"ABI mismatch: HxUps is {ctypes.sizeof(HxUps)} bytes here, {L.hx_ups_sizeof()} in {_lib.SO_PATH}")
-    L.hx_ups_words.restype = ctypes.c_int64
-    L.hx_ups_words.argtypes = [ctypes.c_int64]
     return L
 
 
@@ -262,16 +236,8 @@ def draw_call(upsampler, ring, batch, n_main, idx, rows, x=None, seed=0, call=0,
               _lib.ptr(idx_bc), _lib.ptr(bc_rows), _lib.stream_ptr())
 
 
-class HxNStep(ctypes.Structure):
-    """the n-step window's buffers (include/hirl4ucav.h HxNStep)"""
-    _fields_ = [("win", ctypes.c_void_p), ("hc", ctypes.c_void_p), ("obs_prev", ctypes.c_void_p), ("last_ctr", ctypes.c_void_p),
-                ("n_envs", ctypes.c_int64), ("n", ctypes.c_int32), ("gamma", ctypes.c_float)]
-
-
-_lib.register("hx_nstep_reset", [ctypes.POINTER(HxNStep), _vp, _vp, _vp])
-_lib.register("hx_nstep_push", [ctypes.POINTER(HxNStep), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp])
-
-NSTEP_MAX, NSTEP_FIELDS = 8, 20  # HX_NSTEP_MAX, HX_NSTEP_FIELDS
+HxNStep = _lib.STRUCTS["HxNStep"]  # the n-step window's buffers
+NSTEP_MAX, NSTEP_FIELDS = _lib.DEFINES["HX_NSTEP_MAX"], _lib.DEFINES["HX_NSTEP_FIELDS"]
 
 
 class NStepInserter:
@@ -291,8 +257,6 @@ class NStepInserter:
         L = _lib.load()
         if L.hx_nstep_sizeof() != ctypes.sizeof(HxNStep):
             raise _lib.HxError(f"ABI mismatch: HxNStep is {ctypes.sizeof(HxNStep)} bytes here, {L.hx_nstep_sizeof()} in {_lib.SO_PATH}")
-        L.hx_nstep_workspace_floats.restype = ctypes.c_int64
-        L.hx_nstep_workspace_floats.argtypes = [ctypes.c_int64, ctypes.c_int32]
         N, k = self.num_envs, NSTEP_FIELDS * self.n * self.num_envs
         words = int(L.hx_nstep_workspace_floats(N, self.n))
         assert words == k + 15 * N
