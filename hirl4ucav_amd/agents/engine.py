@@ -84,7 +84,7 @@ def carve(sizes, device):
 
 
 def _noise_mode(noise, sigma):
-    """hx_actor_act*'s noise_mode: 0 none, 1 one shared draw noise[4], 2 noise[N, 4] per row, 3 Philox N(0, sigma^2) per row and component"""
+    """hx_actor_act / hx_actor_act_step's noise_mode: 0 none, 1 one shared draw noise[4], 2 noise[N, 4] per row, 3 Philox N(0, sigma^2) per row and component"""
     if noise is not None:
         return 1 if noise.numel() == 4 else 2
     return 3 if sigma > 0 else 0
@@ -142,7 +142,7 @@ class HirlEngine:
                                                      self.v_critic, self.losses, self.soft_count, self.wstate, self.ws)), None, None, None, None, None)
         self.act_dtype, self.w2_bf16, self.w2_x9, self._x9_live = "f32", None, None, False
         # act_dtype "f32" and at least this many rows: the 256 -> 512 product of the ACTING kernel runs through the exact three-way bf16 split of both operands on the
-        # bf16 matrix cores (hx_actor_act_x9: fp32 operands, every partial product exact, fp32 accumulation — an fp32 result up to summation
+        # bf16 matrix cores (hx_actor_act's w2_x9: fp32 operands, every partial product exact, fp32 accumulation — an fp32 result up to summation
         # order, 1e-5 parity like the fp32-MFMA path) instead of fp32 MFMA: 121 against 163 us at 65,536 rows, 34 against 48 at 16,384
         # (tools/ubench/actp_time.py).  None: never (fp32 MFMA at every size).  The three images are built at the first such call and kept
         # current by the actor's Adam steps from then on.
@@ -158,7 +158,7 @@ class HirlEngine:
         # layer_norm = False: the reference's `layerNorm=False` networks (HIRL.py:70-80,92-97,135-138): both LayerNorms skipped; the modules
         # still exist in its state_dict (HIRL.py:28,33,114,119), untrained at (1, 0) — load_params keeps the flat buffers' slots there
         self.layer_norm = bool(layer_norm)
-        self._mode_bits = 0 if self.layer_norm else 16  # hx_actor_act*: noise_mode + 16
+        self._mode_bits = 0 if self.layer_norm else 16  # hx_actor_act / hx_actor_act_step: noise_mode + 16
         self.hyper = HxHyper(gamma, tau, lr_actor, lr_critic, slope, 0.5, 10000.0, int(use_bc), 0 if self.layer_norm else 1)  # HIRL.py:162,182
         self.use_bc, self.slope = bool(use_bc), float(slope)
         self.actor_trainable, self.update_count = True, 0   # HIRL.py:157,166
@@ -193,7 +193,7 @@ class HirlEngine:
         """"f32": policy inference on fp32 MFMA (parity 1e-5).  "bf16": its 256 -> 512 layer on bf16 MFMA from a bf16 image of W2 that
         every actor Adam step keeps current (BASELINE.json configs[4]); what learn() computes in is set_update_dtype's business.
         "f32x9": fp32 policy inference with the 256 -> 512 product through the EXACT three-way bf16 split of both operands on the bf16 matrix cores (six of
-        the nine partial products — the three below fp32 resolution are not formed; hx_actor_act_x9:
+        the nine partial products — the three below fp32 resolution are not formed; hx_actor_act's w2_x9:
         fp32 operands, every partial product exact, fp32 accumulation — fp32 results up to summation order); fp32 update only."""
         if dtype not in ("f32", "bf16", "f32x9"):
             raise ValueError(dtype)
@@ -272,12 +272,13 @@ class HirlEngine:
         return True
 
     def _act_format(self, n):
-        """the engine's own actor on n rows -> (suffix of the hx_actor_act* / hx_actor_act_step* entry point, its image pointer), the suffix one of "_bf16", "_x9", "_f32i" """
+        """the engine's own actor on n rows -> (label, the (w2_f32i, w2_x9, w2_bf16) arguments of hx_actor_act / hx_actor_act_step): exactly one image is
+        offered, the label — one of "_bf16", "_x9", "_f32i" — says which"""
         if self.act_dtype == "bf16":
-            return "_bf16", self.w2_bf16.data_ptr()
+            return "_bf16", (None, None, self.w2_bf16.data_ptr())
         if self._x9_for(n):
-            return "_x9", self.w2_x9.data_ptr()
-        return "_f32i", self.w2_f32i.data_ptr()
+            return "_x9", (None, self.w2_x9.data_ptr(), None)
+        return "_f32i", (self.w2_f32i.data_ptr(), None, None)
 
     refresh_images = refresh_bf16
 
@@ -323,13 +324,10 @@ class HirlEngine:
             out = torch.empty((n, 4), dtype=torch.float32, device=self.device)
         mode = _noise_mode(noise, sigma) | self._mode_bits
         self.act_calls += 1
-        if net is None:  # the engine's own actor: W2 from an image (fp32 image: same bits as hx_actor_act, no LDS staging of W2)
-            fmt, image = self._act_format(n)
-            _lib.call("hx_actor_act" + fmt, self.actor.data_ptr(), image, obs.data_ptr(), n, out.data_ptr(), mode, _lib.ptr(noise), float(sigma), int(seed),
-                      int(row0), self.act_calls, self.slope, _lib.stream_ptr())
-            return out
-        _lib.call("hx_actor_act", net.data_ptr(), obs.data_ptr(), n, out.data_ptr(), mode, _lib.ptr(noise), float(sigma), int(seed), int(row0), self.act_calls,
-                  self.slope, None, _lib.stream_ptr())
+        # the engine's own actor: W2 from an image (fp32 image: same bits as from W2 itself, no LDS staging of W2); another net: no image
+        actor, images = (self.actor, self._act_format(n)[1]) if net is None else (net, (None, None, None))
+        _lib.call("hx_actor_act", actor.data_ptr(), *images, obs.data_ptr(), n, out.data_ptr(), mode, _lib.ptr(noise), float(sigma), int(seed), int(row0),
+                  self.act_calls, self.slope, _lib.stream_ptr())
         return out
 
     def act_step(self, env, noise=None, sigma=0.0, seed=0, out=None):
@@ -342,8 +340,7 @@ class HirlEngine:
         mode = _noise_mode(noise, sigma) | self._mode_bits
         self.act_calls += 1
         env.steps_issued += 1
-        fmt, image = self._act_format(n)
-        _lib.call("hx_actor_act_step" + fmt, self.actor.data_ptr(), image, env.state.data_ptr(), n, env.pitch, env.obs.data_ptr(), out.data_ptr(), mode,
+        _lib.call("hx_actor_act_step", self.actor.data_ptr(), *self._act_format(n)[1], env.state.data_ptr(), n, env.pitch, env.obs.data_ptr(), out.data_ptr(), mode,
                   _lib.ptr(noise), float(sigma), int(seed), int(env.env_id0), self.act_calls, self.slope, env.reward.data_ptr(), env.done.data_ptr(),
                   env.success.data_ptr(), ctypes.byref(env._opts), _lib.stream_ptr())
         return out, env.obs, env.reward, env.done, env.success

@@ -98,7 +98,7 @@ class SacEngine:
         self.w2_f32i = torch.zeros(512 * 256, dtype=torch.float32, device=self.device)
         self.nets.policy_w2_f32i = self.w2_f32i.data_ptr()
         # From this many rows on the policy's fp32 256 -> 512 product runs through the exact three-way bf16 split of both operands on the bf16 matrix cores
-        # (hx_sac_act*_x9: every partial product exact, fp32 accumulation; 34 against 45 us at 16,384 rows, tools/ubench/actp_time.py);
+        # (hx_sac_act's w2_x9: every partial product exact, fp32 accumulation; 34 against 45 us at 16,384 rows, tools/ubench/actp_time.py);
         # None: fp32 MFMA at every size.  The hi | mid | lo images are built at the first such call, the policy's optimizer step keeps them current.
         self.x9_rows, self.w2_x9 = 16384, None
         # set_act_dtype / set_update_dtype: fp32 by default; the bf16 images (one block for the bf16 update, or the acting image alone) when asked for
@@ -335,17 +335,17 @@ class SacEngine:
             _lib.call("hx_pack_w2_x9", self.policy.data_ptr(), 13, self.w2_x9.data_ptr(), st)
 
     def _act_format(self, n):
-        """Policy inference for n rows -> (suffix of the hx_sac_act* / hx_sac_act_step* entry point, its image pointers): "_bf16", "_x9" (act_dtype "f32"
+        """Policy inference for n rows -> (label, the (w2_f32i, w2_x9, w2_bf16) arguments of hx_sac_act / hx_sac_act_step): "_bf16", "_x9" (act_dtype "f32"
         from x9_rows rows on; with the fp32 image for the library's fallback up to 8,192 rows) or "_f32i"."""
         if self.act_dtype == "bf16":
-            return "_bf16", (self.w2_bf16.data_ptr(),)
+            return "_bf16", (None, None, self.w2_bf16.data_ptr())
         if self.x9_rows is None or n < self.x9_rows:
-            return "_f32i", (self.w2_f32i.data_ptr(),)
+            return "_f32i", (self.w2_f32i.data_ptr(), None, None)
         if self.w2_x9 is None:  # first large call: build the images; nets.policy_w2_x9 makes every later policy step refresh them
             self.w2_x9 = torch.zeros(3 * H2 * H1, dtype=torch.bfloat16, device=self.device)
             self.nets.policy_w2_x9 = self.w2_x9.data_ptr()
             _lib.call("hx_pack_w2_x9", self.policy.data_ptr(), 13, self.w2_x9.data_ptr(), _lib.stream_ptr())
-        return "_x9", (self.w2_x9.data_ptr(), self.w2_f32i.data_ptr())
+        return "_x9", (self.w2_f32i.data_ptr(), self.w2_x9.data_ptr(), None)
 
     refresh_bf16 = refresh_images  # (the name utils/checkpoint.py calls after a restore)
 
@@ -387,8 +387,7 @@ class SacEngine:
             out = torch.empty((n, 4), dtype=torch.float32, device=self.device)
         mode = 0 if not explore else (1 if eps is not None else 2)
         self.act_calls += 1
-        fmt, images = self._act_format(n)
-        _lib.call("hx_sac_act" + fmt, self.policy.data_ptr(), *images, obs.data_ptr(), n, out.data_ptr(), mode, _lib.ptr(eps), int(seed), int(row0),
+        _lib.call("hx_sac_act", self.policy.data_ptr(), *self._act_format(n)[1], obs.data_ptr(), n, out.data_ptr(), mode, _lib.ptr(eps), int(seed), int(row0),
                   self.act_calls, _lib.stream_ptr())
         return out
 
@@ -401,8 +400,7 @@ class SacEngine:
         mode = 0 if not explore else (1 if eps is not None else 2)
         self.act_calls += 1
         env.steps_issued += 1
-        fmt, images = self._act_format(n)
-        _lib.call("hx_sac_act_step" + fmt, self.policy.data_ptr(), *images, env.state.data_ptr(), n, env.pitch, env.obs.data_ptr(), out.data_ptr(), mode,
+        _lib.call("hx_sac_act_step", self.policy.data_ptr(), *self._act_format(n)[1], env.state.data_ptr(), n, env.pitch, env.obs.data_ptr(), out.data_ptr(), mode,
                   _lib.ptr(eps), int(seed), int(env.env_id0), self.act_calls, env.reward.data_ptr(), env.done.data_ptr(), env.success.data_ptr(),
                   ctypes.byref(env._opts), _lib.stream_ptr())
         return out, env.obs, env.reward, env.done, env.success

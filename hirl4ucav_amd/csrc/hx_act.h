@@ -353,7 +353,7 @@ constexpr int64_t kFuseEnvMax = 8192;
 // Returns false when no persistent instantiation covers the request (the caller falls back to act_fused_kernel).
 bool launch_act_persist(const ActFusedArgs& H, bool gauss, hipStream_t st);
 
-// the buffers and options of an env step that rides in an acting launch (hx_*_act_step*, hx_hirl_front, hx_sac_front): obs is then in/out
+// the buffers and options of an env step that rides in an acting launch (hx_actor_act_step, hx_sac_act_step, hx_hirl_front, hx_sac_front): obs is then in/out
 struct ActEnv {
     float* state;
     int64_t stride;
@@ -372,7 +372,7 @@ inline int check_step_args(const float* obs_io, int64_t n, const float* actions,
                "%s: ring needs 512 <= cap < 2^31, total and 16-byte alignment", who);
     return 0;
 }
-// every image an entry point is handed must be there and 16-byte aligned (the kernels read them 16 bytes at a time); `what`: the entry point's words
+// every image the packers and the front launches are handed must be there and 16-byte aligned (the kernels read them 16 bytes at a time); `what`: the entry point's words
 inline int check_images16(const char* who, const char* what, std::initializer_list<const void*> images) {
     for (const void* p : images) HX_REQUIRE(p && (reinterpret_cast<uintptr_t>(p) & 15u) == 0, "%s: %s", who, what);
     return 0;
@@ -384,12 +384,21 @@ inline int check_noise_mode(int32_t noise_mode, const float* noise, const char* 
     return 0;
 }
 
-// The images of W2 a caller offers; ONE acting format per launch: the bf16 image, else the exact split (hi | mid | lo), else the fp32 image, else W2 itself.
+// The images of W2 a caller offers (nullptr: not offered); ONE acting format per launch: the bf16 image, else the exact split (hi | mid | lo), else the fp32
+// image, else W2 itself.
 struct ActImages {
     const float* w2f;
     const uint16_t* w2x;
     const uint16_t* w2b;
 };
+// what the four acting entry points refuse about their images: an offered one that is not 16-byte aligned, and the + 32 of hx_hirl_front's noise_mode (its way
+// of asking for the exact split) where the exact split is the chosen format
+inline int check_act_images(const ActImages& im, int32_t noise_mode, const char* who) {
+    HX_REQUIRE(((reinterpret_cast<uintptr_t>(im.w2f) | reinterpret_cast<uintptr_t>(im.w2x) | reinterpret_cast<uintptr_t>(im.w2b)) & 15u) == 0,
+               "%s: w2_f32i, w2_x9 and w2_bf16 must each be NULL or a 16-byte aligned image of W2", who);
+    HX_REQUIRE(!(im.w2x && !im.w2b && (noise_mode & 32)), "%s: noise_mode + 32 is hx_hirl_front's; here a non-NULL w2_x9 asks for the exact split", who);
+    return 0;
+}
 // what the two heads' descriptions share; env: the env step in the launch's tail, or nullptr
 inline ActFusedArgs act_args(const float* net, const Mlp& m, float* obs, int64_t rows, float* actions, uint64_t seed, uint32_t row0, uint32_t call,
                              const ActImages& im, const ActEnv* env) {
@@ -438,7 +447,7 @@ inline void launch_stamped(K kernel, dim3 grid, hipStream_t st, const HxStepOpts
 namespace hxu {
 // hx_front.hip: the SAC policy's act + env + insert launch (persistent streaming kernel) with the first forward launch of learn() behind it
 int launch_front_sac(const hxact::ActFusedArgs& H, const FwdArgs& FA, hipStream_t st);
-// hx_front.hip: the act + env + insert workgroups of hx_actor_act_step_* (32 rows each, or a persistent role) and the workgroups of launches A and B
+// hx_front.hip: the act + env + insert workgroups of hx_actor_act_step (32 rows each, or a persistent role) and the workgroups of launches A and B
 // [and C] of HIRL's learn() as ONE launch
 int launch_front(const hxact::ActFusedArgs& H, const FwdArgs& FA, const FwdArgs& FB, const BwdArgs* GC, const HxFront& front, hipStream_t st);
 }  // namespace hxu

@@ -1,8 +1,8 @@
 // hx_act.hip — batched policy inference (gfx950): the whole policy for 16 / 32 observation rows in ONE workgroup, optionally with the
 // env step of the same rows in the kernel's tail, and the re-ordered images of W2 it reads.
-//   Agent.chooseAction / chooseActionSmallNoise / chooseActionNoNoise   hirl/agents/HIRL.py:192-212   (U5)  -> hx_actor_act*
-//   chooseAction + HarfangEnv.step                                      hirl/train_all.py:343-345           -> hx_actor_act_step*
-//   SacAgent.explore / exploit                                          hirl/agents/SAC/agent.py:183-196    -> hx_sac_act*
+//   Agent.chooseAction / chooseActionSmallNoise / chooseActionNoNoise   hirl/agents/HIRL.py:192-212   (U5)  -> hx_actor_act
+//   chooseAction + HarfangEnv.step                                      hirl/train_all.py:343-345           -> hx_actor_act_step
+//   SacAgent.explore / exploit                                          hirl/agents/SAC/agent.py:183-196    -> hx_sac_act, hx_sac_act_step
 #include <hip/hip_ext.h>
 
 #include "hx_act_body.h"
@@ -67,7 +67,7 @@ static void launch_act(const ActFusedArgs& H, hipStream_t st) {
         return;
     }
     if (GAUSS || H.slope == 0.0f) {
-        if (H.w2b) launch_act_t<GAUSS, true, true>(H, st);  // bf16 (the Gaussian head: hx_sac_act_bf16, its head in fp32)
+        if (H.w2b) launch_act_t<GAUSS, true, true>(H, st);  // bf16 (the Gaussian head: its head in fp32)
         else if (H.w2f) launch_act_t<GAUSS, false, true, true>(H, st);
         else launch_act_t<GAUSS, false, true>(H, st);
     } else {
@@ -142,56 +142,36 @@ void launch_pack_bf16(const float* w2, uint16_t* image, bool transposed, hipStre
 
 extern "C" {
 
-int64_t hx_act_workspace_floats(int64_t rows) { (void)rows; return 0; }  // the acting kernels keep z2 in LDS: no workspace any more
+/* The four acting entry points take the three images of W2 as nullable pointers (include/hirl4ucav.h "W2 IMAGES"): act_args (hx_act.h) picks the one format. */
 
 /* chooseAction / chooseActionSmallNoise / chooseActionNoNoise for `rows` observations (HIRL.py:192-212):
  * actions = clamp(actor(obs) + noise, -1, 1).  noise_mode 0: none, 1: noise[4] shared by all rows, 2: noise[rows][4],
- * 3: N(0, sigma^2) per row and component from Philox(seed; row0 + row, call); + 16: layerNorm = False.  ws: unused since the whole policy runs in one kernel (may be NULL). */
-static int actor_act_impl(const float* actor, const ActImages& im, const float* obs, int64_t rows, float* actions, int32_t noise_mode, const float* noise,
-                          float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, void* stream) {
+ * 3: N(0, sigma^2) per row and component from Philox(seed; row0 + row, call); + 16: layerNorm = False. */
+int hx_actor_act(const float* actor, const float* w2_f32i, const uint16_t* w2_x9, const uint16_t* w2_bf16, const float* obs, int64_t rows, float* actions,
+                 int32_t noise_mode, const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, void* stream) {
     HX_REQUIRE(actor && obs && actions && rows > 0, "hx_actor_act: bad arguments");
     if (int rc = check_noise_mode(noise_mode, noise, "hx_actor_act")) return rc;
+    const ActImages im{w2_f32i, w2_x9, w2_bf16};
+    if (int rc = check_act_images(im, noise_mode, "hx_actor_act")) return rc;
     launch_act<false>(act_args_det(actor, const_cast<float*>(obs), rows, actions, noise_mode, noise, sigma, seed, row0, call, slope, im), (hipStream_t)stream);
     HX_CHECK_LAUNCH("hx_actor_act");
     return 0;
 }
 /* chooseAction + HarfangEnv.step for n envs in ONE launch (train_all.py:343-345): actions = clamp(actor(obs_io) + noise, -1, 1) as
  * hx_actor_act, then hx_env_step with those actions in the tail of the same kernel — obs_io in: current observation, out: next. */
-static int actor_act_step_impl(const float* actor, const ActImages& im, float* state, int64_t n, int64_t stride, float* obs_io, float* actions, int32_t noise_mode,
-                               const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, float* reward,
-                               uint8_t* done, int8_t* success, const HxStepOpts* opts, void* stream) {
+int hx_actor_act_step(const float* actor, const float* w2_f32i, const uint16_t* w2_x9, const uint16_t* w2_bf16, float* state, int64_t n, int64_t stride,
+                      float* obs_io, float* actions, int32_t noise_mode, const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call,
+                      float slope, float* reward, uint8_t* done, int8_t* success, const HxStepOpts* opts, void* stream) {
     HX_REQUIRE(actor, "hx_actor_act_step: null actor");
     if (int rc = check_noise_mode(noise_mode, noise, "hx_actor_act_step")) return rc;
+    const ActImages im{w2_f32i, w2_x9, w2_bf16};
+    if (int rc = check_act_images(im, noise_mode, "hx_actor_act_step")) return rc;
     const ActEnv E{state, stride, reward, done, success, opts ? *opts : HxStepOpts{}};
     if (int rc = check_step_args(obs_io, n, actions, E, "hx_actor_act_step")) return rc;
     return launch_act_step<false>(act_args_det(actor, obs_io, n, actions, noise_mode, noise, sigma, seed, row0, call, slope, im, &E), opts, "hx_actor_act_step",
                                   "hx_actor_act", (hipStream_t)stream);
 }
 
-int hx_actor_act(const float* actor, const float* obs, int64_t rows, float* actions, int32_t noise_mode, const float* noise,
-                 float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, float* ws, void* stream) {
-    (void)ws;
-    return actor_act_impl(actor, ActImages{}, obs, rows, actions, noise_mode, noise, sigma, seed, row0, call, slope, stream);
-}
-int hx_actor_act_step(const float* actor, float* state, int64_t n, int64_t stride, float* obs_io, float* actions, int32_t noise_mode,
-                      const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, float* reward,
-                      uint8_t* done, int8_t* success, const HxStepOpts* opts, void* stream) {
-    return actor_act_step_impl(actor, ActImages{}, state, n, stride, obs_io, actions, noise_mode, noise, sigma, seed, row0, call, slope, reward, done,
-                               success, opts, stream);
-}
-/* The same with the 256 -> 512 layer on bf16 MFMA (BASELINE.json configs[4]): w2_bf16 = hx_pack_w2_bf16 image of full2.weight. */
-int hx_actor_act_bf16(const float* actor, const uint16_t* w2_bf16, const float* obs, int64_t rows, float* actions, int32_t noise_mode,
-                      const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, void* stream) {
-    if (int rc = check_images16("hx_actor_act_bf16", "w2_bf16 must be a 16-byte aligned bf16 image of W2", {w2_bf16})) return rc;
-    return actor_act_impl(actor, ActImages{nullptr, nullptr, w2_bf16}, obs, rows, actions, noise_mode, noise, sigma, seed, row0, call, slope, stream);
-}
-int hx_actor_act_step_bf16(const float* actor, const uint16_t* w2_bf16, float* state, int64_t n, int64_t stride, float* obs_io, float* actions,
-                           int32_t noise_mode, const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope,
-                           float* reward, uint8_t* done, int8_t* success, const HxStepOpts* opts, void* stream) {
-    if (int rc = check_images16("hx_actor_act_step_bf16", "w2_bf16 must be a 16-byte aligned bf16 image of W2", {w2_bf16})) return rc;
-    return actor_act_step_impl(actor, ActImages{nullptr, nullptr, w2_bf16}, state, n, stride, obs_io, actions, noise_mode, noise, sigma, seed, row0, call, slope,
-                               reward, done, success, opts, stream);
-}
 /* bf16 image (round to nearest even) of an MLP block's W2 [512][256]; in_dim = 13 (actor / policy) or 17 (Q head) locates it. */
 int hx_pack_w2_bf16(const float* net, int32_t in_dim, uint16_t* w2_bf16, void* stream) {
     HX_REQUIRE(net && w2_bf16 && (in_dim == 13 || in_dim == 17), "hx_pack_w2_bf16: bad arguments");
@@ -201,8 +181,7 @@ int hx_pack_w2_bf16(const float* net, int32_t in_dim, uint16_t* w2_bf16, void* s
     HX_CHECK_LAUNCH("hx_pack_w2_bf16");
     return 0;
 }
-
-/* The fp32 policy with the 256 -> 512 product through the exact three-way bf16 split of both operands on the bf16 matrix cores (see the header; hx_act.h HX_X9_TERMS). */
+/* The hi | mid | lo images of the exact three-way bf16 split of W2 (see the header; hx_act.h HX_X9_TERMS). */
 int hx_pack_w2_x9(const float* net, int32_t in_dim, uint16_t* w2_x9, void* stream) {
     HX_REQUIRE(net && (in_dim == 13 || in_dim == 17), "hx_pack_w2_x9: bad arguments");
     if (int rc = check_images16("hx_pack_w2_x9", "bad arguments", {w2_x9})) return rc;
@@ -212,23 +191,7 @@ int hx_pack_w2_x9(const float* net, int32_t in_dim, uint16_t* w2_x9, void* strea
     HX_CHECK_LAUNCH("hx_pack_w2_x9");
     return 0;
 }
-/* (noise_mode + 32 is hx_hirl_front's way of asking for this format: refused here, with the image check's words) */
-int hx_actor_act_x9(const float* actor, const uint16_t* w2_x9, const float* obs, int64_t rows, float* actions, int32_t noise_mode,
-                    const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, void* stream) {
-    HX_REQUIRE((noise_mode & 32) == 0, "hx_actor_act_x9: w2_x9 must be the 16-byte aligned hi | mid | lo images of W2");
-    if (int rc = check_images16("hx_actor_act_x9", "w2_x9 must be the 16-byte aligned hi | mid | lo images of W2", {w2_x9})) return rc;
-    return actor_act_impl(actor, ActImages{nullptr, w2_x9, nullptr}, obs, rows, actions, noise_mode, noise, sigma, seed, row0, call, slope, stream);
-}
-int hx_actor_act_step_x9(const float* actor, const uint16_t* w2_x9, float* state, int64_t n, int64_t stride, float* obs_io, float* actions,
-                         int32_t noise_mode, const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope,
-                         float* reward, uint8_t* done, int8_t* success, const HxStepOpts* opts, void* stream) {
-    HX_REQUIRE((noise_mode & 32) == 0, "hx_actor_act_step_x9: w2_x9 must be the 16-byte aligned hi | mid | lo images of W2");
-    if (int rc = check_images16("hx_actor_act_step_x9", "w2_x9 must be the 16-byte aligned hi | mid | lo images of W2", {w2_x9})) return rc;
-    return actor_act_step_impl(actor, ActImages{nullptr, w2_x9, nullptr}, state, n, stride, obs_io, actions, noise_mode, noise, sigma, seed, row0, call, slope, reward,
-                               done, success, opts, stream);
-}
-
-/* The fp32 policy from the re-ordered fp32 image of W2 (hx_pack_w2_f32i): bit-identical to hx_actor_act / hx_actor_act_step. */
+/* The re-ordered fp32 image of W2: acting from it is bit-identical to acting from W2 itself. */
 int hx_pack_w2_f32i(const float* net, int32_t in_dim, float* w2_f32i, void* stream) {
     HX_REQUIRE(net && (in_dim == 13 || in_dim == 17), "hx_pack_w2_f32i: bad arguments");
     if (int rc = check_images16("hx_pack_w2_f32i", "bad arguments", {w2_f32i})) return rc;
@@ -238,96 +201,39 @@ int hx_pack_w2_f32i(const float* net, int32_t in_dim, float* w2_f32i, void* stre
     HX_CHECK_LAUNCH("hx_pack_w2_f32i");
     return 0;
 }
-int hx_actor_act_f32i(const float* actor, const float* w2_f32i, const float* obs, int64_t rows, float* actions, int32_t noise_mode,
-                      const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, void* stream) {
-    if (int rc = check_images16("hx_actor_act_f32i", "w2_f32i must be a 16-byte aligned fp32 image of W2", {w2_f32i})) return rc;
-    return actor_act_impl(actor, ActImages{w2_f32i, nullptr, nullptr}, obs, rows, actions, noise_mode, noise, sigma, seed, row0, call, slope, stream);
-}
-int hx_actor_act_step_f32i(const float* actor, const float* w2_f32i, float* state, int64_t n, int64_t stride, float* obs_io, float* actions,
-                           int32_t noise_mode, const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope,
-                           float* reward, uint8_t* done, int8_t* success, const HxStepOpts* opts, void* stream) {
-    if (int rc = check_images16("hx_actor_act_step_f32i", "w2_f32i must be a 16-byte aligned fp32 image of W2", {w2_f32i})) return rc;
-    return actor_act_step_impl(actor, ActImages{w2_f32i, nullptr, nullptr}, state, n, stride, obs_io, actions, noise_mode, noise, sigma, seed, row0, call, slope,
-                               reward, done, success, opts, stream);
-}
 
-// im.w2x: the exact split exists for the Gaussian head in the persistent kernel only — up to 8,192 rows (or with HX_ACT_PERSIST=0) im.w2f serves
-static ActImages sac_images(ActImages im, int64_t rows) {
+// The Gaussian head's images.  im.w2x: the exact split exists for the Gaussian head in the persistent kernel only — up to 8,192 rows (or with HX_ACT_PERSIST=0)
+// im.w2f serves, so a caller that offers the split (and no bf16 image, which would be chosen before either) must offer the fp32 image with it.
+static int sac_images(ActImages& im, int64_t rows, const char* who) {
+    if (int rc = check_act_images(im, 0, who)) return rc;
+    HX_REQUIRE(im.w2b || !im.w2x || im.w2f, "%s: w2_x9 needs w2_f32i beside it (the exact split acts beyond 8,192 rows only; up to there the fp32 image does)", who);
     if (!(rows > kFuseEnvMax && persist_enabled())) im.w2x = nullptr;
-    return im;
+    return 0;
 }
 /* SacAgent.explore / exploit (SAC/agent.py:183-196) for `rows` observations.  mode 0: exploit = tanh(mean); 1: sample with the
- * standard-normal draws eps[rows][4]; 2: sample with Philox(seed; row0 + row, call).  ws: unused since the whole policy runs in one kernel (may be NULL). */
-static int sac_act_impl(const float* policy, const ActImages& im, const float* obs, int64_t rows, float* actions, int32_t mode, const float* eps,
-                        uint64_t seed, uint32_t row0, uint32_t call, void* stream) {
+ * standard-normal draws eps[rows][4]; 2: sample with Philox(seed; row0 + row, call).  With w2_bf16: the 256 -> 512 product from the bf16 image, layer 1
+ * and the head in fp32 (include/hirl4ucav.h "SAC bf16 path"); up to 8,192 rows the per-tile kernel, beyond that the streaming persistent kernel
+ * (MODE 2): the same bits for a row either way. */
+int hx_sac_act(const float* policy, const float* w2_f32i, const uint16_t* w2_x9, const uint16_t* w2_bf16, const float* obs, int64_t rows, float* actions,
+               int32_t mode, const float* eps, uint64_t seed, uint32_t row0, uint32_t call, void* stream) {
     HX_REQUIRE(policy && obs && actions && rows > 0 && mode >= 0 && mode <= 2 && (mode != 1 || eps), "hx_sac_act: bad arguments");
-    launch_act<true>(act_args_gauss(policy, const_cast<float*>(obs), rows, actions, mode, eps, seed, row0, call, sac_images(im, rows)), (hipStream_t)stream);
+    ActImages im{w2_f32i, w2_x9, w2_bf16};
+    if (int rc = sac_images(im, rows, "hx_sac_act")) return rc;
+    launch_act<true>(act_args_gauss(policy, const_cast<float*>(obs), rows, actions, mode, eps, seed, row0, call, im), (hipStream_t)stream);
     HX_CHECK_LAUNCH("hx_sac_act");
     return 0;
 }
 /* SacAgent.explore / exploit + HarfangEnv.step in one launch (train_sac.py:238-241): hx_sac_act, then hx_env_step in the kernel's tail. */
-static int sac_act_step_impl(const float* policy, const ActImages& im, float* state, int64_t n, int64_t stride, float* obs_io, float* actions, int32_t mode,
-                             const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done, int8_t* success,
-                             const HxStepOpts* opts, void* stream) {
+int hx_sac_act_step(const float* policy, const float* w2_f32i, const uint16_t* w2_x9, const uint16_t* w2_bf16, float* state, int64_t n, int64_t stride,
+                    float* obs_io, float* actions, int32_t mode, const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done,
+                    int8_t* success, const HxStepOpts* opts, void* stream) {
     HX_REQUIRE(policy && mode >= 0 && mode <= 2 && (mode != 1 || eps), "hx_sac_act_step: bad arguments");
     const ActEnv E{state, stride, reward, done, success, opts ? *opts : HxStepOpts{}};
     if (int rc = check_step_args(obs_io, n, actions, E, "hx_sac_act_step")) return rc;
-    return launch_act_step<true>(act_args_gauss(policy, obs_io, n, actions, mode, eps, seed, row0, call, sac_images(im, n), &E), opts, "hx_sac_act_step", "hx_sac_act",
+    ActImages im{w2_f32i, w2_x9, w2_bf16};
+    if (int rc = sac_images(im, n, "hx_sac_act_step")) return rc;
+    return launch_act_step<true>(act_args_gauss(policy, obs_io, n, actions, mode, eps, seed, row0, call, im, &E), opts, "hx_sac_act_step", "hx_sac_act",
                                  (hipStream_t)stream);
-}
-
-int hx_sac_act(const float* policy, const float* obs, int64_t rows, float* actions, int32_t mode, const float* eps, uint64_t seed,
-               uint32_t row0, uint32_t call, float* ws, void* stream) {
-    (void)ws;
-    return sac_act_impl(policy, ActImages{}, obs, rows, actions, mode, eps, seed, row0, call, stream);
-}
-int hx_sac_act_step(const float* policy, float* state, int64_t n, int64_t stride, float* obs_io, float* actions, int32_t mode,
-                    const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done, int8_t* success,
-                    const HxStepOpts* opts, void* stream) {
-    return sac_act_step_impl(policy, ActImages{}, state, n, stride, obs_io, actions, mode, eps, seed, row0, call, reward, done, success, opts, stream);
-}
-int hx_sac_act_f32i(const float* policy, const float* w2_f32i, const float* obs, int64_t rows, float* actions, int32_t mode, const float* eps,
-                    uint64_t seed, uint32_t row0, uint32_t call, void* stream) {
-    if (int rc = check_images16("hx_sac_act_f32i", "w2_f32i must be a 16-byte aligned fp32 image of W2", {w2_f32i})) return rc;
-    return sac_act_impl(policy, ActImages{w2_f32i, nullptr, nullptr}, obs, rows, actions, mode, eps, seed, row0, call, stream);
-}
-int hx_sac_act_step_f32i(const float* policy, const float* w2_f32i, float* state, int64_t n, int64_t stride, float* obs_io, float* actions,
-                         int32_t mode, const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done,
-                         int8_t* success, const HxStepOpts* opts, void* stream) {
-    if (int rc = check_images16("hx_sac_act_step_f32i", "w2_f32i must be a 16-byte aligned fp32 image of W2", {w2_f32i})) return rc;
-    return sac_act_step_impl(policy, ActImages{w2_f32i, nullptr, nullptr}, state, n, stride, obs_io, actions, mode, eps, seed, row0, call, reward, done, success, opts,
-                             stream);
-}
-
-int hx_sac_act_x9(const float* policy, const uint16_t* w2_x9, const float* w2_f32i, const float* obs, int64_t rows, float* actions, int32_t mode,
-                  const float* eps, uint64_t seed, uint32_t row0, uint32_t call, void* stream) {
-    if (int rc = check_images16("hx_sac_act_x9", "w2_x9 (hi | mid | lo images) and w2_f32i (the fallback up to 8,192 rows) must be 16-byte aligned images of W2",
-                                {w2_x9, w2_f32i})) return rc;
-    return sac_act_impl(policy, ActImages{w2_f32i, w2_x9, nullptr}, obs, rows, actions, mode, eps, seed, row0, call, stream);
-}
-int hx_sac_act_step_x9(const float* policy, const uint16_t* w2_x9, const float* w2_f32i, float* state, int64_t n, int64_t stride, float* obs_io,
-                       float* actions, int32_t mode, const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done,
-                       int8_t* success, const HxStepOpts* opts, void* stream) {
-    if (int rc = check_images16("hx_sac_act_step_x9", "w2_x9 (hi | mid | lo images) and w2_f32i (the fallback up to 8,192 rows) must be 16-byte aligned images of W2",
-                                {w2_x9, w2_f32i})) return rc;
-    return sac_act_step_impl(policy, ActImages{w2_f32i, w2_x9, nullptr}, state, n, stride, obs_io, actions, mode, eps, seed, row0, call, reward, done, success, opts,
-                             stream);
-}
-
-/* bf16 policy inference of the Gaussian policy (include/hirl4ucav.h "SAC bf16 path"): the 256 -> 512 product from the bf16 image w2_bf16
- * (hx_pack_w2_bf16(policy, 13, ...) or the first image of HxSacNets.w2_bf16_all); layer 1 and the head stay fp32.  Up to 8,192 rows the per-tile
- * kernel, beyond that the streaming persistent kernel (MODE 2): the same bits for a row either way. */
-int hx_sac_act_bf16(const float* policy, const uint16_t* w2_bf16, const float* obs, int64_t rows, float* actions, int32_t mode, const float* eps,
-                    uint64_t seed, uint32_t row0, uint32_t call, void* stream) {
-    if (int rc = check_images16("hx_sac_act_bf16", "w2_bf16 must be a 16-byte aligned bf16 image of W2", {w2_bf16})) return rc;
-    return sac_act_impl(policy, ActImages{nullptr, nullptr, w2_bf16}, obs, rows, actions, mode, eps, seed, row0, call, stream);
-}
-int hx_sac_act_step_bf16(const float* policy, const uint16_t* w2_bf16, float* state, int64_t n, int64_t stride, float* obs_io, float* actions,
-                         int32_t mode, const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done,
-                         int8_t* success, const HxStepOpts* opts, void* stream) {
-    if (int rc = check_images16("hx_sac_act_step_bf16", "w2_bf16 must be a 16-byte aligned bf16 image of W2", {w2_bf16})) return rc;
-    return sac_act_step_impl(policy, ActImages{nullptr, nullptr, w2_bf16}, state, n, stride, obs_io, actions, mode, eps, seed, row0, call, reward, done, success, opts,
-                             stream);
 }
 
 }  // extern "C"

@@ -158,7 +158,7 @@ __global__ __launch_bounds__(kWide) void actps_sac_front_kernel(ActFusedArgs H, 
     fwd_l2_body<kNT, true, false, BF16, 0>(FA, NoSample{}, bx, (int)C.order[k], u.f, FrontSync{});
 }
 
-// SAC up to 8,192 envs: the acting role is the PER-TILE workgroup of hx_sac_act_step_f32i / _bf16 (act_fused_body with the Gaussian head and the env tail: fp32 MFMA
+// SAC up to 8,192 envs: the acting role is the PER-TILE workgroup of hx_sac_act_step (act_fused_body with the Gaussian head and the env tail: fp32 MFMA
 // from the fp32 image, or bf16 MFMA from the bf16 image with the bf16 first launch) — one round of 16-row (NRT 1) or 32-row (NRT 2) workgroups, the first forward
 // launch of learn() behind them on the CUs they leave free (or, where they fill the chip, as they leave).  No in-launch wait: the forward jobs depend on nothing.
 constexpr int kSacFrontNrt2F32 = 4097, kSacFrontNrt2Bf16 = 2049;  // defaults of HX_SAC_FRONT_F32_NRT2_ROWS / HX_SAC_FRONT_BF16_NRT2_ROWS (launch_front_sac)

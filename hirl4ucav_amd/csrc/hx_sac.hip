@@ -819,7 +819,7 @@ int hx_sac_learn_imitative(const HxSacNets* N, const HxSacBatch* Bt, const HxHyp
     return sac_policy_grads_imit_impl(N, Bt, Hy, I, stream, step, target_entropy, "hx_sac_learn_imitative");
 }
 
-/* hx_sac_learn in two parts around an env step (include/hirl4ucav.h "SAC front launch"): hx_sac_front = hx_sac_act_step_x9 / _f32i / _bf16 for n envs AND the first
+/* hx_sac_learn in two parts around an env step (include/hirl4ucav.h "SAC front launch"): hx_sac_front = hx_sac_act_step for n envs AND the first
  * forward launch of the learn() call behind it as workgroups of ONE launch, on the minibatch tiles a predraw left in `batch`; hx_sac_learn_back = the rest. */
 int hx_sac_front(const float* policy, const uint16_t* w2_x9, const float* w2_f32i, float* state, int64_t n, int64_t stride, float* obs_io, float* actions, int32_t mode,
                  const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done, int8_t* success, const HxStepOpts* opts,
@@ -828,14 +828,14 @@ int hx_sac_front(const float* policy, const uint16_t* w2_x9, const float* w2_f32
                (mode != 1 || eps), "hx_sac_front: bad arguments");
     if (int rc = sac_check_formats(N, "hx_sac_front")) return rc;
     HX_REQUIRE(N->w2_bf16_all || !N->policy_w2_bf16,
-               "hx_sac_front: bf16 acting beside the fp32 update (policy_w2_bf16 without w2_bf16_all) has no front form: hx_sac_act_step_bf16 + hx_sac_learn");
+               "hx_sac_front: bf16 acting beside the fp32 update (policy_w2_bf16 without w2_bf16_all) has no front form: hx_sac_act_step + hx_sac_learn");
     // the acting format follows nets: the bf16 path acts from its first image (the image arguments must be NULL), the fp32 update from w2_x9 / w2_f32i
     const uint16_t* w2b = N->w2_bf16_all ? sac_act_image(N) : nullptr;
     HX_REQUIRE(policy && (w2b ? (!w2_x9 && !w2_f32i) : (w2_x9 || w2_f32i)),
                "hx_sac_front: with nets->w2_bf16_all the acting image is its first one (w2_x9, w2_f32i NULL); else w2_x9 or w2_f32i");
     const hxact::ActEnv E{state, stride, reward, done, success, *opts};
     if (int rc = hxact::check_step_args(obs_io, n, actions, E, "hx_sac_front")) return rc;
-    // up to 8,192 envs the exact-split image plays no part (as hx_sac_act_step_x9: the per-tile workgroups act from the fp32 image, which must then be given)
+    // up to 8,192 envs the exact-split image plays no part (as in hx_sac_act_step: the per-tile workgroups act from the fp32 image, which must then be given)
     if (n <= hxact::kFuseEnvMax) w2_x9 = nullptr;
     HX_REQUIRE(w2b || w2_x9 || w2_f32i, "hx_sac_front: up to 8,192 envs the fp32 policy acts from the fp32 image: w2_f32i must be given");
     if (int rc = hxact::check_images16("hx_sac_front", "the acting image of W2 must be 16-byte aligned", {w2b ? (const void*)w2b : w2_x9 ? (const void*)w2_x9 : (const void*)w2_f32i})) return rc;

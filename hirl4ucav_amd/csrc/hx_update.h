@@ -4,7 +4,7 @@
 //
 //   hx_fwdbwd.hip   fwd_l2_kernel, bwd_l2_kernel            launch_fwd, launch_bwd
 //   hx_wgrad.hip    wgrad_kernel, adam_kernel, polyak_kernel launch_wg, launch_adam, launch_polyak; hx_adam*, hx_polyak, hx_sac_adam
-//   hx_act.hip      act_fused_kernel + the W2 image packers  hx_actor_act*, hx_sac_act*, hx_pack_w2_*
+//   hx_act.hip      act_fused_kernel + the W2 image packers  hx_actor_act[_step], hx_sac_act[_step], hx_pack_w2_*
 //   hx_sampler.hip  sample_kernel                            hx_sample_batch
 //   hx_sac.hip      gauss_head / q_select / policy_dout      hx_sac_critic_*, hx_sac_policy_grads
 //   hx_score.hip    per_new_index / td_score / per_score_commit  hx_per_score_new (host code only besides: it drives fwd_l2 and gauss_head)

@@ -84,8 +84,10 @@ const char* hx_last_error(void);
  * 123: per-episode statistics by scenario (HxEpStat, hx_epstat_*).
  * 124: the merged actor message carries the soft count as base-32 digit words too, and hx_adam_mixed reads those (exact on the bf16 transports).
  * 125: success upsampling of the replay draw and the BC minibatch's fire row (HxUps, hx_ups_*).
- * 126: the pursuit pilot as a kernel and the online region of the BC table (hx_pilot_act, hx_pilot_refresh). */
-#define HX_ABI_VERSION 126
+ * 126: the pursuit pilot as a kernel and the online region of the BC table (hx_pilot_act, hx_pilot_refresh).
+ * 127: four acting entry points instead of sixteen: hx_actor_act, hx_actor_act_step, hx_sac_act and hx_sac_act_step take the W2 images as three nullable
+ * pointers (w2_f32i, w2_x9, w2_bf16) after the network; their _f32i / _x9 / _bf16 variants, the `ws` argument and hx_act_workspace_floats are gone. */
+#define HX_ABI_VERSION 127
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -177,63 +179,49 @@ int hx_label_transitions(const float* s, const float* a, const float* ns, int64_
 int hx_actor_param_count(void);
 int hx_critic_param_count(void);
 int64_t hx_hirl_workspace_floats(int32_t batch);
-int64_t hx_act_workspace_floats(int64_t rows); /* 0: the acting kernels need no workspace any more; their `ws` argument may be NULL */
+/* W2 IMAGES.  The four acting entry points (hx_actor_act, hx_actor_act_step, hx_sac_act, hx_sac_act_step) take three nullable pointers right after the
+ * network: the copies of its 256 -> 512 matrix W2 that the caller offers, each written by its packer below and kept current by the optimizer steps
+ * through HxNets / HxSacNets.  NULL means "not offered" (until version 126 an entry point per format refused a NULL image).  ONE acting format per
+ * launch: the bf16 image (w2_bf16) if given, else the exact split (w2_x9: hi | mid | lo) if given, else the fp32 image (w2_f32i) if given, else
+ * row-major W2 read from the network itself — all three NULL.  For the Gaussian head the split is used only beyond 8,192 rows with the persistent
+ * kernel enabled; up to there the fp32 image serves, so hx_sac_act / hx_sac_act_step refuse w2_x9 without w2_f32i unless w2_bf16 is given.
+ * Refused with HX_ERR_ARG: a non-NULL image that is not 16-byte aligned; noise_mode + 32 (hx_hirl_front's bit) where the exact split is the chosen format.
+ *
+ * w2_f32i, hx_pack_w2_f32i: a RE-ORDERED fp32 copy of W2 (512 x 256 floats).  The same arithmetic, bit for bit, as acting from W2 itself — but every
+ * wave reads its 32 columns of W2 as contiguous kilobytes straight into registers (MFMA operand order) instead of streaming the row-major matrix
+ * through LDS with a barrier per 16 k-values.  The image order is an internal format (w2f_image_index in hx_update.h).
+ *
+ * w2_bf16, hx_pack_w2_bf16: bf16 policy inference (BASELINE.json configs[4] "bf16 actor/critic + fp32 dynamics"): the 256 -> 512 layer — 96 % of the
+ * policy's FLOPs — runs on v_mfma_f32_16x16x32_bf16 with h1 rounded to bf16 once and W2 read from w2_bf16[512][256] = bf16(W2), round to nearest
+ * even; accumulation, layer 1, both LayerNorms and the head stay fp32, and so do the dynamics, the update and the optimizer.  Tolerance vs the fp32
+ * policy: |da| <= 2e-2 on tanh outputs (tests/test_hirl_gpu.py); vs an fp32 evaluation on the SAME rounded operands: 1e-4.
+ *
+ * w2_x9, hx_pack_w2_x9: fp32 policy inference with the 256 -> 512 product on the bf16 matrix cores, EXACTLY: every fp32 operand is the sum of three
+ * bf16 numbers (x = hi + mid + lo: 3 x 8 significand bits = fp32's 24, the split loses nothing), every one of the 9 partial products of a pair is
+ * exact in fp32, and v_mfma_f32_16x16x32_bf16 accumulates them in fp32 — the small ones in an accumulator of their own that joins hi x hi at the end.
+ * The same products as fp32 arithmetic, summed in another order: results within the fp32 kernels' own rounding noise (tests/test_x9_gpu.py measures
+ * both against an fp64 evaluation), NOT bit-identical to the fp32 formats.  9 bf16 MFMAs per 32 k cost 144 matrix-core cycles against 256 for fp32
+ * MFMA (the bf16 units are 16 x faster).  w2_x9 = [3][512][256] bf16: hi | mid | lo images of W2 in the bf16 acting kernels' format.
+ * The packers read the MLP block at `net` (in_dim 13 or 17). */
+int hx_pack_w2_f32i(const float* net, int32_t in_dim, float* w2_f32i, void* stream);
+int hx_pack_w2_bf16(const float* net, int32_t in_dim, uint16_t* w2_bf16, void* stream);
+int hx_pack_w2_x9(const float* net, int32_t in_dim, uint16_t* w2_x9, void* stream);
 
 /* Agent.chooseAction / chooseActionSmallNoise / chooseActionNoNoise for `rows` observations at once
  * (hirl/agents/HIRL.py:192-212): actions = clamp(actor(obs) + noise, -1, 1).
  * noise_mode 0: none (NoNoise); 1: noise[4] shared by all rows (the reference's one draw per call); 2: noise[rows][4];
  * 3: N(0, sigma^2) per row and component from Philox4x32-10(key = seed; counter = (row0 + row, call)).
- * slope: 0 = ReLU nets (HIRL.py), 0.01 = LeakyReLU nets (TD3.py / BC.py).  ws: unused (may be NULL).
- * noise_mode + 16: the actor was built with layerNorm = False (HIRL.py:135-138): no LayerNorm in its forward (all hx_actor_act* entry points). */
-int hx_actor_act(const float* actor, const float* obs, int64_t rows, float* actions, int32_t noise_mode,
-                 const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, float* ws,
+ * slope: 0 = ReLU nets (HIRL.py), 0.01 = LeakyReLU nets (TD3.py / BC.py).
+ * noise_mode + 16: the actor was built with layerNorm = False (HIRL.py:135-138): no LayerNorm in its forward. */
+int hx_actor_act(const float* actor, const float* w2_f32i, const uint16_t* w2_x9, const uint16_t* w2_bf16, const float* obs, int64_t rows,
+                 float* actions, int32_t noise_mode, const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope,
                  void* stream);
 /* chooseAction + HarfangEnv.step for n envs in ONE launch (train_all.py:343-345): the actions of hx_actor_act (also written to
  * `actions`), then hx_env_step with them in the tail of the same kernel.  obs_io in: current observations, out: next. */
-int hx_actor_act_step(const float* actor, float* state, int64_t n, int64_t stride, float* obs_io, float* actions,
-                      int32_t noise_mode, const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope,
-                      float* reward, uint8_t* done, int8_t* success, const HxStepOpts* opts /* host, may be NULL */, void* stream);
-
-/* bf16 policy inference (BASELINE.json configs[4] "bf16 actor/critic + fp32 dynamics"): the 256 -> 512 layer — 96 % of the policy's
- * FLOPs — runs on v_mfma_f32_16x16x32_bf16 with h1 rounded to bf16 once and W2 read from a bf16 image; accumulation, layer 1, both
- * LayerNorms and the head stay fp32, and so do the dynamics, the update and the optimizer.  Tolerance vs the fp32 policy: |da| <= 2e-2 on
- * tanh outputs (tests/test_hirl_gpu.py); vs an fp32 evaluation on the SAME rounded operands: 1e-4.
- * hx_pack_w2_bf16: w2_bf16[512][256] = bf16(W2) of the MLP block at `net` (in_dim 13 or 17), round to nearest even. */
-int hx_pack_w2_bf16(const float* net, int32_t in_dim, uint16_t* w2_bf16, void* stream);
-int hx_actor_act_bf16(const float* actor, const uint16_t* w2_bf16, const float* obs, int64_t rows, float* actions, int32_t noise_mode,
-                      const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, void* stream);
-int hx_actor_act_step_bf16(const float* actor, const uint16_t* w2_bf16, float* state, int64_t n, int64_t stride, float* obs_io,
-                           float* actions, int32_t noise_mode, const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call,
-                           float slope, float* reward, uint8_t* done, int8_t* success, const HxStepOpts* opts /* host, may be NULL */,
-                           void* stream);
-
-/* fp32 policy inference from a RE-ORDERED fp32 copy of W2 ("image", 512 x 256 floats): the same arithmetic, bit for bit, as
- * hx_actor_act / hx_actor_act_step — but every wave reads its 32 columns of W2 as contiguous kilobytes straight into registers (MFMA
- * operand order) instead of streaming the row-major matrix through LDS with a barrier per 16 k-values.  hx_pack_w2_f32i writes the image
- * of the MLP block at `net`; HxNets.actor_w2_f32i (below) keeps it current through every Adam step of the actor.  The image order is an
- * internal format (w2f_image_index in hx_update.h); both image formats (this and the bf16 one) are for the deterministic policy head. */
-int hx_pack_w2_f32i(const float* net, int32_t in_dim, float* w2_f32i, void* stream);
-int hx_actor_act_f32i(const float* actor, const float* w2_f32i, const float* obs, int64_t rows, float* actions, int32_t noise_mode,
-                      const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, void* stream);
-int hx_actor_act_step_f32i(const float* actor, const float* w2_f32i, float* state, int64_t n, int64_t stride, float* obs_io,
-                           float* actions, int32_t noise_mode, const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call,
-                           float slope, float* reward, uint8_t* done, int8_t* success, const HxStepOpts* opts /* host, may be NULL */,
-                           void* stream);
-
-/* fp32 policy inference with the 256 -> 512 product on the bf16 matrix cores, EXACTLY: every fp32 operand is the sum of three bf16 numbers
- * (x = hi + mid + lo: 3 x 8 significand bits = fp32's 24, the split loses nothing), every one of the 9 partial products of a pair is exact in
- * fp32, and v_mfma_f32_16x16x32_bf16 accumulates them in fp32 — the small ones in an accumulator of their own that joins hi x hi at the end.
- * The same products as fp32 arithmetic, summed in another order: results within the fp32 kernels' own rounding noise (tests/test_x9_gpu.py
- * measures both against an fp64 evaluation), NOT bit-identical to hx_actor_act.  9 bf16 MFMAs per 32 k cost 144 matrix-core cycles against
- * 256 for fp32 MFMA (the bf16 units are 16 x faster).  w2_x9 = [3][512][256] bf16: hi | mid | lo images of W2 in the bf16 acting kernels'
- * format; hx_pack_w2_x9 writes them, HxNets.actor_w2_x9 keeps them current through every Adam step of the actor.  Deterministic head only. */
-int hx_pack_w2_x9(const float* net, int32_t in_dim, uint16_t* w2_x9, void* stream);
-int hx_actor_act_x9(const float* actor, const uint16_t* w2_x9, const float* obs, int64_t rows, float* actions, int32_t noise_mode,
-                    const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call, float slope, void* stream);
-int hx_actor_act_step_x9(const float* actor, const uint16_t* w2_x9, float* state, int64_t n, int64_t stride, float* obs_io,
-                         float* actions, int32_t noise_mode, const float* noise, float sigma, uint64_t seed, uint32_t row0, uint32_t call,
-                         float slope, float* reward, uint8_t* done, int8_t* success, const HxStepOpts* opts /* host, may be NULL */,
-                         void* stream);
+int hx_actor_act_step(const float* actor, const float* w2_f32i, const uint16_t* w2_x9, const uint16_t* w2_bf16, float* state, int64_t n,
+                      int64_t stride, float* obs_io, float* actions, int32_t noise_mode, const float* noise, float sigma, uint64_t seed,
+                      uint32_t row0, uint32_t call, float slope, float* reward, uint8_t* done, int8_t* success,
+                      const HxStepOpts* opts /* host, may be NULL */, void* stream);
 
 /* Minibatch of Agent.learn (HIRL.py:223-251), already assembled by hx_sample_batch into compact row tiles:
  * rows[batch][HX_ROW_WORDS] = s[13] a[4] s'[13] r done (buffer rows first, then expert rows, HIRL.py:229-233);
@@ -254,15 +242,15 @@ typedef struct HxNets {
     float* wstate;       /* [1] the BC weight in force */
     float* ws;           /* hx_hirl_workspace_floats(batch) */
     uint16_t* actor_w2_bf16; /* NULL, or [512][256] bf16 image of the actor's full2.weight: every Adam step of the actor refreshes it
-                                (hx_adam which = 1 / 2), the bf16 acting entry points read it */
-    float* actor_w2_f32i;    /* NULL, or the fp32 image of the same matrix (hx_pack_w2_f32i), refreshed likewise; hx_actor_act*_f32i read it */
+                                (hx_adam which = 1 / 2), the acting entry points' w2_bf16 */
+    float* actor_w2_f32i;    /* NULL, or the fp32 image of the same matrix (hx_pack_w2_f32i), refreshed likewise; the acting entry points' w2_f32i */
     uint16_t* w2_bf16_all;   /* NULL: the update computes in fp32 (parity 1e-5 vs the reference).  Else hx_bf16_images_elems() bf16 elements =
                                 the bf16 images of every W2 the update reads: the bf16 UPDATE path (below).  Its first 512 x 256 elements are
                                 the actor's image in the bf16 acting kernels' format: actor_w2_bf16 must then be NULL or point at them */
     const uint32_t* xchg_status; /* NULL, or the status word of hx_allreduce_oneshot: while it is non-zero (an exchange failed: the summed
                                 gradient is garbage) hx_adam / hx_adam_mixed change nothing — no parameter, moment, target or image */
     uint16_t* actor_w2_x9;   /* NULL, or the [3][512][256] hi | mid | lo bf16 images of the actor's full2.weight (hx_pack_w2_x9): refreshed by
-                                every Adam step of the actor like the other two; hx_actor_act*_x9 read them */
+                                every Adam step of the actor like the other two; the acting entry points' w2_x9 */
 } HxNets;
 
 /* bf16 update path (BASELINE.json configs[4] "bf16 actor/critic + fp32 dynamics"; SURVEY.md 7 "bf16 config").  With HxNets.w2_bf16_all set,
@@ -379,8 +367,8 @@ int hx_hirl_learn_sampled(const HxNets* nets, const HxBatch* batch, const HxHype
                           int32_t actor_phase, int32_t actor_step, int32_t do_polyak, int32_t w_kind, float w_given, float warm, void* stream);
 
 /* The FRONT launch (opt-in; fp32 networks — noise_mode + 32: the policy's W2 from HxNets.actor_w2_x9, the exact three-way bf16 split, as
- * hx_actor_act_step_x9, else from HxNets.actor_w2_f32i — or the bf16 update path, HxNets.w2_bf16_all, with the bf16 acting image
- * HxNets.actor_w2_bf16; n <= 8,192 — with a replay ring any number in the exact-split format and in bf16): hx_actor_act_step_f32i / _x9 / _bf16 for n envs (chooseAction + HarfangEnv.step + replay insert,
+ * hx_actor_act_step with w2_x9, else from HxNets.actor_w2_f32i — or the bf16 update path, HxNets.w2_bf16_all, with the bf16 acting image
+ * HxNets.actor_w2_bf16; n <= 8,192 — with a replay ring any number in the exact-split format and in bf16): hx_actor_act_step with that one image for n envs (chooseAction + HarfangEnv.step + replay insert,
  * train_all.py:343-345) AND the first two launches of the learn() call that follows it (targetActor(s'), Q1/Q2(s, a) [+ the actor call's forwards];
  * then targetCritic Q1/Q2 — HIRL.py:259-272) as workgroups of ONE launch: the acting workgroups take 32 rows each and so leave half of the CUs to
  * the update's workgroups, which would otherwise wait for the env step to finish although they depend on nothing it computes EXCEPT the ring it
@@ -389,7 +377,7 @@ int hx_hirl_learn_sampled(const HxNets* nets, const HxBatch* batch, const HxHype
  * buffer both before and after the step (the reference draws after its one-transition append, buffer.py:45; at n envs per step the population
  * differs by the newest and, once the ring is full, the oldest n transitions).  Who fills the tiles: the previous hx_hirl_learn_back (its `next`:
  * one more workgroup of the critics' gradient launch draws and gathers, on a CU that launch leaves idle), or hx_sample_batch_guarded as a launch of its own.
- * Bit-identical to hx_actor_act_step_f32i / _x9 followed by hx_hirl_learn_sampled with HxSample.total read before the step and HxSample.guard = n
+ * Bit-identical to hx_actor_act_step with the same image followed by hx_hirl_learn_sampled with HxSample.total read before the step and HxSample.guard = n
  * (and launch B in 64-column workgroups: hx_debug_set_fwd_nt).  The target critics wait IN the launch for the target actor's rows (per-row-tile
  * counters `flags`, agent-scope relaxed accesses, bounded wait ~1 s: bit 0 of *status is set if a launch-B workgroup gives up, bit 1 if a launch-C
  * workgroup does (HxFront.with_c)).
@@ -411,7 +399,7 @@ int hx_hirl_learn_sampled(const HxNets* nets, const HxBatch* batch, const HxHype
  * of that launch may have been read half-written, and the caller must not go on: read *status at least every few hundred launches (hirl4ucav_amd/
  * train_all.py --status_check_every, default 256: on a trip it reloads its last snapshot and continues in the reference's order in the same process, or
  * exits with code 3; bench.py reads it after the timed region and the second pass — one decision for all ranks — and on a trip repeats the whole run in
- * the reference's order in the same process and labels the line `reference order (front tripped)`) and fall back to hx_actor_act_step_* +
+ * the reference's order in the same process and labels the line `reference order (front tripped)`) and fall back to hx_actor_act_step +
  * hx_hirl_learn_sampled (no in-launch waits; `train_all --loop reference`, `bench.py --no-front`).
  * (Roles taken in START order from a ticket would need no such assumption; measured, that costs 2.8 us of a 51.4 us step: docs/LEVERS.md, Round 5.)
  * hx_hirl_learn_back = the rest of the call (critic backward + gradients + Adam [+ the delayed actor step]) on the same `batch`; next / next_tiles
@@ -453,11 +441,11 @@ typedef struct HxSacNets {
     float* alpha_state; /* [4]: log_alpha, its Adam m and v, alpha = exp(log_alpha)  (SAC/agent.py:106-108) */
     float* ws;          /* hx_sac_workspace_floats(batch) */
     float* policy_w2_f32i; /* NULL, or the fp32 image of the policy's W2 (hx_pack_w2_f32i(policy, 13, ...)): hx_sac_adam(which = 1) keeps it
-                              current, hx_sac_act*_f32i read it */
+                              current; hx_sac_act's w2_f32i */
     uint16_t* policy_w2_x9; /* NULL, or the hi | mid | lo bf16 images of the policy's W2 (hx_pack_w2_x9(policy, 13, ...), 3 x 512 x 256): the
-                               policy's optimizer step keeps them current, hx_sac_act*_x9 read them */
+                               policy's optimizer step keeps them current; hx_sac_act's w2_x9 */
     uint16_t* w2_bf16_all;  /* NULL: the update computes in fp32.  Else hx_bf16_images_elems() bf16 elements: the SAC bf16 path (below).  Its first
-                               512 x 256 elements are the policy's image in the bf16 acting format (hx_sac_act*_bf16 read it) */
+                               512 x 256 elements are the policy's image in the bf16 acting format (hx_sac_act's w2_bf16) */
     uint16_t* policy_w2_bf16; /* NULL, or the bf16 image of the policy's W2 (hx_pack_w2_bf16(policy, 13, ...)) for bf16 acting beside an fp32
                                update: the policy's optimizer step keeps it current.  With w2_bf16_all set it must be NULL or its first image */
 } HxSacNets;
@@ -469,8 +457,8 @@ typedef struct HxSacNets {
  * Master weights, Adam moments, layer 1 (K = 13 / 17), the Gaussian heads (mean, clamped log_std, exp, tanh, entropy), q_select, the policy's head
  * gradient, the log-alpha step, TD targets and loss sums stay fp32.  Every optimizer step refreshes the forward and transposed images of the network
  * it steps (the policy's forward image is the acting image); every Polyak step refreshes IM_TC1 / IM_TC2.  After any OTHER write to a network call
- * hx_sac_pack_update_images.  Acting (hx_sac_act*_bf16): the 256 -> 512 product as above from the policy's image, layer 1 and the head in fp32 — NOT
- * the deterministic policy's bf16 head (hx_actor_act_bf16): exp(log_std) amplifies head error, and the update's head is fp32 too.
+ * hx_sac_pack_update_images.  Acting (hx_sac_act / hx_sac_act_step with w2_bf16): the 256 -> 512 product as above from the policy's image, layer 1 and the head in fp32 — NOT
+ * the deterministic policy's bf16 head (hx_actor_act with w2_bf16): exp(log_std) amplifies head error, and the update's head is fp32 too.
  * Tolerances (tests/test_sac_bf16_gpu.py): actions against an fp32 evaluation on the same rounded operands: 99 % within 1e-4, all within 2e-3;
  * against the fp32 policy: |da| <= 2e-2, mean |da| <= 2e-3.  learn() against the rounded-operand oracle: losses rtol 1e-4; parameters after Adam
  * as tests/test_bf16_update_gpu.py. */
@@ -488,34 +476,15 @@ typedef struct HxSacBatch {
 int hx_sac_policy_param_count(void);
 int64_t hx_sac_workspace_floats(int32_t batch);
 /* SacAgent.explore / exploit (SAC/agent.py:183-196): mode 0 exploit = tanh(mean); 1 sample with eps[rows][4]; 2 sample with
- * Philox4x32-10(seed; row0 + row, call).  ws: unused (may be NULL). */
-int hx_sac_act(const float* policy, const float* obs, int64_t rows, float* actions, int32_t mode, const float* eps,
-               uint64_t seed, uint32_t row0, uint32_t call, float* ws, void* stream);
-/* The same from the re-ordered fp32 image of the policy's W2 (see hx_actor_act_f32i): bit-identical results, W2 straight into registers. */
-int hx_sac_act_f32i(const float* policy, const float* w2_f32i, const float* obs, int64_t rows, float* actions, int32_t mode, const float* eps,
-                    uint64_t seed, uint32_t row0, uint32_t call, void* stream);
-int hx_sac_act_step_f32i(const float* policy, const float* w2_f32i, float* state, int64_t n, int64_t stride, float* obs_io, float* actions,
-                         int32_t mode, const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done,
-                         int8_t* success, const HxStepOpts* opts /* host, may be NULL */, void* stream);
+ * Philox4x32-10(seed; row0 + row, call).  The images: "W2 IMAGES" above (w2_x9 = hx_pack_w2_x9(policy, 13, ...) is the large-population format of the
+ * fp32 policy — beyond 8,192 rows the persistent kernel streams the three images; up to 8,192 rows w2_f32i, which must be given with it, serves).
+ * With w2_bf16 ("SAC bf16 path" above): the per-tile kernel up to 8,192 rows, the streaming persistent kernel beyond (the same bits for a row). */
+int hx_sac_act(const float* policy, const float* w2_f32i, const uint16_t* w2_x9, const uint16_t* w2_bf16, const float* obs, int64_t rows,
+               float* actions, int32_t mode, const float* eps, uint64_t seed, uint32_t row0, uint32_t call, void* stream);
 /* SacAgent.explore / exploit + HarfangEnv.step in one launch (train_sac.py:238-241). */
-/* The same from the exact three-way bf16 split of the 256 -> 512 product's operands (hx_actor_act_x9's format; w2_x9 = hx_pack_w2_x9(policy, 13, ...)):
- * the large-population format of the fp32 policy — beyond 8,192 rows the persistent kernel streams the three images; up to 8,192 rows these
- * entry points fall back to the fp32 image, which must then be given as well (w2_f32i). */
-int hx_sac_act_x9(const float* policy, const uint16_t* w2_x9, const float* w2_f32i, const float* obs, int64_t rows, float* actions, int32_t mode,
-                  const float* eps, uint64_t seed, uint32_t row0, uint32_t call, void* stream);
-int hx_sac_act_step_x9(const float* policy, const uint16_t* w2_x9, const float* w2_f32i, float* state, int64_t n, int64_t stride, float* obs_io,
-                       float* actions, int32_t mode, const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done,
-                       int8_t* success, const HxStepOpts* opts, void* stream);
-int hx_sac_act_step(const float* policy, float* state, int64_t n, int64_t stride, float* obs_io, float* actions, int32_t mode,
-                    const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done, int8_t* success,
-                    const HxStepOpts* opts /* host, may be NULL */, void* stream);
-/* The same with the 256 -> 512 product on bf16 matrix cores from the bf16 image w2_bf16 ("SAC bf16 path" above): the per-tile kernel up to 8,192
- * rows, the streaming persistent kernel beyond (the same bits for a row). */
-int hx_sac_act_bf16(const float* policy, const uint16_t* w2_bf16, const float* obs, int64_t rows, float* actions, int32_t mode, const float* eps,
-                    uint64_t seed, uint32_t row0, uint32_t call, void* stream);
-int hx_sac_act_step_bf16(const float* policy, const uint16_t* w2_bf16, float* state, int64_t n, int64_t stride, float* obs_io, float* actions,
-                         int32_t mode, const float* eps, uint64_t seed, uint32_t row0, uint32_t call, float* reward, uint8_t* done,
-                         int8_t* success, const HxStepOpts* opts /* host, may be NULL */, void* stream);
+int hx_sac_act_step(const float* policy, const float* w2_f32i, const uint16_t* w2_x9, const uint16_t* w2_bf16, float* state, int64_t n,
+                    int64_t stride, float* obs_io, float* actions, int32_t mode, const float* eps, uint64_t seed, uint32_t row0, uint32_t call,
+                    float* reward, uint8_t* done, int8_t* success, const HxStepOpts* opts /* host, may be NULL */, void* stream);
 /* SacAgent.learn (SAC/agent.py:276-327) in the stages a sharded run separates:
  *   hx_sac_critic_grads   [soft_update of the target critics first on every 3rd call :278-279]; target y = r + (1-d) gamma
  *                         (min Q_target(s', a') + alpha H') :202-210; q1_loss, q2_loss :361-374 -> losses[0..1]; grad_critic
@@ -538,20 +507,20 @@ int hx_sac_policy_grads(const HxSacNets* nets, const HxSacBatch* batch, const Hx
  * hx_sac_policy_grads + hx_sac_adam(which = 1); sample may be NULL (minibatch already assembled); step is 1-based. */
 int hx_sac_learn(const HxSacNets* nets, const HxSacBatch* batch, const HxHyper* hyper, const HxSample* sample, int32_t polyak_first, int32_t step,
                  float target_entropy, void* stream);
-/* The SAC front launch (any n >= 1 envs with a replay ring): hx_sac_act_step_x9 / hx_sac_act_step_f32i / hx_sac_act_step_bf16 — explore / exploit +
+/* The SAC front launch (any n >= 1 envs with a replay ring): hx_sac_act_step with the same images — explore / exploit +
  * HarfangEnv.step + replay insert (train_sac.py:238-241) — AND the first forward launch of the SacAgent.learn call that follows it (policy(s'), policy(s),
  * Q1/Q2(s, a), E-SAC's extra jobs: SAC/agent.py:198-210, 276-290) as workgroups of ONE launch, on the minibatch `batch->rows` holds already.  No workgroup of it
  * waits for another.
- * Which kernel acts: up to 8,192 envs the per-tile workgroups of hx_sac_act_step_f32i / _bf16 (one round of 16- or 32-row workgroups: the tiling is a choice per
+ * Which kernel acts: up to 8,192 envs the per-tile workgroups of hx_sac_act_step from the fp32 or the bf16 image (one round of 16- or 32-row workgroups: the tiling is a choice per
  * size and format, HX_SAC_FRONT_F32_NRT2_ROWS / HX_SAC_FRONT_BF16_NRT2_ROWS, and a row's action does not depend on it), the forward workgroups on the CUs they
  * leave free; beyond, the streaming persistent kernel on every CU, the forward workgroups starting as the acting ones leave.
  * Images: the acting format is taken from nets.  With nets->w2_bf16_all set: the bf16 acting image (its first one) and the bf16 first launch; w2_x9 and w2_f32i
  * must be NULL then.  Else fp32: beyond 8,192 envs from w2_x9 (the exact split) when given, else from w2_f32i; up to 8,192 envs from w2_f32i, which must
- * then be given — a non-NULL w2_x9 is accepted and ignored there, as in hx_sac_act_step_x9.  bf16 acting beside the fp32 update has no front form.
+ * then be given — a non-NULL w2_x9 is accepted and ignored there, as in hx_sac_act_step.  bf16 acting beside the fp32 update has no front form.
  * The draw rule is the same at every size.  As for hx_hirl_front the
  * minibatch is drawn from the ring as it stood BEFORE this env step without the n slots the step may overwrite (HxSample.guard = n): by the previous
  * hx_sac_learn_back (its `next`: one more workgroup of the policy's gradient launch draws and gathers into next_rows) or by hx_sample_batch_guarded.
- * Bit-identical to hx_sac_act_step_x9 / _f32i / _bf16 for the same n (up to 8,192 envs: hx_sac_act_step_f32i / _bf16) followed by hx_sac_learn with
+ * Bit-identical to hx_sac_act_step with the same images for the same n followed by hx_sac_learn with
  * HxSample.total read before the step and HxSample.guard = n.
  * hx_sac_learn_back = the rest of hx_sac_learn (8 launches). */
 int hx_sac_front(const float* policy, const uint16_t* w2_x9, const float* w2_f32i, float* state, int64_t n, int64_t stride, float* obs_io, float* actions,

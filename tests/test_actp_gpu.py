@@ -93,7 +93,7 @@ def test_persistent_act_with_leaky_slope(mods, dtype):
                                               ("f32", 8192 + 40, "mixed"), ("f32", 16384, "serpentine"), ("f32", 65536, "circular"),
                                               ("f32x9", 16384, "mixed")])
 def test_persistent_act_step_equals_act_then_step(mods, dtype, n, scenario):
-    """ONE launch (persistent kernel, env tail on all waves) == hx_actor_act* followed by hx_env_step: actions, every state word,
+    """ONE launch (persistent kernel, env tail on all waves) == hx_actor_act followed by hx_env_step: actions, every state word,
     observations, rewards, masks, episode counters, statistics, and the replay rows as a multiset (slots are handed out per workgroup).
     max_step 9 crosses the time limit twice: unstored steps and in-place resets; a ragged last tile at 8,232 envs."""
     E, Env, Replay = mods
@@ -217,7 +217,7 @@ def test_persistent_sac_policy_equals_the_per_tile_kernel(mods, n):
 
 
 def test_sac_policy_exact_split_format_at_large_populations(mods):
-    """SacEngine's default from 16,384 rows on: the policy's fp32 256 -> 512 product as the exact 9-term bf16 split (hx_sac_act*_x9, the persistent
+    """SacEngine's default from 16,384 rows on: the policy's fp32 256 -> 512 product as the exact 9-term bf16 split (hx_sac_act's w2_x9, the persistent
     kernel's Gaussian-head instantiation).  Against the fp32-MFMA kernel: the same action within 2e-6 (exact products, another summation order;
     the parity bar against the reference is 1e-5); act + env step in one launch == two launches bit for bit; and the hi | mid | lo images
     follow the policy's optimizer step (hx_sac_learn) exactly: hi + mid + lo == W2."""

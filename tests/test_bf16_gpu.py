@@ -1,5 +1,5 @@
 """bf16 policy inference (BASELINE.json configs[4]: "bf16 actor/critic + fp32 dynamics") through the C ABI
-(hx_actor_act_bf16 / hx_actor_act_step_bf16 / hx_pack_w2_bf16).
+(the w2_bf16 of hx_actor_act / hx_actor_act_step, hx_pack_w2_bf16).
 
 Tolerances, stated separately from the fp32 path's 1e-5 (SURVEY.md 7 "bf16 config"):
   * against an fp32 evaluation of the SAME rounded operands — both MATRIX PRODUCTS of the policy beyond its 13-wide input layer take bf16 operands
@@ -146,8 +146,8 @@ def f32_image_order(w2):
 @pytest.mark.parametrize("staged", [False, True])
 @pytest.mark.parametrize("n", [1, 16, 1000, 4096, 9000])
 def test_f32_image_path_is_bit_identical_and_follows_adam(mods, staged, n):
-    """The fp32 policy from the re-ordered image of W2 (hx_actor_act_f32i, what HirlEngine.act uses for its own actor: W2 straight into
-    registers, no LDS staging) equals hx_actor_act (row-major W2 streamed through LDS) BIT FOR BIT at every size class (16- and 32-row
+    """The fp32 policy from the re-ordered image of W2 (hx_actor_act's w2_f32i, what HirlEngine.act uses for its own actor: W2 straight into
+    registers, no LDS staging) equals hx_actor_act without an image (row-major W2 streamed through LDS) BIT FOR BIT at every size class (16- and 32-row
     workgroups, ragged tails), and the image follows the actor through the one-call and the staged Adam steps."""
     import ctypes
 
@@ -168,7 +168,7 @@ def test_f32_image_path_is_bit_identical_and_follows_adam(mods, staged, n):
 
     def plain():
         out = torch.empty((n, 4), dtype=torch.float32, device="cuda")
-        _lib.call("hx_actor_act", e.actor.data_ptr(), obs.data_ptr(), n, out.data_ptr(), 0, None, 0.0, 0, 0, 0, e.slope, None, _lib.stream_ptr())
+        _lib.call("hx_actor_act", e.actor.data_ptr(), None, None, None, obs.data_ptr(), n, out.data_ptr(), 0, None, 0.0, 0, 0, 0, e.slope, _lib.stream_ptr())
         return out
 
     assert torch.equal(e.w2_f32i, f32_image_order(E.unpack(e.actor, E.ACTOR_LAYOUT)["full2.weight"]).to(e.w2_f32i.device))
@@ -185,7 +185,7 @@ def test_f32_image_path_is_bit_identical_and_follows_adam(mods, staged, n):
 
 @pytest.mark.parametrize("n,scenario", [(4096, "straight_line"), (131072, "mixed")])
 def test_bf16_act_step_is_act_then_step(mods, n, scenario):
-    """hx_actor_act_step_bf16 (ONE launch at every size: the per-tile kernel up to 8,192 envs, the persistent kernel of hx_actp.hip beyond) == hx_actor_act_bf16 followed by hx_env_step, bit for bit:
+    """hx_actor_act_step from the bf16 image (ONE launch at every size: the per-tile kernel up to 8,192 envs, the persistent kernel of hx_actp.hip beyond) == hx_actor_act from it followed by hx_env_step, bit for bit:
     actions, every state word, observations, rewards, masks, statistics, the replay rows as a multiset.  The large case is the
     configured size of BASELINE.json configs[4] (131,072 mixed envs: scenario = id mod 3, sorted) — and its dynamics agree
     with the oracle on a sample, from the actions the bf16 policy produced."""

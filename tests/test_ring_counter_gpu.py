@@ -241,7 +241,7 @@ def sac_engine(hx, batch=128):
 
 
 def test_sac_act_step(hx):
-    """SacEngine.act_step (hx_sac_act_step_f32i: the per-tile body of csrc/hx_act_body.h with SAC's 16-row workgroups): 300 envs, cap = 1000"""
+    """SacEngine.act_step (hx_sac_act_step from the fp32 image: the per-tile body of csrc/hx_act_body.h with SAC's 16-row workgroups): 300 envs, cap = 1000"""
     e = sac_engine(hx)
     for t_big in R.EDGE_TOTALS(1000, 300):
         run_twin(hx, 300, 1000, t_big, 9, engine_step(e, seed=3), False, "SAC act_step")

@@ -20,8 +20,10 @@ def test_binding_carries_the_sac_image_fields():
 
 def test_header_declares_the_sac_bf16_entry_points():
     hdr = open(HEADER).read()
-    for name in ("hx_sac_act_bf16", "hx_sac_act_step_bf16", "hx_sac_pack_update_images"):
+    for name in ("hx_sac_act", "hx_sac_act_step", "hx_sac_pack_update_images"):
         assert re.search(r"\bint %s\(" % name, hdr), name
+    for name in ("hx_sac_act", "hx_sac_act_step"):  # the bf16 acting image is an argument of the one entry point
+        assert re.search(r"\bint %s\(const float\* policy, const float\* w2_f32i, const uint16_t\* w2_x9, const uint16_t\* w2_bf16," % name, hdr), name
     body = re.search(r"typedef struct HxSacNets \{(.*?)\} HxSacNets;", hdr, re.S).group(1)
     assert re.search(r"uint16_t\* w2_bf16_all;", body) and re.search(r"uint16_t\* policy_w2_bf16;", body)
     assert int(re.search(r"#define HX_ABI_VERSION (\d+)", hdr).group(1)) >= 115

@@ -110,7 +110,7 @@ def check_actions(got, ref, full, what):
 
 @pytest.mark.parametrize("n", [1, 300, 4096, 8213, 16384])
 def test_sac_bf16_acting_against_rounded_operands(SE, n):
-    """hx_sac_act_bf16 against an fp32 evaluation on the same rounded operands and against the fp32 policy: exploit, injected eps, Philox."""
+    """hx_sac_act from the bf16 image against an fp32 evaluation on the same rounded operands and against the fp32 policy: exploit, injected eps, Philox."""
     p = sac_params()
     e, f = engine(SE), engine(SE, act="f32")
     rng = np.random.default_rng(n)
@@ -149,7 +149,7 @@ def test_sac_bf16_launch_shapes_agree_bit_for_bit(SE):
 
 @pytest.mark.parametrize("n", [4096 + 17, 16384])
 def test_sac_bf16_act_step_equals_act_then_step(SE, n):
-    """hx_sac_act_step_bf16 (per-tile with the env tail / the streaming kernel with env tail and replay insert) == act_bf16 then env.step."""
+    """hx_sac_act_step from the bf16 image (per-tile with the env tail / the streaming kernel with env tail and replay insert) == act_bf16 then env.step."""
     from hirl4ucav_amd.environments.batched import BatchedHarfangEnv
     from hirl4ucav_amd.utils.buffer import DeviceReplay
 

@@ -144,15 +144,15 @@ def plain_act(e, obs, mode, eps=None, seed=0, call=0):
     from hirl4ucav_amd import _lib
 
     out = torch.empty((obs.shape[0], 4), dtype=torch.float32, device="cuda")
-    _lib.call("hx_sac_act", e.policy.data_ptr(), obs.data_ptr(), obs.shape[0], out.data_ptr(), mode, _lib.ptr(eps), seed, 0, call, None, _lib.stream_ptr())
+    _lib.call("hx_sac_act", e.policy.data_ptr(), None, None, None, obs.data_ptr(), obs.shape[0], out.data_ptr(), mode, _lib.ptr(eps), seed, 0, call, _lib.stream_ptr())
     return out
 
 
 @pytest.mark.parametrize("n,fmt", [(37, "plain"), (37, "_f32i"), (8213, "_f32i"), (8213, "_x9")])
 def test_sac_acting_at_the_clamps_and_saturation(SE, n, fmt):
     """exploit and explore (injected eps) against the fp64 oracle with log_std at both clamps in every row: 37 rows (two 16-row tiles and a tail of 5)
-    through hx_sac_act and hx_sac_act_f32i, 8,213 rows (the persistent kernel, past the 8,192-row switch) through hx_sac_act_f32i and the exact-split
-    hx_sac_act_x9 (which falls back to the fp32 image up to 8,192 rows).  One Philox call per format; at 37 rows the two formats are bit-identical."""
+    through hx_sac_act without an image and from the fp32 image, 8,213 rows (the persistent kernel, past the 8,192-row switch) from the fp32 image and from
+    the exact split (which falls back to the fp32 image up to 8,192 rows).  One Philox call per format; at 37 rows the two formats are bit-identical."""
     p = X.case_params("acting")
     e = SE.SacEngine(batch=16)
     e.load_params(p["policy"], p["q1"], p["q2"])
@@ -178,7 +178,7 @@ def test_sac_acting_at_the_clamps_and_saturation(SE, n, fmt):
 
 @pytest.mark.parametrize("n", [37, 8213])
 def test_sac_bf16_acting_at_the_clamps_and_saturation(SE, n):
-    """hx_sac_act_bf16 on the same inputs, against the evaluation on rounded operands and against the fp32 policy (the bounds of
+    """hx_sac_act from the bf16 image on the same inputs, against the evaluation on rounded operands and against the fp32 policy (the bounds of
     tests/test_sac_bf16_gpu.py); finite and inside [-1, 1], Philox included"""
     from tests.test_sac_bf16_gpu import check_actions, engine, rounded_policy
 

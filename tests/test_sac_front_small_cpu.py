@@ -23,9 +23,9 @@ def test_header_describes_the_front_launch_at_every_size():
     block = hdr[start:hdr.index("*/", start)]
     flat = " ".join(block.replace("*", " ").split())
     assert "n > 8,192" not in flat and "any n >= 1" in flat
-    # which kernel acts at which size, the image rules, the unchanged draw rule, the bit-identity statement for the per-tile entry points
+    # which kernel acts at which size, the image rules, the unchanged draw rule, the bit-identity statement against the acting entry point
     for words in ("up to 8,192 envs the per-tile workgroups", "streaming persistent kernel", "w2_x9 is accepted and ignored", "HxSample.guard = n",
-                  "hx_sac_act_step_f32i / _bf16"):
+                  "hx_sac_act_step from the fp32 or the bf16 image", "Bit-identical to hx_sac_act_step with the same images for the same n"):
         assert words in flat, words
     # the signatures stand
     assert re.search(r"int hx_sac_front\(const float\* policy, const uint16_t\* w2_x9, const float\* w2_f32i, float\* state, int64_t n,", hdr)

@@ -1,4 +1,4 @@
-"""The SAC front launch up to 8,192 envs (hx_sac_front's per-tile acting role, act_sac_front_kernel: the workgroups of hx_sac_act_step_f32i / _bf16 and the
+"""The SAC front launch up to 8,192 envs (hx_sac_front's per-tile acting role, act_sac_front_kernel: the workgroups of hx_sac_act_step from the fp32 / bf16 image and the
 first forward launch of SacAgent.learn as ONE launch; SacEngine.step_learn; train_all's default loop for SAC / E-SAC).
 
 Parity statement, as for the role beyond 8,192 envs (tests/test_front_gpu.py): one step_learn == act_step, then learn() on a minibatch drawn with

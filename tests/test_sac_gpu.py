@@ -215,7 +215,7 @@ def test_sac_critic_step_in_the_wgrad_launch_is_bit_identical(SE, defer):
 
 @pytest.mark.parametrize("n", [7, 4096, 16384])
 def test_sac_image_path_is_bit_identical_and_follows_adam(SE, n):
-    """hx_sac_act_f32i (the policy's W2 from its re-ordered fp32 image, what SacEngine.act uses) equals hx_sac_act (row-major W2 streamed
+    """hx_sac_act with w2_f32i (the policy's W2 from its re-ordered fp32 image, what SacEngine.act uses) equals hx_sac_act without an image (row-major W2 streamed
     through LDS) BIT FOR BIT — exploit and Philox-sampled explore, 16- and 32-row workgroups — before and after policy Adam steps, and
     the image is the permuted W2."""
     from hirl4ucav_amd import _lib
@@ -237,7 +237,7 @@ def test_sac_image_path_is_bit_identical_and_follows_adam(SE, n):
 
     def plain(mode, call):
         out = torch.empty((n, 4), dtype=torch.float32, device="cuda")
-        _lib.call("hx_sac_act", e.policy.data_ptr(), obs.data_ptr(), n, out.data_ptr(), mode, None, 3, 0, call, None, _lib.stream_ptr())
+        _lib.call("hx_sac_act", e.policy.data_ptr(), None, None, None, obs.data_ptr(), n, out.data_ptr(), mode, None, 3, 0, call, _lib.stream_ptr())
         return out
 
     for round_ in range(2):

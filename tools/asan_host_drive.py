@@ -78,14 +78,14 @@ def main():
         cap = max(2 * n, 1 << 12)
         o = _lib.HxStepOpts(1500, 1, 1, 0, 7, epi, dev(cap * 128), dev(cap), cap, dev(8), dev(4096), None, None, 0)
         for mode in (0, 3, 3 + 16):
-            ok("hx_actor_act_f32i", actor, w2f, obs, n, act, mode, None, 0.1, 1, 0, 1, 0.0, None)
-            ok("hx_actor_act_x9", actor, w2x, obs, n, act, mode, None, 0.1, 1, 0, 1, 0.0, None)
-            ok("hx_actor_act_bf16", actor, w2b, obs, n, act, mode, None, 0.1, 1, 0, 1, 0.01, None)
-        ok("hx_actor_act", actor, obs, n, act, 1, dev(16), 0.0, 1, 0, 1, 0.0, None, None)
-        ok("hx_actor_act_step_f32i", actor, w2f, state, n, n, obs, act, 3, None, 0.1, 1, 0, 1, 0.0, rew, done, succ, ctypes.byref(o), None)
-        ok("hx_actor_act_step_x9", actor, w2x, state, n, n, obs, act, 3, None, 0.1, 1, 0, 1, 0.0, rew, done, succ, ctypes.byref(o), None)
-        ok("hx_actor_act_step_bf16", actor, w2b, state, n, n, obs, act, 3, None, 0.1, 1, 0, 1, 0.0, rew, done, succ, ctypes.byref(o), None)
-    refused("hx_actor_act_x9", actor, None, dev(64), 16, dev(64), 0, None, 0.0, 1, 0, 1, 0.0, None)
+            ok("hx_actor_act", actor, w2f, None, None, obs, n, act, mode, None, 0.1, 1, 0, 1, 0.0, None)
+            ok("hx_actor_act", actor, None, w2x, None, obs, n, act, mode, None, 0.1, 1, 0, 1, 0.0, None)
+            ok("hx_actor_act", actor, None, None, w2b, obs, n, act, mode, None, 0.1, 1, 0, 1, 0.01, None)
+        ok("hx_actor_act", actor, None, None, None, obs, n, act, 1, dev(16), 0.0, 1, 0, 1, 0.0, None)
+        ok("hx_actor_act_step", actor, w2f, None, None, state, n, n, obs, act, 3, None, 0.1, 1, 0, 1, 0.0, rew, done, succ, ctypes.byref(o), None)
+        ok("hx_actor_act_step", actor, None, w2x, None, state, n, n, obs, act, 3, None, 0.1, 1, 0, 1, 0.0, rew, done, succ, ctypes.byref(o), None)
+        ok("hx_actor_act_step", actor, None, None, w2b, state, n, n, obs, act, 3, None, 0.1, 1, 0, 1, 0.0, rew, done, succ, ctypes.byref(o), None)
+    refused("hx_actor_act", actor, None, w2x + 4, None, dev(64), 16, dev(64), 0, None, 0.0, 1, 0, 1, 0.0, None)  # an image off by 4 bytes
 
     # ---- the HIRL update: one-call, staged, sampled, front + back; fp32 and bf16 images; B = 128 .. 1024 ----
     for B, bf16 in ((128, False), (256, False), (512, False), (1024, False), (128, True)):
@@ -156,9 +156,9 @@ def main():
         ok("hx_sac_adam", ctypes.byref(sn), hs, which, 3, 1.0, -4.0, None)
     for n in (4096, 16384):
         state, obs, act = dev(37 * n * 4), dev(n * 13 * 4), dev(n * 16)
-        ok("hx_sac_act", sn.policy, obs, n, act, 2, None, 1, 0, 1, None, None)
-        ok("hx_sac_act_f32i", sn.policy, w2f, obs, n, act, 2, None, 1, 0, 1, None)
-        ok("hx_sac_act_x9", sn.policy, w2x, w2f, obs, n, act, 2, None, 1, 0, 1, None)
+        ok("hx_sac_act", sn.policy, None, None, None, obs, n, act, 2, None, 1, 0, 1, None)
+        ok("hx_sac_act", sn.policy, w2f, None, None, obs, n, act, 2, None, 1, 0, 1, None)
+        ok("hx_sac_act", sn.policy, w2f, w2x, None, obs, n, act, 2, None, 1, 0, 1, None)
     # the SAC bf16 path: one image block (no fp32 / exact-split image beside it), the acting entry points, the packer; mixed formats are refused
     imgs = dev(int(L.hx_bf16_images_elems()) * 2)
     sb16 = S.HxSacNets(*[getattr(sn, f) for f, _ in S.HxSacNets._fields_])
@@ -172,14 +172,14 @@ def main():
         ok("hx_sac_adam", ctypes.byref(sb16), hs, which, 3, 1.0, -4.0, None)
     for n in (4096, 16384):
         state, obs, act = dev(37 * n * 4), dev(n * 13 * 4), dev(n * 16)
-        ok("hx_sac_act_bf16", sn.policy, imgs, obs, n, act, 2, None, 1, 0, 1, None)
+        ok("hx_sac_act", sn.policy, None, None, imgs, obs, n, act, 2, None, 1, 0, 1, None)
     # act + env step + insert, and the bf16 front launch with its back half (the acting format from nets), at the per-tile and the streaming sizes
     for n in (4096, 16384):
         state, obs, act = dev(37 * n * 4), dev(n * 13 * 4), dev(n * 16)
         rew, done, succ, epi = dev(n * 4), dev(n), dev(n), dev(n * 4)
         rcap = max(2 * n, 1 << 16)
         o = _lib.HxStepOpts(1500, 1, 1, 0, 7, epi, dev(rcap * 128), dev(rcap), rcap, dev(8), dev(4096), None, None, 0)
-        ok("hx_sac_act_step_bf16", sn.policy, imgs, state, n, n, obs, act, 2, None, 1, 0, 1, rew, done, succ, ctypes.byref(o), None)
+        ok("hx_sac_act_step", sn.policy, None, None, imgs, state, n, n, obs, act, 2, None, 1, 0, 1, rew, done, succ, ctypes.byref(o), None)
         if n > 8192:
             nxt = E.HxSample(o.total, rcap, o.ring, None, 0, None, 0, B, 3, 2, 0.0, dev(B * 4), None, n)
             ok("hx_sac_front", sn.policy, None, None, state, n, n, obs, act, 2, None, 1, 0, 1, rew, done, succ, ctypes.byref(o), ctypes.byref(sb16),

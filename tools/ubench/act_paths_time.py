@@ -18,17 +18,17 @@ for n in (4096, 16384):
     obs = torch.rand(n, 13, device="cuda") * 2 - 1
     out = torch.empty(n, 4, device="cuda")
     st = _lib.stream_ptr()
-    print(n, "SAC staged %.1f us" % t(lambda: _lib.call("hx_sac_act", e.policy.data_ptr(), obs.data_ptr(), n, out.data_ptr(), 2, None, 3, 0, 1, None, st)),
-          "SAC image %.1f us" % t(lambda: _lib.call("hx_sac_act_f32i", e.policy.data_ptr(), e.w2_f32i.data_ptr(), obs.data_ptr(), n, out.data_ptr(), 2, None, 3, 0, 1, st)),
-          "HIRL staged %.1f us" % t(lambda: _lib.call("hx_actor_act", h.actor.data_ptr(), obs.data_ptr(), n, out.data_ptr(), 3, None, 0.1, 1, 0, 1, 0.0, None, st)),
-          "HIRL image %.1f us" % t(lambda: _lib.call("hx_actor_act_f32i", h.actor.data_ptr(), h.w2_f32i.data_ptr(), obs.data_ptr(), n, out.data_ptr(), 3, None, 0.1, 1, 0, 1, 0.0, st)))
+    print(n, "SAC staged %.1f us" % t(lambda: _lib.call("hx_sac_act", e.policy.data_ptr(), None, None, None, obs.data_ptr(), n, out.data_ptr(), 2, None, 3, 0, 1, st)),
+          "SAC image %.1f us" % t(lambda: _lib.call("hx_sac_act", e.policy.data_ptr(), e.w2_f32i.data_ptr(), None, None, obs.data_ptr(), n, out.data_ptr(), 2, None, 3, 0, 1, st)),
+          "HIRL staged %.1f us" % t(lambda: _lib.call("hx_actor_act", h.actor.data_ptr(), None, None, None, obs.data_ptr(), n, out.data_ptr(), 3, None, 0.1, 1, 0, 1, 0.0, st)),
+          "HIRL image %.1f us" % t(lambda: _lib.call("hx_actor_act", h.actor.data_ptr(), h.w2_f32i.data_ptr(), None, None, obs.data_ptr(), n, out.data_ptr(), 3, None, 0.1, 1, 0, 1, 0.0, st)))
 n = 4096
 obs = torch.rand(n, 13, device="cuda") * 2 - 1
 out = torch.empty(n, 4, device="cuda")
 st = _lib.stream_ptr()
 for mode in (0, 2):
-    print("SAC n=4096 mode", mode, "staged %.1f us" % t(lambda: _lib.call("hx_sac_act", e.policy.data_ptr(), obs.data_ptr(), n, out.data_ptr(), mode, None, 3, 0, 1, None, st)),
-          "image %.1f us" % t(lambda: _lib.call("hx_sac_act_f32i", e.policy.data_ptr(), e.w2_f32i.data_ptr(), obs.data_ptr(), n, out.data_ptr(), mode, None, 3, 0, 1, st)))
+    print("SAC n=4096 mode", mode, "staged %.1f us" % t(lambda: _lib.call("hx_sac_act", e.policy.data_ptr(), None, None, None, obs.data_ptr(), n, out.data_ptr(), mode, None, 3, 0, 1, st)),
+          "image %.1f us" % t(lambda: _lib.call("hx_sac_act", e.policy.data_ptr(), e.w2_f32i.data_ptr(), None, None, obs.data_ptr(), n, out.data_ptr(), mode, None, 3, 0, 1, st)))
 for mode, sig in ((0, 0.0), (3, 0.1)):
-    print("HIRL n=4096 noise mode", mode, "staged %.1f us" % t(lambda: _lib.call("hx_actor_act", h.actor.data_ptr(), obs.data_ptr(), n, out.data_ptr(), mode, None, sig, 1, 0, 1, 0.0, None, st)),
-          "image %.1f us" % t(lambda: _lib.call("hx_actor_act_f32i", h.actor.data_ptr(), h.w2_f32i.data_ptr(), obs.data_ptr(), n, out.data_ptr(), mode, None, sig, 1, 0, 1, 0.0, st)))
+    print("HIRL n=4096 noise mode", mode, "staged %.1f us" % t(lambda: _lib.call("hx_actor_act", h.actor.data_ptr(), None, None, None, obs.data_ptr(), n, out.data_ptr(), mode, None, sig, 1, 0, 1, 0.0, st)),
+          "image %.1f us" % t(lambda: _lib.call("hx_actor_act", h.actor.data_ptr(), h.w2_f32i.data_ptr(), None, None, obs.data_ptr(), n, out.data_ptr(), mode, None, sig, 1, 0, 1, 0.0, st)))
