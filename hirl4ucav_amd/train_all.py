@@ -329,8 +329,8 @@ def train_bc(config, device, seed, max_step):
     bc_table = torch.from_numpy(tab).to(device)
     table = DeviceReplay(es.shape[0], device)  # the sampler wants a main ring as well; the BC step reads only the BC rows
     table.store_rows(bc_table)
-    if upsample_refusal(config) or expert_online_refusal(config):
-        raise SystemExit("train_all: " + (upsample_refusal(config) or expert_online_refusal(config)))
+    if upsample_refusal(config) or expert_online_refusal(config) or expert_branch_refusal(config):
+        raise SystemExit("train_all: " + (upsample_refusal(config) or expert_online_refusal(config) or expert_branch_refusal(config)))
     if getattr(config, "expert_upsample", False):  # BC.py:152-158, 171-176: one row of every minibatch is a fire row
         from .utils.buffer import fire_rows
 
@@ -452,7 +452,7 @@ def check_agent_flags(run):
     # the reference's two sampling switches (HIRL.py:184-185): success rows of the replay drawn 10 : 1, one fire row forced into the BC minibatch
     run.buffer_upsample, run.expert_upsample = bool(getattr(config, "buffer_upsample", False)), bool(getattr(config, "expert_upsample", False))
     run.upsampler = None
-    for refusal in (per_refusal, nstep_refusal, clip_refusal, upsample_refusal, expert_online_refusal):  # (per_refusal without --per: --per_new td on its own)
+    for refusal in (per_refusal, nstep_refusal, clip_refusal, upsample_refusal, expert_online_refusal, expert_branch_refusal):  # (per_refusal without --per: --per_new td on its own)
         if refusal(config, world):
             raise SystemExit("train_all: " + refusal(config, world))
     run.batch = 128  # train_all.py:190-208
@@ -516,17 +516,28 @@ def build_engine(run):
 def load_expert_tables(run):
     """HIRL / E-SAC / ISAC: the labelled expert ring, the BC (s, a) table and the frozen bc_actor"""
     config, device, eng = run.config, run.device, run.eng
-    run.expert = run.bc_table = run.fire_idx = run.online = None
+    run.expert = run.bc_table = run.fire_idx = run.online = run.branch = None
     if run.upsampler is not None:  # (TD3 has no expert table: the engine hears of the upsampler here)
         eng.set_upsample(run.upsampler, None)
     if not (run.hirl or run.esac or run.isac):
         return
+    why = expert_branch_resume_refusal(config, run.snap["driver"] if run.snap is not None else None)
+    if why:
+        raise SystemExit(f"train_all: --resume {config.resume} {why}")
     tables = load_expert_files(config)
     labelled = [label_expert(es_k, ea_k, device) for es_k, ea_k in tables]  # each file on its own: no transition spans two files
     rows, succ = torch.cat([r for r, _ in labelled]), torch.cat([s_ for _, s_ in labelled])
     es, ea = np.concatenate([t[0] for t in tables]), np.concatenate([t[1] for t in tables])
-    run.expert = DeviceReplay(rows.shape[0] + 10, device)
-    run.expert.store_rows(rows, succ)
+    if int(getattr(config, "expert_branch", 0)) > 0:
+        # An extension (utils/pilot.py): the ring grows by an online region that starts as a cyclic copy of the labelled rows and is rewritten behind
+        # every acting launch by one-step branches of the learner's envs under the pilot.  Its length stays E0 + ROWS: the samplers are untouched.
+        from .utils.pilot import BranchExpert
+
+        run.branch = BranchExpert(run.env, rows, succ, int(config.expert_branch), int(config.expert_branch_per_step), device)
+        run.expert = run.branch.ring
+    else:
+        run.expert = DeviceReplay(rows.shape[0] + 10, device)
+        run.expert.store_rows(rows, succ)
     tab = np.zeros((es.shape[0], 32), np.float32)
     tab[:, 0:13], tab[:, 13:17] = es, ea
     run.bc_table = torch.from_numpy(tab).to(device)
@@ -604,6 +615,8 @@ def stats_record(run):
         rec["episode_stats"] = {"device": run.estats.state(), "last100": run.last100.state()}
     if getattr(run, "online", None) is not None:  # (a snapshot of a run without --expert_online carries no such key)
         rec["expert_online"] = run.online.state_dict()
+    if getattr(run, "branch", None) is not None:  # (likewise without --expert_branch)
+        rec["expert_branch"] = run.branch.state_dict()
     return rec
 
 
@@ -612,6 +625,8 @@ def restore_stats(run, record):
     region of the expert table and its call counter come back here too (load_expert_tables has refused a snapshot without them)."""
     if getattr(run, "online", None) is not None:
         run.online.load_state_dict(record["expert_online"])
+    if getattr(run, "branch", None) is not None:
+        run.branch.load_state_dict(record["expert_branch"])
     if run.estats is None:
         return
     st = record.get("episode_stats")
@@ -660,6 +675,8 @@ def restore_or_explore(run):
                 estats.push()
             if getattr(run, "online", None) is not None:
                 run.online.push()
+            if getattr(run, "branch", None) is not None:
+                run.branch.push()
             if getattr(run, "upsampler", None) is not None:
                 run.upsampler.mark_new(n)
         if run.per and run.per_new == "td":  # the exploration rows are appended with an error of their own too (SAC/agent.py:176-177, 234-246: the start_steps rows are scored as well)
@@ -724,16 +741,25 @@ def write_snapshot(run, episode):
     run.snap_path = path
 
 
+def branch_has_reader(run):
+    """whether anything still draws from the expert ring: ISAC's expert batch for the whole run; HIRL's and E-SAC's expert rows only while expert_num > 0
+    (train_all.py:356-357: one row fewer every warm_up_rate steps, 0 after batch * warm_up_rate vector steps, for good).  Behind that the branches would
+    be written for nobody: the launch is dropped, the ring keeps what it holds."""
+    return bool(run.isac) or run.expert_num > 0
+
+
 # ---- the vector step: two hooks every form shares, three forms --------------------------------------------------------------------------------------
 def after_env_step(run, step):
-    """Behind every acting launch, in this order: the n-step rows, the episode statistics, the pilot's relabelled rows, the new rows' first priorities,
-    the reward sum.  (The front forms run without an inserter and without --per: choose_loop.)"""
+    """Behind every acting launch, in this order: the n-step rows, the episode statistics, the pilot's relabelled rows, the pilot's branches, the new
+    rows' first priorities, the reward sum.  (The front forms run without an inserter and without --per: choose_loop.)"""
     if run.inserter is not None:
         run.inserter.push(run.env, run.actions)  # this step's finished n-step rows (at most multi_step * n of them)
     if run.estats is not None:
         run.estats.push()
     if getattr(run, "online", None) is not None:
         run.online.push()  # --expert_online: per_step envs relabelled by the pilot into the online region of bc_table (one launch, no host sync)
+    if getattr(run, "branch", None) is not None and branch_has_reader(run):
+        run.branch.push()  # --expert_branch: per_step envs flown one step by the pilot, in registers, into the online region of the expert ring (likewise)
     if run.per and run.per_new == "td":
         replay, n, writer = run.replay, run.n, run.writer
         log_new = writer is not None and step % run.log_rate == 0
@@ -908,6 +934,8 @@ def log_episode(run):
         writer.add_scalar("Others/Nonfinite_actions", st.get("nonfinite_actions", 0), episode)
         if getattr(run, "online", None) is not None:
             writer.add_scalar("Expert/Online Rows Written", run.online.rows_written(), episode)  # (host arithmetic: no device read)
+        if getattr(run, "branch", None) is not None:
+            writer.add_scalar("Expert/Branch Rows Written", run.branch.rows_written(), episode)  # (likewise)
         if ret is not None:
             tot = float(ret.mean())
             writer.add_scalar("Training/Episode Reward", tot, episode)
@@ -1098,6 +1126,44 @@ def expert_online_resume_refusal(config, driver):
     return None
 
 
+def expert_branch_refusal(config, world=1):
+    """why `--expert_branch` / `--expert_branch_per_step` cannot run as asked, or None"""
+    rows, k = int(getattr(config, "expert_branch", 0)), int(getattr(config, "expert_branch_per_step", 64))
+    if rows == 0:
+        return None
+    if rows < 0:
+        return f"--expert_branch {rows}: the rows of the expert ring's online region, 0 (off) or more"
+    takes = "--expert_branch goes with --agent HIRL, --agent SAC --type ESAC and --agent SAC --type ISAC"
+    if config.agent == "SAC" and config.type not in ("ESAC", "ISAC"):
+        return f"{takes} (--agent SAC --type {config.type} reads no expert ring)"
+    if config.agent == "TD3":
+        return f"{takes} (TD3 reads no expert ring)"
+    if config.agent == "BC":
+        return f"{takes} (--agent BC reads no expert ring and has no rollouts the pilot could branch from)"
+    if getattr(config, "per", False):
+        return "--expert_branch does not go with --per (the weighted call drops the expert rows: the branch rows would never be drawn)"
+    if (config.gpus and config.gpus > 1) or world > 1:
+        return "--expert_branch runs on one GPU (the branches are rank-local and untested on sharded ranks): use --gpus 1"
+    if not 1 <= k <= min(rows, int(config.num_envs)):
+        return (f"--expert_branch_per_step {k}: 1 <= rows per step <= min(--expert_branch, --num_envs) = {min(rows, int(config.num_envs))} (the picks of a step "
+                "are distinct envs and distinct slots)")
+    return None
+
+
+def expert_branch_resume_refusal(config, driver):
+    """why a snapshot's driver record cannot be resumed under this run's --expert_branch / --expert_branch_per_step, or None (driver None: a fresh run)"""
+    if driver is None:
+        return None
+    was = driver.get("expert_branch")
+    was_rows, was_k = (int(was["online_rows"]), int(was["per_step"])) if was is not None else (0, None)
+    rows, k = int(getattr(config, "expert_branch", 0)), int(getattr(config, "expert_branch_per_step", 64))
+    if was_rows != rows:
+        return f"was run with --expert_branch {was_rows}, --expert_branch {rows} given"
+    if rows and was_k != k:
+        return f"was run with --expert_branch_per_step {was_k}, --expert_branch_per_step {k} given"
+    return None
+
+
 def clip_refusal(config, world=1):
     """why `--grad_clip` / `--fixed_alpha` cannot run as asked, or None"""
     clip, fixed = getattr(config, "grad_clip", None), getattr(config, "fixed_alpha", None)
@@ -1120,7 +1186,7 @@ def parse_args(argv=None):
     """parser().parse_args with the cross-flag checks that are argparse errors"""
     p = parser()
     cfg = p.parse_args(argv)
-    why = per_refusal(cfg) or clip_refusal(cfg) or nstep_refusal(cfg) or mixed_refusal(cfg) or upsample_refusal(cfg) or expert_online_refusal(cfg)
+    why = per_refusal(cfg) or clip_refusal(cfg) or nstep_refusal(cfg) or mixed_refusal(cfg) or upsample_refusal(cfg) or expert_online_refusal(cfg) or expert_branch_refusal(cfg)
     if why:
         p.error(why)
     if cfg.type == "ISAC" and cfg.agent != "SAC":
@@ -1204,6 +1270,13 @@ def parser():
                         "rows that start as a cyclic copy of the expert CSV's and are relabelled by the scripted pursuit pilot in the states the learner "
                         "reaches (dataset aggregation): one small launch behind every acting launch (utils/pilot.py).  0 (default): off, the run is launch "
                         "for launch what it was.  One GPU.  Stored in the snapshot: --resume refuses another value")
+    p.add_argument("--expert_branch", type=int, default=0, metavar="ROWS",
+                   help="an extension: ROWS rows are appended to the labelled expert ring (HIRL's expert rows, E-SAC's, ISAC's expert batch) and rewritten "
+                        "behind every acting launch by BRANCHES of the learner's own envs: K envs are each flown one step by the scripted pursuit pilot, in "
+                        "registers, and (s, a_E, s'_E, r, done) + step_success replace the K oldest of those rows; the envs themselves are untouched.  "
+                        "0 (default): off.  HIRL, E-SAC and ISAC, every --dtype / loop, one GPU, not with --per")
+    p.add_argument("--expert_branch_per_step", type=int, default=64, metavar="K",
+                   help="--expert_branch: envs branched per acting launch, 1 <= K <= min(ROWS, --num_envs)")
     p.add_argument("--expert_online_per_step", type=int, default=64, metavar="K",
                    help="--expert_online: envs relabelled per acting launch, 1 <= K <= min(ROWS, --num_envs); they replace the K oldest online rows")
     p.add_argument("--multi_step", type=int, default=1,

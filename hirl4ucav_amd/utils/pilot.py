@@ -6,6 +6,12 @@ the learner reaches.  OnlineExpert does that behind every acting launch (hx_pilo
 relabelled by the pilot and their (s, a) rows replace the oldest rows of an online region appended to the BC table — dataset aggregation (DAgger), the
 standard remedy for a BC term computed on the recordings' state distribution only.  The table keeps its length, so the sampler and every kernel that
 reads it are untouched.  The rule is stated in include/hirl4ucav.h ("The pilot as a kernel"); the helpers in front of the classes are host-only.
+
+BranchExpert does the same for the LABELLED EXPERT RING, which holds full transitions (s, a, s', r, done) + step_success and is what HIRL's expert rows,
+E-SAC's expert rows and ISAC's expert batch are drawn from: behind every acting launch hx_pilot_branch (hx_branch.hip) loads a few envs' whole state
+into registers, flies each ONE step under the pilot's noise-free action with the env's own step, and writes that branch over the oldest rows of an
+online region appended to the ring.  Nothing is stored back to the env: the learner's trajectory is untouched, and any (s, a, r, s') of the true
+dynamics is valid off-policy data.  The rule is stated in include/hirl4ucav.h ("Expert branches").
 """
 from .. import _lib
 
@@ -91,4 +97,76 @@ class OnlineExpert:
         if st["offline_rows"] != self.offline_rows:
             raise ValueError(f"snapshot's online region stands behind {st['offline_rows']} offline expert rows, this run's table has {self.offline_rows}")
         self.table[self.offline_rows:].copy_(st["online"])
+        self.call = int(st["call"])
+
+
+# ---- expert branches -------------------------------------------------------------------------------------------------------------------------
+BRANCH_SLACK = 10  # the labelled expert ring is built 10 rows longer than it is filled (train_all.load_expert_tables): never full, never wrapped
+
+
+def branch_layout_refusal(rows_shape, rows_dtype, success_shape, success_dtype):
+    """why (rows, step_success) are not what train_all.label_expert builds and DeviceReplay.store_rows takes — fp32 [E0, 32] rows in the column order
+    [s 0..12 | a 13..16 | s' 17..29 | r 30 | done 31], which is the order hx_pilot_branch writes, and int8 [E0] labels —, or None"""
+    if str(rows_dtype) != "torch.float32" or len(rows_shape) != 2 or rows_shape[1] != _lib.ROW_WORDS:
+        return f"the offline rows are fp32 [rows, {_lib.ROW_WORDS}], got {rows_dtype} {list(rows_shape)}"
+    if _lib.OBS_DIM + _lib.ACT_DIM + _lib.OBS_DIM + 2 != _lib.ROW_WORDS:
+        return f"a row is s[{_lib.OBS_DIM}] a[{_lib.ACT_DIM}] s'[{_lib.OBS_DIM}] r done = {_lib.ROW_WORDS} words"
+    if str(success_dtype) != "torch.int8" or list(success_shape) != [rows_shape[0]]:
+        return f"the step_success labels are int8 [{rows_shape[0]}], got {success_dtype} {list(success_shape)}"
+    return None
+
+
+class BranchExpert:
+    """The labelled expert ring as a DeviceReplay of capacity E0 + M + 10 (`ring`): its first E0 rows and labels are the offline ones (never touched),
+    its last M rows start as their cyclic copy (row E0 + i = row i mod E0, labels too) and are rewritten by the pilot's branches: push() behind every
+    acting launch flies `per_step` envs of `env` one step each in registers (FIFO over the online region).  total = E0 + M for good, so every
+    sampler and every kernel that reads the ring is untouched, and the draw starts as the offline distribution.  push() only enqueues on the current
+    torch stream; state_dict() is the one device-to-host copy.  (Building the ring and the state round trip are plain tensor code; only push()
+    needs the GPU.)"""
+
+    def __init__(self, env, rows_offline, success_offline, online_rows, per_step, device=None):
+        import torch
+
+        from .buffer import DeviceReplay
+
+        why = branch_layout_refusal(tuple(rows_offline.shape), rows_offline.dtype, tuple(success_offline.shape), success_offline.dtype)
+        if why:
+            raise ValueError("BranchExpert: " + why)
+        self.env, self.offline_rows, self.online_rows, self.per_step = env, int(rows_offline.shape[0]), int(online_rows), int(per_step)
+        why = online_args_refusal(env.n, self.offline_rows, self.online_rows, self.per_step)  # (the same region rule as the BC table's)
+        if why:
+            raise ValueError("BranchExpert: " + why)
+        device = rows_offline.device if device is None else device
+        fill = torch.tensor(initial_fill_index(self.offline_rows, self.online_rows), dtype=torch.int64, device=rows_offline.device)
+        self.ring = DeviceReplay(self.offline_rows + self.online_rows + BRANCH_SLACK, device)
+        self.ring.store_rows(rows_offline, success_offline)
+        self.ring.store_rows(rows_offline[fill], success_offline[fill])
+        assert self.ring.fixed_len == self.offline_rows + self.online_rows < self.ring.capacity  # (slot = row index: the ring has not wrapped)
+        self.call = 0
+
+    def push(self):
+        e, r = self.env, self.ring
+        if e.device.type != "cuda" or not r.ring.is_cuda:
+            raise _lib.HxError("BranchExpert.push runs on the GPU only (there is no CPU path in the product)")
+        _lib.call("hx_pilot_branch", _lib.ptr(e.state), e.n, e.pitch, _lib.ptr(e.obs), _lib.ptr(r.ring), _lib.ptr(r.success), self.offline_rows,
+                  self.online_rows, self.per_step, self.call, _lib.stream_ptr())
+        self.call += 1
+
+    def rows_written(self):
+        return rows_written(self.call, self.per_step, self.online_rows)
+
+    def state_dict(self):
+        lo, hi = self.offline_rows, self.offline_rows + self.online_rows
+        return {"online": self.ring.ring[lo:hi].cpu().clone(), "success": self.ring.success[lo:hi].cpu().clone(), "call": self.call,
+                "online_rows": self.online_rows, "per_step": self.per_step, "offline_rows": self.offline_rows}
+
+    def load_state_dict(self, st):
+        if (st["online_rows"], st["per_step"]) != (self.online_rows, self.per_step):
+            raise ValueError(f"snapshot was written under --expert_branch {st['online_rows']} --expert_branch_per_step {st['per_step']}, this run has "
+                             f"--expert_branch {self.online_rows} --expert_branch_per_step {self.per_step}")
+        if st["offline_rows"] != self.offline_rows:
+            raise ValueError(f"snapshot's branch rows stand behind {st['offline_rows']} offline expert rows, this run's ring has {self.offline_rows}")
+        lo, hi = self.offline_rows, self.offline_rows + self.online_rows
+        self.ring.ring[lo:hi].copy_(st["online"])
+        self.ring.success[lo:hi].copy_(st["success"])
         self.call = int(st["call"])

@@ -86,8 +86,9 @@ const char* hx_last_error(void);
  * 125: success upsampling of the replay draw and the BC minibatch's fire row (HxUps, hx_ups_*).
  * 126: the pursuit pilot as a kernel and the online region of the BC table (hx_pilot_act, hx_pilot_refresh).
  * 127: four acting entry points instead of sixteen: hx_actor_act, hx_actor_act_step, hx_sac_act and hx_sac_act_step take the W2 images as three nullable
- * pointers (w2_f32i, w2_x9, w2_bf16) after the network; their _f32i / _x9 / _bf16 variants, the `ws` argument and hx_act_workspace_floats are gone. */
-#define HX_ABI_VERSION 127
+ * pointers (w2_f32i, w2_x9, w2_bf16) after the network; their _f32i / _x9 / _bf16 variants, the `ws` argument and hx_act_workspace_floats are gone.
+ * 128: expert branches: one pilot step per pick fills the online region of the labelled expert ring (hx_pilot_branch). */
+#define HX_ABI_VERSION 128
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -897,6 +898,32 @@ int hx_pilot_act(const float* state, int64_t n, int64_t stride, const float* obs
  * every slot holds a complete row.  No atomics, no workgroup waits for another.  Enqueues only. */
 int hx_pilot_refresh(const float* state, int64_t n, int64_t stride, const float* obs, float* table, int64_t offline_rows, int64_t online_rows,
                      int32_t per_call, uint64_t call, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Expert branches (an EXTENSION beside the online region of the BC table above: that one holds (s, a) rows, this one full transitions).  The
+ * labelled expert ring [offline_rows + online_rows][HX_ROW_WORDS] with its step_success bytes [offline_rows + online_rows] is what HIRL's expert
+ * rows, E-SAC's expert rows and ISAC's expert batch are drawn from.  Behind an acting launch, k = per_call envs are each flown ONE step under the
+ * pilot's action, in registers, and that branch is stored over the oldest online rows.  For pick j in [0, k), M = online_rows:
+ *     env   e_j  = (call + j floor(n / k)) mod n            (hx_pilot_refresh's picks)
+ *     slot       = offline_rows + ((call k + j) mod M)      (hx_pilot_refresh's slots; both exact for every 64-bit call, formed from residues)
+ *     s          = obs[e_j]: the stored observation, what the learner saw
+ *     a_E        = the pilot's NOISE-FREE action on the state words of env e_j ("The pilot as a kernel"), clamped by comparisons,
+ *                  fire = +1 iff s[7] > 0 && s[8] > 0, else -1
+ *     one step   = the env state of e_j is loaded and stepped under a_E exactly as hx_env_step steps it: scripted opponent, the latches taken
+ *                  BEFORE the action, missile launch and tick, lock update, the wrapper's observation / reward / termination, the Euler entries.
+ *                  Left out: auto-reset and the time-limit rule (the branch ends nobody's episode), the env's own ring insert, the statistics.
+ *                  NOTHING is stored back to `state` or `obs`.
+ *     row        = [s 0..12 | a_E 13..16 | s' 17..29 | r 30 | done 31] (the replay row's column order), s' assembled as hx_env_step assembles its
+ *                  next observation, r the step's reward, done 1.0 or 0.0 (the env's own _get_reward / _get_termination, NOT hx_label_transitions'
+ *                  get_reward: the altitude penalties and the fire-success latch are in it); written as one whole 128-byte line
+ *     success[slot] = the step's step_success, -1 / 0 / +1
+ *     if any of the 32 words is not finite, neither the row nor the byte is written: the slot keeps what it had
+ * Rows [0, offline_rows) and success[0 .. offline_rows) are never touched.  1 <= k <= min(n, M), ring 128-byte aligned, fewer than 2^31 rows in
+ * all, 0 < n < 2^31, stride >= n, else HX_ERR_ARG and nothing is launched.  Between launches every slot holds a complete row.  One pick per lane, 64
+ * per workgroup; no atomics, no workgroup waits for another.  tests/_branch_model.py is the same rule on the CPU, bit for bit.  Enqueues only.
+ * ------------------------------------------------------------------------------------------------------------ */
+int hx_pilot_branch(const float* state, int64_t n, int64_t stride, const float* obs, float* ring, int8_t* success, int64_t offline_rows,
+                    int64_t online_rows, int32_t per_call, uint64_t call, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Exchange step of a sharded update without a collective library (selectable beside RCCL): one-shot all-reduce over hipIpc peer
