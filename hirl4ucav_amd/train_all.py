@@ -33,6 +33,7 @@ from .utils.seed import set_seed
 MAX_STEP = {"straight_line": 1500, "serpentine": 1500, "circular": 1900}  # train_all.py:159-183
 MIXED = "mixed"  # --env mixed: one population over all of SCENARIOS (BASELINE.json configs[4]); an extension, the reference trains one scenario per run
 MIXED_MAX_STEP = max(MAX_STEP.values())  # HxStepOpts.max_step is one word: a mixed population trains under the longest of its scenarios' limits
+BATCH = 128  # train_all.py:190-208: the minibatch of every agent
 
 
 # ---- pure host logic (unit-tested on CPU) ----------------------------------------------------------------------------
@@ -93,9 +94,17 @@ def bc_weight_schedule(hirl_type, episode, bc_weight, bc_warm_up=False):
     raise ValueError(hirl_type)
 
 
-def expert_num_after(expert_num, step, warm_up_rate=10):
-    """train_all.py:356-357: one expert row fewer whenever step % warm_up_rate == 0, down to 0."""
-    return expert_num - 1 if (step % warm_up_rate == 0 and expert_num != 0) else expert_num
+def expert_num_after(expert_num, step, warm_up_rate=10, floor=0):
+    """train_all.py:356-357: one expert row fewer whenever step % warm_up_rate == 0, down to 0.  floor (--expert_floor, a departure: DESIGN.md
+    section 5): never below `floor` rows, so the expert rows outlive the warm-up; floor = 0 is the reference's rule."""
+    after = expert_num - 1 if (step % warm_up_rate == 0 and expert_num != 0) else expert_num
+    return after if floor == 0 else max(after, floor)
+
+
+def next_expert_num(run, step):
+    """expert_num behind this step's decay, under the run's --expert_floor (without one: the reference's call, argument for argument)"""
+    floor = getattr(run, "expert_floor", 0)
+    return expert_num_after(run.expert_num, step, run.warm_up_rate, floor=floor) if floor else expert_num_after(run.expert_num, step, run.warm_up_rate)
 
 
 def expert_pair_indices(done):
@@ -329,8 +338,8 @@ def train_bc(config, device, seed, max_step):
     bc_table = torch.from_numpy(tab).to(device)
     table = DeviceReplay(es.shape[0], device)  # the sampler wants a main ring as well; the BC step reads only the BC rows
     table.store_rows(bc_table)
-    if upsample_refusal(config) or expert_online_refusal(config) or expert_branch_refusal(config):
-        raise SystemExit("train_all: " + (upsample_refusal(config) or expert_online_refusal(config) or expert_branch_refusal(config)))
+    if upsample_refusal(config) or expert_online_refusal(config) or expert_branch_refusal(config) or expert_floor_refusal(config):
+        raise SystemExit("train_all: " + (upsample_refusal(config) or expert_online_refusal(config) or expert_branch_refusal(config) or expert_floor_refusal(config)))
     if getattr(config, "expert_upsample", False):  # BC.py:152-158, 171-176: one row of every minibatch is a fire row
         from .utils.buffer import fire_rows
 
@@ -452,10 +461,11 @@ def check_agent_flags(run):
     # the reference's two sampling switches (HIRL.py:184-185): success rows of the replay drawn 10 : 1, one fire row forced into the BC minibatch
     run.buffer_upsample, run.expert_upsample = bool(getattr(config, "buffer_upsample", False)), bool(getattr(config, "expert_upsample", False))
     run.upsampler = None
-    for refusal in (per_refusal, nstep_refusal, clip_refusal, upsample_refusal, expert_online_refusal, expert_branch_refusal):  # (per_refusal without --per: --per_new td on its own)
+    for refusal in (per_refusal, nstep_refusal, clip_refusal, upsample_refusal, expert_online_refusal, expert_branch_refusal, expert_floor_refusal):  # (per_refusal without --per: --per_new td on its own)
         if refusal(config, world):
             raise SystemExit("train_all: " + refusal(config, world))
-    run.batch = 128  # train_all.py:190-208
+    run.batch = BATCH  # train_all.py:190-208
+    run.expert_floor = int(getattr(config, "expert_floor", 0))  # --expert_floor: expert_num stops there instead of at 0 (expert_num_after)
     run.warm_up_rate = 20 if run.sac else 10  # train_sac.py:203 / train_all.py:207
 
 
@@ -521,7 +531,8 @@ def load_expert_tables(run):
         eng.set_upsample(run.upsampler, None)
     if not (run.hirl or run.esac or run.isac):
         return
-    why = expert_branch_resume_refusal(config, run.snap["driver"] if run.snap is not None else None)
+    why = (expert_branch_resume_refusal(config, run.snap["driver"] if run.snap is not None else None)
+           or expert_floor_resume_refusal(config, run.snap["driver"] if run.snap is not None else None))
     if why:
         raise SystemExit(f"train_all: --resume {config.resume} {why}")
     tables = load_expert_files(config)
@@ -530,10 +541,12 @@ def load_expert_tables(run):
     es, ea = np.concatenate([t[0] for t in tables]), np.concatenate([t[1] for t in tables])
     if int(getattr(config, "expert_branch", 0)) > 0:
         # An extension (utils/pilot.py): the ring grows by an online region that starts as a cyclic copy of the labelled rows and is rewritten behind
-        # every acting launch by one-step branches of the learner's envs under the pilot.  Its length stays E0 + ROWS: the samplers are untouched.
+        # every acting launch by branches of the learner's envs under the pilot: one step per pick, or (--expert_branch_steps H > 1) resident flights of
+        # up to H steps that advance one step per launch.  Its length stays E0 + ROWS: the samplers are untouched.
         from .utils.pilot import BranchExpert
 
-        run.branch = BranchExpert(run.env, rows, succ, int(config.expert_branch), int(config.expert_branch_per_step), device)
+        run.branch = BranchExpert(run.env, rows, succ, int(config.expert_branch), int(config.expert_branch_per_step), device,
+                                  steps=int(getattr(config, "expert_branch_steps", 1)))
         run.expert = run.branch.ring
     else:
         run.expert = DeviceReplay(rows.shape[0] + 10, device)
@@ -617,6 +630,8 @@ def stats_record(run):
         rec["expert_online"] = run.online.state_dict()
     if getattr(run, "branch", None) is not None:  # (likewise without --expert_branch)
         rec["expert_branch"] = run.branch.state_dict()
+    if getattr(run, "expert_floor", 0):  # (likewise without --expert_floor)
+        rec["expert_floor"] = run.expert_floor
     return rec
 
 
@@ -799,7 +814,7 @@ def log_step_scalars(run, step):
 
 def step_front_hirl(run, step, w_now, warm):
     """HIRL / TD3: env step + the first two launches of learn() as one launch (HirlEngine.step_learn)"""
-    run.expert_num = expert_num_after(run.expert_num, step, run.warm_up_rate)
+    run.expert_num = next_expert_num(run, step)
     run.eng.step_learn(run.env, run.expert, run.bc_table, n_main=run.batch - run.expert_num, act_sigma=0.1, act_seed=run.seed + 1, out=run.actions,
                        sample_seed=run.seed + 2 + run.rank, bc_weight_now=w_now, bc_warm_up_weight=warm)
     after_env_step(run, step)
@@ -808,7 +823,7 @@ def step_front_hirl(run, step, w_now, warm):
 
 def step_front_sac(run, step):
     """SAC / E-SAC / ISAC: explore + env step + the first forward launch of learn() in one launch (SacEngine.step_learn); ISAC's expert batch rides in it"""
-    run.expert_num = expert_num_after(run.expert_num, step, run.warm_up_rate)
+    run.expert_num = next_expert_num(run, step)
     run.eng.step_learn(run.env, run.expert if (run.esac or run.isac) else None, n_main=run.batch - run.expert_num, act_seed=run.seed + 1, out=run.actions,
                        sample_seed=run.seed + 2 + run.rank)
     after_env_step(run, step)
@@ -828,7 +843,7 @@ def step_reference(run, step, w_now, warm):
     after_env_step(run, step)
     if step == run.max_step - 1:
         return
-    run.expert_num = expert_num_after(run.expert_num, step, run.warm_up_rate)
+    run.expert_num = next_expert_num(run, step)
     n_main, sample_seed = run.batch - run.expert_num, seed + 2 + run.rank
     for _ in range(config.updates_per_step):
         if sac:  # train_sac.py:270-273 (SAC) / :401-403 (E-SAC: expert rows mixed in while expert_num > 0)
@@ -936,6 +951,10 @@ def log_episode(run):
             writer.add_scalar("Expert/Online Rows Written", run.online.rows_written(), episode)  # (host arithmetic: no device read)
         if getattr(run, "branch", None) is not None:
             writer.add_scalar("Expert/Branch Rows Written", run.branch.rows_written(), episode)  # (likewise)
+            if run.branch.steps > 1:  # the resident flights' own counters: one device-to-host copy per driver episode
+                _, ended_rows, kill_rows = run.branch.counters()
+                writer.add_scalar("Expert/Branch Episodes Ended", ended_rows, episode)
+                writer.add_scalar("Expert/Branch Kills", kill_rows, episode)
         if ret is not None:
             tot = float(ret.mean())
             writer.add_scalar("Training/Episode Reward", tot, episode)
@@ -1127,8 +1146,13 @@ def expert_online_resume_refusal(config, driver):
 
 
 def expert_branch_refusal(config, world=1):
-    """why `--expert_branch` / `--expert_branch_per_step` cannot run as asked, or None"""
+    """why `--expert_branch` / `--expert_branch_per_step` / `--expert_branch_steps` cannot run as asked, or None"""
     rows, k = int(getattr(config, "expert_branch", 0)), int(getattr(config, "expert_branch_per_step", 64))
+    steps = int(getattr(config, "expert_branch_steps", 1))
+    if not 1 <= steps <= 65535:
+        return f"--expert_branch_steps {steps}: the steps of a resident branch, 1 (one step per pick) to 65,535 (the episode counter's range)"
+    if rows <= 0 and steps != 1:
+        return f"--expert_branch_steps {steps} goes with --expert_branch ROWS > 0 (there are no branches to fly without it)"
     if rows == 0:
         return None
     if rows < 0:
@@ -1161,6 +1185,36 @@ def expert_branch_resume_refusal(config, driver):
         return f"was run with --expert_branch {was_rows}, --expert_branch {rows} given"
     if rows and was_k != k:
         return f"was run with --expert_branch_per_step {was_k}, --expert_branch_per_step {k} given"
+    was_steps, steps = (int(was.get("steps", 1)) if was is not None else 1), int(getattr(config, "expert_branch_steps", 1))
+    if rows and was_steps != steps:
+        return f"was run with --expert_branch_steps {was_steps}, --expert_branch_steps {steps} given"
+    return None
+
+
+def expert_floor_refusal(config, world=1):
+    """why `--expert_floor` cannot run as asked, or None"""
+    floor = int(getattr(config, "expert_floor", 0))
+    if floor == 0:
+        return None
+    if not 0 <= floor <= BATCH:
+        return f"--expert_floor {floor}: the expert rows of a minibatch that stay after the warm-up, 0 (off) to the batch of {BATCH}"
+    takes = "--expert_floor goes with --agent HIRL and --agent SAC --type ESAC"
+    if config.agent == "SAC" and config.type != "ESAC":
+        return f"{takes} (--agent SAC --type {config.type} mixes no expert rows into its minibatch: there is no expert_num to hold)"
+    if config.agent in ("TD3", "BC"):
+        return f"{takes} (--agent {config.agent} mixes no expert rows into its minibatch: there is no expert_num to hold)"
+    if getattr(config, "per", False):
+        return "--expert_floor does not go with --per (the weighted call drops the expert rows)"
+    return None
+
+
+def expert_floor_resume_refusal(config, driver):
+    """why a snapshot's driver record cannot be resumed under this run's --expert_floor, or None (driver None: a fresh run)"""
+    if driver is None:
+        return None
+    was, floor = int(driver.get("expert_floor", 0)), int(getattr(config, "expert_floor", 0))
+    if was != floor:
+        return f"was run with --expert_floor {was}, --expert_floor {floor} given"
     return None
 
 
@@ -1186,7 +1240,7 @@ def parse_args(argv=None):
     """parser().parse_args with the cross-flag checks that are argparse errors"""
     p = parser()
     cfg = p.parse_args(argv)
-    why = per_refusal(cfg) or clip_refusal(cfg) or nstep_refusal(cfg) or mixed_refusal(cfg) or upsample_refusal(cfg) or expert_online_refusal(cfg) or expert_branch_refusal(cfg)
+    why = per_refusal(cfg) or clip_refusal(cfg) or nstep_refusal(cfg) or mixed_refusal(cfg) or upsample_refusal(cfg) or expert_online_refusal(cfg) or expert_branch_refusal(cfg) or expert_floor_refusal(cfg)
     if why:
         p.error(why)
     if cfg.type == "ISAC" and cfg.agent != "SAC":
@@ -1277,6 +1331,14 @@ def parser():
                         "0 (default): off.  HIRL, E-SAC and ISAC, every --dtype / loop, one GPU, not with --per")
     p.add_argument("--expert_branch_per_step", type=int, default=64, metavar="K",
                    help="--expert_branch: envs branched per acting launch, 1 <= K <= min(ROWS, --num_envs)")
+    p.add_argument("--expert_branch_steps", type=int, default=1, metavar="H",
+                   help="--expert_branch: the K branches stay resident on the device and fly up to H steps, one step per acting launch (the launch's cost "
+                        "does not depend on H); a branch that ends (done, a non-finite row, H steps) is reseeded from the learner's envs.  1 (default): one "
+                        "step per pick.  1..65535.  Stored in the snapshot: --resume refuses another value")
+    p.add_argument("--expert_floor", type=int, default=0, metavar="N",
+                   help="HIRL and --type ESAC (a departure from the reference, whose expert rows end with the warm-up): the expert rows of a minibatch never "
+                        "fall below N, 0 <= N <= 128, so the expert ring (and --expert_branch's rows) is read for the whole run.  0 (default): the "
+                        "reference's rule.  Not with --per.  Stored in the snapshot: --resume refuses another value")
     p.add_argument("--expert_online_per_step", type=int, default=64, metavar="K",
                    help="--expert_online: envs relabelled per acting launch, 1 <= K <= min(ROWS, --num_envs); they replace the K oldest online rows")
     p.add_argument("--multi_step", type=int, default=1,

@@ -11,7 +11,10 @@ BranchExpert does the same for the LABELLED EXPERT RING, which holds full transi
 E-SAC's expert rows and ISAC's expert batch are drawn from: behind every acting launch hx_pilot_branch (hx_branch.hip) loads a few envs' whole state
 into registers, flies each ONE step under the pilot's noise-free action with the env's own step, and writes that branch over the oldest rows of an
 online region appended to the ring.  Nothing is stored back to the env: the learner's trajectory is untouched, and any (s, a, r, s') of the true
-dynamics is valid off-policy data.  The rule is stated in include/hirl4ucav.h ("Expert branches").
+dynamics is valid off-policy data.  With steps = H > 1 the branches stay RESIDENT in a device workspace (hx_pilot_branch_steps, hx_branch_steps.hip):
+every push() advances each of them one step, and a branch that ends — done, a non-finite row, H steps — is reseeded from the learner's envs, so the
+ring also gets the rows in which the pursuit pays off, hundreds of steps behind the state it started from.  The rule is stated in
+include/hirl4ucav.h ("Expert branches").
 """
 from .. import _lib
 
@@ -104,6 +107,26 @@ class OnlineExpert:
 BRANCH_SLACK = 10  # the labelled expert ring is built 10 rows longer than it is filled (train_all.load_expert_tables): never full, never wrapped
 
 
+BRANCH_MAX_STEPS = 65535  # hx_pilot_branch_steps' max_steps: the episode counter's range
+BRANCH_COLUMN_BYTES = (37 + 13 + 1) * 4 + 3 * 8  # a workspace column: bstate[37] bobs[13] age, three 64-bit counters (include/hirl4ucav.h)
+
+
+def branch_steps_refusal(steps):
+    """why branches of `steps` steps cannot be built, or None"""
+    if not 1 <= steps <= BRANCH_MAX_STEPS:
+        return f"steps {steps}: 1 (one step per pick) <= steps <= {BRANCH_MAX_STEPS}"
+    return None
+
+
+def branch_counter_sums(counters_host, per_step):
+    """the three sums (rows written, rows with done, kills) of a host copy of the workspace's counters (uint8 [24 kpad]: uint64 [3][kpad]) over its
+    first per_step lanes"""
+    import torch
+
+    cnt = counters_host.contiguous().view(torch.int64).reshape(3, -1)[:, :per_step]
+    return tuple(int(v) for v in cnt.sum(1))
+
+
 def branch_layout_refusal(rows_shape, rows_dtype, success_shape, success_dtype):
     """why (rows, step_success) are not what train_all.label_expert builds and DeviceReplay.store_rows takes — fp32 [E0, 32] rows in the column order
     [s 0..12 | a 13..16 | s' 17..29 | r 30 | done 31], which is the order hx_pilot_branch writes, and int8 [E0] labels —, or None"""
@@ -122,9 +145,10 @@ class BranchExpert:
     acting launch flies `per_step` envs of `env` one step each in registers (FIFO over the online region).  total = E0 + M for good, so every
     sampler and every kernel that reads the ring is untouched, and the draw starts as the offline distribution.  push() only enqueues on the current
     torch stream; state_dict() is the one device-to-host copy.  (Building the ring and the state round trip are plain tensor code; only push()
-    needs the GPU.)"""
+    needs the GPU.)  steps = 1: that object and nothing else.  steps = H > 1: the per_step branches are resident in `work` (the workspace of
+    hx_pilot_branch_steps, zeroed here), push() flies each one step further, counters() reads what they have written."""
 
-    def __init__(self, env, rows_offline, success_offline, online_rows, per_step, device=None):
+    def __init__(self, env, rows_offline, success_offline, online_rows, per_step, device=None, steps=1):
         import torch
 
         from .buffer import DeviceReplay
@@ -133,7 +157,8 @@ class BranchExpert:
         if why:
             raise ValueError("BranchExpert: " + why)
         self.env, self.offline_rows, self.online_rows, self.per_step = env, int(rows_offline.shape[0]), int(online_rows), int(per_step)
-        why = online_args_refusal(env.n, self.offline_rows, self.online_rows, self.per_step)  # (the same region rule as the BC table's)
+        self.steps = int(steps)
+        why = online_args_refusal(env.n, self.offline_rows, self.online_rows, self.per_step) or branch_steps_refusal(self.steps)  # (the BC table's region rule)
         if why:
             raise ValueError("BranchExpert: " + why)
         device = rows_offline.device if device is None else device
@@ -143,30 +168,51 @@ class BranchExpert:
         self.ring.store_rows(rows_offline[fill], success_offline[fill])
         assert self.ring.fixed_len == self.offline_rows + self.online_rows < self.ring.capacity  # (slot = row index: the ring has not wrapped)
         self.call = 0
+        self.work = None
+        if self.steps > 1:  # every age 0: the first push() seeds every branch
+            self.kpad = (self.per_step + 63) // 64 * 64
+            self.work = torch.zeros(self.kpad * BRANCH_COLUMN_BYTES, dtype=torch.uint8, device=self.ring.ring.device)
 
     def push(self):
         e, r = self.env, self.ring
         if e.device.type != "cuda" or not r.ring.is_cuda:
             raise _lib.HxError("BranchExpert.push runs on the GPU only (there is no CPU path in the product)")
-        _lib.call("hx_pilot_branch", _lib.ptr(e.state), e.n, e.pitch, _lib.ptr(e.obs), _lib.ptr(r.ring), _lib.ptr(r.success), self.offline_rows,
-                  self.online_rows, self.per_step, self.call, _lib.stream_ptr())
+        if self.steps == 1:
+            _lib.call("hx_pilot_branch", _lib.ptr(e.state), e.n, e.pitch, _lib.ptr(e.obs), _lib.ptr(r.ring), _lib.ptr(r.success), self.offline_rows,
+                      self.online_rows, self.per_step, self.call, _lib.stream_ptr())
+        else:
+            _lib.call("hx_pilot_branch_steps", _lib.ptr(e.state), e.n, e.pitch, _lib.ptr(e.obs), _lib.ptr(r.ring), _lib.ptr(r.success), self.offline_rows,
+                      self.online_rows, self.per_step, self.steps, self.call, _lib.ptr(self.work), self.kpad, _lib.stream_ptr())
         self.call += 1
+
+    def counters(self):
+        """(rows written, rows with done, kills) of the resident branches since the workspace was zeroed: ONE device-to-host copy"""
+        if self.work is None:
+            raise _lib.HxError("BranchExpert.counters: one-step branches (steps = 1) keep no counters; rows_written() is host arithmetic")
+        return branch_counter_sums(self.work[(BRANCH_COLUMN_BYTES - 24) * self.kpad:].cpu(), self.per_step)
 
     def rows_written(self):
         return rows_written(self.call, self.per_step, self.online_rows)
 
     def state_dict(self):
         lo, hi = self.offline_rows, self.offline_rows + self.online_rows
-        return {"online": self.ring.ring[lo:hi].cpu().clone(), "success": self.ring.success[lo:hi].cpu().clone(), "call": self.call,
-                "online_rows": self.online_rows, "per_step": self.per_step, "offline_rows": self.offline_rows}
+        st = {"online": self.ring.ring[lo:hi].cpu().clone(), "success": self.ring.success[lo:hi].cpu().clone(), "call": self.call,
+              "online_rows": self.online_rows, "per_step": self.per_step, "offline_rows": self.offline_rows}
+        if self.steps > 1:  # (steps = 1 writes the record it always wrote)
+            st["steps"], st["work"] = self.steps, self.work.cpu().clone()
+        return st
 
     def load_state_dict(self, st):
         if (st["online_rows"], st["per_step"]) != (self.online_rows, self.per_step):
             raise ValueError(f"snapshot was written under --expert_branch {st['online_rows']} --expert_branch_per_step {st['per_step']}, this run has "
                              f"--expert_branch {self.online_rows} --expert_branch_per_step {self.per_step}")
+        if int(st.get("steps", 1)) != self.steps:
+            raise ValueError(f"snapshot was written under --expert_branch_steps {int(st.get('steps', 1))}, this run has --expert_branch_steps {self.steps}")
         if st["offline_rows"] != self.offline_rows:
             raise ValueError(f"snapshot's branch rows stand behind {st['offline_rows']} offline expert rows, this run's ring has {self.offline_rows}")
         lo, hi = self.offline_rows, self.offline_rows + self.online_rows
         self.ring.ring[lo:hi].copy_(st["online"])
         self.ring.success[lo:hi].copy_(st["success"])
+        if self.steps > 1:
+            self.work.copy_(st["work"])
         self.call = int(st["call"])

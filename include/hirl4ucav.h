@@ -87,8 +87,10 @@ const char* hx_last_error(void);
  * 126: the pursuit pilot as a kernel and the online region of the BC table (hx_pilot_act, hx_pilot_refresh).
  * 127: four acting entry points instead of sixteen: hx_actor_act, hx_actor_act_step, hx_sac_act and hx_sac_act_step take the W2 images as three nullable
  * pointers (w2_f32i, w2_x9, w2_bf16) after the network; their _f32i / _x9 / _bf16 variants, the `ws` argument and hx_act_workspace_floats are gone.
- * 128: expert branches: one pilot step per pick fills the online region of the labelled expert ring (hx_pilot_branch). */
-#define HX_ABI_VERSION 128
+ * 128: expert branches: one pilot step per pick fills the online region of the labelled expert ring (hx_pilot_branch).
+ * 129: expert branches of up to H steps: resident branches in a device workspace, one step per call (hx_pilot_branch_steps,
+ * hx_branch_workspace_bytes). */
+#define HX_ABI_VERSION 129
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -924,6 +926,33 @@ int hx_pilot_refresh(const float* state, int64_t n, int64_t stride, const float*
  * ------------------------------------------------------------------------------------------------------------ */
 int hx_pilot_branch(const float* state, int64_t n, int64_t stride, const float* obs, float* ring, int8_t* success, int64_t offline_rows,
                     int64_t online_rows, int32_t per_call, uint64_t call, void* stream);
+/* Branches of up to H = max_steps steps, as a conveyor: the k = per_call branches stay RESIDENT in a device workspace, every call advances each of
+ * them ONE step and writes that step's row by the rule above, and a branch that has ended is reseeded from the population on the next call.  The
+ * cost of a call is hx_pilot_branch's plus one coalesced load and store of 50 words per lane, whatever H is; the rows of one pilot flight reach the
+ * ring one per call.
+ * Workspace (part of the ABI): struct-of-arrays over branches, kpad = k rounded up to 64 columns, hx_branch_workspace_bytes(k) = 228 kpad bytes:
+ *     float    bstate[37][kpad]     the branch's env state, word w of branch j at bstate[w kpad + j] ("Env state layout")
+ *     float    bobs[13][kpad]       the observation the branch's pilot fires on: the s' of its last step
+ *     uint32_t age[kpad]            steps flown by the resident flight; 0: not resident, the next call seeds it
+ *     uint64_t counters[3][kpad]    per lane: rows written, rows written with done = 1, kills
+ * The caller zeroes it once (age = 0 everywhere) and passes work_stride = kpad.  For lane j < k at call c:
+ *     source     age[j] == 0: seeded from env e_j = (c + j floor(n / k)) mod n, its state and stored observation gathered as above;
+ *                otherwise the state and observation of workspace column j
+ *     step       a_E = the pilot's noise-free action on the source's state words, fire = +1 iff s[7] > 0 && s[8] > 0; one env step as above;
+ *                row = [s | a_E | s' | r | done]
+ *     write      all 32 words finite: the row and its step_success byte go to slot offline_rows + ((c k + j) mod M), as above; otherwise nothing
+ *     advance    row written, done == 0 and age[j] + 1 < max_steps: the stepped state and s' go to column j, age[j] += 1;
+ *                otherwise age[j] = 0, the column is left as it is, and the next call reseeds
+ *     episode    no time limit, no auto-reset; done is the env's own termination; the opponent's script runs on from the counters the branch carries
+ *     counters   rows written += 1; with done: rows with done += 1; with done, health < 0.1f and the fire-success latch set (the comparison the
+ *                reward's +600 is paid on): kills += 1.  Each lane adds to its own words.
+ * max_steps == 1 is hx_pilot_branch: the same bits in ring and bytes, bstate / bobs / age neither read nor written, only the counters move.
+ * `state` and `obs` are read-only.  Columns >= k are never touched.  1 <= max_steps <= 65,535 (the episode counter's range), work 16-byte aligned,
+ * work_stride == kpad, the other arguments as hx_pilot_branch, else HX_ERR_ARG and nothing is launched.  No atomics, no workgroup waits for
+ * another.  tests/_branch_steps_model.py is the same rule on the CPU, bit for bit.  Enqueues only. */
+int64_t hx_branch_workspace_bytes(int32_t per_call);  /* 0 for per_call < 1 */
+int hx_pilot_branch_steps(const float* state, int64_t n, int64_t stride, const float* obs, float* ring, int8_t* success, int64_t offline_rows,
+                          int64_t online_rows, int32_t per_call, int32_t max_steps, uint64_t call, void* work, int64_t work_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Exchange step of a sharded update without a collective library (selectable beside RCCL): one-shot all-reduce over hipIpc peer

@@ -1,7 +1,7 @@
 """Time the vector step of train_all at the project's two headline shapes under ONE source tree, for the cost of expert branches (DESIGN.md section 8,
-profiles/branch_cost.txt) — tools/ubench/pilot_step.py's method, with the SAC family beside HIRL:
+profiles/branch_cost.txt) and of resident branches of up to H steps (profiles/branch_steps_cost.txt) — tools/ubench/pilot_step.py's method, with the SAC family beside HIRL:
 
-    python tools/ubench/branch_step.py ROOT LABEL hirl|esac [train_all flags, e.g. --expert_branch 4096 --expert_branch_per_step 64]
+    python tools/ubench/branch_step.py ROOT LABEL hirl|esac [train_all flags, e.g. --expert_branch 4096 --expert_branch_per_step 64 [--expert_branch_steps 1500]]
 
 hirl: HIRL soft, fp32, 4,096 straight_line envs, front loop.  esac: E-SAC, fp32, 16,384 serpentine envs, front loop.  B = 128.  ROOT is a built checkout:
 this one, or the parent commit's for the A/B (its own Python and library).  One process = one configuration: alternate the processes (parent, this tree
