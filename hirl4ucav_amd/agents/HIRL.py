@@ -89,7 +89,7 @@ class Agent:
     _slope, _use_bc = 0.0, True
 
     def __init__(self, actorLR, criticLR, stateDim, actionDim, full1Dim, full2Dim, tau, gamma, bufferSize, batchSize,
-                 layerNorm, name, expert_states=None, expert_actions=None, bc_weight=0.0, expert_warm_up=False):
+                 layerNorm, name, expert_states=None, expert_actions=None, bc_weight=0.0, expert_warm_up=False, grad_clip=None):
         _check_dims(stateDim, actionDim, full1Dim, full2Dim, layerNorm)
         self.device = device
         self.tau, self.gamma, self.bufferSize, self.batchSize = tau, gamma, int(bufferSize), int(batchSize)
@@ -100,6 +100,9 @@ class Agent:
         self.eng = E.HirlEngine(batch=batchSize, lr_actor=actorLR, lr_critic=criticLR, tau=tau, gamma=gamma, slope=self._slope,
                                 use_bc=self._use_bc, device=device, layer_norm=self.layerNorm)
         self.eng.load_params(init_actor_state_dict(), init_critic_state_dict(), init_actor_state_dict() if self._use_bc else None)
+        self.grad_clip = grad_clip  # an extension (the reference has none): clip_grad_norm_ once per optimizer, HirlEngine.set_grad_clip
+        if grad_clip is not None:
+            self.eng.set_grad_clip(grad_clip)
         e = self.eng
         ln = self.layerNorm
         self.actor = _NetView(e.actor, E.ACTOR_LAYOUT, "Actor_" + name, on_load=e.refresh_images, layer_norm=ln)

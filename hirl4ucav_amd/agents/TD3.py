@@ -10,8 +10,9 @@ from .HIRL import Agent as _HirlAgent
 class Agent(_HirlAgent):
     _slope, _use_bc = 0.01, False
 
-    def __init__(self, actorLR, criticLR, stateDim, actionDim, full1Dim, full2Dim, tau, gamma, bufferSize, batchSize, layerNorm, name):
-        super().__init__(actorLR, criticLR, stateDim, actionDim, full1Dim, full2Dim, tau, gamma, bufferSize, batchSize, layerNorm, name)
+    def __init__(self, actorLR, criticLR, stateDim, actionDim, full1Dim, full2Dim, tau, gamma, bufferSize, batchSize, layerNorm, name, grad_clip=None):
+        super().__init__(actorLR, criticLR, stateDim, actionDim, full1Dim, full2Dim, tau, gamma, bufferSize, batchSize, layerNorm, name,
+                         grad_clip=grad_clip)
 
     def learn(self):  # TD3.py:201-260
         idx = self.buffer.sample_indices(self.batchSize)

@@ -100,6 +100,8 @@ def _bc_weight_kind(bc_weight_now):
 
 
 class HirlEngine:
+    grad_clip_flag = "--hirl_grad_clip"  # train_all's name for set_grad_clip (utils/checkpoint.py names it when a resume disagrees; SAC's is --grad_clip)
+
     def __init__(self, batch=128, lr_actor=1e-3, lr_critic=1e-3, tau=0.005, gamma=0.99, slope=0.0, use_bc=True,
                  device="cuda", group=None, layer_norm=True):
         self.device = torch.device(device)
@@ -174,6 +176,43 @@ class HirlEngine:
         # — through torch.distributed when a process group exists) so that its cost can be measured on one GPU (bench.py --staged)
         self.sharded_sequence = False
         self.exchange_name, self.xchg, self.rccl = "rccl", None, None
+        self.grad_clip, self.clip_ws = None, None  # set_grad_clip
+
+    def set_grad_clip(self, max_norm):
+        """torch.nn.utils.clip_grad_norm_(optimizer's parameters, max_norm) in front of each optimizer step — the critic's (both Q heads and their
+        LayerNorms: ONE norm) and the actor's — from now on: coef = min(1, max_norm / (norm + 1e-6)).  The reference's HIRL / TD3 have no clip: a
+        declared extension.  The clip lives in the stages of the update (_stage_critic_step, _stage_actor_step, the local actor branch of
+        _learn_staged): hx_hirl_grad_norm, then hx_adam_clipped in place of hx_adam / hx_adam_mixed — so learn() and step_learn() take the staged
+        sequence at world 1 too, and a sharded rank clips the AVERAGED gradient (the norm launch follows the exchange).  Any update dtype, acting format,
+        use_bc and layer_norm.  None: the unclipped paths, call for call."""
+        if max_norm is None:
+            self.grad_clip = None
+            return
+        max_norm = float(max_norm)
+        if not max_norm > 0.0:
+            raise ValueError(f"grad_clip is a positive maximum norm, got {max_norm}")
+        if self.clip_ws is None:
+            self.clip_ws = torch.zeros(int(_lib.load().hx_hirl_clip_floats()), dtype=torch.float32, device=self.device)
+        self.grad_clip = max_norm
+
+    def grad_norms_host(self):
+        """((norm_critic, norm_actor), (coef_critic, coef_actor)) of the last clipped steps: the norms BEFORE clipping.  Synchronises."""
+        if self.clip_ws is None:
+            raise _lib.HxError("grad_norms_host: no clip was ever set (set_grad_clip)")
+        v = self.clip_ws[:4].tolist()
+        return tuple(v[:2]), tuple(v[2:])
+
+    def _adam(self, which, step, scale, w_kind, w_given, warm, batch, msg=None):
+        """one optimizer step of the staged update: hx_adam / hx_adam_mixed, or under set_grad_clip the norm launch and the clipped step"""
+        nets, hyper, st = ctypes.byref(self.nets), ctypes.byref(self.hyper), _lib.stream_ptr()
+        if self.grad_clip is not None:
+            ws = self.clip_ws.data_ptr()
+            _lib.call("hx_hirl_grad_norm", nets, hyper, which & 15, w_kind, w_given, warm, batch, msg, ws, st)
+            _lib.call("hx_adam_clipped", nets, hyper, which, step, scale, w_kind, w_given, warm, batch, msg, self.grad_clip, ws, st)
+        elif msg is not None:
+            _lib.call("hx_adam_mixed", nets, hyper, which >> 4, step, scale, w_kind, w_given, warm, batch, msg, st)
+        else:
+            _lib.call("hx_adam", nets, hyper, which, step, scale, w_kind, w_given, warm, batch, st)
 
     # ---- parameters ------------------------------------------------------------------------------------------
     def load_params(self, actor, critic, bc_actor=None, hard_update_targets=True):
@@ -477,7 +516,7 @@ class HirlEngine:
         nets, hyper = ctypes.byref(self.nets), ctypes.byref(self.hyper)
         w_kind, w_given = _bc_weight_kind(bc_weight_now)
         actor_phase, do_polyak = self._begin_call()
-        if not self.staged:
+        if not self.staged and self.grad_clip is None:
             _lib.call("hx_hirl_learn_sampled", nets, ctypes.byref(batch), hyper, smp, self.critic_step, int(actor_phase), self.actor_step,
                       int(do_polyak), w_kind, w_given, float(bc_warm_up_weight), st)
         else:
@@ -518,16 +557,14 @@ class HirlEngine:
             else:                # one rank running the staged sequence (tests): the weight is known locally, bit-identical to the one-call path
                 B, st, nets, hyper = self.batch, _lib.stream_ptr(), ctypes.byref(self.nets), ctypes.byref(self.hyper)
                 _lib.call("hx_hirl_actor_wgrad", nets, hyper, B, B, w_kind, w_given, float(bc_warm_up_weight), st)
-                _lib.call("hx_adam", nets, hyper, 1 | (16 if do_polyak else 0), self.actor_step, 1.0 / self.world, w_kind, w_given,
-                          float(bc_warm_up_weight), B, st)
+                self._adam(1 | (16 if do_polyak else 0), self.actor_step, 1.0 / self.world, w_kind, w_given, float(bc_warm_up_weight), B)
 
     def _stage_critic_step(self, summed, do_polyak, world=None):
         """the critics' Adam step on the SUMMED gradient (`summed`: a tensor), scaled by 1 / world"""
         own_critic = self.grad_critic.data_ptr()
         self.nets.grad_critic = summed.data_ptr()
         pk = 16 if do_polyak else 0  # + 16: soft_update of the target in the same launch (nothing reads it in between)
-        _lib.call("hx_adam", ctypes.byref(self.nets), ctypes.byref(self.hyper), 0 | pk, self.critic_step, 1.0 / (self.world if world is None else world),
-                  0, 0.0, 0.0, self.batch, _lib.stream_ptr())
+        self._adam(0 | pk, self.critic_step, 1.0 / (self.world if world is None else world), 0, 0.0, 0.0, self.batch)
         self.nets.grad_critic = own_critic
 
     def _stage_actor_backward(self, batch, w_kind):
@@ -546,8 +583,8 @@ class HirlEngine:
     def _stage_actor_step(self, summed, do_polyak, w_kind, w_given, bc_warm_up_weight, world=None):
         """the actor's Adam step from the SUMMED message: w from the global count over batch x world rows, gradient scaled by 1 / world"""
         world = self.world if world is None else world
-        _lib.call("hx_adam_mixed", ctypes.byref(self.nets), ctypes.byref(self.hyper), int(do_polyak), self.actor_step, 1.0 / world, w_kind, w_given,
-                  float(bc_warm_up_weight), self.batch * world, summed.data_ptr(), _lib.stream_ptr())
+        self._adam(1 | (16 if do_polyak else 0), self.actor_step, 1.0 / world, w_kind, w_given, float(bc_warm_up_weight), self.batch * world,
+                   summed.data_ptr())
 
     def step_learn(self, env, expert=None, bc_table=None, n_main=None, act_noise=None, act_sigma=0.0, act_seed=0, out=None, sample_seed=0,
                    smooth_sigma=0.2, bc_weight_now=0.0, bc_warm_up_weight=0.0):
@@ -648,7 +685,7 @@ class HirlEngine:
         self._front_enqueued = True  # from here on a failure leaves the device AHEAD of any rollback (step_learn)
         env.steps_issued += 1
         nxt_draw, nxt_tiles = draw(nxt, self.sample_calls + 1), tiles_of(nxt)
-        if not self.staged:
+        if not self.staged and self.grad_clip is None:
             _lib.call("hx_hirl_learn_back", nets, ctypes.byref(batch), hyper, self.critic_step, int(actor_phase), self.actor_step, int(do_polyak), w_kind, w_given,
                       float(bc_warm_up_weight), ctypes.byref(nxt_draw), ctypes.byref(nxt_tiles), with_c, st)
         else:  # a sharded rank: the same front launch (every rank draws from its own ring), then the stages with the exchanges in between

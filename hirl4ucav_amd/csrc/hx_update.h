@@ -4,6 +4,7 @@
 //
 //   hx_fwdbwd.hip   fwd_l2_kernel, bwd_l2_kernel            launch_fwd, launch_bwd
 //   hx_wgrad.hip    wgrad_kernel, adam_kernel, polyak_kernel launch_wg, launch_adam, launch_polyak; hx_adam*, hx_polyak, hx_sac_adam
+//   hx_hirl_clip.hip  hirl_grad_sumsq_kernel, hirl_adam_clip_kernel  hx_hirl_grad_norm, hx_adam_clipped (the clip in front of hx_adam / hx_adam_mixed)
 //   hx_act.hip      act_fused_kernel + the W2 image packers  hx_actor_act[_step], hx_sac_act[_step], hx_pack_w2_*
 //   hx_sampler.hip  sample_kernel                            hx_sample_batch
 //   hx_sac.hip      gauss_head / q_select / policy_dout      hx_sac_critic_*, hx_sac_policy_grads
@@ -817,6 +818,14 @@ struct AdamArgs {
     const float* countf;
     const uint32_t* guard;  // nullptr, or a word that must be 0 for the step to happen (HxNets.xchg_status: a failed exchange)
 };
+// the BC weight of this call (HIRL.py:299-308); countf: the count words of the all-reduced message (the global count from its digit words)
+__device__ __forceinline__ float adam_w(const AdamArgs& A) {
+    if (A.countf && A.w_kind == 1) {
+        const float w = __builtin_fmaf((float)count_from_digits(A.countf), A.inv_batch, A.warm);  // one rounding, as effective_w's count * inv_batch + warm compiles
+        return w > 1.0f ? 1.0f : w;
+    }
+    return effective_w(A.w_kind, A.w_given, A.warm, A.inv_batch, A.soft_count, A.wstate);
+}
 // The optimizer step on the float4 at word i of the flat buffers (16-B aligned, i + 4 <= n) with everything that follows it: g4 is the gradient as it
 // enters Adam (combined, scaled, clipped by the caller).  p, m, v stepped and stored; then the images of a W2 this float4 lies in (W2 starts at a
 // multiple of 4 floats: a float4 is inside or outside) — bf16 (and the other two parts of the exact split), fp32 —, the target's Polyak step, and on
@@ -977,6 +986,70 @@ inline int sac_adam_fill(AdamArgs& A, const HxSacNets* N, const HxHyper* Hy, int
         A.target_entropy = target_entropy;
         A.alpha_step_size = A.step_size;  // alpha_optim runs at the policy's learning rate
     }
+    return 0;
+}
+
+// the AdamArgs of a HIRL / TD3 optimizer step (which 0 critic, 1 actor with actor_loss / bc_weight bookkeeping, 2 the actor alone; polyak: soft_update
+// of that network's target in the same launch) with every live image of the W2 it changes; msg: NULL, or the merged actor message
+// [dL_rl | dL_bc | count ...] of a sharded rank.  hx_adam, hx_adam_mixed (who / who_msg name them) and the clipped step (hx_hirl_clip.hip) fill alike.
+inline int hirl_adam_fill(AdamArgs& A, const HxNets* N, const HxHyper* Hy, int which, bool polyak, int step, float grad_scale, int w_kind, float w_given,
+                          float warm, int batch, const float* msg, const char* who, const char* who_msg) {
+    A.n = which == 0 ? 2 * kQ.padded() : kActor.size();
+    A.p = which == 0 ? N->critic : N->actor;
+    A.g = which == 0 ? N->grad_critic : N->grad_actor;
+    A.m = which == 0 ? N->m_critic : N->m_actor;
+    A.v = which == 0 ? N->v_critic : N->v_actor;
+    set_adam_scalars(A, which == 0 ? Hy->lr_critic : Hy->lr_actor, step);
+    A.gscale = grad_scale;
+    A.finish_actor = which == 1;  // which == 2: the actor's Adam step alone (BC pre-training)
+    A.w_kind = w_kind; A.w_given = w_given; A.warm = warm; A.inv_batch = 1.0f / (batch > 0 ? batch : 1);
+    A.soft_count = N->soft_count; A.wstate = N->wstate; A.losses = N->losses; A.use_bc = Hy->use_bc;
+    if (polyak) {
+        A.target = which == 0 ? N->target_critic : N->target_actor;
+        A.tau = Hy->tau;
+    }
+    if (which != 0 && N->actor_w2_f32i) {
+        A.w2f = N->actor_w2_f32i;
+        A.w2_lo = kActor.W2();
+    }
+    if (which != 0 && N->actor_w2_bf16 && !N->w2_bf16_all) {
+        A.w2b = N->actor_w2_bf16;
+        A.w2_lo = kActor.W2();
+    }
+    if (which != 0 && N->actor_w2_x9) {
+        HX_REQUIRE(!N->actor_w2_bf16 && !N->w2_bf16_all, "%s: actor_w2_x9 excludes the plain bf16 images (one acting format at a time)", who);
+        A.w2b = N->actor_w2_x9;
+        A.w2b_x9 = 1;
+        A.w2_lo = kActor.W2();
+    }
+    if (uint16_t* im = N->w2_bf16_all) {  // bf16 update path: the images of every W2 this step changes (and of the target it moves) follow it
+        HX_REQUIRE(!N->actor_w2_bf16 || N->actor_w2_bf16 == im + IM_ACTOR * kImgElems, "%s: with w2_bf16_all set, actor_w2_bf16 must be NULL or its first image", who);
+        if (which == 0) {
+            A.nseg = 2;
+            for (int h = 0; h < 2; ++h) {
+                A.seg_lo[h] = h * kQ.padded() + kQ.W2();
+                A.seg_w2b[h] = im + (IM_C1 + h) * kImgElems;
+                A.seg_w2tb[h] = im + (IM_C1_T + h) * kImgElems;
+                A.seg_tgt_w2b[h] = im + (IM_TC1 + h) * kImgElems;
+            }
+        } else {
+            A.nseg = 1;
+            A.seg_lo[0] = kActor.W2();
+            A.seg_w2b[0] = im + IM_ACTOR * kImgElems;
+            A.seg_w2tb[0] = im + IM_ACTOR_T * kImgElems;
+            A.seg_tgt_w2b[0] = im + IM_TA * kImgElems;
+        }
+    }
+    A.guard = N->xchg_status;
+    if (msg) {  // merged actor message: [dL_rl | dL_bc | count ...]
+        HX_REQUIRE(which == 1 && (reinterpret_cast<uintptr_t>(msg) & 15u) == 0, "%s: actor step only, 16-byte aligned message", who_msg);
+        A.g = msg;
+        if (Hy->use_bc) {
+            A.g2 = msg + kActor.padded();
+            A.countf = msg + 2 * kActor.padded();
+        }
+    }
+    HX_REQUIRE((((uintptr_t)A.p | (uintptr_t)A.g | (uintptr_t)A.m | (uintptr_t)A.v) & 15u) == 0, "%s: buffers must be 16-byte aligned", who);
     return 0;
 }
 

@@ -903,15 +903,7 @@ __global__ __launch_bounds__(kWide) void wgrad2_kernel(WgArgsC AC) {
     }
 }
 
-// the BC weight of this call (HIRL.py:299-308); countf: the count words of the all-reduced message (the global count from its digit words)
-__device__ __forceinline__ float adam_w(const AdamArgs& A) {
-    if (A.countf && A.w_kind == 1) {
-        const float w = __builtin_fmaf((float)count_from_digits(A.countf), A.inv_batch, A.warm);  // one rounding, as effective_w's count * inv_batch + warm compiles
-        return w > 1.0f ? 1.0f : w;
-    }
-    return effective_w(A.w_kind, A.w_given, A.warm, A.inv_batch, A.soft_count, A.wstate);
-}
-
+// (the BC weight of the call: adam_w, hx_update.h)
 __global__ __launch_bounds__(kThreads) void adam_kernel(AdamArgs A) {
     if (A.guard && __hip_atomic_load(A.guard, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u) return;  // failed exchange: fail-stop
     if (A.alpha_state && blockIdx.x == 0 && threadIdx.x == 0)  // a SAC policy step: the log-alpha step with the mean entropy
@@ -1042,62 +1034,7 @@ static int adam_impl(const HxNets* N, const HxHyper* Hy, int32_t which, int32_t 
     which &= 15;
     HX_REQUIRE(N && Hy && step >= 1 && which >= 0 && which <= 2, "hx_adam: bad arguments");
     AdamArgs A{};
-    A.n = which == 0 ? 2 * kQ.padded() : kActor.size();
-    A.p = which == 0 ? N->critic : N->actor;
-    A.g = which == 0 ? N->grad_critic : N->grad_actor;
-    A.m = which == 0 ? N->m_critic : N->m_actor;
-    A.v = which == 0 ? N->v_critic : N->v_actor;
-    set_adam_scalars(A, which == 0 ? Hy->lr_critic : Hy->lr_actor, step);
-    A.gscale = grad_scale;
-    A.finish_actor = which == 1;  // which == 2: the actor's Adam step alone (BC pre-training)
-    A.w_kind = w_kind; A.w_given = w_given; A.warm = warm; A.inv_batch = 1.0f / (batch > 0 ? batch : 1);
-    A.soft_count = N->soft_count; A.wstate = N->wstate; A.losses = N->losses; A.use_bc = Hy->use_bc;
-    if (polyak) {
-        A.target = which == 0 ? N->target_critic : N->target_actor;
-        A.tau = Hy->tau;
-    }
-    if (which != 0 && N->actor_w2_f32i) {
-        A.w2f = N->actor_w2_f32i;
-        A.w2_lo = kActor.W2();
-    }
-    if (which != 0 && N->actor_w2_bf16 && !N->w2_bf16_all) {
-        A.w2b = N->actor_w2_bf16;
-        A.w2_lo = kActor.W2();
-    }
-    if (which != 0 && N->actor_w2_x9) {
-        HX_REQUIRE(!N->actor_w2_bf16 && !N->w2_bf16_all, "hx_adam: actor_w2_x9 excludes the plain bf16 images (one acting format at a time)");
-        A.w2b = N->actor_w2_x9;
-        A.w2b_x9 = 1;
-        A.w2_lo = kActor.W2();
-    }
-    if (uint16_t* im = N->w2_bf16_all) {  // bf16 update path: the images of every W2 this step changes (and of the target it moves) follow it
-        HX_REQUIRE(!N->actor_w2_bf16 || N->actor_w2_bf16 == im + IM_ACTOR * kImgElems, "hx_adam: with w2_bf16_all set, actor_w2_bf16 must be NULL or its first image");
-        if (which == 0) {
-            A.nseg = 2;
-            for (int h = 0; h < 2; ++h) {
-                A.seg_lo[h] = h * kQ.padded() + kQ.W2();
-                A.seg_w2b[h] = im + (IM_C1 + h) * kImgElems;
-                A.seg_w2tb[h] = im + (IM_C1_T + h) * kImgElems;
-                A.seg_tgt_w2b[h] = im + (IM_TC1 + h) * kImgElems;
-            }
-        } else {
-            A.nseg = 1;
-            A.seg_lo[0] = kActor.W2();
-            A.seg_w2b[0] = im + IM_ACTOR * kImgElems;
-            A.seg_w2tb[0] = im + IM_ACTOR_T * kImgElems;
-            A.seg_tgt_w2b[0] = im + IM_TA * kImgElems;
-        }
-    }
-    A.guard = N->xchg_status;
-    if (msg) {  // merged actor message: [dL_rl | dL_bc | count ...]
-        HX_REQUIRE(which == 1 && (reinterpret_cast<uintptr_t>(msg) & 15u) == 0, "hx_adam_mixed: actor step only, 16-byte aligned message");
-        A.g = msg;
-        if (Hy->use_bc) {
-            A.g2 = msg + kActor.padded();
-            A.countf = msg + 2 * kActor.padded();
-        }
-    }
-    HX_REQUIRE((((uintptr_t)A.p | (uintptr_t)A.g | (uintptr_t)A.m | (uintptr_t)A.v) & 15u) == 0, "hx_adam: buffers must be 16-byte aligned");
+    if (int rc = hirl_adam_fill(A, N, Hy, which, polyak, step, grad_scale, w_kind, w_given, warm, batch, msg, "hx_adam", "hx_adam_mixed")) return rc;
     launch_adam(A, (hipStream_t)stream);
     HX_CHECK_LAUNCH("hx_adam");
     return 0;

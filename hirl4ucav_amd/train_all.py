@@ -458,10 +458,12 @@ def check_agent_flags(run):
     run.per_new = getattr(config, "per_new", "max")  # how a step's rows get their first priority: at pmax, or at a TD error of their own (agent.py:234-246)
     run.multi_step = int(getattr(config, "multi_step", 1))  # SacAgent(multi_step=n): truncated n-step returns (utils.buffer.NStepInserter)
     run.grad_clip, run.fixed_alpha = getattr(config, "grad_clip", None), getattr(config, "fixed_alpha", None)  # SacAgent(grad_clip=c) / (entropy_tuning=False, ent_coef=x)
+    if not run.sac:  # HIRL / TD3: --hirl_grad_clip, an extension (HirlEngine.set_grad_clip); --grad_clip itself is refused for them (clip_refusal)
+        run.grad_clip = getattr(config, "hirl_grad_clip", None)
     # the reference's two sampling switches (HIRL.py:184-185): success rows of the replay drawn 10 : 1, one fire row forced into the BC minibatch
     run.buffer_upsample, run.expert_upsample = bool(getattr(config, "buffer_upsample", False)), bool(getattr(config, "expert_upsample", False))
     run.upsampler = None
-    for refusal in (per_refusal, nstep_refusal, clip_refusal, upsample_refusal, expert_online_refusal, expert_branch_refusal, expert_floor_refusal):  # (per_refusal without --per: --per_new td on its own)
+    for refusal in (per_refusal, nstep_refusal, clip_refusal, hirl_clip_refusal, upsample_refusal, expert_online_refusal, expert_branch_refusal, expert_floor_refusal):  # (per_refusal without --per: --per_new td on its own)
         if refusal(config, world):
             raise SystemExit("train_all: " + refusal(config, world))
     run.batch = BATCH  # train_all.py:190-208
@@ -520,6 +522,8 @@ def build_engine(run):
     else:
         eng = E.HirlEngine(batch=run.batch, slope=0.0 if run.hirl else 0.01, use_bc=run.hirl, device=run.device)
         eng.load_params(init_actor_state_dict(), init_critic_state_dict(), init_actor_state_dict() if run.hirl else None)
+        if run.grad_clip is not None:  # an extension (the reference's HIRL / TD3 have no clip): clip_grad_norm_ once per optimizer, DESIGN.md section 5
+            eng.set_grad_clip(run.grad_clip)
     run.eng = eng
 
 
@@ -731,6 +735,9 @@ def choose_loop(run):
             which += f" ({' '.join('--' + flag for flag in upsampled)}: the upsampled draw is a launch of its own between the acting launch and learn(), after the step's insert)"
         if sac and run.grad_clip is not None and not run.per:  # the clipped update is the staged sequence (gradients -> norm -> clipped step): its first launch is its own
             which += " (--grad_clip: the clipped update runs as stages, which have no front form)"
+        if not sac and run.grad_clip is not None:  # HIRL / TD3: the stages run behind the front launch as they do on a sharded rank
+            which += (f" (--hirl_grad_clip {run.grad_clip:g}: the clipped update runs as stages" +
+                      (" behind the front launch" if run.front else "") + ", a norm launch in front of each optimizer step)")
         print(f"vector loop: {which}" + (f" ({world} ranks share a GPU: the front launch is for one process per GPU)" if (shared_gpu and config.loop == "front") else ""),
               flush=True)
     # The front launch's in-launch waits (launch B for launch A's rows, launch C for both) assume that the workgroups of ONE launch start in index order —
@@ -792,8 +799,8 @@ def after_env_step(run, step):
 
 
 def log_step_scalars(run, step):
-    """Behind a step's learn(), every log_rate steps on rank 0.  (The front forms write neither grad norms nor stats/per_*: they never run with
-    --grad_clip or --per, choose_loop.)"""
+    """Behind a step's learn(), every log_rate steps on rank 0.  (SAC's front form writes neither grad norms nor stats/per_*: it never runs with
+    --grad_clip or --per, choose_loop; HIRL's and TD3's front form keeps its clip, --hirl_grad_clip, and writes their norms.)"""
     writer, eng = run.writer, run.eng
     if writer is None or step % run.log_rate != 0:
         return
@@ -806,6 +813,9 @@ def log_step_scalars(run, step):
         log_imitative(writer, eng, at)
     if run.sac and run.grad_clip is not None:
         for tag, v in zip(("q1", "q2", "policy"), eng.grad_norms_host()[0]):
+            writer.add_scalar("stats/grad_norm_" + tag, v, at)
+    if not run.sac and run.grad_clip is not None:  # (the actor's norm is that of the last actor call: every second learn())
+        for tag, v in zip(("critic", "actor"), eng.grad_norms_host()[0]):
             writer.add_scalar("stats/grad_norm_" + tag, v, at)
     if run.per:
         writer.add_scalar("stats/per_beta", run.replay.beta, at)
@@ -1226,7 +1236,7 @@ def clip_refusal(config, world=1):
     flag = "--grad_clip" if clip is not None else "--fixed_alpha"
     if config.agent != "SAC":
         return (f"{flag} goes with --agent SAC (gradient clipping and the fixed entropy coefficient are SacAgent's: SAC/agent.py:108-110, 310-320), "
-                f"not --agent {config.agent}")
+                f"not --agent {config.agent}" + (": HIRL and TD3 clip with --hirl_grad_clip C" if clip is not None and config.agent in ("HIRL", "TD3") else ""))
     if clip is not None and not (clip > 0 and math.isfinite(clip)):
         return f"--grad_clip {clip}: the maximum gradient norm is a positive number"
     if fixed is not None and not (fixed >= 0 and math.isfinite(fixed)):
@@ -1236,11 +1246,27 @@ def clip_refusal(config, world=1):
     return None
 
 
+def hirl_clip_refusal(config, world=1):
+    """why `--hirl_grad_clip` cannot run as asked, or None.  (A flag of its own: `--grad_clip` is SacAgent's keyword and stays refused for every other
+    agent.)  HirlEngine.set_grad_clip puts the clip into the stages of the update, behind any exchange: both loop forms, every --dtype, any number of ranks."""
+    clip = getattr(config, "hirl_grad_clip", None)
+    if clip is None:
+        return None
+    if config.agent == "BC":
+        return ("--hirl_grad_clip goes with --agent HIRL or TD3, not --agent BC (behaviour cloning steps its actor inside ONE fused call, hx_bc_train_actor: "
+                "there is no launch boundary between its gradient and its step for a norm to sit at)")
+    if config.agent not in ("HIRL", "TD3"):
+        return f"--hirl_grad_clip goes with --agent HIRL or TD3, not --agent {config.agent}: SAC clips with --grad_clip C (SacAgent(grad_clip=C))"
+    if not (clip > 0 and math.isfinite(clip)):
+        return f"--hirl_grad_clip {clip}: the maximum gradient norm is a positive number"
+    return None
+
+
 def parse_args(argv=None):
     """parser().parse_args with the cross-flag checks that are argparse errors"""
     p = parser()
     cfg = p.parse_args(argv)
-    why = per_refusal(cfg) or clip_refusal(cfg) or nstep_refusal(cfg) or mixed_refusal(cfg) or upsample_refusal(cfg) or expert_online_refusal(cfg) or expert_branch_refusal(cfg) or expert_floor_refusal(cfg)
+    why = per_refusal(cfg) or clip_refusal(cfg) or hirl_clip_refusal(cfg) or nstep_refusal(cfg) or mixed_refusal(cfg) or upsample_refusal(cfg) or expert_online_refusal(cfg) or expert_branch_refusal(cfg) or expert_floor_refusal(cfg)
     if why:
         p.error(why)
     if cfg.type == "ISAC" and cfg.agent != "SAC":
@@ -1349,6 +1375,11 @@ def parser():
     p.add_argument("--grad_clip", type=float, default=None, help="SAC: clip each network's gradient (Q1, Q2, policy) to this global L2 norm before its Adam step "
                                                                  "(SacAgent(grad_clip=C), SAC/utils.py:15-21); one GPU; the vector loop runs in the reference's "
                                                                  "order.  Stored in the snapshot: --resume refuses another value")
+    p.add_argument("--hirl_grad_clip", type=float, default=None, metavar="C",
+                   help="HIRL / TD3 (an extension, the reference has none): clip_grad_norm_ once per optimizer — the critic's two heads and LayerNorms under ONE "
+                        "norm, the whole actor — in front of its Adam step, in both loop forms, at every --dtype and under --gpus N (the norm of the averaged "
+                        "gradient); norms under stats/grad_norm_critic / _actor.  Not --agent BC; SAC has --grad_clip.  Stored in the snapshot: --resume refuses "
+                        "another value")
     p.add_argument("--fixed_alpha", type=float, default=None, help="SAC: a constant entropy coefficient alpha = X and no log-alpha optimiser "
                                                                    "(SacAgent(entropy_tuning=False, ent_coef=X), SAC/agent.py:108-110).  Stored in the snapshot: "
                                                                    "--resume refuses another value")

@@ -74,7 +74,8 @@ def load_engine_state(eng, st):
         raise ValueError(f"snapshot was written under --per_new {st.get('per_new_rows', 'max')}, this engine runs under --per_new "
                          f"{getattr(eng, 'per_new_rows', 'max')}: resume with the flag the run was started with")
     if st.get("grad_clip") != getattr(eng, "grad_clip", None):
-        raise ValueError(f"snapshot was written under --grad_clip {st.get('grad_clip')}, this engine clips at {getattr(eng, 'grad_clip', None)}: "
+        flag = getattr(eng, "grad_clip_flag", "--grad_clip")  # (HirlEngine: --hirl_grad_clip)
+        raise ValueError(f"snapshot was written under {flag} {st.get('grad_clip')}, this engine clips at {getattr(eng, 'grad_clip', None)}: "
                          "resume with the flag the run was started with")
     now_fixed = None if getattr(eng, "entropy_tuning", True) else float(eng.ent_coef)
     if st.get("fixed_alpha") != now_fixed:

@@ -89,8 +89,9 @@ const char* hx_last_error(void);
  * pointers (w2_f32i, w2_x9, w2_bf16) after the network; their _f32i / _x9 / _bf16 variants, the `ws` argument and hx_act_workspace_floats are gone.
  * 128: expert branches: one pilot step per pick fills the online region of the labelled expert ring (hx_pilot_branch).
  * 129: expert branches of up to H steps: resident branches in a device workspace, one step per call (hx_pilot_branch_steps,
- * hx_branch_workspace_bytes). */
-#define HX_ABI_VERSION 129
+ * hx_branch_workspace_bytes).
+ * 130: gradient-norm clipping for HIRL and TD3 (hx_hirl_clip_floats, hx_hirl_clip_shape, hx_hirl_grad_norm, hx_adam_clipped). */
+#define HX_ABI_VERSION 130
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -319,6 +320,27 @@ int64_t hx_actor_message_floats(void);
 int hx_hirl_actor_wgrad_split(const HxNets* nets, const HxHyper* hyper, int32_t batch, float* msg, void* stream);
 int hx_adam_mixed(const HxNets* nets, const HxHyper* hyper, int32_t polyak, int32_t step, float grad_scale, int32_t w_kind, float w_given,
                   float warm, int32_t batch /* global */, const float* msg, void* stream);
+/* Gradient-norm clipping for HIRL and TD3: torch.nn.utils.clip_grad_norm_(optimizer's parameters, max_norm) in front of each optimizer step, two
+ * launches per step.  The reference's agents have no clip (a declared extension); an optimizer covers ALL of its parameters — both Q heads and the
+ * LayerNorm weights for the critic (ONE norm), the whole actor —, never the padding behind a block's parameters.
+ *   hx_hirl_grad_norm  one launch: workgroup c of a block writes the sum of squares of its fixed 4,096-word chunk — a fixed order, no atomics, no
+ *                      workgroup waits for another — into clip_ws (hx_hirl_clip_floats() floats, 16-byte aligned).  which 0: nets->grad_critic (what
+ *                      hx_adam(0) steps on: after an exchange, the summed gradient); which 1: nets->grad_actor, or with msg the merged message
+ *                      [dL_rl | dL_bc | tail] squared AFTER mixing w dL_bc + (1 - w) dL_rl with hx_adam_mixed's own w (TD3: the dL_rl half alone)
+ *   hx_adam_clipped    hx_adam's (msg NULL) / hx_adam_mixed's (msg) step on (g * grad_scale) * coef: every workgroup re-adds the partial sums in the same
+ *                      fixed order, norm = sqrt(sum) * grad_scale (the norm of the AVERAGED gradient on a sharded rank), coef = min(1, max_norm /
+ *                      (norm + 1e-6)); coef == 1 leaves hx_adam's bits.  which 0 | 1, + 16 as hx_adam; which 2 and a msg with which 0 are refused.
+ *                      Honours nets->xchg_status like hx_adam.  clip_ws[0..1] <- the norms (critic, actor), clip_ws[2..3] <- the coefficients.
+ * w_kind / w_given / warm / batch: as hx_adam / hx_adam_mixed (read in the message form only by hx_hirl_grad_norm). */
+int64_t hx_hirl_clip_floats(void);
+/* shape[0..7] (host) <- float4 per thread, words per chunk, partials one wave re-adds at most, chunks of a Q head, chunks of the actor, the depth in
+ * additions (squares included) of the critic's and of the actor's sum, the word of clip_ws where the partials begin (Q head 0 | Q head 1 | actor,
+ * shape[2] words each) */
+int hx_hirl_clip_shape(int32_t* shape8);
+int hx_hirl_grad_norm(const HxNets* nets, const HxHyper* hyper, int32_t which, int32_t w_kind, float w_given, float warm, int32_t batch,
+                      const float* msg, float* clip_ws, void* stream);
+int hx_adam_clipped(const HxNets* nets, const HxHyper* hyper, int32_t which, int32_t step, float grad_scale, int32_t w_kind, float w_given,
+                    float warm, int32_t batch, const float* msg, float max_norm, float* clip_ws, void* stream);
 /* BC.Agent.train_actor (hirl/agents/BC.py:160-185): one behaviour-cloning step on batch->bc_rows: loss = mse(actor(s_bc),
  * a_bc), backward, actor.optimizer.step(); losses[2] receives the loss.  hyper->slope = 0.01 gives BC.py's LeakyReLU actor.
  * (hx_adam's which = 2 is the actor step without HIRL's actor_loss / bc_weight bookkeeping.) */

@@ -7,7 +7,8 @@ ROOT is a built checkout: this one, or the parent commit's for the A/B (its own 
 tree, which cannot be done across an ABI bump).  One process = one configuration: alternate the processes (parent, this tree without the flag, with it) on
 one box and compare the medians.  The step is train_all's own step_front_hirl / step_reference with after_env_step behind the acting launch, 500 warm-up
 steps, then STEP_W (5) windows of STEP_K (4,000) steps, each between two device synchronisations on the host clock.  Prints one RESULT line.  Under
-`rocprofv3 --kernel-trace --stats` (a run of its own, STEP_K=1000 STEP_W=1) the per-kernel durations come from the same step."""
+`rocprofv3 --kernel-trace --stats` (a run of its own, STEP_K=1000 STEP_W=1) the per-kernel durations come from the same step.  STEP_STAGED=1: the update
+runs as stages (HirlEngine.staged), the form --hirl_grad_clip takes (profiles/hirl_clip_cost.txt)."""
 import json
 import os
 import sys
@@ -30,6 +31,8 @@ if run.writer is not None:  # no logging inside the timed windows
     run.writer.close()
 run.writer = None
 assert run.front == (loop == "front")
+if os.environ.get("STEP_STAGED") == "1":  # the update as the stages of a sharded rank (one rank: the exchanges are no-ops): what --hirl_grad_clip's step is measured against
+    run.eng.staged = True
 step = (lambda i, w: T.step_front_hirl(run, i, w, 0.0)) if run.front else (lambda i, w: T.step_reference(run, i, w, 0.0))
 
 
