@@ -101,6 +101,7 @@ def _bc_weight_kind(bc_weight_now):
 
 class HirlEngine:
     grad_clip_flag = "--hirl_grad_clip"  # train_all's name for set_grad_clip (utils/checkpoint.py names it when a resume disagrees; SAC's is --grad_clip)
+    per_flag = "--hirl_per"  # ... and for set_prioritized (SAC's is --per)
 
     def __init__(self, batch=128, lr_actor=1e-3, lr_critic=1e-3, tau=0.005, gamma=0.99, slope=0.0, use_bc=True,
                  device="cuda", group=None, layer_norm=True):
@@ -177,6 +178,7 @@ class HirlEngine:
         self.sharded_sequence = False
         self.exchange_name, self.xchg, self.rccl = "rccl", None, None
         self.grad_clip, self.clip_ws = None, None  # set_grad_clip
+        self.prioritized, self.per_calls, self._weights, self._errors, self._per_n_main = None, 0, None, None, 0  # set_prioritized
 
     def set_grad_clip(self, max_norm):
         """torch.nn.utils.clip_grad_norm_(optimizer's parameters, max_norm) in front of each optimizer step — the critic's (both Q heads and their
@@ -194,6 +196,51 @@ class HirlEngine:
         if self.clip_ws is None:
             self.clip_ws = torch.zeros(int(_lib.load().hx_hirl_clip_floats()), dtype=torch.float32, device=self.device)
         self.grad_clip = max_norm
+
+    def set_prioritized(self, replay, new_rows="max"):
+        """Prioritized replay for HIRL / TD3 (a declared extension: include/hirl4ucav.h "Prioritized replay for HIRL / TD3").  replay: the
+        utils.buffer.PrioritizedReplay the env inserts into.  From now on sample() on it runs the plain draw and then redraws rows [0, n_main) by
+        priority, keeping their importance weights (expert rows [n_main, B) stay as drawn and weigh 1; the BC minibatch is untouched); learn() takes
+        the staged sequence with hx_hirl_critic_grads_weighted in front — the weights through the critic loss only, the actor half unweighted — and
+        hands |Q1(s, a) - y| of rows [0, n_main) back as their new priorities (replay.update).  Everything enqueues; no host sync.  fp32 and bf16
+        update, any use_bc / layer_norm / slope, with set_grad_clip; one GPU; the reference-order step only (step_learn refuses); not with
+        set_upsample.  The caller marks new rows (replay.mark_new) behind every acting launch.  None: the unweighted paths, call for call."""
+        if replay is None:
+            self.prioritized = None
+            return
+        from ..utils.buffer import PrioritizedReplay
+
+        if new_rows != "max":
+            raise ValueError(f"set_prioritized: HIRL / TD3 rows enter at the running maximum priority (new_rows='max'); scoring rows at insert "
+                             f"(new_rows={new_rows!r}) is SacEngine's")
+        if not isinstance(replay, PrioritizedReplay):
+            raise TypeError("set_prioritized takes a utils.buffer.PrioritizedReplay")
+        if self.world > 1 or self.sharded_sequence:
+            raise _lib.HxError("prioritized replay runs on one GPU (priorities and block sums are not exchanged between ranks): run it with --gpus 1")
+        if self.upsampler is not None or self.fire_idx is not None:
+            raise _lib.HxError("set_prioritized does not go with set_upsample (both redraw the same rows; untested together)")
+        self.prioritized = replay
+        if self._weights is None:
+            self._weights = torch.ones(self.batch, dtype=torch.float32, device=self.device)
+            self._errors = torch.zeros(self.batch, dtype=torch.float32, device=self.device)
+        self._per_n_main = 0
+
+    def set_weights(self, weights, n_main, idx=None):
+        """Under set_prioritized, for a minibatch from assemble(): the importance weights of rows [0, n_main) (the rest weigh 1) for the next learn().
+        idx: those rows' replay slots (int32, what assemble() was given) — learn() writes their new priorities there; None: what `_idx` holds."""
+        if self.prioritized is None:
+            raise _lib.HxError("set_weights goes with set_prioritized")
+        n_main = int(n_main)
+        if not 0 <= n_main <= self.batch:
+            raise ValueError(f"set_weights: n_main is 0..batch ({self.batch}), got {n_main}")
+        if n_main:
+            w = torch.as_tensor(weights, device=self.device).to(torch.float32).reshape(-1)
+            if w.numel() < n_main:
+                raise ValueError(f"set_weights: {n_main} weighted rows, {w.numel()} weights")
+            self._weights[:n_main].copy_(w[:n_main])
+            if idx is not None:
+                self._idx[:n_main].copy_(torch.as_tensor(idx, device=self.device).to(torch.int32).reshape(-1)[:n_main])
+        self._per_n_main = n_main
 
     def grad_norms_host(self):
         """((norm_critic, norm_actor), (coef_critic, coef_actor)) of the last clipped steps: the norms BEFORE clipping.  Synchronises."""
@@ -450,18 +497,28 @@ class HirlEngine:
         (defer=True is ignored); learn() is untouched.  Both None: every path as before."""
         if fire_idx is not None and (fire_idx.dtype != torch.int32 or fire_idx.numel() == 0 or not fire_idx.is_contiguous()):
             raise _lib.HxError("set_upsample: fire_idx is a contiguous, non-empty int32 tensor (the expert table has no fire row?)")
+        if self.prioritized is not None and (upsampler is not None or fire_idx is not None):
+            raise _lib.HxError("set_upsample does not go with set_prioritized (both redraw the same rows; untested together)")
         self.upsampler, self.fire_idx = upsampler, fire_idx
 
-    def sample(self, replay, expert=None, bc_table=None, n_main=None, seed=0, sigma=0.2, defer=False):
+    def sample(self, replay, expert=None, bc_table=None, n_main=None, seed=0, sigma=0.2, defer=False, u=None):
         """Draw AND gather the next minibatch on the device (no host sync): UniformMemory.sample (buffer.py:38-48), the
         buffer/expert mix and np.random.choice of HIRL.py:223-251, torch.normal(0, 0.2) of HIRL.py:265.
         defer=True: nothing is launched now — the next learn() draws and gathers inside its first launch (hx_hirl_learn_sampled:
-        the same indices, noise, tiles and update bit for bit, one launch less); the returned tensors are filled by that learn()."""
+        the same indices, noise, tiles and update bit for bit, one launch less); the returned tensors are filled by that learn().
+        Under set_prioritized: the plain draw (defer is ignored), then rows, indices and weights [0, n_main) are redrawn by priority (hx_per_sample with a
+        call counter of its own, per_calls); u: injected uniforms [n_main] for that draw (parity tests)."""
         B = self.batch
+        per = self.prioritized
+        if per is not None and replay is not per:
+            raise _lib.HxError("sample: set_prioritized() was given another replay than the one sampled from (the one the env inserts into)")
+        if per is None and u is not None:
+            raise _lib.HxError("sample(u=...) injects the uniforms of the prioritized draw: set_prioritized first")
         self.sample_calls += 1
         ups = self.upsampler is not None or self.fire_idx is not None
-        if ups:
+        if ups or per is not None:
             defer = False  # the draw behind it rewrites the tiles: they have to exist
+        if ups:
             if self.upsampler is not None and self.upsampler.replay is not replay:
                 raise _lib.HxError("sample: the upsampler given to set_upsample() stands beside another replay ring")
             if self.fire_idx is not None and bc_table is None:
@@ -489,6 +546,16 @@ class HirlEngine:
             if nm > 0 or fire is not None:  # (an all-expert minibatch without the fire row: nothing to redraw)
                 draw_call(self.upsampler if nm > 0 else None, replay.ring, B, nm, self._idx, self.rows, None, seed, self.upsample_calls, fire,
                           bc_table if fire is not None else None, self._idx_bc if fire is not None else None, self.bc_rows if fire is not None else None)
+        if per is not None:
+            nm = B if n_main is None else int(n_main)
+            self._per_n_main = nm
+            if nm > 0:  # rows, indices and weights [0, n_main) again, by priority; the expert rows, the BC tile and the noise stay as drawn
+                self.per_calls += 1
+                if u is not None:
+                    u = torch.as_tensor(u, device=self.device).to(torch.float32).contiguous().reshape(-1)
+                    if u.numel() < nm:
+                        raise ValueError(f"sample: u holds {u.numel()} uniforms, n_main is {nm}")
+                per.sample_into(nm, self._idx, self._weights, self.rows, u=u, seed=seed, call=self.per_calls)
         return self._idx, self._idx_bc, self._noise
 
     def learn(self, noise=None, bc_weight_now=0.0, bc_warm_up_weight=0.0, before_exchange=None):
@@ -515,8 +582,19 @@ class HirlEngine:
         smp = ctypes.byref(pending[0]) if pending is not None else None
         nets, hyper = ctypes.byref(self.nets), ctypes.byref(self.hyper)
         w_kind, w_given = _bc_weight_kind(bc_weight_now)
+        per = self.prioritized
+        if per is not None and (self.world > 1 or self.sharded_sequence or pending is not None):
+            raise _lib.HxError("learn: prioritized replay runs on one GPU, without the sharded sequence, on a minibatch sample() has drawn")
         actor_phase, do_polyak = self._begin_call()
-        if not self.staged and self.grad_clip is None:
+        if per is not None:  # the staged sequence with the weighted TD head in front; the clip (set_grad_clip) lives in _adam as ever
+            actor_fwd = (2 if w_kind == 1 else 1) if actor_phase else 0
+            nm = self._per_n_main
+            grads = lambda: _lib.call("hx_hirl_critic_grads_weighted", nets, ctypes.byref(batch), hyper, self._weights.data_ptr(), nm,  # noqa: E731
+                                      self._errors.data_ptr(), actor_fwd, st)
+            self._learn_staged(grads, batch, actor_phase, do_polyak, w_kind, w_given, bc_warm_up_weight, before_exchange)
+            if nm > 0:  # memory.update_priority: the drawn replay rows' new priorities (expert indices never reach it)
+                per.update(self._idx[:nm], self._errors[:nm])
+        elif not self.staged and self.grad_clip is None:
             _lib.call("hx_hirl_learn_sampled", nets, ctypes.byref(batch), hyper, smp, self.critic_step, int(actor_phase), self.actor_step,
                       int(do_polyak), w_kind, w_given, float(bc_warm_up_weight), st)
         else:
@@ -606,6 +684,9 @@ class HirlEngine:
         if self.upsampler is not None or self.fire_idx is not None:
             raise _lib.HxError("step_learn: the front launch draws its minibatch uniformly inside the launch; set_upsample() goes with sample() + learn() "
                                "(the reference-order step)")
+        if self.prioritized is not None:
+            raise _lib.HxError("step_learn: set_prioritized() goes with sample() + learn() (the reference-order step): the front launch draws before the step's "
+                               "insert, so the priorities of the drawn rows could be written into overwritten slots")
         if self._front is None:
             buf = torch.zeros(96, dtype=torch.int32, device=self.device)
             self._front = (buf[0:64], buf[64:65])

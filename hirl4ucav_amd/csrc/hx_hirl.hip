@@ -99,7 +99,8 @@ static void make_launch_b(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy,
     F.images = N->w2_bf16_all;
 }
 // launch C: y, loss, dq, LN2 backward, dh1 for both heads
-static void make_launch_c(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy, BwdArgs& G) {
+// given: the head gradient was left in ws.dout by hirl_td_head_weighted_kernel (BM_GIVEN, bwd_l2<3>) instead of formed in the prologue
+static void make_launch_c(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy, BwdArgs& G, bool given = false) {
     const Mlp mQ{17, 1, Hy->no_layernorm ? 1 : 0};
     const int B = Bt->batch;
     Slot s[S_COUNT];
@@ -112,8 +113,8 @@ static void make_launch_c(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy,
     for (int h = 0; h < 2; ++h) {
         BwdJob& J = G.job[h];
         J = BwdJob{};
-        J.net = N->critic + h * mQ.padded(); J.m = mQ; J.ws = s[S_C1 + h]; J.rows = B; J.mode = BM_CRITIC_TD;
-        J.t1 = Head{tc1, mQ, s[S_TC1]}; J.t2 = Head{tc2, mQ, s[S_TC2]}; J.src = src; J.gamma = Hy->gamma;
+        J.net = N->critic + h * mQ.padded(); J.m = mQ; J.ws = s[S_C1 + h]; J.rows = B; J.mode = given ? BM_GIVEN : BM_CRITIC_TD;
+        if (!given) { J.t1 = Head{tc1, mQ, s[S_TC1]}; J.t2 = Head{tc2, mQ, s[S_TC2]}; J.src = src; J.gamma = Hy->gamma; }
         J.img_t = IM_C1_T + h;
     }
     G.images = N->w2_bf16_all;
@@ -133,14 +134,26 @@ static bool front_has_c(bool asked) {
 // heads: an actor call — 1: actor(s)'s head rides in launch D (its z2 rows are in S_API since launch A), 2: bc_actor(s)'s too (S_BCS, launch B); launch G
 // then reads the finished action rows (hx_hirl_actor_backward, fwd_done = 2).  Launch D changes the critic only.  HX_HEAD_RIDER=0: no riders.
 static int heads_of(const HxHyper* Hy, int actor_fwd) { return actor_fwd ? ((actor_fwd == 2 && Hy->use_bc) ? 2 : 1) : 0; }
+// given: prioritized replay (hx_hirl_critic_grads_weighted) — the TD head as a per-row kernel with the importance weights, then launch C with the head
+// gradient given
+struct TdGiven {
+    const float* weights; int n_weighted; float* errors;
+};
 static int critic_back(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy, void* stream, int adam_step, bool polyak, int heads, const SampleDev* predraw = nullptr,
-                       bool skip_c = false) {
+                       bool skip_c = false, const TdGiven* given = nullptr) {
     hipStream_t st = (hipStream_t)stream;
     const Mlp mQ{17, 1, Hy->no_layernorm ? 1 : 0};
     const int B = Bt->batch;
     Slot s[S_COUNT];
     make_slots(N, B, s);
-    if (!skip_c) {
+    if (given) {  // y, errors, losses[0] and both head gradients per row, with the weights; then both critics backward from them
+        const HirlTdHead T{N->critic, N->critic + mQ.padded(), N->target_critic, N->target_critic + mQ.padded(), mQ, s[S_C1], s[S_C2], s[S_TC1].z2, s[S_TC2].z2,
+                           Bt->rows, given->weights, given->n_weighted, B, Hy->gamma, 1.0f / B, Hy->slope, given->errors, N->losses};
+        launch_hirl_td_head(T, st);
+        BwdArgs G;
+        make_launch_c(N, Bt, Hy, G, true);
+        if (int rc = launch_bwd(3, G, st)) return rc;
+    } else if (!skip_c) {
         BwdArgs G;
         make_launch_c(N, Bt, Hy, G);
         launch_bwd(0, G, st);
@@ -181,7 +194,7 @@ static int critic_back(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy, vo
     return 0;
 }
 static int critic_grads_impl(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy, int32_t actor_fwd, void* stream, int adam_step, bool polyak,
-                             const HxSample* S = nullptr) {
+                             const HxSample* S = nullptr, const TdGiven* given = nullptr) {
     HX_REQUIRE(N && Bt && Hy && Bt->batch > 0 && Bt->batch % 16 == 0, "hx_hirl_critic_grads: batch must be a positive multiple of 16");
     hipStream_t st = (hipStream_t)stream;
     const int B = Bt->batch;
@@ -197,7 +210,7 @@ static int critic_grads_impl(const HxNets* N, const HxBatch* Bt, const HxHyper* 
     launch_fwd(F, st);
     make_launch_b(N, Bt, Hy, actor_fwd, F);
     launch_fwd(F, st);
-    return critic_back(N, Bt, Hy, stream, adam_step, polyak, heads_of(Hy, actor_fwd));
+    return critic_back(N, Bt, Hy, stream, adam_step, polyak, heads_of(Hy, actor_fwd), nullptr, false, given);
 }
 int hx_hirl_critic_grads(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy, int32_t actor_fwd, void* stream) {
     return critic_grads_impl(N, Bt, Hy, actor_fwd, stream, 0, false);
@@ -205,6 +218,19 @@ int hx_hirl_critic_grads(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy, 
 int hx_hirl_critic_grads_sampled(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy, const HxSample* S, int32_t actor_fwd, void* stream) {
     HX_REQUIRE(S, "hx_hirl_critic_grads_sampled: null sample description");
     return critic_grads_impl(N, Bt, Hy, actor_fwd, stream, 0, false, S);
+}
+/* Stage 1 under prioritized replay (include/hirl4ucav.h "Prioritized replay for HIRL / TD3"): launches A and B as hx_hirl_critic_grads issues them, the TD
+ * head per row with the importance weights (hirl_td_head_weighted_kernel), both critics' backward from the given head gradient (bwd_l2<3>), launch D without
+ * Adam.  Rows [0, n_weighted) weigh weights[r], the rest 1; errors_out[r] = |Q1(s, a) - y| of every row. */
+int hx_hirl_critic_grads_weighted(const HxNets* N, const HxBatch* Bt, const HxHyper* Hy, const float* weights, int32_t n_weighted, float* errors_out,
+                                  int32_t actor_fwd, void* stream) {
+    HX_REQUIRE(N && Bt && Hy && Bt->batch > 0 && Bt->batch % 16 == 0, "hx_hirl_critic_grads_weighted: batch must be a positive multiple of 16");
+    HX_REQUIRE(n_weighted >= 0 && n_weighted <= Bt->batch, "hx_hirl_critic_grads_weighted: n_weighted %d is not in 0..batch (%d)", n_weighted, Bt->batch);
+    HX_REQUIRE(weights || n_weighted == 0, "hx_hirl_critic_grads_weighted: weights may be NULL only with n_weighted == 0");
+    HX_REQUIRE(errors_out, "hx_hirl_critic_grads_weighted: errors_out[batch] is required");
+    HX_REQUIRE(Bt->rows && N->ws && N->losses, "hx_hirl_critic_grads_weighted: null rows, workspace or losses");
+    const TdGiven given{weights, n_weighted, errors_out};
+    return critic_grads_impl(N, Bt, Hy, actor_fwd, stream, 0, false, nullptr, &given);
 }
 
 /* Stage 2a (delayed actor step, HIRL.py:291-319): actor / bc_actor forward, Q1 with the UPDATED critic, the soft

@@ -1074,5 +1074,20 @@ void launch_target_q(const Slot* slots, const float* target_critic, const RowSrc
 int sac_grad_norm(const HxSacNets* N, int which, float* clip_ws, hipStream_t st, const char* who);
 int sac_clipped_step(const HxSacNets* N, const HxHyper* Hy, int which, int step, float grad_scale, float target_entropy, float max_norm, float* clip_ws,
                      bool alpha_step, hipStream_t st, const char* who);
+// hx_hirl_per.hip: HIRL's / TD3's TD head per row with importance weights (hirl_td_head_weighted_kernel) — y, errors, losses[0], both critics' dout and st2
+// from the z2 rows launches A and B left; bwd_l2<3> (BM_GIVEN) follows
+struct HirlTdHead {
+    const float* q1net; const float* q2net; const float* t1net; const float* t2net;
+    Mlp m;
+    Slot s1, s2;                              // Q1 / Q2 (s, a): z2 read; st2 and dout written
+    const float* z2_t1; const float* z2_t2;   // target Q1 / Q2 (s', a')
+    const float* rows;                        // [nrows][32]: reward, done in columns 30, 31
+    const float* weights;                     // [n_weighted]; rows behind them weigh 1 (never read there)
+    int n_weighted, nrows;
+    float gamma, inv_batch, slope;
+    float* errors;                            // [nrows] out: |Q1 - y| of EVERY row
+    float* losses;                            // losses[0] += w ((Q1 - y)^2 + (Q2 - y)^2) / B
+};
+void launch_hirl_td_head(const HirlTdHead& T, hipStream_t st);
 
 }  // namespace hxu

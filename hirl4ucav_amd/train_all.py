@@ -338,8 +338,9 @@ def train_bc(config, device, seed, max_step):
     bc_table = torch.from_numpy(tab).to(device)
     table = DeviceReplay(es.shape[0], device)  # the sampler wants a main ring as well; the BC step reads only the BC rows
     table.store_rows(bc_table)
-    if upsample_refusal(config) or expert_online_refusal(config) or expert_branch_refusal(config) or expert_floor_refusal(config):
-        raise SystemExit("train_all: " + (upsample_refusal(config) or expert_online_refusal(config) or expert_branch_refusal(config) or expert_floor_refusal(config)))
+    if hirl_per_refusal(config) or upsample_refusal(config) or expert_online_refusal(config) or expert_branch_refusal(config) or expert_floor_refusal(config):
+        raise SystemExit("train_all: " + (hirl_per_refusal(config) or upsample_refusal(config) or expert_online_refusal(config) or expert_branch_refusal(config)
+                                          or expert_floor_refusal(config)))
     if getattr(config, "expert_upsample", False):  # BC.py:152-158, 171-176: one row of every minibatch is a fire row
         from .utils.buffer import fire_rows
 
@@ -455,6 +456,10 @@ def check_agent_flags(run):
     if run.isac and (world > 1 or getattr(config, "dtype", "f32") != "f32" or not config.bc_actor):
         raise SystemExit("train_all: " + isac_refusal(config, world))
     run.per = bool(getattr(config, "per", False))  # SacAgent(per=True): prioritized replay, the importance weights through the three losses
+    # --hirl_per: HirlEngine.set_prioritized (an extension) on the same store — the replay, the marking of new rows behind every acting
+    # launch and the stats/per_* scalars are --per's (run.per); what differs hangs on run.hirl_per
+    run.hirl_per = bool(getattr(config, "hirl_per", False))
+    run.per = run.per or run.hirl_per
     run.per_new = getattr(config, "per_new", "max")  # how a step's rows get their first priority: at pmax, or at a TD error of their own (agent.py:234-246)
     run.multi_step = int(getattr(config, "multi_step", 1))  # SacAgent(multi_step=n): truncated n-step returns (utils.buffer.NStepInserter)
     run.grad_clip, run.fixed_alpha = getattr(config, "grad_clip", None), getattr(config, "fixed_alpha", None)  # SacAgent(grad_clip=c) / (entropy_tuning=False, ent_coef=x)
@@ -463,9 +468,11 @@ def check_agent_flags(run):
     # the reference's two sampling switches (HIRL.py:184-185): success rows of the replay drawn 10 : 1, one fire row forced into the BC minibatch
     run.buffer_upsample, run.expert_upsample = bool(getattr(config, "buffer_upsample", False)), bool(getattr(config, "expert_upsample", False))
     run.upsampler = None
-    for refusal in (per_refusal, nstep_refusal, clip_refusal, hirl_clip_refusal, upsample_refusal, expert_online_refusal, expert_branch_refusal, expert_floor_refusal):  # (per_refusal without --per: --per_new td on its own)
+    for refusal in (per_refusal, hirl_per_refusal, nstep_refusal, clip_refusal, hirl_clip_refusal, upsample_refusal, expert_online_refusal, expert_branch_refusal, expert_floor_refusal):  # (per_refusal without --per: --per_new td on its own)
         if refusal(config, world):
             raise SystemExit("train_all: " + refusal(config, world))
+    if hirl_per_resume_refusal(config, getattr(run, "snap", None)):
+        raise SystemExit(f"train_all: --resume {config.resume} " + hirl_per_resume_refusal(config, run.snap))
     run.batch = BATCH  # train_all.py:190-208
     run.expert_floor = int(getattr(config, "expert_floor", 0))  # --expert_floor: expert_num stops there instead of at 0 (expert_num_after)
     run.warm_up_rate = 20 if run.sac else 10  # train_sac.py:203 / train_all.py:207
@@ -524,6 +531,8 @@ def build_engine(run):
         eng.load_params(init_actor_state_dict(), init_critic_state_dict(), init_actor_state_dict() if run.hirl else None)
         if run.grad_clip is not None:  # an extension (the reference's HIRL / TD3 have no clip): clip_grad_norm_ once per optimizer, DESIGN.md section 5
             eng.set_grad_clip(run.grad_clip)
+        if run.hirl_per:  # an extension too: proportional draws of the replay rows, importance weights through the critic loss, |Q1 - y| back as priorities
+            eng.set_prioritized(run.replay)
     run.eng = eng
 
 
@@ -722,13 +731,13 @@ def choose_loop(run):
     shared_gpu = world > torch.cuda.device_count() and not os.environ.get("HX_FRONT_SHARED_GPU")
     upsampled = tuple(flag for flag in ("buffer_upsample", "expert_upsample") if getattr(run, flag, False))  # the weighted draw is a launch behind the plain one
     run.front = (config.loop == "front" and not sac and not config.separate_launches and config.updates_per_step == 1 and run.batch <= 256
-                 and getattr(config, "dtype", "f32") in ("f32", "f32x9", "bf16") and not shared_gpu and not upsampled)
+                 and getattr(config, "dtype", "f32") in ("f32", "f32x9", "bf16") and not shared_gpu and not upsampled and not getattr(run, "hirl_per", False))
     run.front_sac = (config.loop == "front" and sac and world == 1 and not config.separate_launches and config.updates_per_step == 1 and run.batch <= 256 and not run.per
                      and run.grad_clip is None and run.inserter is None)
     if rank == 0:
         which = "front launch (env step + first launches of learn() in one launch; draw before the insert)" if (run.front or run.front_sac) else "reference order"
         if run.per:  # the front loop draws before the step's insert: update_priority could then hit slots the step has overwritten
-            which += " (--per: the front launch draws before the step's insert, so the priorities of the drawn rows could be written into overwritten slots)"
+            which += f" ({'--hirl_per' if getattr(run, 'hirl_per', False) else '--per'}: the front launch draws before the step's insert, so the priorities of the drawn rows could be written into overwritten slots)"
         if run.inserter is not None:  # the front launch's acting workgroups insert one-step rows themselves
             which += f" (--multi_step {run.multi_step}: the n-step rows are written by a launch of their own behind the acting launch)"
         if upsampled:  # the front launch draws uniformly, inside the launch and before the step's insert
@@ -1262,11 +1271,43 @@ def hirl_clip_refusal(config, world=1):
     return None
 
 
+def hirl_per_refusal(config, world=1):
+    """why `--hirl_per` cannot run as asked, or None.  (A flag of its own: `--per` is SacAgent's keyword and stays refused for every other agent.)
+    HirlEngine.set_prioritized: every --type, --dtype bf16, --hirl_grad_clip, --expert_floor / --expert_branch* / --expert_online, --env mixed and
+    --separate_launches are fine; the vector loop takes the reference's order (choose_loop)."""
+    if not getattr(config, "hirl_per", False):
+        return None
+    if config.agent == "SAC":
+        return "--hirl_per goes with --agent HIRL or TD3, not --agent SAC: SAC has --per (SacAgent(per=True))"
+    if config.agent == "BC":
+        return "--hirl_per goes with --agent HIRL or TD3, not --agent BC (behaviour cloning draws from the expert table alone: there is no replay ring to prioritize)"
+    if config.agent not in ("HIRL", "TD3"):
+        return f"--hirl_per goes with --agent HIRL or TD3, not --agent {config.agent}"
+    if (config.gpus and config.gpus > 1) or world > 1:
+        return "--hirl_per runs on one GPU (priorities and block sums are not exchanged between ranks): use --gpus 1"
+    for flag in ("buffer_upsample", "expert_upsample"):
+        if getattr(config, flag, False):
+            return f"--hirl_per does not go with --{flag} (both redraw the same rows of the minibatch; untested together): drop one of the two"
+    if int(getattr(config, "buffer_size", 0)) > (1 << 24):
+        return f"--hirl_per with --buffer_size {config.buffer_size}: prioritized replay holds at most 2^24 = 16,777,216 slots (the sampler scans 16,384 block sums)"
+    return None
+
+
+def hirl_per_resume_refusal(config, snap):
+    """why a snapshot cannot be resumed under this run's --hirl_per, or None (snap None: a fresh run)"""
+    if snap is None:
+        return None
+    was, now = bool(snap["engine"].get("prioritized", False)), bool(getattr(config, "hirl_per", False))
+    if was != now and config.agent in ("HIRL", "TD3"):
+        return f"was run {'with' if was else 'without'} --hirl_per, this run is {'with' if now else 'without'} it: resume with the flag the run was started with"
+    return None
+
+
 def parse_args(argv=None):
     """parser().parse_args with the cross-flag checks that are argparse errors"""
     p = parser()
     cfg = p.parse_args(argv)
-    why = per_refusal(cfg) or clip_refusal(cfg) or hirl_clip_refusal(cfg) or nstep_refusal(cfg) or mixed_refusal(cfg) or upsample_refusal(cfg) or expert_online_refusal(cfg) or expert_branch_refusal(cfg) or expert_floor_refusal(cfg)
+    why = per_refusal(cfg) or hirl_per_refusal(cfg) or clip_refusal(cfg) or hirl_clip_refusal(cfg) or nstep_refusal(cfg) or mixed_refusal(cfg) or upsample_refusal(cfg) or expert_online_refusal(cfg) or expert_branch_refusal(cfg) or expert_floor_refusal(cfg)
     if why:
         p.error(why)
     if cfg.type == "ISAC" and cfg.agent != "SAC":
@@ -1333,9 +1374,16 @@ def parser():
                    help="--per: the priority a newly stored row enters at.  max (default): the running maximum priority; td: a TD error of its own, "
                         "|Q1(s, a) - y| with the networks as they stand, as the reference's train_episode computes it for every append "
                         "(SAC/agent.py:234-246): one scoring pass over the step's rows per vector step (fp32, one GPU)")
-    p.add_argument("--per_alpha", type=float, default=0.6, help="--per: priority exponent (SAC/agent.py:62)")
-    p.add_argument("--per_beta", type=float, default=0.4, help="--per: importance-weight exponent at the start (SAC/agent.py:62)")
-    p.add_argument("--per_beta_annealing", type=float, default=0.0001, help="--per: beta <- min(1, beta + this) per sample call (SAC/agent.py:63)")
+    p.add_argument("--per_alpha", type=float, default=0.6, help="--per / --hirl_per: priority exponent (SAC/agent.py:62)")
+    p.add_argument("--per_beta", type=float, default=0.4, help="--per / --hirl_per: importance-weight exponent at the start (SAC/agent.py:62)")
+    p.add_argument("--per_beta_annealing", type=float, default=0.0001, help="--per / --hirl_per: beta <- min(1, beta + this) per sample call (SAC/agent.py:63)")
+    p.add_argument("--hirl_per", action="store_true",
+                   help="HIRL (every --type) and TD3 (an extension: the reference's prioritized branch is dead code, HIRL.py:236,283): prioritized replay — the "
+                        "replay rows of a minibatch are drawn proportionally to (|Q1 - y| + 1e-4)^alpha with replacement and weigh (n p / S)^-beta / max in the "
+                        "critic loss; expert rows weigh 1 and are kept, the actor loss is unweighted.  New rows enter at the running maximum priority.  Every "
+                        "--dtype, --hirl_grad_clip, --expert_floor / --expert_branch / --expert_online, --env mixed; one GPU, the reference's step order, not with "
+                        "--buffer_upsample / --expert_upsample, --buffer_size <= 2^24.  (--per is SacAgent's and stays SAC's.)  Stored in the snapshot: "
+                        "--resume refuses the other setting")
     p.add_argument("--buffer_upsample", action="store_true",
                    help="HIRL (every --type) and TD3: the reference's UniformMemory(upsample=True) (HIRL.py:184, 189): a replay row whose step_success is 1 "
                         "is drawn --upsample_boost times as often as any other, with replacement.  TD3 is an extension (the same engine draws for both).  "

@@ -26,6 +26,8 @@ def engine_state(eng):
         st["imitative"] = {"bc_actor": eng.bc_actor.detach().cpu().clone(), "bc_slope": eng.bc_slope, "expert_calls": eng.expert_calls}
     if getattr(eng, "prioritized", None) is not None:  # (a plain snapshot carries no such key)
         st["prioritized"] = True
+        if hasattr(eng, "per_calls"):  # (HirlEngine: the call word of its prioritized draws keys their Philox stream)
+            st["per_calls"] = eng.per_calls
         if getattr(eng, "per_new_rows", "max") != "max":  # (a snapshot of a run whose new rows enter at pmax stays as it was)
             st["per_new_rows"] = eng.per_new_rows
     if getattr(eng, "grad_clip", None) is not None:  # (a snapshot of an unclipped run with entropy tuning carries neither key)
@@ -69,7 +71,8 @@ def load_engine_state(eng, st):
         warnings.warn(f"snapshot was written under acting format {was if was is not None else 'unrecorded (a round <= 5 snapshot)'}, this engine "
                       f"acts under {now}: the run continues under other acting arithmetic (fp32 results up to summation order)", stacklevel=2)
     if bool(st.get("prioritized", False)) != (getattr(eng, "prioritized", None) is not None):
-        raise ValueError("snapshot and engine disagree about prioritized replay (--per): resume with the flag the run was started with")
+        raise ValueError(f"snapshot and engine disagree about prioritized replay ({getattr(eng, 'per_flag', '--per')}): resume with the flag the run was "
+                         "started with")
     if st.get("per_new_rows", "max") != getattr(eng, "per_new_rows", "max"):
         raise ValueError(f"snapshot was written under --per_new {st.get('per_new_rows', 'max')}, this engine runs under --per_new "
                          f"{getattr(eng, 'per_new_rows', 'max')}: resume with the flag the run was started with")
@@ -90,6 +93,8 @@ def load_engine_state(eng, st):
         raise ValueError("snapshot and engine disagree about SAC's imitative branch (--type ISAC): resume with the type the run was started with")
     check_upsample(eng, st)
     eng.arena.copy_(st["arena"])
+    if "per_calls" in st:
+        eng.per_calls = st["per_calls"]
     if "upsample" in st:
         eng.upsample_calls = st["upsample"]["calls"]
     if "multi_step" in st:

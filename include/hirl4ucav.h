@@ -90,8 +90,9 @@ const char* hx_last_error(void);
  * 128: expert branches: one pilot step per pick fills the online region of the labelled expert ring (hx_pilot_branch).
  * 129: expert branches of up to H steps: resident branches in a device workspace, one step per call (hx_pilot_branch_steps,
  * hx_branch_workspace_bytes).
- * 130: gradient-norm clipping for HIRL and TD3 (hx_hirl_clip_floats, hx_hirl_clip_shape, hx_hirl_grad_norm, hx_adam_clipped). */
-#define HX_ABI_VERSION 130
+ * 130: gradient-norm clipping for HIRL and TD3 (hx_hirl_clip_floats, hx_hirl_clip_shape, hx_hirl_grad_norm, hx_adam_clipped).
+ * 131: prioritized replay for HIRL and TD3: the weighted TD head (hx_hirl_critic_grads_weighted). */
+#define HX_ABI_VERSION 131
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -341,6 +342,29 @@ int hx_hirl_grad_norm(const HxNets* nets, const HxHyper* hyper, int32_t which, i
                       const float* msg, float* clip_ws, void* stream);
 int hx_adam_clipped(const HxNets* nets, const HxHyper* hyper, int32_t which, int32_t step, float grad_scale, int32_t w_kind, float w_given,
                     float warm, int32_t batch, const float* msg, float max_norm, float* clip_ws, void* stream);
+/* Prioritized replay for HIRL / TD3.  A declared extension: the reference ships a SumTree beside UniformMemory (hirl/utils/buffer.py) and HIRL.py:236,283
+ * guard on isinstance(self.buffer, UniformMemory), but its prioritized branch is dead — there is no live counterpart to reproduce.  The rule:
+ *     store, draw, weights   "Prioritized replay" below, unchanged: p = (|delta| + 1e-4)^alpha, proportional draws with replacement,
+ *                            w = (n p / S)^-beta / max, new rows at pmax (hx_per_mark_new)
+ *     which rows             the minibatch is n_main replay rows, then batch - n_main expert rows (HIRL.py:226-227).  Only rows [0, n_main) are drawn by
+ *                            priority, carry a weight and give their error back; expert rows weigh exactly 1 and touch no priority; the BC minibatch
+ *                            is untouched.  Unlike SAC's --per the expert rows are KEPT (warm-up, --expert_floor, --expert_branch keep working)
+ *     loss                   y = r + gamma min(Q1', Q2') (1 - d) (HIRL.py:270-274; the discount folded into the done column keeps working);
+ *                            critic_loss = mean_r(w_r (Q1 - y)^2) + mean_r(w_r (Q2 - y)^2), both means over all `batch` rows -> losses[0];
+ *                            head gradients 2 w_r (Q_h - y) / batch; errors_out[r] = |Q1(s, a) - y|_r, as hx_per_update expects
+ *     the actor half         UNWEIGHTED and unchanged — the rule's one design decision: its loss already mixes a second (BC) batch and a counted gate, and
+ *                            PER-TD3 in its usual form weights the critic alone
+ *     order per vector step  act_step -> hx_per_mark_new(n) -> draw -> learn -> hx_per_update(idx[:n_main], errors[:n_main]): the reference's step order
+ *                            only (the front launch draws before the step's insert, so the priorities of the drawn rows could be written into
+ *                            overwritten slots)
+ * hx_hirl_critic_grads_weighted: stage 1 (hx_hirl_critic_grads) with the weights.  Launches A and B as there (actor_fwd's riding forwards included); the TD
+ * head as a per-row kernel of its own (one wave per row: y, errors_out, losses[0], both critics' head gradients and LayerNorm stats; fp32 on the bf16
+ * update path too); both critics' backward from the given head gradient; the weight-gradient launch without Adam (actor_fwd's head riders kept).  The
+ * caller follows with hx_adam(0) or hx_hirl_grad_norm + hx_adam_clipped.  n_weighted in 0..batch: rows [0, n_weighted) weigh weights[r], the rows
+ * behind them 1 — weights is not read there and may be NULL when n_weighted == 0.  errors_out[batch] is required and written for EVERY row.  batch: a
+ * positive multiple of 16. */
+int hx_hirl_critic_grads_weighted(const HxNets* nets, const HxBatch* batch, const HxHyper* hyper, const float* weights, int32_t n_weighted,
+                                  float* errors_out, int32_t actor_fwd, void* stream);
 /* BC.Agent.train_actor (hirl/agents/BC.py:160-185): one behaviour-cloning step on batch->bc_rows: loss = mse(actor(s_bc),
  * a_bc), backward, actor.optimizer.step(); losses[2] receives the loss.  hyper->slope = 0.01 gives BC.py's LeakyReLU actor.
  * (hx_adam's which = 2 is the actor step without HIRL's actor_loss / bc_weight bookkeeping.) */
