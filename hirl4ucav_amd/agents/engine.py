@@ -102,6 +102,7 @@ def _bc_weight_kind(bc_weight_now):
 class HirlEngine:
     grad_clip_flag = "--hirl_grad_clip"  # train_all's name for set_grad_clip (utils/checkpoint.py names it when a resume disagrees; SAC's is --grad_clip)
     per_flag = "--hirl_per"  # ... and for set_prioritized (SAC's is --per)
+    multi_step_flag = "--hirl_multi_step"  # ... and for set_multi_step (SAC's is --multi_step)
 
     def __init__(self, batch=128, lr_actor=1e-3, lr_critic=1e-3, tau=0.005, gamma=0.99, slope=0.0, use_bc=True,
                  device="cuda", group=None, layer_norm=True):
@@ -179,6 +180,7 @@ class HirlEngine:
         self.exchange_name, self.xchg, self.rccl = "rccl", None, None
         self.grad_clip, self.clip_ws = None, None  # set_grad_clip
         self.prioritized, self.per_calls, self._weights, self._errors, self._per_n_main = None, 0, None, None, 0  # set_prioritized
+        self.multi_step = None  # set_multi_step: the n-step inserter behind the acting launch
 
     def set_grad_clip(self, max_norm):
         """torch.nn.utils.clip_grad_norm_(optimizer's parameters, max_norm) in front of each optimizer step — the critic's (both Q heads and their
@@ -224,6 +226,30 @@ class HirlEngine:
             self._weights = torch.ones(self.batch, dtype=torch.float32, device=self.device)
             self._errors = torch.zeros(self.batch, dtype=torch.float32, device=self.device)
         self._per_n_main = 0
+
+    def set_multi_step(self, inserter):
+        """Truncated n-step returns for HIRL / TD3 (a declared extension: DESIGN.md 5; the rule is include/hirl4ucav.h "n-step returns").  inserter: a
+        utils.buffer.NStepInserter over the replay ring; the env is built with replay=None.  The reference order is act_step(env) -> inserter.push(env,
+        actions) -> sample(inserter.replay, ...) -> learn(): the caller pushes, sample() and learn() are unchanged — every consumer reads the done column
+        arithmetically, so a row's discount gamma^m rides in it and HxHyper keeps the one-step gamma.  step_learn(): the front launch runs with the
+        env's options (no ring: the per-tile acting role, at most 8,192 envs), both of its draws read inserter.replay, and step_learn pushes ONCE, behind
+        its last launch — so a call's minibatch comes from the ring as it stood before the PREVIOUS step's push, one step older than in the one-step
+        front loop.  With set_grad_clip in every form; with set_prioritized / set_upsample in the reference order (mark_new(inserter.max_rows)); one GPU.
+        None: the one-step paths, call for call."""
+        if inserter is None:
+            self.multi_step = None
+            return
+        from ..utils.buffer import NStepInserter
+
+        if not isinstance(inserter, NStepInserter):
+            raise TypeError("set_multi_step takes a utils.buffer.NStepInserter")
+        if self.world > 1 or self.sharded_sequence:
+            raise _lib.HxError("set_multi_step: n-step returns run on one GPU (the per-env windows are rank-local and untested on sharded ranks): run it with --gpus 1")
+        if abs(inserter.gamma - float(self.hyper.gamma)) > 1e-7:
+            raise ValueError(f"set_multi_step: the inserter folds gamma = {inserter.gamma} into its rows, the update bootstraps with gamma = {float(self.hyper.gamma)}")
+        if self.prioritized is not None and self.prioritized is not inserter.replay:
+            raise _lib.HxError("set_multi_step: the inserter writes into another replay than the one given to set_prioritized")
+        self.multi_step = inserter
 
     def set_weights(self, weights, n_main, idx=None):
         """Under set_prioritized, for a minibatch from assemble(): the importance weights of rows [0, n_main) (the rest weigh 1) for the next learn().
@@ -674,7 +700,16 @@ class HirlEngine:
         n_main, seed and sigma finds its tiles ready, any other draws them with a launch of its own first.
         fp32 networks, or bf16 acting + bf16 update; at most 8,192 envs per GPU, batch <= 256; one-call and sharded (staged) update paths.
         -> (actions, obs, reward, done, success) as act_step."""
-        replay, n, B = env.replay, env.n, self.batch
+        ms = self.multi_step
+        if ms is not None:
+            if env.replay is not None:
+                raise _lib.HxError("HirlEngine.step_learn after set_multi_step: the env inserts one-step rows itself: build it with replay=None")
+            if env.n != ms.num_envs:
+                raise ValueError(f"step_learn: the n-step inserter was built for {ms.num_envs} envs, the env has {env.n}")
+            if env.n > 8192:
+                raise _lib.HxError(f"HirlEngine.step_learn after set_multi_step: at most 8,192 envs ({env.n} given): beyond that the front launch's acting roles are "
+                                   "the persistent and the streaming one, which need a ring in the env: use act_step + push + sample + learn (the reference order)")
+        replay, n, B = (ms.replay if ms is not None else env.replay), env.n, self.batch
         bf16 = self.update_dtype == "bf16"
         if replay is None or (self.act_dtype != "bf16" if bf16 else self.act_dtype not in ("f32", "f32x9")):
             raise _lib.HxError("step_learn: the front launch exists for the fp32 networks (acting format 'f32' or 'f32x9') and for the bf16 update path with "
@@ -709,8 +744,11 @@ class HirlEngine:
         held = (self._front_epoch, self._front_c_epoch, self.critic_step, self.actor_step, self.update_count, self.sample_calls, self.act_calls, env.steps_issued)
         self._front_enqueued = False
         try:
-            return self._step_learn(env, expert, bc_table, n_main, act_noise, act_sigma, act_seed, out, sample_seed, smooth_sigma, bc_weight_now,
-                                    bc_warm_up_weight, bf16, flags, status, cur, nxt)
+            got = self._step_learn(env, expert, bc_table, n_main, act_noise, act_sigma, act_seed, out, sample_seed, smooth_sigma, bc_weight_now,
+                                   bc_warm_up_weight, bf16, flags, status, cur, nxt)
+            if ms is not None:  # this step's finished n-step rows, behind the call's last launch: the next call's tiles were drawn without them
+                ms.push(env, got[0])
+            return got
         except _lib.HxError:
             if self._front_enqueued:
                 self.needs_reload = True
@@ -721,7 +759,7 @@ class HirlEngine:
 
     def _step_learn(self, env, expert, bc_table, n_main, act_noise, act_sigma, act_seed, out, sample_seed, smooth_sigma, bc_weight_now, bc_warm_up_weight,
                     bf16, flags, status, cur, nxt):
-        replay, n, B = env.replay, env.n, self.batch
+        replay, n, B = (self.multi_step.replay if self.multi_step is not None else env.replay), env.n, self.batch
         self.sample_calls += 1
 
         def draw(tiles, call):

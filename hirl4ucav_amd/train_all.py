@@ -148,6 +148,12 @@ def checkpoint_tag(arttir, success, episodes, mean_score):
 def label_expert(states, actions, device):
     """Expert replay rows [k, 32] + step_success from consecutive expert states, labelled on the GPU
     (HarfangEnv.get_reward / get_termination, HarfangEnv_GYM.py:299-336)."""
+    rows, succ, _keep = label_expert_pairs(states, actions, device)
+    return rows, succ
+
+
+def label_expert_pairs(states, actions, device):
+    """label_expert with the pair indices it kept (expert_pair_indices): utils.buffer.segment_last reads a file's segments off them"""
     s = torch.as_tensor(np.asarray(states[:-1], np.float32), device=device).contiguous()
     a = torch.as_tensor(np.asarray(actions[:-1], np.float32), device=device).contiguous()
     ns = torch.as_tensor(np.asarray(states[1:], np.float32), device=device).contiguous()
@@ -158,7 +164,7 @@ def label_expert(states, actions, device):
     _lib.call("hx_label_transitions", s.data_ptr(), a.data_ptr(), ns.data_ptr(), m, r.data_ptr(), sc.data_ptr(), dn.data_ptr(), _lib.stream_ptr())
     keep = torch.as_tensor(expert_pair_indices(dn.cpu().numpy().astype(bool)), device=device)
     rows = torch.cat([s, a, ns, r[:, None], dn.float()[:, None]], 1)[keep]
-    return rows, sc[keep]
+    return rows, sc[keep], keep
 
 
 def validate(engine, scenario, episodes, max_step, if_random, seed, device, sac=False, env=None, recorder=None):
@@ -462,17 +468,24 @@ def check_agent_flags(run):
     run.per = run.per or run.hirl_per
     run.per_new = getattr(config, "per_new", "max")  # how a step's rows get their first priority: at pmax, or at a TD error of their own (agent.py:234-246)
     run.multi_step = int(getattr(config, "multi_step", 1))  # SacAgent(multi_step=n): truncated n-step returns (utils.buffer.NStepInserter)
+    # --hirl_multi_step: HirlEngine.set_multi_step (an extension) on the same inserter — the env without a ring, the push behind every
+    # acting launch and the bound of mark_new are --multi_step's (run.multi_step, run.inserter); what differs hangs on run.hirl_multi_step
+    run.hirl_multi_step = int(getattr(config, "hirl_multi_step", 1)) if not run.sac else 1
+    if run.hirl_multi_step != 1:
+        run.multi_step = run.hirl_multi_step
     run.grad_clip, run.fixed_alpha = getattr(config, "grad_clip", None), getattr(config, "fixed_alpha", None)  # SacAgent(grad_clip=c) / (entropy_tuning=False, ent_coef=x)
     if not run.sac:  # HIRL / TD3: --hirl_grad_clip, an extension (HirlEngine.set_grad_clip); --grad_clip itself is refused for them (clip_refusal)
         run.grad_clip = getattr(config, "hirl_grad_clip", None)
     # the reference's two sampling switches (HIRL.py:184-185): success rows of the replay drawn 10 : 1, one fire row forced into the BC minibatch
     run.buffer_upsample, run.expert_upsample = bool(getattr(config, "buffer_upsample", False)), bool(getattr(config, "expert_upsample", False))
     run.upsampler = None
-    for refusal in (per_refusal, hirl_per_refusal, nstep_refusal, clip_refusal, hirl_clip_refusal, upsample_refusal, expert_online_refusal, expert_branch_refusal, expert_floor_refusal):  # (per_refusal without --per: --per_new td on its own)
+    for refusal in (per_refusal, hirl_per_refusal, nstep_refusal, hirl_multi_step_refusal, clip_refusal, hirl_clip_refusal, upsample_refusal, expert_online_refusal, expert_branch_refusal, expert_floor_refusal):  # (per_refusal without --per: --per_new td on its own)
         if refusal(config, world):
             raise SystemExit("train_all: " + refusal(config, world))
     if hirl_per_resume_refusal(config, getattr(run, "snap", None)):
         raise SystemExit(f"train_all: --resume {config.resume} " + hirl_per_resume_refusal(config, run.snap))
+    if hirl_multi_step_resume_refusal(config, getattr(run, "snap", None)):
+        raise SystemExit(f"train_all: --resume {config.resume} " + hirl_multi_step_resume_refusal(config, run.snap))
     run.batch = BATCH  # train_all.py:190-208
     run.expert_floor = int(getattr(config, "expert_floor", 0))  # --expert_floor: expert_num stops there instead of at 0 (expert_num_after)
     run.warm_up_rate = 20 if run.sac else 10  # train_sac.py:203 / train_all.py:207
@@ -499,7 +512,7 @@ def build_env(run):
     if run.multi_step > 1:  # the acting launches run without a ring; the inserter's launch behind each step writes the finished n-step rows
         from .utils.buffer import NStepInserter
 
-        run.inserter = NStepInserter(run.replay, n, run.multi_step, 0.99)  # (SacEngine's gamma, SAC/agent.py:60)
+        run.inserter = NStepInserter(run.replay, n, run.multi_step, 0.99)  # (SacEngine's gamma, SAC/agent.py:60; HirlEngine's, HIRL.py:162: set_multi_step checks it)
     # Episode statistics by scenario (utils/epstat.py): one small launch behind every acting launch.  On under --env mixed, opt-in (--episode_stats) for
     # one scenario; off, the run is launch for launch what it was.  Every rank keeps its own shard's statistics; rank 0 writes its own.
     run.estats = run.last100 = None
@@ -533,6 +546,8 @@ def build_engine(run):
             eng.set_grad_clip(run.grad_clip)
         if run.hirl_per:  # an extension too: proportional draws of the replay rows, importance weights through the critic loss, |Q1 - y| back as priorities
             eng.set_prioritized(run.replay)
+        if run.inserter is not None:  # an extension too (--hirl_multi_step): n-step rows in the ring, the row's discount in its done column
+            eng.set_multi_step(run.inserter)
     run.eng = eng
 
 
@@ -549,8 +564,15 @@ def load_expert_tables(run):
     if why:
         raise SystemExit(f"train_all: --resume {config.resume} {why}")
     tables = load_expert_files(config)
-    labelled = [label_expert(es_k, ea_k, device) for es_k, ea_k in tables]  # each file on its own: no transition spans two files
-    rows, succ = torch.cat([r for r, _ in labelled]), torch.cat([s_ for _, s_ in labelled])
+    labelled = [label_expert_pairs(es_k, ea_k, device) for es_k, ea_k in tables]  # each file on its own: no transition spans two files
+    rows, succ = torch.cat([r for r, _, _ in labelled]), torch.cat([s_ for _, s_, _ in labelled])
+    if run.hirl and getattr(run, "hirl_multi_step", 1) > 1:
+        # --hirl_multi_step: the offline expert rows become n-step rows too (hx_nstep_label), before they are stored — and so before BranchExpert copies
+        # them.  Row j stays row j: succ, fire_idx and the ring's layout stay valid.  Each file ends a segment.  (E-SAC's rows under --multi_step stay one-step.)
+        from .utils.buffer import nstep_relabel, segment_last
+
+        last = np.concatenate([segment_last(r[:, 31], keep) for r, _, keep in labelled])
+        rows = nstep_relabel(rows, last, run.hirl_multi_step, float(eng.hyper.gamma))
     es, ea = np.concatenate([t[0] for t in tables]), np.concatenate([t[1] for t in tables])
     if int(getattr(config, "expert_branch", 0)) > 0:
         # An extension (utils/pilot.py): the ring grows by an online region that starts as a cyclic copy of the labelled rows and is rewritten behind
@@ -706,7 +728,7 @@ def restore_or_explore(run):
             if getattr(run, "branch", None) is not None:
                 run.branch.push()
             if getattr(run, "upsampler", None) is not None:
-                run.upsampler.mark_new(n)
+                run.upsampler.mark_new(n if inserter is None else inserter.max_rows)
         if run.per and run.per_new == "td":  # the exploration rows are appended with an error of their own too (SAC/agent.py:176-177, 234-246: the start_steps rows are scored as well)
             eng.score_new(run.replay, math.ceil(20 * run.max_step / (n * run.world)) * n, seed=run.seed + 3 + run.rank)
         elif run.per:
@@ -731,15 +753,20 @@ def choose_loop(run):
     shared_gpu = world > torch.cuda.device_count() and not os.environ.get("HX_FRONT_SHARED_GPU")
     upsampled = tuple(flag for flag in ("buffer_upsample", "expert_upsample") if getattr(run, flag, False))  # the weighted draw is a launch behind the plain one
     run.front = (config.loop == "front" and not sac and not config.separate_launches and config.updates_per_step == 1 and run.batch <= 256
-                 and getattr(config, "dtype", "f32") in ("f32", "f32x9", "bf16") and not shared_gpu and not upsampled and not getattr(run, "hirl_per", False))
+                 and getattr(config, "dtype", "f32") in ("f32", "f32x9", "bf16") and not shared_gpu and not upsampled and not getattr(run, "hirl_per", False)
+                 and (run.inserter is None or run.n <= 8192))  # (--hirl_multi_step: the env has no ring, so the front launch acts per tile: up to 8,192 envs)
     run.front_sac = (config.loop == "front" and sac and world == 1 and not config.separate_launches and config.updates_per_step == 1 and run.batch <= 256 and not run.per
                      and run.grad_clip is None and run.inserter is None)
     if rank == 0:
         which = "front launch (env step + first launches of learn() in one launch; draw before the insert)" if (run.front or run.front_sac) else "reference order"
         if run.per:  # the front loop draws before the step's insert: update_priority could then hit slots the step has overwritten
             which += f" ({'--hirl_per' if getattr(run, 'hirl_per', False) else '--per'}: the front launch draws before the step's insert, so the priorities of the drawn rows could be written into overwritten slots)"
-        if run.inserter is not None:  # the front launch's acting workgroups insert one-step rows themselves
+        if run.inserter is not None and sac:  # the front launch's acting workgroups insert one-step rows themselves
             which += f" (--multi_step {run.multi_step}: the n-step rows are written by a launch of their own behind the acting launch)"
+        if run.inserter is not None and not sac:  # HIRL / TD3: the front launch takes an env without a ring up to 8,192 envs (per-tile acting workgroups)
+            which += (f" (--hirl_multi_step {run.multi_step}: the n-step rows are written by a launch of their own behind " +
+                      ("the front launch's call; the minibatch is drawn before the previous step's rows" if run.front else "the acting launch") +
+                      ("; more than 8,192 envs: the front launch's persistent and streaming acting roles need a ring in the env" if run.n > 8192 and config.loop == "front" else "") + ")")
         if upsampled:  # the front launch draws uniformly, inside the launch and before the step's insert
             which += f" ({' '.join('--' + flag for flag in upsampled)}: the upsampled draw is a launch of its own between the acting launch and learn(), after the step's insert)"
         if sac and run.grad_clip is not None and not run.per:  # the clipped update is the staged sequence (gradients -> norm -> clipped step): its first launch is its own
@@ -780,10 +807,11 @@ def branch_has_reader(run):
 
 
 # ---- the vector step: two hooks every form shares, three forms --------------------------------------------------------------------------------------
-def after_env_step(run, step):
+def after_env_step(run, step, pushed=False):
     """Behind every acting launch, in this order: the n-step rows, the episode statistics, the pilot's relabelled rows, the pilot's branches, the new
-    rows' first priorities, the reward sum.  (The front forms run without an inserter and without --per: choose_loop.)"""
-    if run.inserter is not None:
+    rows' first priorities, the reward sum.  (SAC's front form runs without an inserter, every front form without --per: choose_loop.)  pushed: the
+    step's n-step rows are in the ring already — HirlEngine.step_learn pushes behind its own launches; one push per env step."""
+    if run.inserter is not None and not pushed:
         run.inserter.push(run.env, run.actions)  # this step's finished n-step rows (at most multi_step * n of them)
     if run.estats is not None:
         run.estats.push()
@@ -802,7 +830,7 @@ def after_env_step(run, step):
     elif run.per:
         run.replay.mark_new(run.n if run.inserter is None else run.inserter.max_rows)  # this step's rows enter at the running maximum priority (one launch, no host sync)
     if getattr(run, "upsampler", None) is not None:
-        run.upsampler.mark_new(run.n)  # the blocks this step's rows fell into are recounted (one launch, no host sync)
+        run.upsampler.mark_new(run.n if run.inserter is None else run.inserter.max_rows)  # the blocks this step's rows fell into are recounted (one launch, no host sync)
     if run.ret is not None:
         run.ret += run.env.reward
 
@@ -836,7 +864,7 @@ def step_front_hirl(run, step, w_now, warm):
     run.expert_num = next_expert_num(run, step)
     run.eng.step_learn(run.env, run.expert, run.bc_table, n_main=run.batch - run.expert_num, act_sigma=0.1, act_seed=run.seed + 1, out=run.actions,
                        sample_seed=run.seed + 2 + run.rank, bc_weight_now=w_now, bc_warm_up_weight=warm)
-    after_env_step(run, step)
+    after_env_step(run, step, pushed=run.inserter is not None)
     log_step_scalars(run, step)
 
 
@@ -1093,7 +1121,8 @@ def nstep_refusal(config, world=1):
     if not 2 <= n <= 8:
         return f"--multi_step {n}: the number of steps is 1 (off) or 2..8"
     if config.agent != "SAC":
-        return f"--multi_step goes with --agent SAC (n-step returns are SacAgent's: SAC/agent.py:121-124), not --agent {config.agent}"
+        return (f"--multi_step goes with --agent SAC (n-step returns are SacAgent's: SAC/agent.py:121-124), not --agent {config.agent}" +
+                (": HIRL and TD3 have --hirl_multi_step N" if config.agent in ("HIRL", "TD3") else ""))
     if config.type == "ISAC":
         return "--multi_step with --type ISAC: n-step returns with the imitative branch are not built: use --type SAC or ESAC"
     if config.type not in ("SAC", "ESAC"):
@@ -1293,6 +1322,40 @@ def hirl_per_refusal(config, world=1):
     return None
 
 
+def hirl_multi_step_refusal(config, world=1):
+    """why `--hirl_multi_step` cannot run as asked, or None.  (A flag of its own: `--multi_step` is SacAgent's keyword and stays refused for every other
+    agent.)  HirlEngine.set_multi_step: every --type and --dtype, --separate_launches, --hirl_grad_clip, --hirl_per, --buffer_upsample / --expert_upsample,
+    --expert_floor, --expert_online, --expert_branch[_steps] (branch rows stay one-step rows) and --env mixed are fine."""
+    n = int(getattr(config, "hirl_multi_step", 1))
+    if n == 1:
+        return None
+    if config.agent == "SAC":
+        return "--hirl_multi_step goes with --agent HIRL or TD3, not --agent SAC: SAC has --multi_step (SacAgent(multi_step=N))"
+    if config.agent == "BC":
+        return "--hirl_multi_step goes with --agent HIRL or TD3, not --agent BC (behaviour cloning has no replay ring and no TD target)"
+    if config.agent not in ("HIRL", "TD3"):
+        return f"--hirl_multi_step goes with --agent HIRL or TD3, not --agent {config.agent}"
+    if not 2 <= n <= 8:
+        return f"--hirl_multi_step {n}: the number of steps is 1 (off) or 2..8"
+    if (config.gpus and config.gpus > 1) or world > 1:
+        return "--hirl_multi_step runs on one GPU (the per-env windows are rank-local and untested on sharded ranks): use --gpus 1"
+    if int(getattr(config, "buffer_size", 0)) < n * int(config.num_envs):
+        return (f"--hirl_multi_step {n} with --buffer_size {config.buffer_size}: one step can store N * --num_envs = {n * int(config.num_envs)} rows: "
+                "use a larger --buffer_size")
+    return None
+
+
+def hirl_multi_step_resume_refusal(config, snap):
+    """why a snapshot cannot be resumed under this run's --hirl_multi_step, or None (snap None: a fresh run)"""
+    if snap is None or config.agent not in ("HIRL", "TD3"):
+        return None
+    was = int(snap["engine"]["multi_step"]["n"]) if "multi_step" in snap["engine"] else 1
+    now = int(getattr(config, "hirl_multi_step", 1))
+    if was != now:
+        return f"was run with --hirl_multi_step {was}, --hirl_multi_step {now} given: resume with the flag the run was started with"
+    return None
+
+
 def hirl_per_resume_refusal(config, snap):
     """why a snapshot cannot be resumed under this run's --hirl_per, or None (snap None: a fresh run)"""
     if snap is None:
@@ -1307,7 +1370,7 @@ def parse_args(argv=None):
     """parser().parse_args with the cross-flag checks that are argparse errors"""
     p = parser()
     cfg = p.parse_args(argv)
-    why = per_refusal(cfg) or hirl_per_refusal(cfg) or clip_refusal(cfg) or hirl_clip_refusal(cfg) or nstep_refusal(cfg) or mixed_refusal(cfg) or upsample_refusal(cfg) or expert_online_refusal(cfg) or expert_branch_refusal(cfg) or expert_floor_refusal(cfg)
+    why = per_refusal(cfg) or hirl_per_refusal(cfg) or clip_refusal(cfg) or hirl_clip_refusal(cfg) or nstep_refusal(cfg) or hirl_multi_step_refusal(cfg) or mixed_refusal(cfg) or upsample_refusal(cfg) or expert_online_refusal(cfg) or expert_branch_refusal(cfg) or expert_floor_refusal(cfg)
     if why:
         p.error(why)
     if cfg.type == "ISAC" and cfg.agent != "SAC":
@@ -1420,6 +1483,12 @@ def parser():
                         "every acting launch keeps the last N steps per env and stores finished rows with r = sum gamma^k r_k and the row's discount folded "
                         "into the done column; no transition is dropped.  Any --dtype, --per with --per_new max; one GPU; the vector loop runs in the "
                         "reference's order.  Stored in the snapshot: --resume refuses another value")
+    p.add_argument("--hirl_multi_step", type=int, default=1,
+                   help="HIRL / TD3: truncated n-step returns, N in 2..8; 1 (default): one-step rows.  An extension (the reference's HIRL and TD3 learn from "
+                        "one-step rows): the env runs without a ring, a launch of its own behind every acting launch stores finished rows with r = sum gamma^k "
+                        "r_k and the row's discount folded into the done column, and HIRL's offline expert rows are relabelled the same way (expert branch "
+                        "rows stay one-step rows).  Every --type and --dtype, both loop forms up to 8,192 envs (the reference's order beyond), "
+                        "--hirl_grad_clip, --hirl_per, the upsampling switches; one GPU.  Stored in the snapshot: --resume refuses another value")
     p.add_argument("--grad_clip", type=float, default=None, help="SAC: clip each network's gradient (Q1, Q2, policy) to this global L2 norm before its Adam step "
                                                                  "(SacAgent(grad_clip=C), SAC/utils.py:15-21); one GPU; the vector loop runs in the reference's "
                                                                  "order.  Stored in the snapshot: --resume refuses another value")

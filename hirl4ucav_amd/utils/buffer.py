@@ -308,6 +308,39 @@ class NStepInserter:
         self.ws.copy_(st["ws"])
 
 
+def segment_last(done, keep=None):
+    """the `last` bytes nstep_relabel takes, for the rows train_all.label_expert keeps of ONE file.  done [k]: their done column; keep [k]: their pair
+    indices in the recording (train_all.expert_pair_indices; None: consecutive).  A segment ends at a terminal row, in front of any gap in `keep` (the
+    reference skips the pair behind a terminal one) and at the file's last row: no transition spans two files.  -> uint8 numpy [k]"""
+    done = np.asarray(done.cpu() if torch.is_tensor(done) else done).reshape(-1) != 0
+    last = done.copy()
+    if keep is not None:
+        keep = np.asarray(keep.cpu() if torch.is_tensor(keep) else keep).reshape(-1).astype(np.int64)
+        if keep.shape != done.shape:
+            raise ValueError(f"segment_last: {done.size} rows, {keep.size} pair indices")
+        last[:-1] |= np.diff(keep) != 1
+    if last.size:
+        last[-1] = True
+    return last.astype(np.uint8)
+
+
+def nstep_relabel(rows, last, n, gamma):
+    """n-step relabelling of a labelled expert table (hx_nstep_label: include/hirl4ucav.h "n-step returns for a labelled expert table").  rows [E, 32]:
+    one-step rows in recording order on the device; last [E]: nonzero on the final row of every segment (segment_last).  -> rows_out [E, 32], a new
+    tensor: row j holds s, a of row j, r = sum_k gamma^k r_{j+k} over m = min(n, rows left in the segment) steps, s' of row j + m - 1 and the row's
+    discount in the done column.  Row j stays row j.  Enqueues only."""
+    if not torch.is_tensor(rows) or rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[1] != _lib.ROW_WORDS or not rows.is_cuda:
+        raise ValueError("nstep_relabel: rows is an fp32 [E, 32] tensor on the GPU")
+    rows = rows.contiguous()
+    E = rows.shape[0]
+    last = torch.as_tensor(last).to(device=rows.device, dtype=torch.uint8).contiguous().reshape(-1)
+    if last.numel() != E:
+        raise ValueError(f"nstep_relabel: {E} rows, {last.numel()} last bytes")
+    out = torch.empty_like(rows)
+    _lib.call("hx_nstep_label", rows.data_ptr(), last.data_ptr(), E, int(n), float(gamma), out.data_ptr(), _lib.stream_ptr())
+    return out
+
+
 class HostNStep:
     """the same rule on the host for ONE env, one transition per append (SacAgent(multi_step=n).memory): fp32 numpy arithmetic in the kernel's order.
     append -> the finished rows [(row[32], step_success)], oldest first."""

@@ -87,7 +87,8 @@ def load_engine_state(eng, st):
     was_n = st["multi_step"]["n"] if "multi_step" in st else 1
     now_n = eng.multi_step.n if getattr(eng, "multi_step", None) is not None else 1
     if was_n != now_n or ("multi_step" in st) != (getattr(eng, "multi_step", None) is not None):
-        raise ValueError(f"snapshot was written under --multi_step {was_n}, this engine runs under --multi_step {now_n}: resume with the flag the run was "
+        flag = getattr(eng, "multi_step_flag", "--multi_step")  # (HirlEngine: --hirl_multi_step)
+        raise ValueError(f"snapshot was written under {flag} {was_n}, this engine runs under {flag} {now_n}: resume with the flag the run was "
                          "started with")
     if ("imitative" in st) != bool(getattr(eng, "imitative", False)):
         raise ValueError("snapshot and engine disagree about SAC's imitative branch (--type ISAC): resume with the type the run was started with")

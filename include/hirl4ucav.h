@@ -91,8 +91,9 @@ const char* hx_last_error(void);
  * 129: expert branches of up to H steps: resident branches in a device workspace, one step per call (hx_pilot_branch_steps,
  * hx_branch_workspace_bytes).
  * 130: gradient-norm clipping for HIRL and TD3 (hx_hirl_clip_floats, hx_hirl_clip_shape, hx_hirl_grad_norm, hx_adam_clipped).
- * 131: prioritized replay for HIRL and TD3: the weighted TD head (hx_hirl_critic_grads_weighted). */
-#define HX_ABI_VERSION 131
+ * 131: prioritized replay for HIRL and TD3: the weighted TD head (hx_hirl_critic_grads_weighted).
+ * 132: n-step returns for HIRL and TD3: n-step relabelling of a labelled expert table (hx_nstep_label). */
+#define HX_ABI_VERSION 132
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -784,6 +785,20 @@ int hx_nstep_reset(const HxNStep* ns, const float* obs, const uint32_t* episode_
  * rows: cap >= n * n_envs (and < 2^31).  ring_success may be NULL.  Enqueues only. */
 int hx_nstep_push(const HxNStep* ns, const float* obs_new, const float* actions, const float* reward, const uint8_t* done, const int8_t* success,
                   const uint32_t* episode_ctr, float* ring, int8_t* ring_success, int64_t cap, uint64_t* total, void* stream);
+/* n-step returns for a labelled expert table (HIRL / TD3 on n-step rows, a declared extension: HirlEngine.set_multi_step, train_all --hirl_multi_step).
+ * rows_in [E][32]: what hx_label_transitions leaves once the reference's pairs have been picked (train_all.label_expert) — one-step rows in recording
+ * order, done exactly 0 or 1, and within a segment row j + 1 starts where row j ended.  last[j] != 0 marks the final row of a segment: a terminal row,
+ * the last row of a file, or the row in front of any gap.  Per row j, fp32 without contraction, in this order — the fold a head performs in
+ * hx_nstep_push (tests/_nstep_label_model.py is the same in numpy, bit for bit):
+ *     m = min(n, rows from j to the end of j's segment, inclusive)
+ *     acc = 0; boot = 1;  for k = 0 .. m - 1:  w = k == 0 ? 1 : boot * gamma;  acc = acc + w * r[j + k];  boot = w
+ *     rows_out[j] = (s_j, a_j, s' = s'[j + m - 1], r = acc, d' = done[j + m - 1] ? 1 : 1 - boot)
+ * Row j stays row j, so success bytes, fire-row indices and an expert ring's layout stay valid; a terminal row keeps its recorded s' (it is multiplied
+ * by 1 - d' = 0).  At n = 1 the output equals the input in value (0 + r turns a -0 reward into +0).  One launch, one row per lane, 64 rows per
+ * workgroup, rows written as whole 128-byte lines; a row's gathers reach up to n - 1 rows past its workgroup's last row, never past E and never past a
+ * `last` row.  No atomics, no workgroup waits for another.  rows_in and rows_out 16-byte aligned; rows_out must not overlap rows_in.  n in
+ * 1 .. HX_NSTEP_MAX, 0 < E < 2^31, gamma in [0, 1].  Enqueues only. */
+int hx_nstep_label(const float* rows_in, const uint8_t* last, int64_t E, int32_t n, float gamma, float* rows_out, void* stream);
 
 
 /* ------------------------------------------------------------------------------------------------------------
