@@ -344,9 +344,9 @@ def train_bc(config, device, seed, max_step):
     bc_table = torch.from_numpy(tab).to(device)
     table = DeviceReplay(es.shape[0], device)  # the sampler wants a main ring as well; the BC step reads only the BC rows
     table.store_rows(bc_table)
-    if hirl_per_refusal(config) or upsample_refusal(config) or expert_online_refusal(config) or expert_branch_refusal(config) or expert_floor_refusal(config):
+    if hirl_per_refusal(config) or upsample_refusal(config) or expert_online_refusal(config) or expert_branch_refusal(config) or expert_self_refusal(config) or expert_floor_refusal(config):
         raise SystemExit("train_all: " + (hirl_per_refusal(config) or upsample_refusal(config) or expert_online_refusal(config) or expert_branch_refusal(config)
-                                          or expert_floor_refusal(config)))
+                                          or expert_self_refusal(config) or expert_floor_refusal(config)))
     if getattr(config, "expert_upsample", False):  # BC.py:152-158, 171-176: one row of every minibatch is a fire row
         from .utils.buffer import fire_rows
 
@@ -479,7 +479,7 @@ def check_agent_flags(run):
     # the reference's two sampling switches (HIRL.py:184-185): success rows of the replay drawn 10 : 1, one fire row forced into the BC minibatch
     run.buffer_upsample, run.expert_upsample = bool(getattr(config, "buffer_upsample", False)), bool(getattr(config, "expert_upsample", False))
     run.upsampler = None
-    for refusal in (per_refusal, hirl_per_refusal, nstep_refusal, hirl_multi_step_refusal, clip_refusal, hirl_clip_refusal, upsample_refusal, expert_online_refusal, expert_branch_refusal, expert_floor_refusal):  # (per_refusal without --per: --per_new td on its own)
+    for refusal in (per_refusal, hirl_per_refusal, nstep_refusal, hirl_multi_step_refusal, clip_refusal, hirl_clip_refusal, upsample_refusal, expert_online_refusal, expert_branch_refusal, expert_self_refusal, expert_floor_refusal):  # (per_refusal without --per: --per_new td on its own)
         if refusal(config, world):
             raise SystemExit("train_all: " + refusal(config, world))
     if hirl_per_resume_refusal(config, getattr(run, "snap", None)):
@@ -554,12 +554,13 @@ def build_engine(run):
 def load_expert_tables(run):
     """HIRL / E-SAC / ISAC: the labelled expert ring, the BC (s, a) table and the frozen bc_actor"""
     config, device, eng = run.config, run.device, run.eng
-    run.expert = run.bc_table = run.fire_idx = run.online = run.branch = None
+    run.expert = run.bc_table = run.fire_idx = run.online = run.branch = run.selfx = None
     if run.upsampler is not None:  # (TD3 has no expert table: the engine hears of the upsampler here)
         eng.set_upsample(run.upsampler, None)
     if not (run.hirl or run.esac or run.isac):
         return
     why = (expert_branch_resume_refusal(config, run.snap["driver"] if run.snap is not None else None)
+           or expert_self_resume_refusal(config, run.snap["driver"] if run.snap is not None else None)
            or expert_floor_resume_refusal(config, run.snap["driver"] if run.snap is not None else None))
     if why:
         raise SystemExit(f"train_all: --resume {config.resume} {why}")
@@ -583,12 +584,21 @@ def load_expert_tables(run):
         run.branch = BranchExpert(run.env, rows, succ, int(config.expert_branch), int(config.expert_branch_per_step), device,
                                   steps=int(getattr(config, "expert_branch_steps", 1)))
         run.expert = run.branch.ring
-    else:
+    elif int(getattr(config, "expert_self", 0)) <= 0:
         run.expert = DeviceReplay(rows.shape[0] + 10, device)
         run.expert.store_rows(rows, succ)
     tab = np.zeros((es.shape[0], 32), np.float32)
     tab[:, 0:13], tab[:, 13:17] = es, ea
     run.bc_table = torch.from_numpy(tab).to(device)
+    if int(getattr(config, "expert_self", 0)) > 0:
+        # An extension (utils/selfimit.py): the same online region, rewritten by the LEARNER's own episodes that ended in a kill (hx_self_push behind
+        # every acting launch: a device tape of the last --expert_self_steps steps per env).  --expert_self_bc: the BC table grows by the same region and
+        # takes the same rows as (s, a).  Under --hirl_multi_step the self rows stay one-step rows, as branch rows do.
+        from .utils.selfimit import SelfExpert
+
+        run.selfx = SelfExpert(run.env, rows, succ, int(config.expert_self), int(config.expert_self_steps),
+                               bc_table_offline=run.bc_table if getattr(config, "expert_self_bc", False) else None, device=device)
+        run.expert = run.selfx.ring
     if (run.hirl or run.isac) and config.bc_actor and not os.path.exists(config.bc_actor):  # agent.load_bc_actor: a missing file is an error, as in the reference
         raise FileNotFoundError(f"--bc_actor {config.bc_actor}: no such file")
     if run.hirl and config.bc_actor:  # agent.load_bc_actor (train_all.py:311-312)
@@ -614,6 +624,8 @@ def load_expert_tables(run):
 
         run.online = OnlineExpert(run.env, run.bc_table, int(config.expert_online), int(config.expert_online_per_step))
         run.bc_table = run.online.table
+    if run.selfx is not None and run.selfx.table is not None:  # --expert_self_bc: the widened table (fire_idx above was taken from the offline rows, likewise)
+        run.bc_table = run.selfx.table
 
 
 def set_dtype(run):
@@ -665,6 +677,8 @@ def stats_record(run):
         rec["expert_online"] = run.online.state_dict()
     if getattr(run, "branch", None) is not None:  # (likewise without --expert_branch)
         rec["expert_branch"] = run.branch.state_dict()
+    if getattr(run, "selfx", None) is not None:  # (likewise without --expert_self)
+        rec["expert_self"] = run.selfx.state_dict()
     if getattr(run, "expert_floor", 0):  # (likewise without --expert_floor)
         rec["expert_floor"] = run.expert_floor
     return rec
@@ -677,6 +691,9 @@ def restore_stats(run, record):
         run.online.load_state_dict(record["expert_online"])
     if getattr(run, "branch", None) is not None:
         run.branch.load_state_dict(record["expert_branch"])
+    if getattr(run, "selfx", None) is not None:  # the tape is not in the snapshot: every env's episode starts empty at the restored env's observation
+        run.selfx.load_state_dict(record["expert_self"])
+        run.selfx.reset()
     if run.estats is None:
         return
     st = record.get("episode_stats")
@@ -716,6 +733,8 @@ def restore_or_explore(run):
             inserter.reset(env)
         if estats is not None:
             estats.reset()
+        if getattr(run, "selfx", None) is not None:
+            run.selfx.reset()
         for _ in range(math.ceil(20 * run.max_step / (n * run.world))):
             a0 = torch.rand((n, 4), device=run.device) * 2 - 1
             env.step(a0)
@@ -727,6 +746,8 @@ def restore_or_explore(run):
                 run.online.push()
             if getattr(run, "branch", None) is not None:
                 run.branch.push()
+            if getattr(run, "selfx", None) is not None:
+                run.selfx.push(a0)
             if getattr(run, "upsampler", None) is not None:
                 run.upsampler.mark_new(n if inserter is None else inserter.max_rows)
         if run.per and run.per_new == "td":  # the exploration rows are appended with an error of their own too (SAC/agent.py:176-177, 234-246: the start_steps rows are scored as well)
@@ -808,7 +829,7 @@ def branch_has_reader(run):
 
 # ---- the vector step: two hooks every form shares, three forms --------------------------------------------------------------------------------------
 def after_env_step(run, step, pushed=False):
-    """Behind every acting launch, in this order: the n-step rows, the episode statistics, the pilot's relabelled rows, the pilot's branches, the new
+    """Behind every acting launch, in this order: the n-step rows, the episode statistics, the pilot's relabelled rows, the pilot's branches, the learner's own kill episodes, the new
     rows' first priorities, the reward sum.  (SAC's front form runs without an inserter, every front form without --per: choose_loop.)  pushed: the
     step's n-step rows are in the ring already — HirlEngine.step_learn pushes behind its own launches; one push per env step."""
     if run.inserter is not None and not pushed:
@@ -819,6 +840,8 @@ def after_env_step(run, step, pushed=False):
         run.online.push()  # --expert_online: per_step envs relabelled by the pilot into the online region of bc_table (one launch, no host sync)
     if getattr(run, "branch", None) is not None and branch_has_reader(run):
         run.branch.push()  # --expert_branch: per_step envs flown one step by the pilot, in registers, into the online region of the expert ring (likewise)
+    if getattr(run, "selfx", None) is not None and branch_has_reader(run):
+        run.selfx.push(run.actions)  # --expert_self: the step goes onto the episode tape; kill episodes leave for the same region (two launches, no host sync)
     if run.per and run.per_new == "td":
         replay, n, writer = run.replay, run.n, run.writer
         log_new = writer is not None and step % run.log_rate == 0
@@ -1002,6 +1025,9 @@ def log_episode(run):
                 _, ended_rows, kill_rows = run.branch.counters()
                 writer.add_scalar("Expert/Branch Episodes Ended", ended_rows, episode)
                 writer.add_scalar("Expert/Branch Kills", kill_rows, episode)
+        if getattr(run, "selfx", None) is not None:  # the device counters: one device-to-host copy per driver episode
+            for tag, v in zip(("Kills", "Episodes Written", "Rows Written", "Episodes Dropped"), run.selfx.counters()):
+                writer.add_scalar("Expert/Self " + tag, v, episode)
         if ret is not None:
             tot = float(ret.mean())
             writer.add_scalar("Training/Episode Reward", tot, episode)
@@ -1239,6 +1265,56 @@ def expert_branch_resume_refusal(config, driver):
     return None
 
 
+def expert_self_refusal(config, world=1):
+    """why `--expert_self` / `--expert_self_steps` / `--expert_self_bc` cannot run as asked, or None"""
+    rows, steps, bc = int(getattr(config, "expert_self", 0)), int(getattr(config, "expert_self_steps", 256)), bool(getattr(config, "expert_self_bc", False))
+    if rows == 0:
+        if bc:
+            return "--expert_self_bc goes with --expert_self ROWS > 0 (there are no self rows to mirror without it)"
+        return None
+    if rows < 0:
+        return f"--expert_self {rows}: the rows of the expert ring's online region, 0 (off) or more"
+    if not 1 <= steps <= 65535:
+        return f"--expert_self_steps {steps}: the steps of an episode the tape keeps, 1 to 65,535 (the episode counter's range)"
+    takes = "--expert_self goes with --agent HIRL, --agent SAC --type ESAC and --agent SAC --type ISAC"
+    if config.agent == "SAC" and config.type not in ("ESAC", "ISAC"):
+        return f"{takes} (--agent SAC --type {config.type} reads no expert ring)"
+    if config.agent == "TD3":
+        return f"{takes} (TD3 reads no expert ring)"
+    if config.agent == "BC":
+        return f"{takes} (--agent BC reads no expert ring and has no rollouts whose kills could be kept)"
+    if int(getattr(config, "expert_branch", 0)) > 0:
+        return "--expert_self does not go with --expert_branch (both want the online region of the expert ring): drop one of the two"
+    if bc and config.agent != "HIRL":
+        return "--expert_self_bc goes with --agent HIRL (SAC / ESAC / ISAC read no BC table)"
+    if bc and int(getattr(config, "expert_online", 0)) > 0:
+        return "--expert_self_bc does not go with --expert_online (both want the online region of the BC table): drop one of the two"
+    if getattr(config, "per", False):
+        return "--expert_self does not go with --per (the weighted call drops the expert rows: the self rows would never be drawn)"
+    if (config.gpus and config.gpus > 1) or world > 1:
+        return "--expert_self runs on one GPU (the tape is rank-local and untested on sharded ranks): use --gpus 1"
+    if steps > rows:
+        return f"--expert_self_steps {steps} > --expert_self {rows}: an episode of L rows must fit into the online region (L <= ROWS)"
+    return None
+
+
+def expert_self_resume_refusal(config, driver):
+    """why a snapshot's driver record cannot be resumed under this run's --expert_self / --expert_self_steps / --expert_self_bc, or None (driver None: a
+    fresh run)"""
+    if driver is None:
+        return None
+    was = driver.get("expert_self")
+    was_rows, was_steps, was_bc = (int(was["online_rows"]), int(was["steps"]), bool(was["bc"])) if was is not None else (0, None, False)
+    rows, steps, bc = int(getattr(config, "expert_self", 0)), int(getattr(config, "expert_self_steps", 256)), bool(getattr(config, "expert_self_bc", False))
+    if was_rows != rows:
+        return f"was run with --expert_self {was_rows}, --expert_self {rows} given"
+    if rows and was_steps != steps:
+        return f"was run with --expert_self_steps {was_steps}, --expert_self_steps {steps} given"
+    if rows and was_bc != bc:
+        return f"was run {'with' if was_bc else 'without'} --expert_self_bc, this run is {'with' if bc else 'without'} it"
+    return None
+
+
 def expert_floor_refusal(config, world=1):
     """why `--expert_floor` cannot run as asked, or None"""
     floor = int(getattr(config, "expert_floor", 0))
@@ -1370,7 +1446,7 @@ def parse_args(argv=None):
     """parser().parse_args with the cross-flag checks that are argparse errors"""
     p = parser()
     cfg = p.parse_args(argv)
-    why = per_refusal(cfg) or hirl_per_refusal(cfg) or clip_refusal(cfg) or hirl_clip_refusal(cfg) or nstep_refusal(cfg) or hirl_multi_step_refusal(cfg) or mixed_refusal(cfg) or upsample_refusal(cfg) or expert_online_refusal(cfg) or expert_branch_refusal(cfg) or expert_floor_refusal(cfg)
+    why = per_refusal(cfg) or hirl_per_refusal(cfg) or clip_refusal(cfg) or hirl_clip_refusal(cfg) or nstep_refusal(cfg) or hirl_multi_step_refusal(cfg) or mixed_refusal(cfg) or upsample_refusal(cfg) or expert_online_refusal(cfg) or expert_branch_refusal(cfg) or expert_self_refusal(cfg) or expert_floor_refusal(cfg)
     if why:
         p.error(why)
     if cfg.type == "ISAC" and cfg.agent != "SAC":
@@ -1472,6 +1548,15 @@ def parser():
                    help="--expert_branch: the K branches stay resident on the device and fly up to H steps, one step per acting launch (the launch's cost "
                         "does not depend on H); a branch that ends (done, a non-finite row, H steps) is reseeded from the learner's envs.  1 (default): one "
                         "step per pick.  1..65535.  Stored in the snapshot: --resume refuses another value")
+    p.add_argument("--expert_self", type=int, default=0, metavar="ROWS",
+                   help="HIRL (every --type), ESAC, ISAC: self-imitation (an extension) — the labelled expert ring grows by ROWS online rows that the learner's "
+                        "own episodes rewrite: every env's last --expert_self_steps steps are kept on a device tape, and an episode that ends in a kill (done "
+                        "with reward > 0) is written, oldest step first, as full transitions over the oldest online rows.  0 (default): off.  Not with "
+                        "--expert_branch, --per, --gpus > 1")
+    p.add_argument("--expert_self_steps", type=int, default=256, metavar="L",
+                   help="--expert_self: steps of an episode the tape keeps, 1 <= L <= min(ROWS, 65535); the tape takes 76 L num_envs bytes of device memory")
+    p.add_argument("--expert_self_bc", action="store_true",
+                   help="--expert_self, HIRL only: the BC table grows by the same ROWS and takes the same rows as (s, a).  Not with --expert_online")
     p.add_argument("--expert_floor", type=int, default=0, metavar="N",
                    help="HIRL and --type ESAC (a departure from the reference, whose expert rows end with the warm-up): the expert rows of a minibatch never "
                         "fall below N, 0 <= N <= 128, so the expert ring (and --expert_branch's rows) is read for the whole run.  0 (default): the "

@@ -92,8 +92,9 @@ const char* hx_last_error(void);
  * hx_branch_workspace_bytes).
  * 130: gradient-norm clipping for HIRL and TD3 (hx_hirl_clip_floats, hx_hirl_clip_shape, hx_hirl_grad_norm, hx_adam_clipped).
  * 131: prioritized replay for HIRL and TD3: the weighted TD head (hx_hirl_critic_grads_weighted).
- * 132: n-step returns for HIRL and TD3: n-step relabelling of a labelled expert table (hx_nstep_label). */
-#define HX_ABI_VERSION 132
+ * 132: n-step returns for HIRL and TD3: n-step relabelling of a labelled expert table (hx_nstep_label).
+ * 133: self-imitation: the learner's own kill episodes join the online region of the labelled expert ring (hx_self_*). */
+#define HX_ABI_VERSION 133
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -1014,6 +1015,66 @@ int hx_pilot_branch(const float* state, int64_t n, int64_t stride, const float* 
 int64_t hx_branch_workspace_bytes(int32_t per_call);  /* 0 for per_call < 1 */
 int hx_pilot_branch_steps(const float* state, int64_t n, int64_t stride, const float* obs, float* ring, int8_t* success, int64_t offline_rows,
                           int64_t online_rows, int32_t per_call, int32_t max_steps, uint64_t call, void* work, int64_t work_stride, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Self-imitation (an EXTENSION beside the expert branches above, after Oh et al. 2018: the rows above are all the scripted pilot's actions, these are
+ * the LEARNER's own, taken from the episodes it won).  An episode tape keeps the last L executed steps of every env.  One hx_self_push follows every
+ * acting launch (a front launch or hx_env_step) and reads the buffers as that launch left them: obs_new [n][13], actions [n][4], reward, done, success,
+ * episode_ctr [n]; envs are auto-reset, as for hx_epstat_push.  Per env and call, in this order (tests/_selfimit_model.py is the same in numpy, rows
+ * as bit patterns):
+ *     trunc = episode_ctr != last_ctr && !done      (the time-limit step: executed, not stored; hx_nstep_push's rule)
+ *     trunc: len = 0, nothing recorded
+ *     else:  record (s = obs_prev, a = action as given, r = reward, step_success) as the episode's newest step;  len = min(len + 1, L)
+ *            done: kill = reward > 0;  a kill episode EMITS its m = len recorded steps, oldest first;  len = 0 either way
+ *     obs_prev = obs_new;  last_ctr = episode_ctr
+ * The kill test is reward > 0 on the done step: every term of the env's reward is <= 0 except the +600 paid on health < 0.1f with the fire-success
+ * latch set (hx_env_dev.h), the comparison hx_pilot_branch_steps counts its kills on; HX_F_EPISODE_SUCCESS itself is gone by the time a trailing launch
+ * runs (see hx_epstat_push).  The negative terms are bounded by 1e-4 dist + 30, so the identification holds for dist < 5.7e6 m.
+ * Emitted row j of an episode is [s_j | a_j | s'_j | r_j | done_j] in the replay row's column order: s'_j = s_{j+1} for every row but the last, whose
+ * s' is obs_new as found (under auto-reset the next episode's first observation, multiplied by 1 - done = 0: hx_nstep_push's convention); done is 1.0 on
+ * the last row and 0.0 before it; the row's step_success byte comes from the tape.
+ * Destination: the online region of the labelled expert ring, [offline_rows + M][32] + success bytes, M = online_rows.  A 64-bit device cursor
+ * drives the slots: the k-th row accepted by a call goes to slot offline_rows + ((cursor + k) mod M) — the sum taken exactly, so the slots of one call
+ * are distinct for EVERY cursor value —, then cursor = (cursor + accepted) mod 2^64.  Order within a call: kill envs in ascending env index, each
+ * episode oldest row first.  Overflow: with P_e the rows of all kill episodes of this call up to and including env e, env e's episode is accepted iff
+ * P_e <= M, else dropped whole: acceptance is a function of the prefix alone and the accepted episodes form a leading run.  A row with a non-finite
+ * word among its 32 is written nowhere: its slot keeps what it had, the cursor still advances (hx_pilot_branch's rule).  Rows [0, offline_rows) are
+ * never touched; between launches every slot holds a complete row.  bc_table: NULL, or [bc_offline_rows + M][32]: the same accepted rows go to
+ * bc_offline_rows + ((cursor + k) mod M) as (s, a, zeros), hx_pilot_refresh's row format.
+ * Workspace `work` (part of the ABI; one pointer, carved by the library as hx_pilot_branch_steps carves its own: no struct crosses the boundary),
+ * caller-owned device memory of hx_self_workspace_words(n, L) 4-byte words, 16-byte aligned — the caller states that count as work_words and a call
+ * whose work_words is not hx_self_workspace_words(n_envs, L) is refused, so a wrong (n_envs, L) pair cannot write outside the buffer —, G = ceil(n / 64) groups,
+ * Gp = G rounded up to even, in this order:
+ *     float    tape[L][HX_SELF_FIELDS][n]   indexed by the CALL: the step of call c lies at position c mod L, fields s[13] a[4] r step_success (as a
+ *                                           float); an env's episode is the last len positions ending at the current one
+ *     float    obs_prev[13][n]
+ *     uint32_t len[n]  last_ctr[n]  klen[n] klen: rows the env emits in the current call, 0 if none
+ *     uint32_t wcount[Gp]  wkills[Gp]       per 64-env group: the sum of klen, and the number of kill episodes
+ *     (one pad word if the count so far is odd)
+ *     uint64_t cursor[2]                    double-buffered by call parity: call c reads cursor[c & 1] and writes cursor[(c + 1) & 1]
+ *     uint64_t counters[HX_SELF_COUNTERS][G]  per group, each word added to by its group alone; a statistic is the SUM over the groups:
+ *                                           kills seen, episodes written (accepted), rows written (non-finite rows left out), episodes dropped
+ * Two launches per call.  record: one env per lane, 64 per workgroup, updates the tape and stores klen / wcount / wkills.  flush: one workgroup per
+ * group; wcount[g] == 0 leaves after one load; the others add wcount[0 .. g), take the lane prefix of klen, apply the acceptance rule and copy, 8
+ * lanes per row, whole 128-byte lines.  The same inputs give the same bits in ring, bytes, table, cursor and counters at every n, however workgroups
+ * are scheduled: no atomics of any kind, no workgroup waits for another, no workgroup reads a word that another writes in the same launch.
+ * `call` must advance by one per push (it selects the tape position and the cursor's parity); 1 <= L <= HX_SELF_MAX_STEPS, L <= M, 0 < n < 2^31,
+ * fewer than 2^31 rows in ring and table, ring and table 128-byte aligned, obs_new and actions 16-byte aligned, else HX_ERR_ARG and nothing is
+ * launched.  hx_self_reset (after env.reset(), and after a snapshot came back: the tape is not part of one) zeroes tape, len, klen, wcount and
+ * wkills and sets obs_prev <- obs, last_ctr <- episode_ctr; it leaves cursor and counters alone.  Both enqueue only.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define HX_SELF_FIELDS 19
+#define HX_SELF_MAX_STEPS 65535
+#define HX_SELF_COUNTERS 4
+#define HX_SELF_KILLS 0
+#define HX_SELF_EPISODES 1
+#define HX_SELF_ROWS 2
+#define HX_SELF_DROPPED 3
+int64_t hx_self_workspace_words(int64_t n_envs, int32_t L); /* 0 for L outside 1 .. HX_SELF_MAX_STEPS or n_envs outside (0, 2^31) */
+int hx_self_reset(void* work, int64_t work_words, int64_t n_envs, int32_t L, const float* obs, const uint32_t* episode_ctr, void* stream);
+int hx_self_push(void* work, int64_t work_words, int64_t n_envs, int32_t L, const float* obs_new, const float* actions, const float* reward, const uint8_t* done, const int8_t* success,
+                 const uint32_t* episode_ctr, float* ring, int8_t* ring_success, int64_t offline_rows, int64_t online_rows, float* bc_table,
+                 int64_t bc_offline_rows, uint64_t call, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Exchange step of a sharded update without a collective library (selectable beside RCCL): one-shot all-reduce over hipIpc peer
