@@ -344,9 +344,9 @@ def train_bc(config, device, seed, max_step):
     bc_table = torch.from_numpy(tab).to(device)
     table = DeviceReplay(es.shape[0], device)  # the sampler wants a main ring as well; the BC step reads only the BC rows
     table.store_rows(bc_table)
-    if hirl_per_refusal(config) or upsample_refusal(config) or expert_online_refusal(config) or expert_branch_refusal(config) or expert_self_refusal(config) or expert_floor_refusal(config):
+    if hirl_per_refusal(config) or upsample_refusal(config) or expert_online_refusal(config) or expert_branch_refusal(config) or expert_self_refusal(config) or expert_floor_refusal(config) or explore_refusal(config):
         raise SystemExit("train_all: " + (hirl_per_refusal(config) or upsample_refusal(config) or expert_online_refusal(config) or expert_branch_refusal(config)
-                                          or expert_self_refusal(config) or expert_floor_refusal(config)))
+                                          or expert_self_refusal(config) or expert_floor_refusal(config) or explore_refusal(config)))
     if getattr(config, "expert_upsample", False):  # BC.py:152-158, 171-176: one row of every minibatch is a fire row
         from .utils.buffer import fire_rows
 
@@ -479,7 +479,7 @@ def check_agent_flags(run):
     # the reference's two sampling switches (HIRL.py:184-185): success rows of the replay drawn 10 : 1, one fire row forced into the BC minibatch
     run.buffer_upsample, run.expert_upsample = bool(getattr(config, "buffer_upsample", False)), bool(getattr(config, "expert_upsample", False))
     run.upsampler = None
-    for refusal in (per_refusal, hirl_per_refusal, nstep_refusal, hirl_multi_step_refusal, clip_refusal, hirl_clip_refusal, upsample_refusal, expert_online_refusal, expert_branch_refusal, expert_self_refusal, expert_floor_refusal):  # (per_refusal without --per: --per_new td on its own)
+    for refusal in (per_refusal, hirl_per_refusal, nstep_refusal, hirl_multi_step_refusal, clip_refusal, hirl_clip_refusal, upsample_refusal, expert_online_refusal, expert_branch_refusal, expert_self_refusal, expert_floor_refusal, explore_refusal):  # (per_refusal without --per: --per_new td on its own)
         if refusal(config, world):
             raise SystemExit("train_all: " + refusal(config, world))
     if hirl_per_resume_refusal(config, getattr(run, "snap", None)):
@@ -668,6 +668,30 @@ def open_run_dir(run):
                           missing="--load_model: {} not found (--load_dir / --load_tag name the checkpoint)")
 
 
+def build_explore(run):
+    """--explore_*: the scale of the learner's action noise and, for any colour but white or a ladder of scales, the generator that draws it (an
+    extension).  white at one scale: run.explore stays None and the acting kernels draw as ever, call for call."""
+    config = run.config
+    why = explore_resume_refusal(config, run.snap["driver"] if run.snap is not None else None)
+    if why:
+        raise ValueError(f"train_all: --resume {config.resume} {why}")
+    e = explore_settings(config)
+    run.act_sigma, run.explore = float(e["explore_sigma"]), None
+    if not explore_uses_generator(config):
+        return
+    from .utils.noise import ColoredNoise, lag_autocorr
+
+    # SAC / ESAC / ISAC: unit-variance eps for the Gaussian head (the policy's log-std scales it).  Seed + 4: the acting kernels key seed + 1, the draws
+    # seed + 2 + rank, the scoring pass seed + 3 + rank; the generator's counters carry the env id, so every rank takes the same key
+    gen = ColoredNoise(run.n, e["explore_noise"], tau=e["explore_tau"], octaves=e["explore_octaves"], sigma=1.0 if run.sac else run.act_sigma,
+                       sigma_max=e["explore_sigma_max"], seed=run.seed + 4, env_id0=run.env.env_id0, chunk=e["explore_chunk"], device=run.device)
+    run.explore = gen
+    if run.writer is not None:
+        lo, hi = gen.sigma_range()
+        for tag, v in (("Explore/Sigma Min", lo), ("Explore/Sigma Max", hi), ("Explore/Lag1 Autocorr", lag_autocorr(gen.a, gen.w, 1))):
+            run.writer.add_scalar(tag, v, 0)
+
+
 def stats_record(run):
     """what every snapshot's driver record carries beside the driver's scalars"""
     rec = {"env": run.env_type}
@@ -681,6 +705,9 @@ def stats_record(run):
         rec["expert_self"] = run.selfx.state_dict()
     if getattr(run, "expert_floor", 0):  # (likewise without --expert_floor)
         rec["expert_floor"] = run.expert_floor
+    flags = {k: v for (k, default), v in zip(EXPLORE_FLAGS, explore_settings(getattr(run, "config", None)).values()) if v != default}
+    if flags:  # (likewise without any --explore_* flag)
+        rec["explore"] = {"flags": flags, "generator": run.explore.state_dict() if getattr(run, "explore", None) is not None else None}
     return rec
 
 
@@ -694,6 +721,8 @@ def restore_stats(run, record):
     if getattr(run, "selfx", None) is not None:  # the tape is not in the snapshot: every env's episode starts empty at the restored env's observation
         run.selfx.load_state_dict(record["expert_self"])
         run.selfx.reset()
+    if getattr(run, "explore", None) is not None:  # the bank's state, the chunk and the step counter: the noise goes on as if the run had never stopped
+        run.explore.load_state_dict(record["explore"]["generator"])
     if run.estats is None:
         return
     st = record.get("episode_stats")
@@ -777,7 +806,7 @@ def choose_loop(run):
                  and getattr(config, "dtype", "f32") in ("f32", "f32x9", "bf16") and not shared_gpu and not upsampled and not getattr(run, "hirl_per", False)
                  and (run.inserter is None or run.n <= 8192))  # (--hirl_multi_step: the env has no ring, so the front launch acts per tile: up to 8,192 envs)
     run.front_sac = (config.loop == "front" and sac and world == 1 and not config.separate_launches and config.updates_per_step == 1 and run.batch <= 256 and not run.per
-                     and run.grad_clip is None and run.inserter is None)
+                     and run.grad_clip is None and run.inserter is None and getattr(run, "explore", None) is None)
     if rank == 0:
         which = "front launch (env step + first launches of learn() in one launch; draw before the insert)" if (run.front or run.front_sac) else "reference order"
         if run.per:  # the front loop draws before the step's insert: update_priority could then hit slots the step has overwritten
@@ -792,6 +821,9 @@ def choose_loop(run):
             which += f" ({' '.join('--' + flag for flag in upsampled)}: the upsampled draw is a launch of its own between the acting launch and learn(), after the step's insert)"
         if sac and run.grad_clip is not None and not run.per:  # the clipped update is the staged sequence (gradients -> norm -> clipped step): its first launch is its own
             which += " (--grad_clip: the clipped update runs as stages, which have no front form)"
+        if sac and getattr(run, "explore", None) is not None:  # SacEngine.step_learn draws its eps in-kernel; act / act_step take the generator's
+            which += (f" (--explore_noise {run.explore.params['kind']}: the coloured draws are the Gaussian head's eps, which act_step takes and the front "
+                      "launch does not)")
         if not sac and run.grad_clip is not None:  # HIRL / TD3: the stages run behind the front launch as they do on a sharded rank
             which += (f" (--hirl_grad_clip {run.grad_clip:g}: the clipped update runs as stages" +
                       (" behind the front launch" if run.front else "") + ", a norm launch in front of each optimizer step)")
@@ -882,11 +914,18 @@ def log_step_scalars(run, step):
         writer.add_scalar("stats/per_max_priority", run.replay.pmax, at)
 
 
+def explore_kw(run, key):
+    """{key: this step's [n, 4] slice of the generator's chunk} under coloured noise or a ladder of scales; {} without a generator: the acting call is
+    then word for word the one it was (Philox draws inside the acting kernel)"""
+    gen = getattr(run, "explore", None)
+    return {key: gen.next()} if gen is not None else {}
+
+
 def step_front_hirl(run, step, w_now, warm):
     """HIRL / TD3: env step + the first two launches of learn() as one launch (HirlEngine.step_learn)"""
     run.expert_num = next_expert_num(run, step)
-    run.eng.step_learn(run.env, run.expert, run.bc_table, n_main=run.batch - run.expert_num, act_sigma=0.1, act_seed=run.seed + 1, out=run.actions,
-                       sample_seed=run.seed + 2 + run.rank, bc_weight_now=w_now, bc_warm_up_weight=warm)
+    run.eng.step_learn(run.env, run.expert, run.bc_table, n_main=run.batch - run.expert_num, **explore_kw(run, "act_noise"), act_sigma=getattr(run, "act_sigma", 0.1),
+                       act_seed=run.seed + 1, out=run.actions, sample_seed=run.seed + 2 + run.rank, bc_weight_now=w_now, bc_warm_up_weight=warm)
     after_env_step(run, step, pushed=run.inserter is not None)
     log_step_scalars(run, step)
 
@@ -903,13 +942,14 @@ def step_front_sac(run, step):
 def step_reference(run, step, w_now, warm):
     """the reference's order: act -> env step -> insert -> draw -> learn (--updates_per_step times); an episode's last step only acts"""
     config, eng, env, seed, sac = run.config, run.eng, run.env, run.seed, run.sac
+    noise = explore_kw(run, "eps" if sac else "noise")  # coloured noise: per-row additive noise (HIRL / TD3, noise_mode 2), the Gaussian head's eps (SAC)
     if config.separate_launches:  # chooseAction, then env.step: two launches
-        eng.act(env.obs, seed=seed + 1, row0=env.env_id0, out=run.actions) if sac else eng.act(env.obs, sigma=0.1, seed=seed + 1, row0=env.env_id0, out=run.actions)
+        eng.act(env.obs, **noise, seed=seed + 1, row0=env.env_id0, out=run.actions) if sac else eng.act(env.obs, **noise, sigma=getattr(run, "act_sigma", 0.1), seed=seed + 1, row0=env.env_id0, out=run.actions)
         env.step(run.actions)
     elif sac:                     # the same in ONE launch (identical values; only the order in which a step's rows enter the
-        eng.act_step(env, seed=seed + 1, out=run.actions)              # replay ring depends on the workgroup schedule)
+        eng.act_step(env, **noise, seed=seed + 1, out=run.actions)     # replay ring depends on the workgroup schedule)
     else:
-        eng.act_step(env, sigma=0.1, seed=seed + 1, out=run.actions)
+        eng.act_step(env, **noise, sigma=getattr(run, "act_sigma", 0.1), seed=seed + 1, out=run.actions)
     after_env_step(run, step)
     if step == run.max_step - 1:
         return
@@ -1071,7 +1111,7 @@ def main(config):
     run = start_run(config)
     if config.agent == "BC":
         return train_bc(config, run.device, run.seed, run.max_step)
-    for phase in (check_agent_flags, build_env, build_engine, load_expert_tables, set_dtype, open_run_dir, restore_or_explore, choose_loop):
+    for phase in (check_agent_flags, build_env, build_engine, load_expert_tables, set_dtype, open_run_dir, build_explore, restore_or_explore, choose_loop):
         phase(run)
     while run.episode < config.episodes:
         tripped = run_episode(run)
@@ -1342,6 +1382,64 @@ def expert_floor_resume_refusal(config, driver):
     return None
 
 
+EXPLORE_FLAGS = (("explore_noise", "white"), ("explore_tau", 16.0), ("explore_octaves", 6), ("explore_sigma", 0.1), ("explore_sigma_max", None), ("explore_chunk", 16))
+
+
+def explore_settings(config):
+    """the six --explore_* values of a config (a namespace from before the flags has the defaults)"""
+    return {k: getattr(config, k, default) for k, default in EXPLORE_FLAGS}
+
+
+def explore_uses_generator(config):
+    """whether the action noise comes from utils.noise.ColoredNoise: any colour but white, or a ladder of scales"""
+    e = explore_settings(config)
+    return e["explore_noise"] != "white" or e["explore_sigma_max"] is not None
+
+
+def explore_refusal(config, world=1):
+    """why the `--explore_*` flags cannot run as asked, or None.  Every --dtype, both loop forms of HIRL / TD3, any number of envs and --gpus N are fine
+    (each rank has its own generator, keyed by its envs' ids)."""
+    e = explore_settings(config)
+    given = [k for k, default in EXPLORE_FLAGS if e[k] != default]
+    if not given:
+        return None
+    noise, tau, octaves, sigma, sigma_max, chunk = (e[k] for k, _ in EXPLORE_FLAGS)
+    if config.agent == "BC":
+        return f"--{given[0]} goes with --agent HIRL, TD3 or SAC, not --agent BC (behaviour cloning never acts while it trains)"
+    if not (math.isfinite(tau) and tau > 0):
+        return f"--explore_tau {tau:g}: the OU process's correlation time in vector steps, > 0"
+    if not 1 <= octaves <= 8:
+        return f"--explore_octaves {octaves}: the poles of the 1 / f bank, 1..8"
+    if not 1 <= chunk <= 64:
+        return f"--explore_chunk {chunk}: the vector steps of one generator launch, 1..64"
+    if tau != 16.0 and noise != "ou":
+        return "--explore_tau goes with --explore_noise ou"
+    if octaves != 6 and noise != "pink":
+        return "--explore_octaves goes with --explore_noise pink"
+    if config.agent == "SAC" and (sigma != 0.1 or sigma_max is not None):
+        return ("--explore_sigma / --explore_sigma_max go with --agent HIRL or TD3: SAC's noise scale is the policy's own log-std (the generator feeds the "
+                "Gaussian head unit-variance eps)")
+    if not (math.isfinite(sigma) and sigma >= 0):
+        return f"--explore_sigma {sigma:g}: the action noise's standard deviation, >= 0"
+    if sigma_max is not None and not (math.isfinite(sigma_max) and 0 < sigma <= sigma_max):
+        return f"--explore_sigma_max {sigma_max:g} with --explore_sigma {sigma:g}: the ladder runs from --explore_sigma > 0 up to --explore_sigma_max >= it"
+    if chunk != 16 and not explore_uses_generator(config):
+        return "--explore_chunk goes with --explore_noise ou or pink, or --explore_sigma_max (white noise of one scale is drawn inside the acting kernels)"
+    return None
+
+
+def explore_resume_refusal(config, driver):
+    """why a snapshot's driver record cannot be resumed under this run's --explore_* flags, or None (driver None: a fresh run; a record from before the
+    flags was run with their defaults)"""
+    if driver is None:
+        return None
+    was, now = {**dict(EXPLORE_FLAGS), **driver.get("explore", {}).get("flags", {})}, explore_settings(config)
+    for k, _ in EXPLORE_FLAGS:
+        if was[k] != now[k]:
+            return f"was run with --{k} {was[k]}, --{k} {now[k]} given: resume with the flag the run was started with"
+    return None
+
+
 def clip_refusal(config, world=1):
     """why `--grad_clip` / `--fixed_alpha` cannot run as asked, or None"""
     clip, fixed = getattr(config, "grad_clip", None), getattr(config, "fixed_alpha", None)
@@ -1446,7 +1544,7 @@ def parse_args(argv=None):
     """parser().parse_args with the cross-flag checks that are argparse errors"""
     p = parser()
     cfg = p.parse_args(argv)
-    why = per_refusal(cfg) or hirl_per_refusal(cfg) or clip_refusal(cfg) or hirl_clip_refusal(cfg) or nstep_refusal(cfg) or hirl_multi_step_refusal(cfg) or mixed_refusal(cfg) or upsample_refusal(cfg) or expert_online_refusal(cfg) or expert_branch_refusal(cfg) or expert_self_refusal(cfg) or expert_floor_refusal(cfg)
+    why = per_refusal(cfg) or hirl_per_refusal(cfg) or clip_refusal(cfg) or hirl_clip_refusal(cfg) or nstep_refusal(cfg) or hirl_multi_step_refusal(cfg) or mixed_refusal(cfg) or upsample_refusal(cfg) or expert_online_refusal(cfg) or expert_branch_refusal(cfg) or expert_self_refusal(cfg) or expert_floor_refusal(cfg) or explore_refusal(cfg)
     if why:
         p.error(why)
     if cfg.type == "ISAC" and cfg.agent != "SAC":
@@ -1563,6 +1661,20 @@ def parser():
                         "reference's rule.  Not with --per.  Stored in the snapshot: --resume refuses another value")
     p.add_argument("--expert_online_per_step", type=int, default=64, metavar="K",
                    help="--expert_online: envs relabelled per acting launch, 1 <= K <= min(ROWS, --num_envs); they replace the K oldest online rows")
+    p.add_argument("--explore_noise", type=str, default="white", choices=["white", "ou", "pink"],
+                   help="HIRL / TD3 / SAC (an extension, the reference's exploration noise is white): the colour of the learner's action noise.  white "
+                        "(default): drawn fresh per env, component and step inside the acting kernels, as ever.  ou: an Ornstein-Uhlenbeck process of "
+                        "correlation time --explore_tau.  pink: 1 / f noise from --explore_octaves octave-spaced AR(1) poles.  ou and pink come from a "
+                        "generator launch every --explore_chunk steps and are not reset at episode ends; SAC, ESAC and ISAC take them as the Gaussian "
+                        "head's eps, in the reference's order.  Stored in the snapshot: --resume refuses another value.  Not --agent BC")
+    p.add_argument("--explore_tau", type=float, default=16.0, metavar="STEPS", help="--explore_noise ou: the correlation time in vector steps, a = exp(-1 / tau) (default 16)")
+    p.add_argument("--explore_octaves", type=int, default=6, metavar="K", help="--explore_noise pink: the poles a[k] = exp(-2^-k) of the bank, 1..8 (default 6)")
+    p.add_argument("--explore_sigma", type=float, default=0.1, metavar="S",
+                   help="HIRL / TD3: the standard deviation of the action noise (default 0.1, the reference's).  SAC's noise scale is the policy's own: refused")
+    p.add_argument("--explore_sigma_max", type=float, default=None, metavar="S",
+                   help="HIRL / TD3: a ladder of noise scales over the envs, sigma_i = S0 (S / S0)^(u_i) with S0 = --explore_sigma and u_i a fixed hash of the env "
+                        "id in [0, 1); the noise then comes from the generator whatever its colour")
+    p.add_argument("--explore_chunk", type=int, default=16, metavar="STEPS", help="vector steps one generator launch fills, 1..64 (default 16)")
     p.add_argument("--multi_step", type=int, default=1,
                    help="SAC / E-SAC: truncated n-step returns (SacAgent(multi_step=N)), N in 2..8; 1 (default): one-step rows.  A launch of its own behind "
                         "every acting launch keeps the last N steps per env and stores finished rows with r = sum gamma^k r_k and the row's discount folded "

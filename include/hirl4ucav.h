@@ -93,8 +93,9 @@ const char* hx_last_error(void);
  * 130: gradient-norm clipping for HIRL and TD3 (hx_hirl_clip_floats, hx_hirl_clip_shape, hx_hirl_grad_norm, hx_adam_clipped).
  * 131: prioritized replay for HIRL and TD3: the weighted TD head (hx_hirl_critic_grads_weighted).
  * 132: n-step returns for HIRL and TD3: n-step relabelling of a labelled expert table (hx_nstep_label).
- * 133: self-imitation: the learner's own kill episodes join the online region of the labelled expert ring (hx_self_*). */
-#define HX_ABI_VERSION 133
+ * 133: self-imitation: the learner's own kill episodes join the online region of the labelled expert ring (hx_self_*).
+ * 134: correlated exploration noise: a bank of AR(1) processes per env and action component (hx_noise_*). */
+#define HX_ABI_VERSION 134
 int hx_version(void);
 /* sizes[0..7] (host) <- sizeof HxStepOpts, HxNets, HxHyper, HxBatch, HxSample, HxSacNets, HxSacBatch, and the words of a statistics buffer
  * (HX_STAT_WAYS * HX_STAT_PITCH): a binding checks these against its own declarations at load time (hirl4ucav_amd/_lib.py does). */
@@ -1075,6 +1076,40 @@ int hx_self_reset(void* work, int64_t work_words, int64_t n_envs, int32_t L, con
 int hx_self_push(void* work, int64_t work_words, int64_t n_envs, int32_t L, const float* obs_new, const float* actions, const float* reward, const uint8_t* done, const int8_t* success,
                  const uint32_t* episode_ctr, float* ring, int8_t* ring_success, int64_t offline_rows, int64_t online_rows, float* bc_table,
                  int64_t bc_offline_rows, uint64_t call, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Exploration noise (hx_noise.hip): temporally correlated action noise for the per-row noise input of the acting kernels (noise_mode 2 of
+ * hx_actor_act / hx_actor_act_step / hx_hirl_front, the Gaussian head's eps of hx_sac_act / hx_sac_act_step).  An extension: the reference draws white
+ * Gaussian noise (chooseAction, HIRL.py:192-212).  Per env i and action component c a bank of `poles` (1 .. HX_NOISE_MAX_POLES) stationary AR(1)
+ * processes, every coefficient from the host; per vector step t, all in fp32:
+ *     z[k] <- a[k] * z[k] + b[k] * eps[k]        one product, one product, one sum, each rounded: no fused multiply-add
+ *     x    <- ((w[0] * z[0]) + w[1] * z[1]) + ...  k ascending, every product rounded, then added
+ *     out[t][i][c] = s_i * x                       s_i = sigma_env[i] if sigma_env is given, else sigma
+ * With b[k] = sqrt(1 - a[k]^2) and sum w[k]^2 = 1 every z[k] and x has unit variance, so sigma means what the acting kernels' own sigma means.  poles = 1
+ * with a = exp(-1 / tau) is Ornstein-Uhlenbeck noise, poles = K with a[k] = exp(-2^-k), w[k] = 1 / sqrt(K) approximates a 1 / f spectrum between
+ * 1 / (2 pi 2^(K - 1)) and 1 / (2 pi) cycles per step, a = 0 is white noise: the library knows a, b, w alone, the colours are the caller's recipes
+ * (hirl4ucav_amd/utils/noise.py; the rule in numpy: tests/_noise_model.py).
+ *   z        [poles][4][n_envs] device floats (hx_noise_workspace_floats of them): the state, struct-of-arrays over envs
+ *   coef     [3][HX_NOISE_MAX_POLES] HOST floats: a | b | w, the first `poles` of each row are read
+ *   out      [steps][n_envs][4]: out[t] is the [n, 4] tensor of vector step step0 + t
+ *   eps_in   [steps][poles][n_envs][4] standard-normal draws, or NULL: Philox4x32-10, key = seed, counter (row0 + i, lo32(step0 + t), hi32(step0 + t),
+ *            0x4E4F4900 | k); the four words go through u01 and Box-Muller as the acting kernels' draws do (cos / sin per pair), so one Philox call gives
+ *            one pole's four components.  The acting kernels' counters have 0 in the fourth word: no draw is shared.
+ *   eps_out  the same shape or NULL: receives the draws that were USED, whichever source they came from
+ *   row0     the env id of env 0 (HxStepOpts.env_id0): a shard's envs draw what they would draw in one population
+ * hx_noise_init: z <- N(0, 1) from the counter (row0 + i, 0, 0, 0x4E4F4980 | k) — the stationary law, so the first step is coloured already.  Episodes
+ * do NOT reset z: a stationary process continued across an auto-reset is, for the new episode, a stationary draw.  hx_noise_fill advances z by `steps`
+ * (1 .. HX_NOISE_MAX_STEPS) steps in ONE launch: one env per lane, the 4 poles words of an env in registers, no atomics, no workgroup waits for another,
+ * the same inputs give the same bits; fills of s1 + s2 steps equal one fill of s1 + s2.  poles or steps out of range, n_envs <= 0 or >= 2^31, a NULL z,
+ * out or coef, an out / eps_in / eps_out that is not 16-byte aligned, an a[k] outside [0, 1), a non-finite a, b, w or sigma: HX_ERR_ARG and nothing is
+ * launched.  Both enqueue only.  (The arguments are scalars and plain pointers, no struct: the binding's header reader takes no array fields.)
+ * ------------------------------------------------------------------------------------------------------------ */
+#define HX_NOISE_MAX_POLES 8
+#define HX_NOISE_MAX_STEPS 64
+int64_t hx_noise_workspace_floats(int64_t n_envs, int32_t poles); /* 4 poles n_envs; 0 for poles outside 1 .. HX_NOISE_MAX_POLES or n_envs outside (0, 2^31) */
+int hx_noise_init(float* z, int64_t n_envs, int32_t poles, uint64_t seed, uint32_t row0, void* stream);
+int hx_noise_fill(float* z, const float* sigma_env, int64_t n_envs, int32_t poles, float sigma, const float* coef /* host */, uint64_t seed, uint32_t row0,
+                  uint64_t step0, int32_t steps, float* out, const float* eps_in, float* eps_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Exchange step of a sharded update without a collective library (selectable beside RCCL): one-shot all-reduce over hipIpc peer
