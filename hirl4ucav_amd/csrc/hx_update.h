@@ -328,6 +328,8 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     }
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
+// (in (0, 1]: from u >> 8 = 2^23 on the sum rounds to even in fp32, and for u >> 8 = 0xFFFFFF it is 2^24 — the value is exactly 1.0f, whose logarithm 0 makes both
+//  normals of a Box-Muller pair 0; tests/_philox_model.py restates this in float32 and tests/test_draws_gpu.py holds a kernel to it at such a counter)
 __device__ __forceinline__ float u01(uint32_t u) { return ((float)(u >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
 // ---- the minibatch draw inside launch A (HxSample, hx_hirl_learn_sampled) --------------------------------------------------------

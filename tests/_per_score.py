@@ -111,21 +111,7 @@ SCORE_ROW0, LEARN_NEXT_ROW0 = 0xC0000000, 0x40000000  # the Philox rows of the s
 
 def philox_normals(seed, row0, call, n):
     """the Gaussian head's in-kernel draws on the host: Philox4x32-10(key = seed; counter = (row0 + row, call, 0x53414331, 0)) -> Box-Muller, [n, 4]
-    (float64 transcendentals: equal to the device's up to its logf / sinf / cosf rounding)"""
-    M = 0xFFFFFFFF
-    c0 = (np.uint64(row0) + np.arange(n, dtype=np.uint64)) & np.uint64(M)
-    c1 = np.full(n, call, np.uint64)
-    c2 = np.full(n, 0x53414331, np.uint64)
-    c3 = np.zeros(n, np.uint64)
-    k0, k1 = int(seed) & M, (int(seed) >> 32) & M
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
-        h0, l0, h1, l1 = p0 >> np.uint64(32), p0 & np.uint64(M), p1 >> np.uint64(32), p1 & np.uint64(M)
-        c0, c1, c2, c3 = h1 ^ c1 ^ np.uint64(k0), l1, h0 ^ c3 ^ np.uint64(k1), l0
-        k0, k1 = (k0 + 0x9E3779B9) & M, (k1 + 0xBB67AE85) & M
-    u = [((c >> np.uint64(8)).astype(np.float64) + 0.5) / 16777216.0 for c in (c0, c1, c2, c3)]
-    out = np.zeros((n, 4))
-    for j in range(4):
-        rad, ang = np.sqrt(-2.0 * np.log(u[j & 2])), 2.0 * np.pi * u[(j & 2) + 1]
-        out[:, j] = rad * (np.sin(ang) if j & 1 else np.cos(ang))
-    return out.astype(np.float32)
+    (tests/_philox_model.py: the device's float32 uniforms, float64 transcendentals — equal to the device's up to its logf / sinf / cosf rounding)"""
+    from tests import _philox_model as PM
+
+    return PM.act_normals(seed, row0, n, call, tag=PM.TAG_GAUSS).astype(np.float32)
